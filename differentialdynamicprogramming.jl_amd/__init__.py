@@ -19,6 +19,7 @@ trajectories (``K[m,n,N,B]``), which the reference does not have.
 from __future__ import annotations
 
 import ctypes as _C
+import os as _os
 import time as _time
 from dataclasses import dataclass, field
 
@@ -28,7 +29,7 @@ from . import _lib
 from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
-           "df", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff"]
+           "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -150,6 +151,82 @@ class _DevProblem:
         P.cost_diag = int(not np.any(self.Q - np.diag(np.diag(self.Q))) and not np.any(self.R - np.diag(np.diag(self.R))))
         self.struct = P
         self.cost_len = N + 1 if prob.kind == 1 else N
+
+
+# ------------------------------------------------------------------ user problems (HIP device source, compiled at run time)
+_EXAMPLES = _os.path.join(_lib._HERE, "user_examples")
+
+
+def example_source(name):
+    """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``)."""
+    with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
+        return f.read()
+
+
+class DeviceProblem:
+    """The user's own ``f``, ``costfun`` and ``df`` (iLQG.jl:143) as HIP device source: ``dynamics``, ``stage_cost``,
+    ``derivatives`` and, with ``terminal=True``, ``terminal_cost`` (``const_hessian=True``: ``cost_hessians``) — the contract is in
+    include/ddp_amd.h.  The library compiles the source for gfx950 with hiprtc, once per handle, and runs ``forward_pass``, ``df``,
+    ``costfun`` and the whole ``iLQG`` on the device.  ``params``: ``[nparam]`` shared by the batch or ``[nparam, B]`` per trajectory
+    (may be replaced per call through the ``params=`` keyword of the entry points).  ``diff``: ``None`` (``-``) or a ``WrappedDiff``."""
+    kind = 2
+
+    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, diff=None):
+        self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
+        self.terminal, self.const_hessian = bool(terminal), bool(const_hessian)
+        self.flags = (1 if self.terminal else 0) | (2 if self.const_hessian else 0)
+        self.diff_mask = _diff_mask(diff, self.n) if self.n <= 32 else 0
+        self.params = params
+        self._made = {}                                          # id(handle) -> (handle, problem pointer)
+
+    def check(self, extra_options=None):
+        """Compile for gfx950 without a device (ddp_user_check); returns the compiler log, raises DDPError with it on failure."""
+        L = _lib.lib()
+        rc = L.ddp_user_check(self.source.encode(), self.n, self.m, self.nparam, self.flags,
+                              extra_options.encode() if extra_options else None)
+        log = L.ddp_user_compile_log().decode()
+        if rc != 0:
+            raise DDPError("libddp_amd: %s (rc=%d)\n%s" % (L.ddp_last_error().decode(), rc, log))
+        return log
+
+    def cost_len(self, N):
+        return N + 1 if self.terminal else N
+
+    def _ptr(self, h):
+        """the compiled problem on handle `h` (compiled / loaded at first use)"""
+        e = self._made.get(id(h))
+        if e is None or e[0] is not h:
+            up = _C.c_void_p()
+            _lib.check(_lib.lib().ddp_user_create(h.raw, self.source.encode(), self.n, self.m, self.nparam, self.flags,
+                                                  int(self.diff_mask), _C.byref(up)))
+            e = self._made[id(h)] = (h, up)
+        return e[1]
+
+    def _params(self, B, params=None):
+        P = self.params if params is None else params
+        if self.nparam == 0:
+            return None, 0
+        if P is None:
+            raise DDPError("DeviceProblem: nparam = %d but no params were given" % self.nparam)
+        P = _lib.f64(P)
+        if P.shape == (self.nparam,):
+            return P, 0
+        if P.shape == (self.nparam, B):
+            return P, 1
+        raise DDPError("DeviceProblem: params should be (%d,) or (%d, B=%d), got %s" % (self.nparam, self.nparam, B, P.shape))
+
+    def __del__(self):
+        try:
+            for h, up in self._made.values():
+                _lib.lib().ddp_user_destroy(up)
+            self._made = {}
+        except Exception:
+            pass
+
+
+def _user_shapes(problem, n, m):
+    if (n, m) != (problem.n, problem.m):
+        raise DDPError("DeviceProblem was compiled for n = %d, m = %d; the arrays have n = %d, m = %d" % (problem.n, problem.m, n, m))
 
 
 def _lims(lims):
@@ -330,12 +407,15 @@ def _check_problem(problem, n, m, N, B):
 
 
 # ------------------------------------------------------------------------------- forward_pass
-def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None):
+def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None):
     """Drop-in for ``forward_pass(traj_new,x0,u,x,α,f,costfun,lims,diff)`` (forward_pass.jl:9) with a
     registered ``problem`` standing in for the closures ``f``/``costfun``; ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
     ``traj_new`` may be an empty ``GaussianPolicy`` (then ``x`` is ignored, iLQG.jl:185).
     A vector ``α`` rolls all step sizes out concurrently (outputs get a trailing α axis).
+    A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in.
     Returns ``(xnew, unew, cnew)``."""
+    if isinstance(problem, DeviceProblem):
+        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params)
     h = handle or default_handle()
     u, x0 = _lib.f64(u), _lib.f64(x0)
     batched = u.ndim == 3
@@ -371,9 +451,12 @@ def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=Non
 
 
 # ------------------------------------------------------------------------------------------ df
-def df(problem, x, u, *, handle=None):
+def df(problem, x, u, *, handle=None, params=None):
     """The ``df`` closure of the registered families (STEP 1, iLQG.jl:225-229).  Returns
-    ``(fx,fu,fxx,fxu,fuu,cx,cu,cxx,cxu,cuu)`` like the reference (second-order terms are ``[]``)."""
+    ``(fx,fu,fxx,fxu,fuu,cx,cu,cxx,cxu,cuu)`` like the reference (second-order terms are ``[]``).
+    A ``DeviceProblem`` returns its ``derivatives``: ``cxx[n,n,N(,B)]`` ... (``[n,n(,B)]`` with ``const_hessian``)."""
+    if isinstance(problem, DeviceProblem):
+        return _user_df(problem, x, u, handle=handle, params=params)
     h = handle or default_handle()
     x, u = _lib.f64(x), _lib.f64(u)
     batched = u.ndim == 3
@@ -397,6 +480,93 @@ def df(problem, x, u, *, handle=None):
     return fx, fu, e, e, e, cx, cu, dp.Q, np.zeros((n, m)), dp.R
 
 
+def _user_batch(x_or_x0, u, problem, x0_has_time=False):
+    u = _lib.f64(u)
+    if u.ndim not in (2, 3):
+        raise DDPError("u should be (m, N) or (m, N, B)")
+    batched = u.ndim == 3
+    m, N = u.shape[:2]
+    B = u.shape[2] if batched else 1
+    n = np.shape(x_or_x0)[0]
+    _user_shapes(problem, n, m)
+    return u, batched, n, m, N, B
+
+
+def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None):
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x0, u, problem)
+    x0 = _lib.f64(x0)
+    if x0.shape != ((n, B) if batched else (n,)) and not (not batched and x0.shape == (n, 1)):
+        raise DDPError("x0 should be (n,) — (n, B) with a batched u")
+    if diff is not None and _diff_mask(diff, n) != problem.diff_mask:
+        raise DDPError("DeviceProblem: diff is compiled into the problem (DeviceProblem(..., diff=...))")
+    P, pb = problem._params(B, params)
+    alphas = np.atleast_1d(np.asarray(α, dtype=np.float64))
+    na = len(alphas)
+    if not 1 <= na <= 16:
+        raise DDPError("1 to 16 step sizes")
+    empty = traj_new is None or traj_new.isempty()
+    K = None if empty else _lib.f64(traj_new.K)
+    k = None if empty else _lib.f64(traj_new.k)
+    xx = None if empty else _lib.f64(x)
+    if not empty:
+        tb = (B,) if batched else ()
+        if K.shape != (m, n, N) + tb or k.shape != (m, N) + tb or xx.shape != (n, N) + tb:
+            raise DDPError("traj_new.K, traj_new.k, x should be (m,n,N), (m,N), (n,N) [+ batch axis]")
+    L = _lims(lims)
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    CL = problem.cost_len(N)
+    xnew = _lib.result_array((n, N, B, na)); unew = _lib.result_array((m, N, B, na))
+    cnew = _lib.result_array((CL, B, na)); csum = np.zeros((B, na), order="F")
+    up = problem._ptr(h)
+    _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
+                                                    _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
+                                                    _lib.ptr(cnew), _lib.ptr(csum)))
+    if not batched:
+        xnew, unew, cnew = xnew[:, :, 0], unew[:, :, 0], cnew[:, 0]
+    if np.ndim(α) == 0:
+        xnew, unew, cnew = xnew[..., 0], unew[..., 0], cnew[..., 0]
+    return xnew, unew, cnew
+
+
+def _user_df(problem, x, u, *, handle=None, params=None):
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x, u, problem)
+    x = _lib.f64(x)
+    if x.shape != ((n, N, B) if batched else (n, N)):
+        raise DDPError("x should be (n, N) — (n, N, B) with a batched u")
+    P, pb = problem._params(B, params)
+    ht = () if problem.const_hessian else (N,)
+    fx = _lib.result_array((n, n, N, B)); fu = _lib.result_array((n, m, N, B))
+    cx = _lib.result_array((n, N, B)); cu = _lib.result_array((m, N, B))
+    cxx = _lib.result_array((n, n) + ht + (B,)); cxu = _lib.result_array((n, m) + ht + (B,)); cuu = _lib.result_array((m, m) + ht + (B,))
+    up = problem._ptr(h)
+    _lib.check(_lib.lib().ddp_user_df_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u),
+                                          *map(_lib.ptr, (fx, fu, cx, cu, cxx, cxu, cuu))))
+    if not batched:
+        fx, fu, cx, cu, cxx, cxu, cuu = (a[..., 0] for a in (fx, fu, cx, cu, cxx, cxu, cuu))
+    e = np.zeros((0,))
+    return fx, fu, e, e, e, cx, cu, cxx, cxu, cuu
+
+
+def costfun(problem, x, u, *, handle=None, params=None):
+    """The ``costfun`` closure of a ``DeviceProblem`` on given trajectories: ``cost[CL(,B)]`` (CL = N, N+1 with ``terminal``)."""
+    if not isinstance(problem, DeviceProblem):
+        raise TypeError("costfun: a DeviceProblem is needed (the registered families evaluate their cost inside forward_pass)")
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x, u, problem)
+    x = _lib.f64(x)
+    if x.shape != ((n, N, B) if batched else (n, N)):
+        raise DDPError("x should be (n, N) — (n, N, B) with a batched u")
+    P, pb = problem._params(B, params)
+    cost = _lib.result_array((problem.cost_len(N), B))
+    csum = np.zeros(B)
+    _lib.check(_lib.lib().ddp_user_costfun_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost),
+                                               _lib.ptr(csum)))
+    return cost if batched else cost[:, 0]
+
+
 # ---------------------------------------------------------------------------------------- iLQG
 def print_timing(trace):
     """The timing summary of iLQG.jl:343-366 from the trace keys ``time_derivs``, ``time_backward``, ``time_forward``."""
@@ -418,7 +588,7 @@ STATUS = {1: "SUCCESS: gradient norm < tol_grad", 2: "SUCCESS: cost change < tol
 
 def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
          λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, verbosity=0, trace_cap=None, cost=None,
-         timing=True, diff_fun=None, handle=None):
+         timing=True, diff_fun=None, handle=None, params=None):
     """Drop-in for ``iLQG(f,costfun,df,x0,u0; lims, α, tol_fun, ...)`` (iLQG.jl:143-163) with a registered
     ``problem`` standing in for the three closures (``diff_fun``: ``None`` = ``-``, or a ``WrappedDiff``).  ``u0[m,N,B]`` / ``x0[n,B]`` solve a batch of
     independent problems, each with its own λ schedule, line search and termination.
@@ -431,8 +601,14 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     ``min(4 max_iter + 64, 4096, max(64, 256e6 / (56 B)))`` (136 rows at B = 32768), so that ``history[7, cap, B]`` stays under 256 MB.
     ``trace["trace_cap"]`` is the cap used and ``trace["truncated"]`` says, per trajectory, whether it took more iterations than rows
     were kept (its later rows are missing, ``stats`` / ``iter`` are complete).
-    Returns ``None`` when the initial control sequence diverges (iLQG.jl:205-210) in the unbatched case."""
+    Returns ``None`` when the initial control sequence diverges (iLQG.jl:205-210) in the unbatched case.
+    A ``DeviceProblem`` (the user's own closures as device source) takes ``params`` (default: its own); its ``diff`` is compiled in."""
     h = handle or default_handle()
+    user = isinstance(problem, DeviceProblem)
+    if user:
+        if np.ndim(u0) not in (2, 3):
+            raise DDPError("u0 should be (m, N) or (m, N, B)")
+        _user_shapes(problem, np.shape(x0)[0], np.shape(u0)[0])
     u0, x0 = _lib.f64(u0), _lib.f64(x0)
     batched = u0.ndim == 3
     m, N = u0.shape[:2]
@@ -448,8 +624,15 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
             raise ValueError("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")     # iLQG.jl:199
     if x0.shape != (((n, N) if prerolled else (n,)) + ((B,) if batched else ())):
         raise ValueError("x0 should be (n,) / pre-rolled (n, N) — with a batched u0: (n, B) / (n, N, B)")
-    _check_problem(problem, n, m, N, B)
-    dp = _DevProblem(problem, N, B, diff_fun)
+    if user:
+        P, pb = problem._params(B, params)
+        if diff_fun is not None and _diff_mask(diff_fun, n) != problem.diff_mask:
+            raise DDPError("DeviceProblem: diff_fun is compiled into the problem (DeviceProblem(..., diff=...))")
+        CL = problem.cost_len(N)
+    else:
+        _check_problem(problem, n, m, N, B)
+        dp = _DevProblem(problem, N, B, diff_fun)
+        CL = dp.cost_len
     o = _lib.ILQGOpts()
     _lib.lib().ddp_ilqg_default_opts(_C.byref(o))
     o.lambda_, o.dlambda, o.lambda_factor, o.lambda_max, o.lambda_min = λ, dλ, λfactor, λmax, λmin
@@ -461,7 +644,8 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     for i, a in enumerate(alphas):
         o.alpha[i] = a
     L = _lims(lims)
-    CL = dp.cost_len
+    if user and L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
     x = _lib.result_array((n, N, B)); u = _lib.result_array((m, N, B))
     K = _lib.result_array((m, n, N, B)); k = _lib.result_array((m, N, B)); Quu = _lib.result_array((m, m, N, B))
     Vx = _lib.result_array((n, N, B)); Vxx = _lib.result_array((n, n, N, B))
@@ -480,9 +664,14 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     t_start = _time.time()
     _lib.check(_lib.lib().ddp_ilqg_set_timing(h.raw, _lib.ptr(timing) if timing_on else None, tcap if timing_on else 0))
     try:
-        _lib.check(_lib.lib().ddp_ilqg_ex_f64(h.raw, _C.byref(dp.struct), _C.byref(o), _lib.ptr(x0), int(prerolled), _lib.ptr(u0),
-                                              _lib.ptr(c0), _lib.ptr(L), *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), cap,
-                                              _lib.ptr(tr7), _C.byref(git)))
+        if user:
+            _lib.check(_lib.lib().ddp_user_ilqg_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _C.byref(o), _lib.ptr(x0), int(prerolled),
+                                                    _lib.ptr(u0), _lib.ptr(c0), _lib.ptr(L), *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)),
+                                                    cap, _lib.ptr(tr7), _C.byref(git)))
+        else:
+            _lib.check(_lib.lib().ddp_ilqg_ex_f64(h.raw, _C.byref(dp.struct), _C.byref(o), _lib.ptr(x0), int(prerolled), _lib.ptr(u0),
+                                                  _lib.ptr(c0), _lib.ptr(L), *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), cap,
+                                                  _lib.ptr(tr7), _C.byref(git)))
     finally:
         _lib.lib().ddp_ilqg_set_timing(h.raw, None, 0)
     total_t = _time.time() - t_start

@@ -30,6 +30,9 @@ EXPORTS = [
     "ddp_kl_dual_begin_f64_dev", "ddp_kl_dual_retry_f64_dev", "ddp_kl_dual_update_f64_dev",
     "ddp_ilqgkl_default_opts", "ddp_ilqgkl_f64_dev", "ddp_ilqgkl_f64",
     "ddp_comm_rccl_info", "ddp_comm_unique_id", "ddp_comm_create", "ddp_comm_destroy", "ddp_allreduce_stats_f64_dev",
+    "ddp_user_check", "ddp_user_compile_log", "ddp_user_create", "ddp_user_destroy", "ddp_user_df_f64_dev", "ddp_user_df_f64",
+    "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
+    "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64",
 ]
 
 
@@ -146,9 +149,13 @@ def lib():
         L.ddp_stream.argtypes = [vp]
         L.ddp_last_kernel.restype = C.c_char_p
         L.ddp_last_kernel.argtypes = [vp, C.c_int]
+        L.ddp_user_compile_log.restype = C.c_char_p
+        L.ddp_user_check.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
+        L.ddp_user_create.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.ddp_user_destroy.argtypes = [vp]
         for name in EXPORTS:
             fn = getattr(L, name)
-            if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel"):
+            if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):
                 fn.restype = C.c_int
         L.ddp_ilqg_default_opts.restype = None
         L.ddp_ilqgkl_default_opts.restype = None
@@ -200,7 +207,7 @@ class Handle:
         return self._h
 
     def last_kernel(self, which=0):
-        """kernel of the last back_pass (0) / forward_pass (1) dispatch (ddp_last_kernel)"""
+        """kernel of the last back_pass (0) / forward_pass (1) dispatch, or user-problem derivative (2) / cost (3) kernel (ddp_last_kernel)"""
         return lib().ddp_last_kernel(self._h, int(which)).decode()
 
     def sh_timeouts(self):

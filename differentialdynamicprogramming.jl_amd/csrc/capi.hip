@@ -43,7 +43,7 @@ int ddp_reload_env(ddp_handle h)
 
 const char *ddp_last_kernel(ddp_handle h, int which)
 {
-    if (!h || which < 0 || which > 1 || !h->last_kernel[which]) return "";
+    if (!h || which < 0 || which > 3 || !h->last_kernel[which]) return "";
     return h->last_kernel[which];
 }
 
@@ -101,6 +101,7 @@ int ddp_destroy(ddp_handle h)
     if (h->sh) hipFree(h->sh);
     if (h->sched_aux) { hipStreamDestroy(h->sched_aux); hipEventDestroy(h->sched_ev[0]); hipEventDestroy(h->sched_ev[1]); }
     if (h->tev_ok) for (int e = 0; e < 4; ++e) hipEventDestroy(h->tev[e]);
+    ddp_user_release(h);
     if (h->owns_stream) hipStreamDestroy(h->stream);
     delete h;
     return 0;

@@ -36,12 +36,13 @@ struct ddp_handle_s {
     hipEvent_t   sched_ev[2];
     char         envv[ENV_COUNT][24];
     bool         envset[ENV_COUNT];
-    const char  *last_kernel[2];  // what the last backward / forward dispatch launched (ddp_last_kernel)
+    const char  *last_kernel[4];  // what the last backward / forward / user-derivative / user-cost dispatch launched (ddp_last_kernel)
     void        *sink;            // 4 KB of device memory that masked-out lanes may write (stores without an exec-mask branch)
     double      *timing;          // ddp_ilqg_set_timing: host buffer [3, timing_cap] or NULL
     int          timing_cap;
     hipEvent_t   tev[4];          // created on first use
     bool         tev_ok;
+    void        *user_cache;      // user_problem.hip: the modules of the user problems compiled for this handle (unloaded by ddp_destroy)
 };
 
 void ddp_set_error(const char *fmt, ...);
@@ -83,6 +84,31 @@ int ddp_check_cost_diag(ddp_handle h, const ddp_problem *p);
 // device-side test is skipped for this handle (the staging addresses are recycled from call to call: a pointer-keyed verdict would go stale)
 int ddp_check_cost_diag_host(const ddp_problem *p);
 struct DiagVerified { ddp_handle h; explicit DiagVerified(ddp_handle h_) : h(h_) { ++h->diag_skip; } ~DiagVerified() { --h->diag_skip; } };
+
+// user_problem.hip: unloads the handle's user-problem modules (ddp_destroy)
+void ddp_user_release(ddp_handle h);
+
+// A problem family the iLQG driver (ilqg.hip) runs besides the registered ddp_problem kinds: the user's compiled problems
+// (user_problem.hip).  `map` (may be NULL) is the slot -> trajectory map of a compacted working set; the family reads what it keeps
+// per trajectory (its parameters) through it.  Derivatives are time-varying and per trajectory (fx[n,n,N,B] ...); the cost Hessians
+// too, or, with const_hessian, one set per trajectory written by hessians() (cxx[n,n,B] ...).
+struct ddp_family {
+    int n, m, N, B, CL;
+    bool const_hessian;
+    virtual ~ddp_family() {}
+    virtual int df(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx,
+                   double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu) const = 0;
+    virtual int hessians(ddp_handle h, int B, const int32_t *map, double *cxx, double *cxu, double *cuu) const = 0;
+    virtual int rollout(ddp_handle h, int B, const int32_t *map, const double *K, const double *k, const double *x0, const double *u,
+                        const double *x, const double *alpha, int nalpha, const double *lims, const int32_t *active, double *xnew,
+                        double *unew, double *cnew, double *csum) const = 0;
+    virtual int costfun(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *cost,
+                        double *csum) const = 0;
+};
+// the device-resident iLQG of ilqg.hip for such a family (arguments as ddp_ilqg_ex_f64_dev)
+int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *o, const double *x0, int x0_prerolled, const double *u0,
+                        const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
+                        double *Vxx, double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
 
 // kernel launchers (each in its own .hip)
 int ddp_launch_back_pass(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,

@@ -481,7 +481,7 @@ void ddp_ilqg_default_opts(ddp_ilqg_opts *o)
 static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo, const double *x0, const double *u0,
                      const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                      double *Vxx, double *cost, double *stats, int trace_cap, double *trace_cost, int *global_iters,
-                     bool prerolled, const double *cost0, double *trace7 = nullptr)
+                     bool prerolled, const double *cost0, double *trace7 = nullptr, const ddp_family *fam = nullptr)
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && p && x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg: null argument");
@@ -489,24 +489,29 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     if (!oo) { ddp_ilqg_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->n_alpha >= 1 && oo->n_alpha <= 16, "ilqg: n_alpha=%d out of [1,16]", oo->n_alpha);
     DDP_CHECK(x0 != x && u0 != u, "ilqg: x0/u0 must not alias the outputs x/u (the outputs are cleared before the initial rollout)");
-    const size_t n = p->n, m = p->m, N = p->N, B = p->B, na = oo->n_alpha, CL = ddp_cost_len(p);
+    const size_t n = p->n, m = p->m, N = p->N, B = p->B, na = oo->n_alpha, CL = fam ? fam->CL : ddp_cost_len(p);
     const bool pend = p->kind == DDP_PROBLEM_PENDCART;
+    // a user family (fam): time-varying per-trajectory fx, fu like the pendulum, and cost Hessians of its own (per step, or once per
+    // trajectory with const_hessian)
+    const bool own_fx = pend || fam, chess = fam && fam->const_hessian;
 
     // ---- workspace (device): derivatives, candidates, scalar state
     size_t bytes = 0;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t s_cx = al(n * N * B * 8), s_cu = al(m * N * B * 8), s_fx = pend ? al(n * n * N * B * 8) : 0,
-                 s_fu = pend ? al(n * m * N * B * 8) : 0, s_xn = al(n * N * B * na * 8), s_un = al(m * N * B * na * 8),
+    const size_t s_cx = al(n * N * B * 8), s_cu = al(m * N * B * 8), s_fx = own_fx ? al(n * n * N * B * 8) : 0,
+                 s_fu = own_fx ? al(n * m * N * B * 8) : 0, hT = chess ? 1 : N, s_hxx = fam ? al(n * n * hT * B * 8) : 0,
+                 s_hxu = fam ? al(n * m * hT * B * 8) : 0, s_huu = fam ? al(m * m * hT * B * 8) : 0, s_xn = al(n * N * B * na * 8), s_un = al(m * N * B * na * 8),
                  s_cn = al(CL * B * na * 8), s_cs = al(B * na * 8), s_dV = al(2 * B * 8), s_div = al(B * 4),
                  s_cxu = al(n * m * 8), s_us = al(m * N * B * 8), s_d = al(B * 8), s_i = al(B * 4), s_x0 = al(n * B * 8);
-    bytes = s_cx + s_cu + s_fx + s_fu + s_xn + s_un + s_cn + s_cs + s_dV + s_div + s_cxu + s_us + 4 * s_d + 10 * s_i + 256 + s_x0 + 2 * s_i;
+    bytes = s_cx + s_cu + s_fx + s_fu + s_hxx + s_hxu + s_huu + s_xn + s_un + s_cn + s_cs + s_dV + s_div + s_cxu + s_us + 4 * s_d + 10 * s_i + 256 + s_x0 + 2 * s_i;
     void *base;
     int rc = ddp_scratch(h, bytes, &base);
     if (rc) return rc;
     char *pp = (char *)base;
     auto take = [&](size_t b) { void *r = pp; pp += b; return r; };
-    double *cx = (double *)take(s_cx), *cu = (double *)take(s_cu), *fxw = pend ? (double *)take(s_fx) : nullptr,
-           *fuw = pend ? (double *)take(s_fu) : nullptr, *xn = (double *)take(s_xn), *un = (double *)take(s_un),
+    double *cx = (double *)take(s_cx), *cu = (double *)take(s_cu), *fxw = own_fx ? (double *)take(s_fx) : nullptr,
+           *fuw = own_fx ? (double *)take(s_fu) : nullptr, *hxx = fam ? (double *)take(s_hxx) : nullptr,
+           *hxu = fam ? (double *)take(s_hxu) : nullptr, *huu = fam ? (double *)take(s_huu) : nullptr, *xn = (double *)take(s_xn), *un = (double *)take(s_un),
            *cn = (double *)take(s_cn), *cs = (double *)take(s_cs), *dV = (double *)take(s_dV);
     int32_t *div = (int32_t *)take(s_div);
     double *cxu = (double *)take(s_cxu), *us = (double *)take(s_us);
@@ -544,7 +549,10 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     if (prerolled) {                                     // iLQG.jl:193-197: x = x0, cost given or costfun(x, u); no divergence test
         hipLaunchKernelGGL(preroll_init_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, x0, u0, cost0, s,
                            x, u, cost, x0c);
-        if (!cost0)
+        if (!cost0 && fam) {
+            rc = fam->costfun(h, (int)B, nullptr, x, u, nullptr, cost, s.csum);
+            if (rc) return rc;
+        } else if (!cost0)
             hipLaunchKernelGGL(costfun_kernel, dim3((unsigned)B), dim3(64), 0, st, p->kind, (int)n, (int)m, (int)N, (int)CL, p->Q, p->R,
                                p->goal[0], p->goal[1], p->goal[2], p->goal[3], x, u, (const int32_t *)nullptr, cost, s.csum);
         x0 = x0c;
@@ -553,7 +561,8 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
         const size_t tot = m * N * B;
         hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m * N, (int)B, oo->alpha[ai], u0,
                            s.div0, us);
-        rc = ddp_forward_pass_f64_dev(h, p, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, xn, un, cn, cs);
+        rc = fam ? fam->rollout(h, (int)B, nullptr, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, xn, un, cn, cs)
+                 : ddp_forward_pass_f64_dev(h, p, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, xn, un, cn, cs);
         if (rc) return rc;
         hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, xn, un, cn, cs, s,
                            x, u, cost);
@@ -574,9 +583,14 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
 
     ddp_bp_desc d;
     d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B;
-    d.fx_tv = pend ? 1 : p->dyn_tv; d.fx_batched = pend ? 1 : p->dyn_batched;
-    d.cost_tv = 0; d.cost_batched = 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
-    const double *fx = pend ? fxw : p->A, *fu = pend ? fuw : p->Bm;
+    d.fx_tv = own_fx ? 1 : p->dyn_tv; d.fx_batched = own_fx ? 1 : p->dyn_batched;
+    d.cost_tv = (fam && !chess) ? 1 : 0; d.cost_batched = fam ? 1 : 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
+    const double *fx = own_fx ? fxw : p->A, *fu = own_fx ? fuw : p->Bm;
+    const double *cxx = fam ? hxx : p->Q, *cxu_ = fam ? hxu : cxu, *cuu = fam ? huu : p->R;
+    if (chess) {                                           // the constant cost Hessians: once per trajectory (again after a compaction)
+        rc = fam->hessians(h, (int)B, nullptr, hxx, hxu, huu);
+        if (rc) return rc;
+    }
 
     // ---- the working set: the caller's arrays until the first compaction
     WorkSet user = {x, u, cost, K, k, Quu, Vx, Vxx, const_cast<double *>(x0), s, nullptr};
@@ -660,13 +674,19 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
             ws = nw;
             Bw = R;
             pw.B = (int)R; d.B = (int)R;
+            if (chess) {
+                rc = fam->hessians(h, (int)R, ws.map, hxx, hxu, huu);
+                if (rc) return rc;
+            }
         }
         polled = false;
         if (timed) DDP_HIP(hipEventRecord(h->tev[0], st));
-        rc = ddp_df_f64_dev(h, &pw, ws.x, ws.u, ws.s.dodf, cx, cu, fxw, fuw);                                  // STEP 1
+        rc = fam ? fam->df(h, (int)Bw, ws.map, ws.x, ws.u, ws.s.dodf, fxw, fuw, cx, cu, chess ? nullptr : hxx, chess ? nullptr : hxu,
+                           chess ? nullptr : huu)
+                 : ddp_df_f64_dev(h, &pw, ws.x, ws.u, ws.s.dodf, cx, cu, fxw, fuw);                              // STEP 1
         if (rc) return rc;
         if (timed) DDP_HIP(hipEventRecord(h->tev[1], st));
-        rc = ddp_launch_back_pass(h, &d, cx, cu, p->Q, cxu, p->R, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx,
+        rc = ddp_launch_back_pass(h, &d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx,
                                   dV, div);                                                                  // STEP 2
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, ws.s);
@@ -683,8 +703,10 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
                                    gi == 1 ? (const int32_t *)nullptr : (const int32_t *)more, mk);
                 mask = mk;
             }
-            rc = ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * Bw * a0,
-                                          un + m * N * Bw * a0, cn + CL * Bw * a0, cs + Bw * a0);
+            rc = fam ? fam->rollout(h, (int)Bw, ws.map, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask,
+                                    xn + n * N * Bw * a0, un + m * N * Bw * a0, cn + CL * Bw * a0, cs + Bw * a0)
+                     : ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask,
+                                                xn + n * N * Bw * a0, un + m * N * Bw * a0, cn + CL * Bw * a0, cs + Bw * a0);
             if (rc) return rc;
         }
         if (timed) DDP_HIP(hipEventRecord(h->tev[3], st));
@@ -721,6 +743,22 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     if (global_iters) *global_iters = git;
     return 0;
 }
+
+}   // extern "C"
+
+// the same loop for a family of ddp_family (user_problem.hip): a problem struct that carries the sizes only
+int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *oo, const double *x0, int x0_prerolled, const double *u0,
+                        const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
+                        double *Vxx, double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
+{
+    DDP_CHECK(f, "ilqg: null family");
+    ddp_problem pf = {};
+    pf.kind = -1; pf.n = f->n; pf.m = f->m; pf.N = f->N; pf.B = f->B;
+    return ilqg_impl(h, &pf, oo, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, nullptr, global_iters, x0_prerolled != 0,
+                     x0_prerolled ? cost0 : nullptr, trace7, f);
+}
+
+extern "C" {
 
 int ddp_ilqg_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo, const double *x0, const double *u0,
                      const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,

@@ -1,0 +1,534 @@
+// user_problem.hip — user-defined problems: the user's f / costfun / df as HIP device source, compiled at run time for gfx950.
+//
+// The reference's iLQG(f, costfun, df, x0, u0; ...) takes the user's own closures.  Here the user writes four device functions
+// (include/ddp_amd.h lists the contract); the library wraps them in its kernel templates (user_problem_kernels.h), compiles the
+// program with hiprtc once per (source, n, m, nparam, flags, diff_wrap) and handle, and loads it on the handle's device.  The
+// device-resident iLQG of ilqg.hip runs such a problem through its ddp_family interface, so the whole loop — statuses, trace keys,
+// timing, pre-rolled starts, compaction — is the one of the registered families.
+// hiprtc is loaded at first use (dlopen), like RCCL in comm.hip: the library has no link-time dependency on it.
+#include <dlfcn.h>
+#include <string.h>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "ddp_internal.h"
+#include "user_problem_kernels.h"
+
+DDP_USER_ABI
+
+namespace {
+
+typedef void *rtc_program;
+struct Hiprtc {
+    void *lib = nullptr;
+    int (*CreateProgram)(rtc_program *, const char *, const char *, int, const char *const *, const char *const *) = nullptr;
+    int (*CompileProgram)(rtc_program, int, const char *const *) = nullptr;
+    int (*GetProgramLogSize)(rtc_program, size_t *) = nullptr;
+    int (*GetProgramLog)(rtc_program, char *) = nullptr;
+    int (*GetCodeSize)(rtc_program, size_t *) = nullptr;
+    int (*GetCode)(rtc_program, char *) = nullptr;
+    int (*DestroyProgram)(rtc_program *) = nullptr;
+    const char *(*GetErrorString)(int) = nullptr;
+};
+
+Hiprtc *hiprtc()
+{
+    static Hiprtc r;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const char *names[] = {"libhiprtc.so", "libhiprtc.so.7", "libhiprtc.so.6", "/opt/rocm/lib/libhiprtc.so"};
+        for (const char *name : names) {
+            r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+            if (r.lib) break;
+        }
+        if (!r.lib) return;
+        r.CreateProgram = (decltype(r.CreateProgram))dlsym(r.lib, "hiprtcCreateProgram");
+        r.CompileProgram = (decltype(r.CompileProgram))dlsym(r.lib, "hiprtcCompileProgram");
+        r.GetProgramLogSize = (decltype(r.GetProgramLogSize))dlsym(r.lib, "hiprtcGetProgramLogSize");
+        r.GetProgramLog = (decltype(r.GetProgramLog))dlsym(r.lib, "hiprtcGetProgramLog");
+        r.GetCodeSize = (decltype(r.GetCodeSize))dlsym(r.lib, "hiprtcGetCodeSize");
+        r.GetCode = (decltype(r.GetCode))dlsym(r.lib, "hiprtcGetCode");
+        r.DestroyProgram = (decltype(r.DestroyProgram))dlsym(r.lib, "hiprtcDestroyProgram");
+        r.GetErrorString = (decltype(r.GetErrorString))dlsym(r.lib, "hiprtcGetErrorString");
+    });
+    return (r.lib && r.CreateProgram && r.CompileProgram && r.GetProgramLogSize && r.GetProgramLog && r.GetCodeSize && r.GetCode &&
+            r.DestroyProgram) ? &r : nullptr;
+}
+
+std::mutex g_log_mu;
+std::string g_log;                                          // log of the last compile (ddp_user_compile_log)
+
+// LDS budgets of the generated kernels (per 64-lane work-group): the rollout keeps several waves per CU (its time loop is a
+// dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
+constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024;
+
+struct Layout { int chunk, rlanes, dflanes; };
+
+// chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit
+Layout layout_of(int n, int m, int flags)
+{
+    Layout L;
+    const int ps = 2 * m + m * n + n;                            // DDP_PS
+    L.rlanes = 64;
+    L.chunk = (ROLL_LDS / 8 / 64 - 1) / ps;
+    if (L.chunk > 16) L.chunk = 16;
+    if (L.chunk < 1) {                                           // large n·m: one step per chunk, fewer rollouts per work-group
+        L.chunk = 1;
+        while (L.rlanes > 1 && (size_t)L.rlanes * (ps | 1) * 8 > (size_t)MAX_LDS) L.rlanes /= 2;
+    }
+    const int dt = n * n + n * m + n + m + ((flags & DDP_USER_CONST_HESSIAN) ? 0 : n * n + n * m + m * m);
+    L.dflanes = 64;
+    while (L.dflanes > 1 && (size_t)L.dflanes * (dt | 1) * 8 > (size_t)DF_LDS) L.dflanes /= 2;
+    return L;
+}
+
+// `name` appears in `src` as a whole identifier (outside // and /* */ comments)
+bool has_identifier(const std::string &src, const char *name)
+{
+    const size_t ln = strlen(name);
+    auto ident = [](char c) { return c == '_' || (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); };
+    for (size_t i = 0; i < src.size();) {
+        if (src.compare(i, 2, "//") == 0) { i = src.find('\n', i); if (i == std::string::npos) return false; continue; }
+        if (src.compare(i, 2, "/*") == 0) { i = src.find("*/", i + 2); if (i == std::string::npos) return false; i += 2; continue; }
+        if (src.compare(i, ln, name) == 0 && (i == 0 || !ident(src[i - 1])) && (i + ln >= src.size() || !ident(src[i + ln]))) return true;
+        ++i;
+    }
+    return false;
+}
+
+int validate(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
+{
+    DDP_CHECK(source, "user problem: null source");
+    DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER, "user problem: n = %d out of [1, %d] (DDP_MAX_N_USER)", n, DDP_MAX_N_USER);
+    DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M)", m, DDP_MAX_M);
+    DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
+              DDP_USER_MAX_NPARAM);
+    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN)) == 0, "user problem: unknown flags 0x%x", flags);
+    DDP_CHECK(n >= 32 || (wrap >> n) == 0, "user problem: diff_wrap = 0x%x names coordinates at or above n = %d", wrap, n);
+    const std::string src(source);
+    const char *need[] = {"dynamics", "stage_cost", "derivatives"};
+    for (const char *f : need) DDP_CHECK(has_identifier(src, f), "user problem: the source defines no `%s` (the contract of ddp_amd.h)", f);
+    if (flags & DDP_USER_TERMINAL)
+        DDP_CHECK(has_identifier(src, "terminal_cost"), "user problem: DDP_USER_TERMINAL is set but the source defines no `terminal_cost`");
+    if (flags & DDP_USER_CONST_HESSIAN)
+        DDP_CHECK(has_identifier(src, "cost_hessians"), "user problem: DDP_USER_CONST_HESSIAN is set but the source defines no `cost_hessians`");
+    const Layout L = layout_of(n, m, flags);
+    const int ps = 2 * m + m * n + n;
+    DDP_CHECK((size_t)L.rlanes * ((L.chunk * ps) | 1) * 8 <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the rollout's LDS", n, m);
+    return 0;
+}
+
+std::string program_text(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
+{
+    const Layout L = layout_of(n, m, flags);
+    char head[512];
+    snprintf(head, sizeof head,
+             "#define DDP_N %d\n#define DDP_M %d\n#define DDP_NP %d\n#define DDP_TERMINAL %d\n#define DDP_CONST_HESSIAN %d\n"
+             "#define DDP_WRAP 0x%xu\n#define DDP_CHUNK %d\n#define DDP_RLANES %d\n#define DDP_DFLANES %d\n",
+             n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes);
+    std::string s(head);
+    s += "#line 1 \"user_source\"\n";
+    s += source;
+    s += "\n#line 1 \"ddp_user_kernels\"\n";
+    s += DDP_USER_ABI_TEXT;
+    s += "\n";
+    s += kUserKernels;
+    return s;
+}
+
+// hiprtc: program text -> gfx950 code object; the log goes to g_log
+int compile(const char *source, int n, int m, int nparam, int flags, unsigned wrap, const char *extra, std::vector<char> *code)
+{
+    int rc = validate(source, n, m, nparam, flags, wrap);
+    if (rc) return rc;
+    Hiprtc *R = hiprtc();
+    DDP_CHECK(R, "user problem: hiprtc (libhiprtc.so) could not be loaded");
+    const std::string text = program_text(source, n, m, nparam, flags, wrap);
+    std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
+    if (extra) {
+        const std::string e(extra);
+        size_t i = 0;
+        while (i < e.size()) {
+            while (i < e.size() && e[i] == ' ') ++i;
+            size_t j = i;
+            while (j < e.size() && e[j] != ' ') ++j;
+            if (j > i) opts.push_back(e.substr(i, j - i));
+            i = j;
+        }
+    }
+    std::vector<const char *> argv;
+    for (auto &o : opts) argv.push_back(o.c_str());
+    rtc_program prog = nullptr;
+    int e = R->CreateProgram(&prog, text.c_str(), "ddp_user_problem.hip", 0, nullptr, nullptr);
+    DDP_CHECK(e == 0, "user problem: hiprtcCreateProgram failed (%d)", e);
+    e = R->CompileProgram(prog, (int)argv.size(), argv.data());
+    size_t ls = 0;
+    std::string log;
+    if (R->GetProgramLogSize(prog, &ls) == 0 && ls > 1) {
+        log.resize(ls);
+        if (R->GetProgramLog(prog, &log[0]) != 0) log.clear();
+        while (!log.empty() && log.back() == '\0') log.pop_back();
+    }
+    {
+        std::lock_guard<std::mutex> g(g_log_mu);
+        g_log = log;
+    }
+    if (e != 0) {
+        R->DestroyProgram(&prog);
+        // the first error line of the log names the cause (user_source:LINE:COL: error: ...)
+        std::string first = log;
+        const size_t at = log.find("error");
+        if (at != std::string::npos) {
+            const size_t b = log.rfind('\n', at), en = log.find('\n', at);
+            first = log.substr(b == std::string::npos ? 0 : b + 1, en == std::string::npos ? std::string::npos : en - (b == std::string::npos ? 0 : b + 1));
+        }
+        ddp_set_error("user problem: compilation failed (%s): %s", R->GetErrorString ? R->GetErrorString(e) : "hiprtc error", first.c_str());
+        return -4;
+    }
+    size_t cs = 0;
+    if (R->GetCodeSize(prog, &cs) != 0 || cs == 0) { R->DestroyProgram(&prog); ddp_set_error("user problem: hiprtc returned no code"); return -4; }
+    code->resize(cs);
+    e = R->GetCode(prog, code->data());
+    R->DestroyProgram(&prog);
+    DDP_CHECK(e == 0, "user problem: hiprtcGetCode failed (%d)", e);
+    return 0;
+}
+
+struct Module {
+    hipModule_t mod = nullptr;
+    hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr;
+    Layout L{};
+};
+struct Cache { std::map<std::string, Module> mods; };
+
+}   // namespace
+
+struct UserProblem final : ddp_family {
+    ddp_handle h;
+    int nparam, flags;
+    unsigned wrap;
+    const Module *mod;
+    // per call (ddp_user_ilqg_*): the parameters
+    const double *params = nullptr;
+    int params_batched = 0;
+
+    int df(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx, double *fu,
+           double *cx, double *cu, double *cxx, double *cxu, double *cuu) const override
+    {
+        UserDfArgs a;
+        a.N = N; a.B = Bc; a.params_batched = params_batched; a.pad_ = 0;
+        a.params = params; a.x = x; a.u = u; a.active = active; a.map = map;
+        a.fx = fx; a.fu = fu; a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu;
+        void *args[] = {&a};
+        const long R = (long)N * Bc;
+        DDP_HIP(hipModuleLaunchKernel(mod->df, (unsigned)((R + mod->L.dflanes - 1) / mod->L.dflanes), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
+        hh->last_kernel[2] = "ddp_user_df";
+        return 0;
+    }
+    int hessians(ddp_handle hh, int Bc, const int32_t *map, double *cxx, double *cxu, double *cuu) const override
+    {
+        DDP_CHECK(mod->hess, "user problem: compiled without DDP_USER_CONST_HESSIAN");
+        UserHessArgs a;
+        a.B = Bc; a.params_batched = params_batched; a.params = params; a.map = map; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu;
+        void *args[] = {&a};
+        DDP_HIP(hipModuleLaunchKernel(mod->hess, (unsigned)((Bc + 63) / 64), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
+        hh->last_kernel[2] = "ddp_user_hessians";
+        return 0;
+    }
+    int rollout(ddp_handle hh, int Bc, const int32_t *map, const double *K, const double *k, const double *x0, const double *u, const double *x,
+                const double *alpha, int nalpha, const double *lims, const int32_t *active, double *xnew, double *unew, double *cnew,
+                double *csum) const override
+    {
+        DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
+        DDP_CHECK((K == nullptr) == (k == nullptr), "forward_pass: K and k must both be given or both NULL");
+        DDP_CHECK(!K || x, "forward_pass: a non-empty policy needs the nominal trajectory x");
+        UserRollArgs a;
+        a.N = N; a.B = Bc; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr; a.params_batched = params_batched;
+        a.params = params; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active; a.map = map;
+        a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum;
+        for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
+        void *args[] = {&a};
+        const long total = (long)Bc * nalpha;
+        DDP_HIP(hipModuleLaunchKernel(mod->roll, (unsigned)((total + mod->L.rlanes - 1) / mod->L.rlanes), 1, 1, 64, 1, 1, 0, hh->stream, args,
+                                      nullptr));
+        hh->last_kernel[1] = "ddp_user_rollout";
+        return 0;
+    }
+    int costfun(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *cost,
+                double *csum) const override
+    {
+        UserCostArgs a;
+        a.N = N; a.B = Bc; a.params_batched = params_batched; a.pad_ = 0;
+        a.params = params; a.x = x; a.u = u; a.active = active; a.map = map; a.cost = cost; a.csum = csum;
+        void *args[] = {&a};
+        DDP_HIP(hipModuleLaunchKernel(mod->cost, (unsigned)Bc, 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
+        hh->last_kernel[3] = "ddp_user_cost";
+        return 0;
+    }
+};
+
+void ddp_user_release(ddp_handle h)
+{
+    if (!h || !h->user_cache) return;
+    Cache *c = (Cache *)h->user_cache;
+    for (auto &kv : c->mods)
+        if (kv.second.mod) hipModuleUnload(kv.second.mod);
+    delete c;
+    h->user_cache = nullptr;
+}
+
+namespace {
+
+UserProblem *as_problem(ddp_handle h, void *up)
+{
+    UserProblem *P = (UserProblem *)up;
+    if (!P) { ddp_set_error("user problem: null problem"); return nullptr; }
+    if (P->h != h) { ddp_set_error("user problem: used with a handle other than the one it was created on"); return nullptr; }
+    return P;
+}
+
+// sizes and parameters of one call
+int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
+{
+    DDP_CHECK(N >= 1 && B >= 1, "user problem: N = %d, B = %d (both >= 1)", N, B);
+    DDP_CHECK(params_batched == 0 || params_batched == 1, "user problem: params_batched = %d (0 or 1)", params_batched);
+    DDP_CHECK(P->nparam == 0 || params, "user problem: nparam = %d but params is NULL", P->nparam);
+    P->N = N; P->B = B; P->CL = (P->flags & DDP_USER_TERMINAL) ? N + 1 : N;
+    P->params = P->nparam ? params : nullptr; P->params_batched = params_batched;
+    return 0;
+}
+
+// host-pointer flavours: device copies of the inputs, the _dev entry, copies of the outputs back
+struct Staging {
+    ddp_handle h;
+    struct Buf { void *d; void *hdst; size_t bytes; };
+    std::vector<Buf> bufs;
+    bool failed = false;
+    explicit Staging(ddp_handle h_) : h(h_) {}
+    ~Staging() { hipStreamSynchronize(h->stream); for (auto &b : bufs) hipFree(b.d); }
+    double *in(const double *src, size_t n) { return src ? (double *)put(src, nullptr, n * 8) : nullptr; }
+    double *out(double *dst, size_t n) { return dst ? (double *)put(nullptr, dst, n * 8) : nullptr; }
+    void *put(const void *src, void *dst, size_t bytes)
+    {
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) { failed = true; return nullptr; }
+        if (src && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) failed = true;
+        bufs.push_back({d, dst, bytes});
+        return d;
+    }
+    int finish(int rc)
+    {
+        if (!rc)
+            for (auto &b : bufs)
+                if (b.hdst && hipMemcpyAsync(b.hdst, b.d, b.bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = -2;
+        if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { ddp_set_error("user problem: stream synchronisation failed"); rc = -2; }
+        return rc;
+    }
+};
+#define DDP_STAGED(S)                                                                                  \
+    do {                                                                                               \
+        if ((S).failed) { ddp_set_error("user problem: device allocation / upload failed"); return -2; } \
+    } while (0)
+
+}   // namespace
+
+extern "C" {
+
+int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options)
+{
+    std::vector<char> code;
+    return compile(source, n, m, nparam, flags, 0u, extra_options, &code);
+}
+
+const char *ddp_user_compile_log(void)
+{
+    static thread_local std::string copy;
+    std::lock_guard<std::mutex> g(g_log_mu);
+    copy = g_log;
+    return copy.c_str();
+}
+
+int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out)
+{
+    DDP_DEVICE(h);
+    DDP_CHECK(out, "user problem: null output");
+    *out = nullptr;
+    const unsigned wrap = (unsigned)diff_wrap;
+    int rc = validate(source, n, m, nparam, flags, wrap);
+    if (rc) return rc;
+    char key_head[96];
+    snprintf(key_head, sizeof key_head, "%d,%d,%d,%d,%x\n", n, m, nparam, flags, wrap);
+    const std::string key = std::string(key_head) + source;
+    if (!h->user_cache) h->user_cache = new Cache();
+    Cache *c = (Cache *)h->user_cache;
+    auto it = c->mods.find(key);
+    if (it == c->mods.end()) {
+        std::vector<char> code;
+        rc = compile(source, n, m, nparam, flags, wrap, nullptr, &code);
+        if (rc) return rc;
+        Module M;
+        M.L = layout_of(n, m, flags);
+        DDP_HIP(hipModuleLoadData(&M.mod, code.data()));
+        const bool ok = hipModuleGetFunction(&M.roll, M.mod, "ddp_user_rollout") == hipSuccess &&
+                        hipModuleGetFunction(&M.df, M.mod, "ddp_user_df") == hipSuccess &&
+                        hipModuleGetFunction(&M.cost, M.mod, "ddp_user_cost") == hipSuccess &&
+                        (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess);
+        if (!ok) {
+            hipModuleUnload(M.mod);
+            ddp_set_error("user problem: a kernel of the compiled program is missing");
+            return -4;
+        }
+        it = c->mods.emplace(key, M).first;
+    }
+    UserProblem *P = new UserProblem();
+    P->h = h; P->n = n; P->m = m; P->N = 0; P->B = 0; P->CL = 0; P->const_hessian = (flags & DDP_USER_CONST_HESSIAN) != 0;
+    P->nparam = nparam; P->flags = flags; P->wrap = wrap; P->mod = &it->second;
+    *out = P;
+    return 0;
+}
+
+int ddp_user_destroy(void *up)
+{
+    delete (UserProblem *)up;
+    return 0;
+}
+
+int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                        const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
+    rc = P->df(h, B, nullptr, x, u, active, fx, fu, cx, cu, P->const_hessian ? nullptr : cxx, P->const_hessian ? nullptr : cxu,
+               P->const_hessian ? nullptr : cuu);
+    if (rc) return rc;
+    if (P->const_hessian && cxx && cxu && cuu) return P->hessians(h, B, nullptr, cxx, cxu, cuu);
+    return 0;
+}
+
+int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                    double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, HT = P->const_hessian ? (size_t)B : T;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T);
+    double *dfx = S.out(fx, n * n * T), *dfu = S.out(fu, n * m * T), *dcx = S.out(cx, n * T), *dcu = S.out(cu, m * T),
+           *dxx = S.out(cxx, n * n * HT), *dxu = S.out(cxu, n * m * HT), *duu = S.out(cuu, m * m * HT);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_df_f64_dev(h, up, N, B, dp, params_batched, dx, du, nullptr, dfx, dfu, dcx, dcu, dxx, dxu, duu));
+}
+
+int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                                  const double *K, const double *k, const double *x0, const double *u, const double *x,
+                                  const double *alpha, int nalpha, const double *lims, const int32_t *active,
+                                  double *xnew, double *unew, double *cnew, double *csum)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && u && alpha && xnew && unew && cnew && csum, "forward_pass: null argument");
+    return P->rollout(h, B, nullptr, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
+}
+
+int ddp_user_forward_pass_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                              const double *K, const double *k, const double *x0, const double *u, const double *x,
+                              const double *alpha, int nalpha, const double *lims,
+                              double *xnew, double *unew, double *cnew, double *csum)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && u && alpha && xnew && unew && cnew && csum, "forward_pass: null argument");
+    DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, na = nalpha;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dK = S.in(K, m * n * T), *dk = S.in(k, m * T),
+           *dx0 = S.in(x0, n * B), *du = S.in(u, m * T), *dx = S.in(x, n * T), *dl = S.in(lims, 2 * m);
+    double *dxn = S.out(xnew, n * T * na), *dun = S.out(unew, m * T * na), *dcn = S.out(cnew, (size_t)P->CL * B * na),
+           *dcs = S.out(csum, (size_t)B * na);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_forward_pass_f64_dev(h, up, N, B, dp, params_batched, dK, dk, dx0, du, dx, alpha, nalpha, dl, nullptr, dxn, dun,
+                                                  dcn, dcs));
+}
+
+int ddp_user_costfun_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                             const double *u, const int32_t *active, double *cost, double *csum)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x && u && cost, "costfun: null argument");
+    return P->costfun(h, B, nullptr, x, u, active, cost, csum);
+}
+
+int ddp_user_costfun_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                         const double *u, double *cost, double *csum)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x && u && cost, "costfun: null argument");
+    const size_t n = P->n, m = P->m, T = (size_t)N * B;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T);
+    double *dc = S.out(cost, (size_t)P->CL * B), *ds = S.out(csum, (size_t)B);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_costfun_f64_dev(h, up, N, B, dp, params_batched, dx, du, nullptr, dc, ds));
+}
+
+int ddp_user_ilqg_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                          const double *x0, int x0_prerolled, const double *u0, const double *cost0, const double *lims,
+                          double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                          double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    return ddp_ilqg_family_dev(h, P, o, x0, x0_prerolled, u0, cost0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, trace7,
+                               global_iters);
+}
+
+int ddp_user_ilqg_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                      const double *x0, int x0_prerolled, const double *u0, const double *cost0, const double *lims,
+                      double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                      double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg: null argument");
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, CL = P->CL;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * (x0_prerolled ? T : (size_t)B)),
+           *du0 = S.in(u0, m * T), *dc0 = x0_prerolled ? S.in(cost0, CL * B) : nullptr, *dl = S.in(lims, 2 * m);
+    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T),
+           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * B), *ds = S.out(stats, (size_t)DDP_ILQG_NSTATS * B),
+           *dt7 = (trace7 && trace_cap > 0) ? S.out(trace7, (size_t)7 * trace_cap * B) : nullptr;
+    DDP_STAGED(S);
+    return S.finish(ddp_user_ilqg_f64_dev(h, up, N, B, dp, params_batched, o, dx0, x0_prerolled, du0, dc0, dl, dx, du, dK, dk, dQ, dVx, dVxx,
+                                          dc, ds, trace_cap, dt7, global_iters));
+}
+
+}   // extern "C"

@@ -913,4 +913,171 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
     return x_r, u_r, traj_new, Vx_r, Vxx_r, cnew_r, trace
 end
 
+# ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, diff) holds the source; it is compiled with hiprtc for the
+# handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
+mutable struct DeviceProblem
+    source::String
+    n::Int
+    m::Int
+    nparam::Int
+    flags::Int
+    wrap::Int
+    params::Array{Float64}
+    made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
+end
+function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
+                       const_hessian::Bool=false, diff=-)
+    wrap = Int(_diff_mask(diff, n))
+    p = DeviceProblem(String(source), n, m, nparam, (terminal ? 1 : 0) | (const_hessian ? 2 : 0), wrap, _f64(params),
+                      Dict{Ptr{Cvoid},Ptr{Cvoid}}())
+    finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
+    return p
+end
+# compile-only check for gfx950 (no device): the compiler log, or a DDPError carrying it
+function check_source(p::DeviceProblem; extra_options::AbstractString="")
+    rc = @ccall libddp.ddp_user_check(p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint, extra_options::Cstring)::Cint
+    log = unsafe_string(@ccall libddp.ddp_user_compile_log()::Cstring)
+    rc == 0 || throw(DDPError(Int(rc), last_error() * "\n" * log))
+    return log
+end
+cost_len(p::DeviceProblem, N) = (p.flags & 1) != 0 ? N + 1 : N
+function _user_ptr(p::DeviceProblem, handle::Handle)
+    get!(p.made, handle.ptr) do
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        check(@ccall libddp.ddp_user_create(handle.ptr::Ptr{Cvoid}, p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint,
+                                            p.wrap::Cint, r::Ptr{Ptr{Cvoid}})::Cint)
+        r[]
+    end
+end
+function _user_params(p::DeviceProblem, B, params)
+    P = params === nothing ? p.params : _f64(params)
+    p.nparam == 0 && return Float64[], 0
+    size(P) == (p.nparam,) && return P, 0
+    size(P) == (p.nparam, B) && return P, 1
+    throw(DDPError(-1, "DeviceProblem: params must be [nparam] or [nparam, B]"))
+end
+
+function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff=-; handle::Handle=default_handle(), params=nothing)
+    batched = ndims(u) == 3
+    m, N = size(u, 1), size(u, 2)
+    n = size(x0, 1)
+    B = batched ? size(u, 3) : 1
+    (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
+    P, pb = _user_params(problem, B, params)
+    CL = cost_len(problem, N)
+    empty = _isempty_policy(traj_new)
+    al = α isa Number ? [Float64(α)] : _f64(α)
+    na = length(al)
+    fin(lead...) = (lead..., (batched ? (B,) : ())..., (α isa Number ? () : (na,))...)
+    xnew, xnew_r = result_pair((n, N, B, na), fin(n, N)); unew, unew_r = result_pair((m, N, B, na), fin(m, N))
+    cnew, cnew_r = result_pair((CL, B, na), fin(CL)); csum = zeros(B, na)
+    x0 = _f64(x0); u = _f64(u)
+    Kh = empty ? Float64[] : _f64(traj_new.K); kh = empty ? Float64[] : _f64(traj_new.k); xh = empty ? Float64[] : _f64(x)
+    limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P Kh kh xh x0 u al limsp xnew unew cnew csum begin
+        check(@ccall libddp.ddp_user_forward_pass_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, _ptr_or_null(Kh)::Ptr{Float64}, _ptr_or_null(kh)::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64},
+            _ptr_or_null(xh)::Ptr{Float64}, al::Ptr{Float64}, na::Cint, _ptr_or_null(limsp)::Ptr{Float64},
+            xnew::Ptr{Float64}, unew::Ptr{Float64}, cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+    end
+    return xnew_r, unew_r, cnew_r
+end
+
+# df(problem, x, u) -> (fx, fu, fxx, fxu, fuu, cx, cu, cxx, cxu, cuu) like the reference (second-order dynamics terms are [])
+function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)
+    batched = ndims(u) == 3
+    m, N = size(u, 1), size(u, 2)
+    n = size(x, 1)
+    B = batched ? size(u, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    bt = batched ? (B,) : ()
+    ht = (problem.flags & 2) != 0 ? () : (N,)
+    fx = result_array(n, n, N, bt...); fu = result_array(n, m, N, bt...); cx = result_array(n, N, bt...); cu = result_array(m, N, bt...)
+    cxx = result_array(n, n, ht..., bt...); cxu = result_array(n, m, ht..., bt...); cuu = result_array(m, m, ht..., bt...)
+    x = _f64(x); u = _f64(u)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x u fx fu cx cu cxx cxu cuu begin
+        check(@ccall libddp.ddp_user_df_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
+            x::Ptr{Float64}, u::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64},
+            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64})::Cint)
+    end
+    return fx, fu, Float64[], Float64[], Float64[], cx, cu, cxx, cxu, cuu
+end
+
+function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)
+    batched = ndims(u) == 3
+    N = size(u, 2)
+    B = batched ? size(u, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    cost = result_array(cost_len(problem, N), (batched ? (B,) : ())...); csum = zeros(B)
+    x = _f64(x); u = _f64(u)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x u cost csum begin
+        check(@ccall libddp.ddp_user_costfun_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, cost::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+    end
+    return cost
+end
+
+function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
+              λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0, cost=[], handle::Handle=default_handle(),
+              params=nothing, policy=GaussianPolicy{Float64})
+    batched = ndims(u0) == 3
+    m, N = size(u0, 1), size(u0, 2)
+    n = size(x0, 1)
+    B = batched ? size(u0, 3) : 1
+    prerolled = size(x0, 2) == N && ndims(x0) == (batched ? 3 : 2) && N != 1
+    P, pb = _user_params(problem, B, params)
+    CL = cost_len(problem, N)
+    o = _opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    bt = batched ? (B,) : ()
+    x = result_array(n, N, bt...); u = result_array(m, N, bt...); K = result_array(m, n, N, bt...); k = result_array(m, N, bt...)
+    Quu = result_array(m, m, N, bt...); Vx = result_array(n, N, bt...); Vxx = result_array(n, n, N, bt...); costo = result_array(CL, bt...)
+    stats = zeros(8, B)
+    cap = min(4max_iter + 64, 4096); tr7 = zeros(7, cap, B); git = Ref{Cint}(0)
+    x0h = prerolled ? _f64(x0) : _f64(reshape(x0, n, B)); u0h = _f64(u0)
+    c0 = (prerolled && !isempty(cost)) ? _f64(cost) : Float64[]
+    limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x0h u0h c0 limsp x u K k Quu Vx Vxx costo stats tr7 begin
+        check(@ccall libddp.ddp_user_ilqg_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
+            Ref(o)::Ptr{ILQGOpts}, x0h::Ptr{Float64}, (prerolled ? 1 : 0)::Cint, u0h::Ptr{Float64}, _ptr_or_null(c0)::Ptr{Float64},
+            _ptr_or_null(limsp)::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64},
+            Vx::Ptr{Float64}, Vxx::Ptr{Float64}, costo::Ptr{Float64}, stats::Ptr{Float64}, cap::Cint, tr7::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    end
+    (!batched && stats[1, 1] == -1) && return nothing
+    keys7 = (:λ, :dλ, :α, :improvement, :cost, :reduce_ratio, :grad_norm)
+    trace = Dict{Symbol,Any}(:stats => stats, :status => Int.(stats[1, :]), :iter => Int.(stats[2, :]), :global_iters => Int(git[]))
+    for (r, key) in enumerate(keys7)
+        trace[key] = batched ? tr7[r, :, :] : tr7[r, 1:max(Int(stats[2, 1]) - 1, 0), 1]
+    end
+    return x, u, policy(N, n, m, K, k, zeros(m, m, N, bt...), Quu), Vx, Vxx, costo, trace
+end
+
+# device-pointer flavours (arrays already on the handle's device, e.g. from ddp_malloc): thin wrappers over the C entries
+user_df_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, x, u, active, fx, fu, cx, cu, cxx, cxu, cuu; handle::Handle=default_handle()) =
+    check(@ccall libddp.ddp_user_df_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint, params::Ptr{Float64},
+        pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, active::Ptr{Int32}, fx::Ptr{Float64}, fu::Ptr{Float64}, cx::Ptr{Float64},
+        cu::Ptr{Float64}, cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64})::Cint)
+user_forward_pass_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, K, k, x0, u, x, al::Vector{Float64}, lims, active, xnew, unew,
+                       cnew, csum; handle::Handle=default_handle()) =
+    GC.@preserve al check(@ccall libddp.ddp_user_forward_pass_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint,
+        B::Cint, params::Ptr{Float64}, pb::Cint, K::Ptr{Float64}, k::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64}, x::Ptr{Float64},
+        al::Ptr{Float64}, length(al)::Cint, lims::Ptr{Float64}, active::Ptr{Int32}, xnew::Ptr{Float64}, unew::Ptr{Float64},
+        cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+user_costfun_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, x, u, active, cost, csum; handle::Handle=default_handle()) =
+    check(@ccall libddp.ddp_user_costfun_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, active::Ptr{Int32}, cost::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+function user_ilqg_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQGOpts, x0, prerolled, u0, cost0, lims, x, u, K, k, Quu,
+                        Vx, Vxx, cost, stats, cap, trace7; handle::Handle=default_handle())
+    git = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqg_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint, params::Ptr{Float64},
+        pb::Cint, Ref(o)::Ptr{ILQGOpts}, x0::Ptr{Float64}, prerolled::Cint, u0::Ptr{Float64}, cost0::Ptr{Float64}, lims::Ptr{Float64},
+        x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+        cost::Ptr{Float64}, stats::Ptr{Float64}, cap::Cint, trace7::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    return Int(git[])
+end
+
 end # module

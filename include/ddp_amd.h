@@ -43,7 +43,8 @@ int  ddp_sync(ddp_handle h);
  * production) are read ONCE, in ddp_create(); no launch calls getenv().  ddp_reload_env() reads them again for this handle.          */
 int  ddp_reload_env(ddp_handle h);
 /* name of the kernel the last back_pass (which = 0) / forward_pass (which = 1) dispatch of this handle launched ("" before the first
- * one): a debug query — the tests assert through it that the timed path is the one they checked                                    */
+ * one): a debug query — the tests assert through it that the timed path is the one they checked.  which = 2 / 3: the last derivative /
+ * cost kernel of a user problem (ddp_user_df*, ddp_user_costfun*; the hessians of DDP_USER_CONST_HESSIAN count as derivatives).     */
 const char *ddp_last_kernel(ddp_handle h, int which);
 /* The shared-operand backward pass (one fx, fu, cxx, cxu, cuu for the batch) hands work between work-groups of one launch; every such
  * wait is time-bounded (4 s).  A tile whose wait ran out gives its trajectories to the per-trajectory kernels launched behind it — the
@@ -442,6 +443,73 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
                    const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
                    double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
                    double *dV, double *stats, int *iters);
+
+/* ---- user-defined problems: the user's f / costfun / df as HIP device source, compiled at run time for gfx950 ---------------------
+ * The reference's entry point is iLQG(f, costfun, df, x0, u0; ...) with the user's own closures.  Here the user writes four plain
+ * device functions; the library puts its kernel templates around them and compiles the program with hiprtc (loaded with dlopen at
+ * first use: no link-time dependency; without it these entry points return < 0).  Before the user's source the library #defines
+ * DDP_N, DDP_M, DDP_NP (state / control / parameter counts, compile-time constants), DDP_TERMINAL and DDP_CONST_HESSIAN (0 / 1).
+ * The source must not #include <hip/hip_runtime.h> (hiprtc provides it).  All arrays are column-major, i is the 0-based time step:
+ *
+ *   __device__ void   dynamics(const double *x, const double *u, int i, const double *p, double *xnext);     f(x, u, i+1)
+ *   __device__ double stage_cost(const double *x, const double *u, int i, const double *p);                 costfun column i < N
+ *   __device__ double terminal_cost(const double *x, const double *p);       DDP_USER_TERMINAL only: cost[N] on x[:,N-1], CL = N+1
+ *   __device__ void   derivatives(const double *x, const double *u, int i, int N, const double *p,         df column i
+ *                                 double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
+ *            fx[n,n] fu[n,m] cx[n] cu[m] cxx[n,n] cxu[n,m] cuu[m,m]; every entry must be written (the buffers are not cleared).
+ *            With DDP_USER_CONST_HESSIAN the cxx / cxu / cuu written here are discarded.
+ *   __device__ void   cost_hessians(const double *p, double *cxx, double *cxu, double *cuu);               DDP_USER_CONST_HESSIAN only:
+ *            evaluated once per trajectory per solve; the backward pass then reads cxx[n,n,B] cxu[n,m,B] cuu[m,m,B].
+ *
+ * `p` points at the trajectory's parameters: params[nparam] shared by the batch (params_batched = 0) or its column of
+ * params[nparam,B] (params_batched = 1); NULL when nparam = 0.  Semantics of the rollout: src/forward_pass.jl:9-33 (u + α k +
+ * K diff(x̂, x), clamp to lims[m,2], x̂_{i+1} = f(x̂_i, û_i, i) for i < N-1 — the reference's last call of f is discarded, so it is not
+ * made); diff_wrap is the bit mask of ddp_problem::diff_wrap.  Limits: n <= DDP_MAX_N_USER, m <= DDP_MAX_M, nparam <= DDP_USER_MAX_NPARAM;
+ * anything else is refused before compiling.  A problem is compiled once per (source, n, m, nparam, flags) and handle: the handle keeps
+ * the module until ddp_destroy.  Kernel names (rocprofv3, ddp_last_kernel): ddp_user_rollout, ddp_user_df, ddp_user_cost,
+ * ddp_user_hessians. */
+#define DDP_MAX_N_USER 32
+#define DDP_USER_MAX_NPARAM 4096
+enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2 };
+/* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
+ * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
+int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
+/* the log of the last compile in this process ("" before the first one) */
+const char *ddp_user_compile_log(void);
+/* compile (or take from the handle's cache) and load on the handle's device: *out is the problem, used with this handle only */
+int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out);
+int ddp_user_destroy(void *up);
+/* df: x[n,N,B] u[m,N,B] -> fx[n,n,N,B] fu[n,m,N,B] cx[n,N,B] cu[m,N,B], cxx[n,n,N,B] cxu[n,m,N,B] cuu[m,m,N,B] (CONST_HESSIAN: [.,.,B]);
+ * fx .. cu may not be NULL, the Hessians may (not computed then).  `active` as in ddp_back_pass_f64_dev.                        */
+int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                        const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
+int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                    double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
+/* forward_pass: arguments and outputs as ddp_forward_pass_f64_dev; cnew[CL,B,nalpha]                                           */
+int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                                  const double *K, const double *k, const double *x0, const double *u, const double *x,
+                                  const double *alpha, int nalpha, const double *lims, const int32_t *active,
+                                  double *xnew, double *unew, double *cnew, double *csum);
+int ddp_user_forward_pass_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                              const double *K, const double *k, const double *x0, const double *u, const double *x,
+                              const double *alpha, int nalpha, const double *lims,
+                              double *xnew, double *unew, double *cnew, double *csum);
+/* costfun(x, u): cost[CL,B], csum[B] (may be NULL)                                                                              */
+int ddp_user_costfun_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                             const double *u, const int32_t *active, double *cost, double *csum);
+int ddp_user_costfun_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                         const double *u, double *cost, double *csum);
+/* iLQG with the user's closures: arguments and outputs as ddp_ilqg_ex_f64(_dev) (pre-rolled x0 + cost0, trace7, stats[8,B]);
+ * ddp_ilqg_set_timing applies.  The live trajectories are compacted like those of the registered families; the kernels then read
+ * params[:, b] through the working set's slot map.                                                                             */
+int ddp_user_ilqg_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                          const double *x0, int x0_prerolled, const double *u0, const double *cost0, const double *lims,
+                          double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                          double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
+int ddp_user_ilqg_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                      const double *x0, int x0_prerolled, const double *u0, const double *cost0, const double *lims,
+                      double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                      double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
 
 #ifdef __cplusplus
 }
