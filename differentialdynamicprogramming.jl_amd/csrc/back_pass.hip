@@ -584,32 +584,52 @@ int launch_nm(ddp_handle h, const ddp_bp_desc *d, const BPArgs &a)
     return 0;
 }
 
+BPArgs bp_args(const BPCall &c)
+{
+    BPArgs a = {};
+    a.n = c.d.n; a.m = c.d.m; a.N = c.d.N; a.B = c.d.B;
+    a.fx_batched = c.d.fx_batched; a.cost_batched = c.d.cost_batched; a.regType = c.d.regType;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu;
+    a.lambda = c.lambda; a.lims = c.lims; a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    return a;
+}
+
+// the general kernel: exact instantiations of three shapes, run-time sizes n <= 32 for the rest
+int launch_general(ddp_handle h, const BPCall &c)
+{
+    const ddp_bp_desc *d = &c.d;
+    const BPArgs a = bp_args(c);
+    if (d->n == 10 && d->m == 2) return launch_nm<10, 2>(h, d, a);
+#ifndef DDP_FAST_BUILD
+    if (d->n == 4 && d->m == 1) return launch_nm<4, 1>(h, d, a);
+    if (d->n == 6 && d->m == 3) return launch_nm<6, 3>(h, d, a);
+    return launch_nm<0, 0>(h, d, a);
+#else
+    DDP_CHECK(false, "back_pass: DDP_FAST_BUILD only has the (10,2) LTI kernel");
+#endif
+}
+
 }   // namespace
 
 // back_pass_gps (backward_pass.jl:259-350): run-time sizes n <= 32, m <= 8, all cost/dynamics arrays 3-D as the
 // reference's method signature requires.  Quui must be zero-filled by the caller (steps before a failure stay zero).
-int ddp_launch_back_pass_gps(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge)
+int ddp_launch_back_pass_gps(ddp_handle h, const BPCall &c)
 {
     DDP_DEVICE(h);
 #ifndef DDP_FAST_BUILD
+    const ddp_bp_desc *d = &c.d;
+    const ddp_kl_cost_terms *kl = c.kl;
     DDP_CHECK(d->n >= 1 && d->m >= 1 && d->N >= 1 && d->B >= 1, "back_pass_gps: bad sizes n=%d m=%d N=%d B=%d", d->n, d->m, d->N, d->B);
     DDP_CHECK(d->fx_tv && d->cost_tv, "back_pass_gps: needs time-varying (3-D) fx/fu and cxx/cxu/cuu like backward_pass.jl:259");
-    DDP_CHECK(!d->has_lims || (lims && u), "back_pass_gps: has_lims needs lims and u");
+    DDP_CHECK(!d->has_lims || (c.lims && c.u), "back_pass_gps: has_lims needs lims and u");
     DDP_CHECK(d->n <= DDP_MAX_N_GENERIC && d->m <= DDP_MAX_M, "back_pass_gps: n=%d m=%d has no kernel (n <= %d, m <= %d)", d->n, d->m,
               DDP_MAX_N_GENERIC, DDP_MAX_M);
     DDP_CHECK(kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta, "back_pass_gps: incomplete kl_cost_terms");
-    BPArgs a;
-    a.n = d->n; a.m = d->m; a.N = d->N; a.B = d->B;
-    a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.regType = 1;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu;
-    a.lambda = nullptr; a.lims = lims; a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    BPArgs a = bp_args(c);
+    a.regType = 1; a.lambda = nullptr;
     a.cxkl = kl->cx; a.cukl = kl->cu; a.cxxkl = kl->cxx; a.cxukl = kl->cxu; a.cuukl = kl->cuu; a.eta = kl->eta; a.eta_tv = kl->eta_tv;
-    a.Quui = Quui;
+    a.Quui = c.Quui;
     const BPLds L(d->n, d->m, d->has_lims != 0);
     const size_t shmem = (size_t)L.total * sizeof(double);
     const dim3 grid(d->B), block(DDP_WAVE);
@@ -650,20 +670,10 @@ __global__ __launch_bounds__(256) void unpad2d_kernel(const double *src, double 
 }
 }   // namespace
 
-// the embedded problem's work space in bytes (operands and results at the padded sizes)
-static size_t padded_bytes(const ddp_bp_desc *d, int np_, int mp)
+// (np_, mp): the next even sizes, the problem embedded in them for back_pass_big_kernel
+static int launch_back_pass_padded(ddp_handle h, const BPCall &c, int np_, int mp)
 {
-    const size_t N = d->N, B = d->B, cf = (d->fx_tv ? N : 1) * (d->fx_batched ? B : 1), cc = (d->cost_tv ? N : 1) * (d->cost_batched ? B : 1), NB = N * B;
-    return 8 * ((size_t)np_ * NB * 2 + (size_t)mp * NB * 3 + ((size_t)np_ * np_ + (size_t)np_ * mp + (size_t)mp * mp) * cc + ((size_t)np_ * np_ + (size_t)np_ * mp) * cf +
-                ((size_t)mp * np_ + (size_t)mp * mp + (size_t)np_ * np_) * NB) + 16 * 256;
-}
-
-// (np_, mp): the sizes the problem is embedded in — the next even ones for back_pass_big_kernel, or (64, 8) for the matrix-core kernel
-static int launch_back_pass_padded(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu, const double *cxx, const double *cxu,
-                                   const double *cuu, const double *fx, const double *fu, const double *lambda, const double *lims,
-                                   const double *u, const int32_t *active, double *K, double *k, double *Quu, double *Vx, double *Vxx,
-                                   double *dV, int32_t *diverge, int np_, int mp, bool to_mfma)
-{
+    const ddp_bp_desc *d = &c.d;
     const int n = d->n, m = d->m;
     const long N = d->N, B = d->B;
     const long cf = (d->fx_tv ? N : 1) * (d->fx_batched ? B : 1), cc = (d->cost_tv ? N : 1) * (d->cost_batched ? B : 1), NB = N * B;
@@ -685,193 +695,222 @@ static int launch_back_pass_padded(ddp_handle h, const ddp_bp_desc *d, const dou
     double *pcx = tk(s_cx), *pcu = tk(s_cu), *pu = tk(s_cu), *pcxx = tk(s_cxx), *pcxu = tk(s_cxu), *pcuu = tk(s_cuu), *pfx = tk(s_fx),
            *pfu = tk(s_fu), *pl = tk(s_l), *pK = tk(s_K), *pk = tk(s_cu), *pQuu = tk(s_Quu), *pVx = tk(s_cx), *pVxx = tk(s_Vxx);
     hipStream_t st = h->stream;
-    auto pad = [&](const double *src, double *dst, int r, int c, int rp, int cp, long cnt, int one_from) {
+    auto pad = [&](const double *src, double *dst, int r, int c_, int rp, int cp, long cnt, int one_from) {
         const long tot = (long)rp * cp * cnt;
-        hipLaunchKernelGGL(pad2d_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, dst, r, c, rp, cp, cnt, one_from);
+        hipLaunchKernelGGL(pad2d_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, dst, r, c_, rp, cp, cnt, one_from);
     };
-    pad(cx, pcx, n, 1, np_, 1, NB, 1 << 30); pad(cu, pcu, m, 1, mp, 1, NB, 1 << 30);
-    if (u) pad(u, pu, m, 1, mp, 1, NB, 1 << 30);
-    pad(cxx, pcxx, n, n, np_, np_, cc, 1 << 30); pad(cxu, pcxu, n, m, np_, mp, cc, 1 << 30); pad(cuu, pcuu, m, m, mp, mp, cc, m);
-    pad(fx, pfx, n, n, np_, np_, cf, 1 << 30); pad(fu, pfu, n, m, np_, mp, cf, 1 << 30);
-    if (lims) {                                                 // the extra control is free inside [-1, 1] (it stays at 0)
+    pad(c.cx, pcx, n, 1, np_, 1, NB, 1 << 30); pad(c.cu, pcu, m, 1, mp, 1, NB, 1 << 30);
+    if (c.u) pad(c.u, pu, m, 1, mp, 1, NB, 1 << 30);
+    pad(c.cxx, pcxx, n, n, np_, np_, cc, 1 << 30); pad(c.cxu, pcxu, n, m, np_, mp, cc, 1 << 30); pad(c.cuu, pcuu, m, m, mp, mp, cc, m);
+    pad(c.fx, pfx, n, n, np_, np_, cf, 1 << 30); pad(c.fu, pfu, n, m, np_, mp, cf, 1 << 30);
+    if (c.lims) {                                               // the extra control is free inside [-1, 1] (it stays at 0)
         double hl[2 * DDP_MAX_M];
-        DDP_HIP(hipMemcpyAsync(hl, lims, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, st));
+        DDP_HIP(hipMemcpyAsync(hl, c.lims, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, st));
         DDP_HIP(hipStreamSynchronize(st));
         double hp[2 * DDP_MAX_M + 4];
         for (int q2 = 0; q2 < mp; ++q2) { hp[q2] = q2 < m ? hl[q2] : -1.0; hp[q2 + mp] = q2 < m ? hl[q2 + m] : 1.0; }
         DDP_HIP(hipMemcpyAsync(pl, hp, (size_t)mp * 2 * 8, hipMemcpyHostToDevice, st));
         DDP_HIP(hipStreamSynchronize(st));                      // hp lives on this stack frame
     }
-    ddp_bp_desc dp = *d;
-    dp.n = np_; dp.m = mp;
-    const int rc = to_mfma ? ddp_launch_back_pass_mfma(h, &dp, pcx, pcu, pcxx, pcxu, pcuu, pfx, pfu, lambda, lims ? pl : nullptr, u ? pu : nullptr, active,
-                                                       pK, pk, pQuu, pVx, pVxx, dV, diverge)
-                           : ddp_launch_back_pass_big(h, &dp, pcx, pcu, pcxx, pcxu, pcuu, pfx, pfu, lambda, lims ? pl : nullptr, u ? pu : nullptr, active,
-                                                      pK, pk, pQuu, pVx, pVxx, dV, diverge);
-    if (rc) return rc < 0 ? rc : -1;
-    auto unpad = [&](const double *src, double *dst, int r, int c, int rp, int cp) {
-        const long tot = (long)r * c * NB;
-        hipLaunchKernelGGL(unpad2d_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, dst, r, c, rp, cp, NB, N, active);
+    BPCall cp = c;
+    cp.d.n = np_; cp.d.m = mp;
+    cp.cx = pcx; cp.cu = pcu; cp.cxx = pcxx; cp.cxu = pcxu; cp.cuu = pcuu; cp.fx = pfx; cp.fu = pfu;
+    cp.lims = c.lims ? pl : nullptr; cp.u = c.u ? pu : nullptr;
+    cp.K = pK; cp.k = pk; cp.Quu = pQuu; cp.Vx = pVx; cp.Vxx = pVxx;
+    if (int rc = ddp_launch_back_pass_big(h, cp)) return rc;
+    auto unpad = [&](const double *src, double *dst, int r, int c_, int rp, int cp_) {
+        const long tot = (long)r * c_ * NB;
+        hipLaunchKernelGGL(unpad2d_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, dst, r, c_, rp, cp_, NB, N, c.active);
     };
-    unpad(pK, K, m, n, mp, np_); unpad(pk, k, m, 1, mp, 1); unpad(pQuu, Quu, m, m, mp, mp); unpad(pVx, Vx, n, 1, np_, 1);
-    unpad(pVxx, Vxx, n, n, np_, np_);
+    unpad(pK, c.K, m, n, mp, np_); unpad(pk, c.k, m, 1, mp, 1); unpad(pQuu, c.Quu, m, m, mp, mp); unpad(pVx, c.Vx, n, 1, np_, 1);
+    unpad(pVxx, c.Vxx, n, n, np_, np_);
     DDP_HIP(hipGetLastError());
     return 0;
 }
 
-// back_pass_dppw.hip: the row kernel with a write-back wave per chain wave (n = 10, m = 2, LTI, no limits, large batches); 1 = not applicable
-int ddp_launch_back_pass_dppw(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                              const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                              const double *fu, const double *lambda, const int32_t *active, double *K,
-                              double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge);
+// ---- kernel choice
+// Several implementations of the same arithmetic exist, one family per enumerator; the name is what ddp_last_kernel(h, 0) reports:
+//   sh      the shared-operand kernel (back_pass_sh.hip): the matrix recursion once per distinct λ, then a per-trajectory family below
+//           for the trajectories it left out;
+//   x (mx)  one 16x16 fp64 MFMA tile per trajectory, one wave each (back_pass_mx.hip; n=10, m=2, no limits): shortest dependent chain
+//           per time step, best while the batch gives a SIMD only one or two waves (B=1024: 0.55 ms against 0.90 ms for the 64-lane
+//           vector kernel it replaced); measured cross-over with `dpp` between B=4096 and B=6144; mx2: the same with a write-back wave;
+//   dpp     16 lanes per trajectory (back_pass_dpp.hip): fewest instructions per trajectory-step, best once the batch gives every SIMD
+//           a few wavefronts; also the kernel for control limits; dppw: the same with write-back waves (back_pass_dppw.hip);
+//   q4      n = 4, m = 1: one trajectory per 4x4x4 MFMA block (back_pass_q4.hip);
+//   general 64 lanes per trajectory, any n <= 32 / m <= 8 / limits (this file);
+//   row     the same row kernel compiled for PADDED sizes (back_pass_row.hip): any n <= 14, m <= 4, n + m <= 15 that has no exact instantiation;
+//   tile    the mx kernel with run-time sizes n <= 10, m <= 2 (back_pass_mx.hip, RT), small and medium batches without limits;
+//   wtile   the tile kernel for n <= 12, m <= 4 (back_pass_mxg.hip), same batches, and small ones with limits;
+//   mid     one wave per trajectory with LDS operands (back_pass_mid.hip): n <= 32, m <= 8;
+//   mf2     32 < n <= 64, m <= 8 on the matrix cores with run-time sizes (back_pass_mf2.hip); mfma: the round-5 kernel of the exact
+//           (64, 8) shape (back_pass_mfma.hip); big: the 256-thread vector kernel of even sizes (back_pass_big.hip), padded: big on the
+//           next even sizes.
+enum BPKernel { BP_NONE, BP_SH, BP_MX2, BP_MX, BP_Q4, BP_DPPW, BP_MXG, BP_DPP, BP_MXR, BP_ROW, BP_MID, BP_GENERAL, BP_MFMA, BP_MF2, BP_BIG, BP_PADDED };
+static const char *const bp_kernel_name[] = {"", "sh_back_kernel", "back_pass_mx2_kernel", "back_pass_mx_kernel", "back_pass_q4", "back_pass_dppw_kernel",
+                                             "back_pass_mxg_kernel", "back_pass_dpp_kernel", "back_pass_mx_kernel<RT>", "back_pass_row_kernel",
+                                             "back_pass_mid_kernel", "back_pass_kernel", "back_pass_mfma_kernel", "back_pass_mf2_kernel",
+                                             "back_pass_big_kernel", "back_pass_big_kernel"};
+
+enum { BP_AL_IN = 1, BP_AL_COST = 2, BP_AL_OUT = 4 };      // 16-byte aligned: cx, cu | cxx, cuu | K, k, Quu, Vx, Vxx
+
+// What the choice depends on besides the descriptor.  Host facts only: the choice itself reads no device memory.
+struct BPChoiceIn {
+    unsigned al16;                                        // BP_AL_* bits
+    bool sink;                                            // the handle has its sink buffer
+    bool lims_active;                                     // has_lims with real limits (lims[1,1] <= lims[1,2]); looked at for 32 < n <= 64 only
+    const char *backpass, *sh_min_b, *mx2, *dppw;        // the handle's DDP_BACKPASS, DDP_SH_MIN_B, DDP_MX2, DDP_DPPW (nullptr: unset)
+};
 
 constexpr int MXG_LIMS_MAX_B = 2048;             // (measured cross-over with the row kernels: profiles/r05_lims_sweep.sh)
 
-static int launch_back_pass_inner(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                         const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                         const double *fu, const double *lambda, const double *lims, const double *u,
-                         const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                         double *Vxx, double *dV, int32_t *diverge)
+// DDP_BACKPASS=x|q|dpp|general|big|s|row|tile|wtile|mid|old|new forces one family by its first letter (A/B timing, tests of every code
+// path); a forced family that cannot take the shape falls through to the general kernel.  `shared`: whether the shared-operand kernel
+// may be chosen (not for the trajectories it leaves to the others).
+static BPKernel bp_choose(const ddp_bp_desc &d, const BPChoiceIn &q, bool shared)
 {
-    // Kernel choice.  Several implementations of the same arithmetic exist:
-    //   x (mx)  one 16x16 fp64 MFMA tile per trajectory, one wave each (back_pass_mx.hip; n=10, m=2, no limits): shortest
-    //           dependent chain per time step, best while the batch gives a SIMD only one or two waves (B=1024: 0.55 ms
-    //           against 0.90 ms for the 64-lane vector kernel it replaced); measured cross-over with `dpp` between B=4096 and B=6144;
-    //   dpp     16 lanes per trajectory (back_pass_dpp.hip): fewest instructions per trajectory-step, best once the
-    //           batch gives every SIMD a few wavefronts; also the kernel for control limits;
-    //   general 64 lanes per trajectory, any n <= 32 / m <= 8 / limits (this file).
-    //   row     the same row kernel compiled for PADDED sizes (back_pass_row.hip): any n <= 14, m <= 4, n + m <= 15 that has no exact instantiation;
-    //   tile    the mx kernel with run-time sizes n <= 10, m <= 2 (back_pass_mx.hip, RT), small and medium batches without limits;
-    //   mid     one wave per trajectory with LDS operands (back_pass_mid.hip): n <= 32, m <= 8;
-    //   wtile   the tile kernel for n <= 12, m <= 4 (back_pass_mxg.hip), same batches;
-    // DDP_BACKPASS=x|q|general|dpp|row|tile|wtile|mid|big forces one (A/B timing, tests of every code path).
-    const char *force_env = ddp_env(h, ENV_BACKPASS);          // read per call so tests can switch paths
-    const char force = force_env ? force_env[0] : 0;
-    if (force == 'x' || (force == 0 && d->B < 5120)) {
-        // two waves per trajectory (chain + write-back, back_pass_mx2.hip) while a CU's four SIMDs hold one trajectory each;
-        // DDP_MX2=0 / 1 forces the one-wave / two-wave kernel
-        const char *mx2_env = ddp_env(h, ENV_MX2);
-        if (mx2_env ? mx2_env[0] == '1' : d->B <= 1024) {
-            const int r2 = ddp_launch_back_pass_mx2(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, active, K, k, Quu, Vx, Vxx, dV, diverge);
-            if (r2 <= 0) { h->last_kernel[0] = "back_pass_mx2_kernel"; return r2; }
-        }
-        const int rc = ddp_launch_back_pass_mx(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mx_kernel"; return rc; }
-    }
-    if (force == 'q' || force == 0) {                             // n = 4, m = 1: one trajectory per 4x4x4 MFMA block
-        const int rc = ddp_launch_back_pass_q4(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_q4"; return rc; }
-    }
-    if (force == 0 || force == 'd') {                             // machine-filling batches of the LTI shape: row kernel + write-back waves
-        const int rw = ddp_launch_back_pass_dppw(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rw <= 0) { h->last_kernel[0] = "back_pass_dppw_kernel"; return rw; }
-    }
-    // control limits at small and medium batches (any n <= 12, m <= 4): one WAVE per trajectory with the box-QP as a wave-uniform solve
-    // (back_pass_mxg.hip) instead of 16 lanes per trajectory with a divergent one — at B = 1 024 the row kernels leave three quarters of
-    // the SIMDs without a wave (n=10, m=2, N=1000 with limits: 2.8 ms there; profiles/r05_lims_sweep.sh)
-    // (measured cross-over, profiles/r05_lims_threshold.txt: a wave-uniform QP is bound by its own latency, so the time doubles with a
-    // second wave on a SIMD; the row kernels hold their time up to B = 4 096 — n=6, m=2: 1.53 vs 2.31 ms at B = 1 024, 3.0 vs 2.45 at 1 536)
-    const int mxg_lims_max = d->m == 1 ? 512 : ((d->n > 8 || d->m >= 3 || d->n <= 4) ? MXG_LIMS_MAX_B : 1024);   // (m = 1: the row kernels' straight-line QP — 0.73 vs 0.81 ms at n=3, B = 1 024)
-    if (d->has_lims && (force == 'w' || (force == 0 && d->B <= mxg_lims_max))) {
-        const int rc = ddp_launch_back_pass_mxg(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mxg_kernel"; return rc; }
-    }
-    if (force != 'g' && force != 'b' && force != 'r' && force != 't' && force != 'w' && force != 'm') {      // (a forced family either runs or falls through to the general kernel)
-        const int rc = ddp_launch_back_pass_dpp(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_dpp_kernel"; return rc; }
-    }
-    // n <= 10, m <= 2 without limits: the fp64 tile kernel with run-time sizes while a SIMD holds one to three waves — its step is half the
-    // row kernel's (0.49 vs 0.99 ms at n=6, m=2, N=1000, B=1024) but costs seven 16x16x4 products whatever n is, so the row kernel
-    // wins once the matrix pipe is the bound (profiles/r05_tile_vs_row.txt: B=3072 1.33 vs 1.47 ms at n=6, 1.21 vs 0.79 at n=3)
-    if (force == 't' || (force == 0 && (d->B <= 1024 || (d->B <= 3072 && d->n >= 5)))) {
-        const int rc = ddp_launch_back_pass_mxr(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mx_kernel<RT>"; return rc; }
-    }
-    // the same for n <= 12, m <= 4 (back_pass_mxg.hip; profiles/r05_wtile_vs_row.txt: ahead of the row kernel up to B = 4096 — 0.83 vs 1.16 ms at
-    // n=12, m=3, N=500, B=2048; 1.15 vs 1.55 at n=8, m=4, B=4096 — level with it there for n <= 4)
-    if (force == 'w' || (force == 0 && !d->has_lims && (d->B <= 3072 || (d->B <= 4096 && d->n >= 5)))) {      // (with limits: the block above, up to MXG_LIMS_MAX_B)
-        const int rc = ddp_launch_back_pass_mxg(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mxg_kernel"; return rc; }
-    }
-    if (force == 0 || force == 'r') {                             // every other shape a 16-lane row holds: the row kernel compiled for padded sizes
-        const int rc = ddp_launch_back_pass_row(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_row_kernel"; return rc; }
-    }
-    if (force == 0 || force == 'm') {                             // 14 < n <= 32 (or m > 4): one wave per trajectory on the matrix cores, LDS operands
-        const int rc = ddp_launch_back_pass_mid(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mid_kernel"; return rc; }
-    }
-    h->last_kernel[0] = "back_pass_kernel";
-    BPArgs a = {};
-    a.n = d->n; a.m = d->m; a.N = d->N; a.B = d->B;
-    a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.regType = d->regType;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu;
-    a.lambda = lambda; a.lims = lims; a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
-    if (d->n == 10 && d->m == 2) return launch_nm<10, 2>(h, d, a);
-#ifndef DDP_FAST_BUILD
-    if (d->n == 4 && d->m == 1) return launch_nm<4, 1>(h, d, a);
-    if (d->n == 6 && d->m == 3) return launch_nm<6, 3>(h, d, a);
-    // 32 < n <= 64, m <= 8: the fp64 matrix-core kernel with run-time sizes (back_pass_mf2_kernel.h; round 5 embedded 32 < n < 64 in the
-    // (64, 8) problem through padded COPIES of every operand and result — up to 48 GB of scratch on the handle, half of the time in the
-    // copy kernels).  DDP_BACKPASS=old: the round-5 kernel of the exact (64, 8) shape (A/B timing).
-    if (force == 'o') {
-        const int rc = ddp_launch_back_pass_mfma(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mfma_kernel"; return rc; }
-    }
-    if (force != 'b' && force != 'g') {
-        // (rc 2: the exact (64, 8) shape with a time-varying cost, or with REAL control limits — lims[1,1] <= lims[1,2], which the launcher has just looked at — stays
-        // on the round-5 kernel by default: its gain wave runs the 8 x 8 box-QP in 16 400 ticks per step against 21 200 in the
-        // run-time-sized kernel, 10.8 vs 13.3 ms at C4 with limits; DDP_BACKPASS=new forces the new one)
-        const int rc = ddp_launch_back_pass_mf2(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge, force != 'n');
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_mf2_kernel"; return rc; }
-        if (rc == 2) {
-            const int ro = ddp_launch_back_pass_mfma(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-            if (ro <= 0) { h->last_kernel[0] = "back_pass_mfma_kernel"; return ro; }
-        }
-    }
-    if (d->n > DDP_MAX_N_GENERIC || force == 'b') {               // large states: 256-thread work-group per trajectory
-        const int rc = ddp_launch_back_pass_big(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
-        if (rc <= 0) { h->last_kernel[0] = "back_pass_big_kernel"; return rc; }
-    }
-    if (d->n > DDP_MAX_N_GENERIC && d->n <= 64 && ((d->n | d->m) & 1))      // odd n or m: embed in the next even sizes
-        return launch_back_pass_padded(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge, d->n + (d->n & 1), d->m + (d->m & 1), false);
-    DDP_CHECK(d->n <= DDP_MAX_N_GENERIC, "back_pass: n=%d m=%d has no kernel (n <= %d with m <= %d, or n <= 64)", d->n, d->m, DDP_MAX_N_GENERIC, DDP_MAX_M);
-    return launch_nm<0, 0>(h, d, a);
-#else
-    DDP_CHECK(false, "back_pass: DDP_FAST_BUILD only has the (10,2) LTI kernel");
-#endif
-}
-
-int ddp_launch_back_pass(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                         const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                         const double *fu, const double *lambda, const double *lims, const double *u,
-                         const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                         double *Vxx, double *dV, int32_t *diverge)
-{
-    DDP_DEVICE(h);
-    DDP_CHECK(d->n >= 1 && d->m >= 1 && d->N >= 1 && d->B >= 1, "back_pass: bad sizes n=%d m=%d N=%d B=%d", d->n, d->m, d->N, d->B);
-    DDP_CHECK(d->regType == 1 || d->regType == 2, "back_pass: regType must be 1 or 2 (got %d)", d->regType);
-    DDP_CHECK(!d->has_lims || (lims && u), "back_pass: has_lims needs lims and u");
-    DDP_CHECK(d->m <= DDP_MAX_M, "back_pass: m=%d exceeds DDP_MAX_M=%d", d->m, DDP_MAX_M);
-    const char *force_env = ddp_env(h, ENV_BACKPASS);
-    const char force = force_env ? force_env[0] : 0;
+    const char force = q.backpass ? q.backpass[0] : 0;
+    const int n = d.n, m = d.m, B = d.B;
+    const bool lti_shared = !d.fx_tv && !d.cost_tv && !d.fx_batched && !d.cost_batched;
+    const bool n10m2 = n == 10 && m == 2 && !d.has_lims;
     // Operands shared by the batch (the reference's LTI method with ONE fx, fu, cxx, cxu, cuu): the matrix recursion once per distinct
     // λ (back_pass_sh.hip).  What it leaves out (λ values that occur once, more distinct values than it has groups) comes back as the
     // activity mask of the per-trajectory kernels, which are launched behind it and exit at once when there is nothing for them.
     // Measured (profiles/ab_sh.py): B = 1 024 0.42 ms (= the per-trajectory kernel: both wait for one 999-step matrix chain),
     // 2 048 0.45 vs 0.97 ms, 32 768 6.7 vs 9.4 ms.  DDP_SH_MIN_B moves the threshold (tests run it at B = 6).
-    const char *sh_env = ddp_env(h, ENV_SH_MIN_B);
-    const int sh_min = sh_env ? atoi(sh_env) : 1024;
-    if ((force == 0 || force == 's') && d->B >= sh_min) {
-        const int32_t *fb = nullptr;
-        const int rs = ddp_launch_back_pass_sh(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, active, K, k, Quu, Vx, Vxx, dV, diverge, &fb);
-        if (rs < 0) return rs;
-        if (rs == 0) {
-            const int rc = launch_back_pass_inner(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, fb, K, k, Quu, Vx, Vxx, dV, diverge);
-            h->last_kernel[0] = "sh_back_kernel";
-            return rc;
-        }
+    const int sh_min = q.sh_min_b ? atoi(q.sh_min_b) : 1024;
+    if (shared && (force == 0 || force == 's') && B >= sh_min && n10m2 && lti_shared && d.N >= DDP_SH_MIN_N && q.sink &&
+        q.al16 == (BP_AL_IN | BP_AL_COST | BP_AL_OUT))
+        return BP_SH;
+    if (force == 'x' || (force == 0 && B < 5120)) {
+        // two waves per trajectory (chain + write-back, back_pass_mx2.hip) while a CU's four SIMDs hold one trajectory each;
+        // DDP_MX2=0 / 1 forces the one-wave / two-wave kernel.  Its group write-back and [cx;cu] image need 16-byte aligned arrays.
+        if (n10m2 && (q.mx2 ? q.mx2[0] == '1' : B <= 1024) && (q.al16 & (BP_AL_IN | BP_AL_OUT)) == (BP_AL_IN | BP_AL_OUT)) return BP_MX2;
+        if (n10m2) return BP_MX;
     }
-    return launch_back_pass_inner(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
+    if ((force == 'q' || force == 0) && n == 4 && m == 1) return BP_Q4;
+    // machine-filling batches of the LTI shape: row kernel + write-back waves (16-byte pieces of the results; N <= 400 000: 32-bit lane
+    // offsets inside a chain wave's four trajectories).  Measured cross-over (profiles/ab_fill_crossover.sh): 4 096: dpp 1.81, this
+    // 1.97 ms; 6 144: mx 2.84, this 2.21.  DDP_DPPW=0 / 1: never / whenever the shape allows (A/B timing, tests)
+    if ((force == 0 || force == 'd') && n10m2 && lti_shared && d.N <= 400000 && q.sink && (q.al16 & BP_AL_OUT) && !(q.dppw && q.dppw[0] == '0') &&
+        ((q.dppw && q.dppw[0] == '1') || B >= 6144))
+        return BP_DPPW;
+    const bool wtile = m <= 4 && n <= 12 && n + m <= 15 && !(n > 8 && m > 3);
+    // control limits at small and medium batches (any n <= 12, m <= 4): one WAVE per trajectory with the box-QP as a wave-uniform solve
+    // (back_pass_mxg.hip) instead of 16 lanes per trajectory with a divergent one — at B = 1 024 the row kernels leave three quarters of
+    // the SIMDs without a wave (n=10, m=2, N=1000 with limits: 2.8 ms there; profiles/r05_lims_sweep.sh)
+    // (measured cross-over, profiles/r05_lims_threshold.txt: a wave-uniform QP is bound by its own latency, so the time doubles with a
+    // second wave on a SIMD; the row kernels hold their time up to B = 4 096 — n=6, m=2: 1.53 vs 2.31 ms at B = 1 024, 3.0 vs 2.45 at 1 536)
+    const int mxg_lims_max = m == 1 ? 512 : ((n > 8 || m >= 3 || n <= 4) ? MXG_LIMS_MAX_B : 1024);   // (m = 1: the row kernels' straight-line QP — 0.73 vs 0.81 ms at n=3, B = 1 024)
+    if (d.has_lims && (force == 'w' || (force == 0 && B <= mxg_lims_max)) && wtile) return BP_MXG;
+    if (force != 'g' && force != 'b' && force != 'r' && force != 't' && force != 'w' && force != 'm' && ((n == 10 && m == 2) || (n == 4 && m == 1)))
+        return BP_DPP;
+    // n <= 10, m <= 2 without limits: the fp64 tile kernel with run-time sizes while a SIMD holds one to three waves — its step is half the
+    // row kernel's (0.49 vs 0.99 ms at n=6, m=2, N=1000, B=1024) but costs seven 16x16x4 products whatever n is, so the row kernel
+    // wins once the matrix pipe is the bound (profiles/r05_tile_vs_row.txt: B=3072 1.33 vs 1.47 ms at n=6, 1.21 vs 0.79 at n=3)
+    if ((force == 't' || (force == 0 && (B <= 1024 || (B <= 3072 && n >= 5)))) && !d.has_lims && n <= 10 && m <= 2) return BP_MXR;
+    // the same for n <= 12, m <= 4 (back_pass_mxg.hip; profiles/r05_wtile_vs_row.txt: ahead of the row kernel up to B = 4096 — 0.83 vs 1.16 ms at
+    // n=12, m=3, N=500, B=2048; 1.15 vs 1.55 at n=8, m=4, B=4096 — level with it there for n <= 4)
+    if ((force == 'w' || (force == 0 && !d.has_lims && (B <= 3072 || (B <= 4096 && n >= 5)))) && wtile) return BP_MXG;    // (with limits: above, up to MXG_LIMS_MAX_B)
+    // every other shape a 16-lane row holds: the row kernel compiled for padded sizes
+    if ((force == 0 || force == 'r') && m <= 4 && n <= 14 && n + m <= 15 && !(n > 12 && m > 1) && !(n > 10 && m > 3) && q.sink) return BP_ROW;
+    // 14 < n <= 32 (or m > 4): one wave per trajectory on the matrix cores, LDS operands
+    if ((force == 0 || force == 'm') && n <= 32 && m <= 8) return BP_MID;
+    if ((n == 10 && m == 2) || (n == 4 && m == 1) || (n == 6 && m == 3)) return BP_GENERAL;
+    // 32 < n <= 64, m <= 8: the fp64 matrix-core kernel with run-time sizes (back_pass_mf2_kernel.h; round 5 embedded 32 < n < 64 in the
+    // (64, 8) problem through padded COPIES of every operand and result — up to 48 GB of scratch on the handle, half of the time in the
+    // copy kernels).  DDP_BACKPASS=old: the round-5 kernel of the exact (64, 8) shape (A/B timing).
+    if (force == 'o' && n == 64 && m == 8) return BP_MFMA;
+    if (force != 'b' && force != 'g' && n > 32 && n <= 64 && m <= 8) {
+        // The exact (64, 8) shape with a time-varying cost, or with REAL control limits, stays on the round-5 kernel: with limits its gain
+        // wave runs the 8 x 8 box-QP in 16 400 ticks per step against 21 200 in the run-time-sized kernel (10.8 vs 13.3 ms at C4 with
+        // limits); with a time-varying cost it is 3-4 % faster (8.42 vs 8.66-8.78 ms at N = 256, B = 1 024: the run-time-sized kernel
+        // fetches its cost tiles with run-time strides at the top of every step).  DDP_BACKPASS=new forces the new one.
+        if (force != 'n' && n == 64 && m == 8 && (d.cost_tv || q.lims_active)) return BP_MFMA;
+        return BP_MF2;
+    }
+    if ((n > DDP_MAX_N_GENERIC || force == 'b') && n <= 64 && m <= 8 && !(n & 1) && !(m & 1)) return BP_BIG;   // large states: 256-thread work-group per trajectory
+    if (n > DDP_MAX_N_GENERIC && n <= 64 && m <= 8) return BP_PADDED;      // odd n or m: embedded in the next even sizes
+    return n <= DDP_MAX_N_GENERIC && m <= DDP_MAX_M ? BP_GENERAL : BP_NONE;
+}
+
+static BPChoiceIn bp_choice_in(ddp_handle h, const BPCall &c)
+{
+    auto al16 = [](uintptr_t p) { return (p & 15) == 0; };
+    BPChoiceIn q;
+    q.al16 = (al16((uintptr_t)c.cx | (uintptr_t)c.cu) ? BP_AL_IN : 0) | (al16((uintptr_t)c.cxx | (uintptr_t)c.cuu) ? BP_AL_COST : 0) |
+             (al16((uintptr_t)c.K | (uintptr_t)c.k | (uintptr_t)c.Quu | (uintptr_t)c.Vx | (uintptr_t)c.Vxx) ? BP_AL_OUT : 0);
+    q.sink = h->sink != nullptr;
+    q.lims_active = c.d.has_lims != 0;
+    q.backpass = ddp_env(h, ENV_BACKPASS);
+    q.sh_min_b = ddp_env(h, ENV_SH_MIN_B);
+    q.mx2 = ddp_env(h, ENV_MX2);
+    q.dppw = ddp_env(h, ENV_DPPW);
+    return q;
+}
+
+static int launch_family(ddp_handle h, BPKernel k, const BPCall &c, bool lims_active)
+{
+    switch (k) {
+    case BP_MX2: return ddp_launch_back_pass_mx2(h, c);
+    case BP_MX: return ddp_launch_back_pass_mx(h, c);
+    case BP_Q4: return ddp_launch_back_pass_q4(h, c);
+    case BP_DPPW: return ddp_launch_back_pass_dppw(h, c);
+    case BP_MXG: return ddp_launch_back_pass_mxg(h, c);
+    case BP_DPP: return ddp_launch_back_pass_dpp(h, c);
+    case BP_MXR: return ddp_launch_back_pass_mxr(h, c);
+    case BP_ROW: return ddp_launch_back_pass_row(h, c);
+    case BP_MID: return ddp_launch_back_pass_mid(h, c);
+    case BP_GENERAL: return launch_general(h, c);
+    case BP_MFMA: return ddp_launch_back_pass_mfma(h, c, lims_active);
+    case BP_MF2: return ddp_launch_back_pass_mf2(h, c, lims_active);
+    case BP_BIG: return ddp_launch_back_pass_big(h, c);
+    case BP_PADDED: return launch_back_pass_padded(h, c, c.d.n + (c.d.n & 1), c.d.m + (c.d.m & 1));
+    default: break;
+    }
+    DDP_CHECK(false, "back_pass: n=%d m=%d has no kernel (n <= %d with m <= %d, or n <= 64)", c.d.n, c.d.m, DDP_MAX_N_GENERIC, DDP_MAX_M);
+}
+
+int ddp_launch_back_pass(ddp_handle h, const BPCall &c)
+{
+    DDP_DEVICE(h);
+    const ddp_bp_desc &d = c.d;
+    DDP_CHECK(d.n >= 1 && d.m >= 1 && d.N >= 1 && d.B >= 1, "back_pass: bad sizes n=%d m=%d N=%d B=%d", d.n, d.m, d.N, d.B);
+    DDP_CHECK(d.regType == 1 || d.regType == 2, "back_pass: regType must be 1 or 2 (got %d)", d.regType);
+    DDP_CHECK(!d.has_lims || (c.lims && c.u), "back_pass: has_lims needs lims and u");
+    DDP_CHECK(d.m <= DDP_MAX_M, "back_pass: m=%d exceeds DDP_MAX_M=%d", d.m, DDP_MAX_M);
+    BPChoiceIn q = bp_choice_in(h, c);
+    BPKernel k = bp_choose(d, q, true);
+    if ((k == BP_MF2 || k == BP_MFMA) && d.has_lims) {
+        // lims[1,1] > lims[1,2] means "no limits" upstream (backward_pass.jl:31): the matrix-core kernels of 32 < n <= 64 take the Cholesky
+        // branch then, and (64, 8) may change kernel.  Two doubles come down once per call — a pass of these shapes takes milliseconds.
+        DDP_CHECK(h->h_pinned, "back_pass: the handle has no pinned buffer");
+        double *lh = (double *)h->h_pinned;
+        DDP_HIP(hipMemcpyAsync(lh, c.lims, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DDP_HIP(hipMemcpyAsync(lh + 1, c.lims + d.m, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        DDP_HIP(hipStreamSynchronize(h->stream));
+        q.lims_active = !(lh[0] > lh[1]);
+        k = bp_choose(d, q, true);
+    }
+    if (k == BP_SH) {                                 // then the per-trajectory family for what it left out
+        const int32_t *fb = nullptr;
+        if (int rs = ddp_launch_back_pass_sh(h, c, &fb)) return rs;
+        BPCall rest = c;
+        rest.active = fb;
+        h->last_kernel[0] = bp_kernel_name[BP_SH];
+        return launch_family(h, bp_choose(d, q, false), rest, q.lims_active);
+    }
+    h->last_kernel[0] = bp_kernel_name[k];
+    return launch_family(h, k, c, q.lims_active);
+}
+
+// Unlisted debug hook (not in ddp_amd.h): the name ddp_last_kernel(h, 0) reports after a backward pass with these facts — the same
+// choice the dispatcher makes, callable without a GPU (tests/test_bp_choice_cpu.py).  al16: bit 0 cx, cu; bit 1 cxx, cuu; bit 2 K, k,
+// Quu, Vx, Vxx 16-byte aligned; lims_active: for 32 < n <= 64 with has_lims, whether lims[1,1] <= lims[1,2]; the switches as strings
+// (NULL: unset)
+extern "C" const char *ddp_bp_choice(const ddp_bp_desc *d, unsigned al16, int sink, int lims_active, const char *backpass,
+                                     const char *sh_min_b, const char *mx2, const char *dppw)
+{
+    const BPChoiceIn q = {al16, sink != 0, d->has_lims && lims_active != 0, backpass, sh_min_b, mx2, dppw};
+    return bp_kernel_name[bp_choose(*d, q, true)];
 }

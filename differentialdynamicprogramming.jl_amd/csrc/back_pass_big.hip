@@ -339,28 +339,20 @@ __global__ __launch_bounds__(NT) void back_pass_big_kernel(BPBArgs a)
 
 }   // namespace
 
-// returns 1 if this shape is not handled here, 0 launched, <0 error
-int ddp_launch_back_pass_big(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge)
+// even n <= 64, even m <= 8
+int ddp_launch_back_pass_big(ddp_handle h, const BPCall &c)
 {
-    if (d->n > 64 || d->m > MMAX || (d->n & 1) || (d->m & 1) || d->n < 2) return 1;
+    const ddp_bp_desc *d = &c.d;
     BPBArgs a;
     a.n = d->n; a.m = d->m; a.N = d->N; a.B = d->B;
     a.fx_tv = d->fx_tv; a.fx_batched = d->fx_batched; a.cost_tv = d->cost_tv; a.cost_batched = d->cost_batched;
     a.regType = d->regType; a.has_lims = d->has_lims;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.lims = lims;
-    a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     const BigLds L(d->n, d->m);
     const size_t shmem = (size_t)L.total * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        DDP_HIP(hipFuncSetAttribute((const void *)back_pass_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    if (int rc = ddp_raise_lds(h, (const void *)back_pass_big_kernel, 160 * 1024)) return rc;
     DDP_CHECK(shmem <= 160 * 1024, "back_pass: n=%d m=%d needs %zu bytes of LDS (> 160 KiB)", d->n, d->m, shmem);
     hipLaunchKernelGGL(back_pass_big_kernel, dim3(d->B), dim3(NT), shmem, h->stream, a);
     DDP_HIP(hipGetLastError());

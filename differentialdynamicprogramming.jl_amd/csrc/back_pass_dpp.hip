@@ -479,19 +479,15 @@ int launch_dpp_bp(ddp_handle h, const ddp_bp_desc *d, const BPDArgs &a)
 
 }   // namespace
 
-// returns 1 if this shape has no DPP kernel (caller falls back), 0 launched, <0 error
-int ddp_launch_back_pass_dpp(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge)
+// (10, 2) and (4, 1)
+int ddp_launch_back_pass_dpp(ddp_handle h, const BPCall &c)
 {
+    const ddp_bp_desc *d = &c.d;
     BPDArgs a;
     a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.regType = d->regType;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.lims = lims;
-    a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     if (d->n == 10 && d->m == 2) return launch_dpp_bp<10, 2>(h, d, a);
-    if (d->n == 4 && d->m == 1) return launch_dpp_bp<4, 1>(h, d, a);
-    return 1;
+    return launch_dpp_bp<4, 1>(h, d, a);
 }

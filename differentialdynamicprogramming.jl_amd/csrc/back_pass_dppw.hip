@@ -22,7 +22,7 @@
 //     non-temporal stores: 9.8 ms;
 //   - the chain's accumulators start from the cost Hessians / from Qxx (no clears, no final adds), broadcasts without an "old" operand:
 //     421 -> 383 fp64 vector instructions per step, 9.45 ms (= 0.51 of 8 TB/s algorithmic).
-// Removal experiments (DDP_DPPW_EXP, profiles/ab_dppw_exp.sh): no result stores 7.67 ms (the vector-issue floor of two chain waves per
+// Removal experiments (round 3, profiles/r03_fill_dppw_exp.txt): no result stores 7.67 ms (the vector-issue floor of two chain waves per
 // SIMD: 2.05 ns per fp64 instruction and SIMD, profiles/microbench/dpp_fma_bench2.hip), only Vxx stored 8.75 ms; stores aimed at an
 // L2-resident region cost nothing, i.e. the remaining 1.8 ms is HBM write back-pressure, not instruction issue; staggering the chain
 // waves in time changes nothing.
@@ -80,8 +80,7 @@ typedef __attribute__((address_space(3))) int lds_int;
 __device__ __forceinline__ int lds_load_flag(const int *p) { return *(const volatile lds_int *)p; }
 __device__ __forceinline__ void lds_store_flag(int *p, int v) { asm volatile("" ::: "memory"); *(volatile lds_int *)p = v; asm volatile("" ::: "memory"); }
 
-// EXP (removal experiments, profiles/ab_dppw_exp.sh): 1 = the writer reads the records but stores nothing, 2 = only Vxx leaves
-template <int NS, int MS, int EXP>
+template <int NS, int MS>
 __global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(BPWArgs a)
 {
     constexpr int n = NS, m = MS, p = n + m, G = 16, GPW = DDP_WAVE / G;
@@ -187,7 +186,6 @@ __global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(
                         const char *sb = (const char *)(gb[A] + (size_t)PER[A] * ((size_t)N * (size_t)tb0)) + (long)PER[A] * 8 * (long)ilo;
                         static_for<0, NPA[A]>([&](auto qc) {
                             constexpr int qa = decltype(qc)::value, q = Q0[A] + qa;
-                            if constexpr (EXP == 1 || (EXP == 2 && A >= 1)) return;
                             const unsigned vo = voff[q];         // (asm operands do not capture)
                             const d2 vv = v[q];
                             const char *sbq = sb;
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(
         asm volatile("s_nop 1" : "+v"(vj));
         int g = 0, slot = GW - 1 - (N - 2) % GW;                // groups end on multiples of GW of the step index (the writer's whole lines)
         for (int i = N - 2; i >= 0; --i) {
-            const double rc4 = EXP == 3 ? 0.001 : rc_at(i - 4);
+            const double rc4 = rc_at(i - 4);
             double *rec = rw + slot * SLOT;
             // ================= P1: w = Vxx·F[:,j],  q = c + F[:,j]'Vx ==================================
             double w[n], qj = 0.0;
@@ -475,29 +473,16 @@ __global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(
 
 }   // namespace
 
-// returns 1 if this launch is not for this kernel (the caller goes on to back_pass_dpp), 0 launched, <0 error
-int ddp_launch_back_pass_dppw(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                              const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                              const double *fu, const double *lambda, const int32_t *active, double *K,
-                              double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge)
+// n = 10, m = 2, LTI, no limits, N <= 400 000, 16-byte aligned results, with a sink (back_pass.hip tests them)
+int ddp_launch_back_pass_dppw(ddp_handle h, const BPCall &c)
 {
-    if (d->N > 400000) return 1;                                 // 32-bit lane offsets inside a chain wave's four trajectories
-    if (d->n != 10 || d->m != 2 || d->has_lims || d->fx_tv || d->cost_tv || d->fx_batched || d->cost_batched || !h->sink) return 1;
-    const char *env = ddp_env(h, ENV_DPPW);                        // 0: never, 1: whenever the shape allows (A/B timing, tests)
-    if (env && env[0] == '0') return 1;
-    if (!(env && env[0] == '1') && d->B < 6144) return 1;        // measured cross-over (profiles/ab_fill_crossover.sh): 4 096: dpp 1.81, this 1.97 ms; 6 144: mx 2.84, this 2.21
-    if ((((uintptr_t)K | (uintptr_t)k | (uintptr_t)Quu | (uintptr_t)Vx | (uintptr_t)Vxx) & 15) != 0) return 1;     // 16-byte pieces
+    const ddp_bp_desc *d = &c.d;
     BPWArgs a;
     a.N = d->N; a.B = d->B; a.regType = d->regType;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge; a.sink = (double *)h->sink;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge; a.sink = (double *)h->sink;
     const dim3 grid((unsigned)((d->B + NCW * 4 - 1) / (NCW * 4))), block(DDP_WAVE * (NCW + NWW));
-    const char *exp_env = ddp_env(h, ENV_DPPW_EXP);
-    const int exp = exp_env ? atoi(exp_env) : 0;
-    if (exp == 1) hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2, 1>), grid, block, 0, h->stream, a);
-    else if (exp == 2) hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2, 2>), grid, block, 0, h->stream, a);
-    else if (exp == 3) hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2, 3>), grid, block, 0, h->stream, a);
-    else hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2, 0>), grid, block, 0, h->stream, a);
+    hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2>), grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }

@@ -304,19 +304,17 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_gps_lane_kernel(GLArgs a)
 }   // namespace
 
 // returns 1 if this shape is not handled here (caller falls back), 0 launched, <0 error
-int ddp_launch_back_pass_gps_lane(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                                  const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                                  const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                                  const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                                  double *Vxx, double *dV, int32_t *diverge)
+int ddp_launch_back_pass_gps_lane(ddp_handle h, const BPCall &c)
 {
+    const ddp_bp_desc *d = &c.d;
     if (!(d->n == 4 && (d->m == 1 || d->m == 2)) || d->N < 2 || !d->fx_tv || !d->cost_tv) return 1;
+    const ddp_kl_cost_terms *kl = c.kl;
     GLArgs a;
     a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.eta_tv = kl->eta_tv;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lims = lims; a.u = u;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lims = c.lims; a.u = c.u;
     a.cxkl = kl->cx; a.cukl = kl->cu; a.cxxkl = kl->cxx; a.cxukl = kl->cxu; a.cuukl = kl->cuu; a.eta = kl->eta;
-    a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Quui = Quui; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Quui = c.Quui; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     const dim3 grid((unsigned)((d->B + DDP_WAVE - 1) / DDP_WAVE)), block(DDP_WAVE);
     if (d->m == 1) {
         if (d->has_lims) hipLaunchKernelGGL((back_pass_gps_lane_kernel<4, 1, true>), grid, block, 0, h->stream, a);

@@ -322,10 +322,11 @@ __global__ __launch_bounds__(NTH) void back_pass_mf2_kernel(BPM2Args a)
         asm volatile("" : "+s"(nv));                     // took 600 scalar registers (spilled through v_writelane / v_readlane)
         char *goutb = (char *)(Vxxg + (size_t)(nv * nv) * (i + 1));
         const char *fxb = (const char *)(fx + (size_t)(nv * nv) * (tvF ? inext : 0)), *fub = (const char *)(fu + (size_t)(nv * m) * (tvF ? inext : 0));
-        // side traffic, one piece per product of phase B (waves 1..3): FIRST the next Jacobian (NFL loads), THEN Vxx_{i+1} out — column
-        // c = 3 q + wave - 1: an LDS read and (one product later) its store; rows / columns past n repeat the last one (the same value to
-        // the same address: no mask, no second base).  Loads in front of the stores: the in-order vmcnt wait of the Jacobian in phase C
-        // then never waits for a store to be acknowledged (with the stores in phase A it cost 2 500 ticks per step).
+        // side traffic, one piece per product: the next Jacobian (NFL loads) behind the products of phase A (sideA), Vxx_{i+1} out behind
+        // those of phase B (sideB, waves 1..3) — column c = 3 q + wave - 1: an LDS read and (one product later) its store; rows / columns
+        // past n repeat the last one (the same value to the same address: no mask, no second base).  Loads in front of the stores: the
+        // in-order vmcnt wait of the Jacobian in phase C then never waits for a store to be acknowledged (with the stores in phase A it
+        // cost 2 500 ticks per step).
         constexpr int NVX = PAIR ? (8 * NT + 2) / 3 : (16 * NT + 2) / 3, VD = 3, NSIDE = 2 * NVX + VD;
         // (the LDS read of column (pair) j sits in slot 2 j, its store VD slots later: one product is not enough for the LDS round trip;
         // LDS address = a per-wave base + an immediate, global address = a scalar base per column + the lane offset: no vector
@@ -706,11 +707,7 @@ template <int NT, bool LIMS, bool CTV, bool PAIR>
 static int launch_k(ddp_handle h, const BPM2Args &a)
 {
     const size_t shmem = (size_t)oTot * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        DDP_HIP(hipFuncSetAttribute((const void *)back_pass_mf2_kernel<NT, LIMS, CTV, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    if (int rc = ddp_raise_lds(h, (const void *)back_pass_mf2_kernel<NT, LIMS, CTV, PAIR>, 160 * 1024)) return rc;
     hipLaunchKernelGGL((back_pass_mf2_kernel<NT, LIMS, CTV, PAIR>), dim3(a.B), dim3(NTH), shmem, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;

@@ -663,11 +663,7 @@ template <bool LIMS, bool CTV>
 static int ddp_bpm_launch_tv(ddp_handle h, const BPMArgs &a)
 {
     const size_t shmem = (size_t)oTot * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        DDP_HIP(hipFuncSetAttribute((const void *)back_pass_mfma_kernel<LIMS, CTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
+    if (int rc = ddp_raise_lds(h, (const void *)back_pass_mfma_kernel<LIMS, CTV>, 160 * 1024)) return rc;
     hipLaunchKernelGGL((back_pass_mfma_kernel<LIMS, CTV>), dim3(a.B), dim3(NT), shmem, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;

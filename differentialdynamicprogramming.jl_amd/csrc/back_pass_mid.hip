@@ -615,7 +615,7 @@ int launch_mid2(ddp_handle h, const ddp_bp_desc *d, const BPMidArgs &a)
 {
     const size_t bytes = ((size_t)MidLds<NTR, PT, MMX>::oTot + ((MMX == 8 && a.regType == 2) ? 8 * MidLds<NTR, PT, MMX>::PC : 0)) * sizeof(double);
     const dim3 grid((unsigned)d->B), block(DDP_WAVE);
-    DDP_HIP(hipFuncSetAttribute((const void *)back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (int rc = ddp_raise_lds(h, (const void *)back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV>, (int)bytes)) return rc;
     hipLaunchKernelGGL((back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV>), grid, block, bytes, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
@@ -631,15 +631,11 @@ int launch_mid(ddp_handle h, const ddp_bp_desc *d, const BPMidArgs &a)
 
 }   // namespace
 
-// returns 1 if the shape is not handled here (n > 32, m > 8, n + m + 1 > 48), 0 launched, < 0 error
-int ddp_launch_back_pass_mid(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge)
+// n <= 32, m <= 8
+int ddp_launch_back_pass_mid(ddp_handle h, const BPCall &c)
 {
+    const ddp_bp_desc *d = &c.d;
     const int n = d->n, m = d->m;
-    if (n < 1 || m < 1 || n > 32 || m > 8) return 1;
     const long N = d->N;
     BPMidArgs a;
     a.n = n; a.m = m; a.N = d->N; a.B = d->B; a.regType = d->regType;
@@ -649,9 +645,9 @@ int ddp_launch_back_pass_mid(ddp_handle h, const ddp_bp_desc *d, const double *c
     a.cxx_t = d->cost_tv ? nn : 0; a.cxx_b = d->cost_batched ? nn * (d->cost_tv ? N : 1) : 0;
     a.cxu_t = d->cost_tv ? nm : 0; a.cxu_b = d->cost_batched ? nm * (d->cost_tv ? N : 1) : 0;
     a.cuu_t = d->cost_tv ? mm : 0; a.cuu_b = d->cost_batched ? mm * (d->cost_tv ? N : 1) : 0;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.lims = lims;
-    a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     const int ntr = n <= 16 ? 1 : 2, pt = (n + m + 1 + 15) / 16;           // pt = 1 only for n + m <= 15: the row kernels' range, padded to 2 here
     if (m <= 4) {
         if (ntr == 1) return launch_mid<1, 2, 4>(h, d, a);

@@ -441,34 +441,21 @@ int launch_mx(ddp_handle h, const ddp_bp_desc *d, const BPXArgs &a)
 
 }   // namespace
 
-// returns 1 if this shape is not handled here, 0 launched, <0 error
-int ddp_launch_back_pass_mx(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const int32_t *active, double *K,
-                            double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge)
+// n = 10, m = 2 without limits
+int ddp_launch_back_pass_mx(ddp_handle h, const BPCall &c)
 {
-    if (d->has_lims || d->m != 2 || d->n != 10) return 1;
-    BPXArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.n = d->n; a.m = d->m;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    const ddp_bp_desc *d = &c.d;
+    const BPXArgs a = bpx_args(c);
     // the group write-back needs 16-byte aligned arrays (every per-step size of this shape is a multiple of 16 bytes)
     const char *lv = ddp_env(h, ENV_MX_LDS);                    // 0: results straight to global memory, step by step (A/B, tests)
-    const bool al16 = ((((uintptr_t)cx | (uintptr_t)cu | (uintptr_t)K | (uintptr_t)k | (uintptr_t)Quu | (uintptr_t)Vx | (uintptr_t)Vxx) & 15) == 0);
+    const bool al16 = ((((uintptr_t)c.cx | (uintptr_t)c.cu | (uintptr_t)c.K | (uintptr_t)c.k | (uintptr_t)c.Quu | (uintptr_t)c.Vx | (uintptr_t)c.Vxx) & 15) == 0);
     if (al16 && !(lv && lv[0] == '0')) return d->regType == 2 ? launch_mx<true, true>(h, d, a) : launch_mx<false, true>(h, d, a);
     return d->regType == 2 ? launch_mx<true, false>(h, d, a) : launch_mx<false, false>(h, d, a);
 }
 
-// The same tile kernel for any n <= 10, m <= 2 without control limits (run-time sizes inside the (10, 2) tile layout); 1 = not applicable
-int ddp_launch_back_pass_mxr(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge)
+// The same tile kernel for any n <= 10, m <= 2 without control limits (run-time sizes inside the (10, 2) tile layout)
+int ddp_launch_back_pass_mxr(ddp_handle h, const BPCall &c)
 {
-    if (d->has_lims || d->m > 2 || d->n > 10) return 1;
-    BPXArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.n = d->n; a.m = d->m;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
-    return d->regType == 2 ? launch_mx<true, false, true>(h, d, a) : launch_mx<false, false, true>(h, d, a);
+    const BPXArgs a = bpx_args(c);
+    return c.d.regType == 2 ? launch_mx<true, false, true>(h, &c.d, a) : launch_mx<false, false, true>(h, &c.d, a);
 }

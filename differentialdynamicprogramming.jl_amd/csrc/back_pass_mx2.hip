@@ -455,18 +455,9 @@ int launch_mx2(ddp_handle h, const ddp_bp_desc *d, const BPXArgs &a)
 
 }   // namespace
 
-// returns 1 if this shape / alignment is not handled here (the caller goes on to back_pass_mx), 0 launched, <0 error
-int ddp_launch_back_pass_mx2(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge)
+// n = 10, m = 2 without limits; the group write-back and the [cx;cu] image need 16-byte aligned arrays (back_pass.hip tests them)
+int ddp_launch_back_pass_mx2(ddp_handle h, const BPCall &c)
 {
-    if (d->has_lims || d->m != 2 || d->n != 10) return 1;
-    // the group write-back and the [cx;cu] image need 16-byte aligned arrays (every per-step size of this shape is a multiple of 16 bytes)
-    if ((((uintptr_t)cx | (uintptr_t)cu | (uintptr_t)K | (uintptr_t)k | (uintptr_t)Quu | (uintptr_t)Vx | (uintptr_t)Vxx) & 15) != 0) return 1;
-    BPXArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
-    return d->regType == 2 ? launch_mx2<true>(h, d, a) : launch_mx2<false>(h, d, a);
+    const BPXArgs a = bpx_args(c);
+    return c.d.regType == 2 ? launch_mx2<true>(h, &c.d, a) : launch_mx2<false>(h, &c.d, a);
 }

@@ -17,6 +17,15 @@ struct BPXArgs {
     const double *lims, *u;                         // control limits (back_pass_mxg_kernel<..., LIMS = true> only)
 };
 
+inline BPXArgs bpx_args(const BPCall &c)
+{
+    BPXArgs a;
+    a.N = c.d.N; a.B = c.d.B; a.fx_batched = c.d.fx_batched; a.cost_batched = c.d.cost_batched; a.n = c.d.n; a.m = c.d.m;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge; a.lims = c.lims; a.u = c.u;
+    return a;
+}
+
 __device__ const double mx_zero[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 __device__ const double mx_one[2] = {1.0, 1.0};
 

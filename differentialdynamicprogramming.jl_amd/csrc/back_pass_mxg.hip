@@ -654,24 +654,15 @@ int launch_mxg(ddp_handle h, const ddp_bp_desc *d, const BPXArgs &a)
 
 }   // namespace
 
-// returns 1 if this shape is not handled here, 0 launched, <0 error
-int ddp_launch_back_pass_mxg(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge)
+// n <= 12, m <= 4, n + m <= 15 (m <= 3 above n = 8)
+int ddp_launch_back_pass_mxg(ddp_handle h, const BPCall &c)
 {
-    if (d->m > 4 || d->n > 12 || d->n + d->m > 15) return 1;
-    if (d->has_lims && !(lims && u)) return 1;
+    const ddp_bp_desc *d = &c.d;
     const int np = d->n <= 4 ? 4 : (d->n <= 8 ? 8 : 12);
-    if (np == 12 && d->m > 3) return 1;
-    BPXArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.n = d->n; a.m = d->m;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge; a.lims = lims; a.u = u;
+    const BPXArgs a = bpx_args(c);
     const bool r2 = d->regType == 2;
-    const char *ce = ddp_env(h, ENV_MXG_COAL);                  // 0: one 8-byte element per lane straight from / to global memory (A/B, tests)
-    if (ce && ce[0] == '0') {
-        if (d->has_lims) return 1;                                // (limits: the piece-wise path only)
+    const char *ce = ddp_env(h, ENV_MXG_COAL);                  // 0: one 8-byte element per lane straight from / to global memory (A/B, tests;
+    if (ce && ce[0] == '0' && !d->has_lims) {                   // without limits: with them there is only the path of 16-byte pieces)
         switch (np) {
         case 4: return r2 ? launch_mxg<4, true, false>(h, d, a) : launch_mxg<4, false, false>(h, d, a);
         case 8: return r2 ? launch_mxg<8, true, false>(h, d, a) : launch_mxg<8, false, false>(h, d, a);

@@ -155,7 +155,7 @@ struct Q4NoMid { __device__ __forceinline__ void operator()() const {} };
 // step there: behind the products their latency costs nothing, in front of them it delays the first product)
 // GPS (back_pass_gps, backward_pass.jl:290-307): Q• = (c• + f'V f)/η + c•kl.  The caller hands in c̃• = c•/η + c•kl (a prepass), so what is
 // left is the factor 1/η on the products with V: on Vx and on W = Vxx fx, W2 = Vxx'fu — three multiplications per step.
-template <bool LIMS, bool REG2, int EXP, class Mid = Q4NoMid, bool GPS = false>
+template <bool LIMS, bool REG2, class Mid = Q4NoMid, bool GPS = false>
 __device__ __forceinline__ void q4_step(int i, const Q4In &o, Q4State &s, Q4Out &out, const Q4Par &p, Mid mid = Mid())
 {
     const QPOptsDev qpo = {100, 1e-8, 1e-8, 0.6, 1e-22, 0.1};                                   // boxQP.jl:30-35
@@ -185,7 +185,7 @@ __device__ __forceinline__ void q4_step(int i, const Q4In &o, Q4State &s, Q4Out 
     // ---- gains (:31-61), scalar system
     double kk, rH;
     bool clamped = false, fail;
-    if (!LIMS || p.nolims || (EXP & 4)) {
+    if (!LIMS || p.nolims) {
         fail = !(QuuF > 0.0);                                   // cholesky(Hermitian(QuuF)) (:35)
         rH = ddp_rcp_nr(QuuF);
         kk = -(Qu * rH);                                        // k_i = -(R\Qu) (:41)
@@ -238,7 +238,7 @@ __device__ __forceinline__ void q4_zero_fill(const Q4Args &a, int b, int q16, in
 }
 
 // ---- one time step at a time: any N, time-varying cost (CTV) or not
-template <bool LIMS, bool CTV, bool REG2, int EXP = 0, bool GPS = false>
+template <bool LIMS, bool CTV, bool REG2, bool GPS = false>
 __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4_kernel(Q4Args a)
 {
     constexpr int n = 4, D = 8;
@@ -297,11 +297,11 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4_kernel(Q4Args a)
     auto step = [&](int i, Q4In &o) __attribute__((always_inline)) {
         if (!CTV) { o.cxx = cst.cxx; o.cxxT = cst.cxxT; o.cxuc = cst.cxuc; o.cxur = cst.cxur; o.cuu = cst.cuu; }
         Q4Out out;
-        q4_step<LIMS, REG2, EXP, Q4NoMid, GPS>(i, o, s, out, par);
+        q4_step<LIMS, REG2, Q4NoMid, GPS>(i, o, s, out, par);
         // ---- stores (a diverged trajectory keeps writing; its range is zero-filled after the loop)
-        if (act && !(EXP & 1)) Vxxg[(size_t)(unsigned)(16 * i)] = out.Vn;
+        if (act) Vxxg[(size_t)(unsigned)(16 * i)] = out.Vn;
         const double v0 = st_K ? out.Kc : st_Vx ? out.vx : st_k ? out.kk : out.Quu;       // :75-76
-        if (st_on && !(EXP & 1)) *(double *)((char *)st_base + (size_t)((unsigned)i * st_stride)) = v0;
+        if (st_on) *(double *)((char *)st_base + (size_t)((unsigned)i * st_stride)) = v0;
     };
 
     if (N >= 2) {
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4_kernel(Q4Args a)
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 step(i0 - d, ring[d]);
-                if (!(EXP & 2)) fetch(i0 - d - D, ring[d]);
+                fetch(i0 - d - D, ring[d]);
             }
         }
         for (; i0 >= 0; i0 -= D) {
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4_kernel(Q4Args a)
                 const int i = i0 - d;
                 if (i >= 0) {
                     step(i, ring[d]);
-                    if (!(EXP & 2)) fetch(i - D >= 0 ? i - D : 0, ring[d]);
+                    fetch(i - D >= 0 ? i - D : 0, ring[d]);
                 }
             }
         }
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4_kernel(Q4Args a)
 }
 
 // ---- two time steps per memory instruction (even N, time-invariant cost)
-template <bool LIMS, bool REG2, int EXP = 0>
+template <bool LIMS, bool REG2>
 __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4p_kernel(Q4Args a)
 {
     constexpr int n = 4, DP = Q4_DP;                            // ring of DP pairs
@@ -392,7 +392,6 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4p_kernel(Q4Args a)
         A.cuu = Bs.cuu = cst.cuu;
     };
     auto store_pair = [&](int p, const Q4Out &oa, const Q4Out &ob) {
-        if (EXP & 1) return;
         double x, y;
         row_swap(oa.Vn, ob.Vn, x, y);
         *(d2 *)((char *)Vxxp + (size_t)((unsigned)p * vxx_stride)) = d2{x, y};
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4p_kernel(Q4Args a)
         Q4Out oa, ob;
         s.V = cst.cxx; s.VT = cst.cxxT; s.vxc = A.cx;
         oa.Vn = s.V; oa.Kc = 0.0; oa.vx = A.cx; oa.kk = 0.0; oa.Quu = cst.cuu;
-        q4_step<LIMS, REG2, EXP>(N - 2, Bs, s, ob, par);
+        q4_step<LIMS, REG2>(N - 2, Bs, s, ob, par);
         store_pair(NP - 1, oa, ob);
         fetch(NP - 1 - DP >= 0 ? NP - 1 - DP : 0, ring[0]);
     }
@@ -424,10 +423,10 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4p_kernel(Q4Args a)
         Q4In A, Bs;
         unpack(slot, A, Bs);
         Q4Out oa, ob;
-        q4_step<LIMS, REG2, EXP>(2 * p + 1, A, s, oa, par);
-        q4_step<LIMS, REG2, EXP>(2 * p, Bs, s, ob, par);
+        q4_step<LIMS, REG2>(2 * p + 1, A, s, oa, par);
+        q4_step<LIMS, REG2>(2 * p, Bs, s, ob, par);
         store_pair(p, oa, ob);
-        if (!(EXP & 2)) fetch(pnext, slot);
+        fetch(pnext, slot);
     };
     // slot of pair p is (NP-1-p) % DP; the first pair used slot 0
     int p0 = NP - 2;
@@ -592,10 +591,10 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4l_kernel(Q4Args a)
                 s.V = in.cxx; s.VT = in.cxxT; s.vxc = in.cx;
                 o.Vn = s.V; o.Kc = 0.0; o.vx = in.cx; o.kk = 0.0; o.Quu = in.cuu;
             } else if (sidx == CH - 1)
-                q4_step<LIMS, REG2, 0, Q4NoMid, GPS>(CH * ch + sidx, in, s, o, par);
+                q4_step<LIMS, REG2, Q4NoMid, GPS>(CH * ch + sidx, in, s, o, par);
             else {
                 auto mid = [&]() __attribute__((always_inline)) { writeout(sidx + 1, prev); };
-                q4_step<LIMS, REG2, 0, decltype(mid), GPS>(CH * ch + sidx, in, s, o, par, mid);
+                q4_step<LIMS, REG2, decltype(mid), GPS>(CH * ch + sidx, in, s, o, par, mid);
             }
             if (sidx == 0) { writeout(0, o); }
             prev = o;
@@ -645,7 +644,7 @@ struct Q4C {
     static constexpr int NBUF = GPS ? 3 : 2;                                          // input images (see the kernel)
 };
 
-template <bool LIMS, bool REG2, bool GPS, int CH, int EXP = 0>
+template <bool LIMS, bool REG2, bool GPS, int CH>
 __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4c_kernel(Q4Args a, const ddp_kl_cost_terms kl)
 {
     typedef Q4C<CH, GPS> L;
@@ -812,7 +811,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4c_kernel(Q4Args a, const
     // at the end of a chunk is COUNTED: vmcnt(NLD) leaves the loads of the chunk after next and the result stores of the last two
     // chunks in flight — at most NLD operations outstanding means at least the OLDER half of the 2 NLD loads has landed, whatever
     // the stores do (loads return in order among themselves; stores may pass them).  With vmcnt(0) and two images a chunk of four
-    // steps (~4 us) waited for its predecessor's result stores to reach memory: 0.13 of 0.58 ms (DDP_Q4_EXP, C5).
+    // steps (~4 us) waited for its predecessor's result stores to reach memory: 0.13 of 0.58 ms (a removal experiment, C5).
     constexpr int NBUF = L::NBUF;
     dma(NC - 1, lin[0]);
     if (NC > 1) dma(NC - 2, lin[1]);
@@ -844,18 +843,18 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_q4c_kernel(Q4Args a, const
                 s.V = in.cxx; s.VT = in.cxxT; s.vxc = in.cx;
                 o.Vn = s.V; o.Kc = 0.0; o.vx = in.cx; o.kk = 0.0; o.Quu = in.cuu;
             } else if (sidx == CH - 1)
-                q4_step<LIMS, REG2, 0, Q4NoMid, GPS>(CH * ch + sidx, in, s, o, par);
+                q4_step<LIMS, REG2, Q4NoMid, GPS>(CH * ch + sidx, in, s, o, par);
             else {
                 auto mid = [&]() __attribute__((always_inline)) { writeout(sidx + 1, prev); };
-                q4_step<LIMS, REG2, 0, decltype(mid), GPS>(CH * ch + sidx, in, s, o, par, mid);
+                q4_step<LIMS, REG2, decltype(mid), GPS>(CH * ch + sidx, in, s, o, par, mid);
             }
             if (sidx == 0) { writeout(0, o); }
             prev = o;
             in = nx;
         }
         // the image of this chunk is free: it takes the chunk NBUF further on
-        if (ch >= NBUF && !(EXP & 2)) dma(ch - NBUF, lin[ib]);
-        if (!(EXP & 1)) drain(ch);
+        if (ch >= NBUF) dma(ch - NBUF, lin[ib]);
+        drain(ch);
         ib = inx;
     }
     if (s.diverge && act) {
@@ -910,14 +909,10 @@ __global__ __launch_bounds__(256) void gps_quui_kernel(int N, long NB, const dou
 
 }   // namespace
 
-// returns 1 if this shape has no such kernel (caller falls back), 0 launched, <0 error
-int ddp_launch_back_pass_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const double *lims, const double *u,
-                            const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                            double *Vxx, double *dV, int32_t *diverge)
+// n = 4, m = 1
+int ddp_launch_back_pass_q4(ddp_handle h, const BPCall &c)
 {
-    if (!(d->n == 4 && d->m == 1)) return 1;
+    const ddp_bp_desc *d = &c.d;
     Q4Args a;
     const long N = d->N;
     a.N = d->N; a.B = d->B; a.regType = d->regType;
@@ -926,32 +921,23 @@ int ddp_launch_back_pass_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx
     a.cxx_t = d->cost_tv ? 16 : 0; a.cxx_b = d->cost_batched ? 16 * (d->cost_tv ? N : 1) : 0;
     a.cxu_t = d->cost_tv ? 4 : 0; a.cxu_b = d->cost_batched ? 4 * (d->cost_tv ? N : 1) : 0;
     a.cuu_t = d->cost_tv ? 1 : 0; a.cuu_b = d->cost_batched ? (d->cost_tv ? N : 1) : 0;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.lims = lims;
-    a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     a.sink = (double *)h->sink;
     const dim3 grid((unsigned)((d->B + 3) / 4)), block(DDP_WAVE);
-    // DDP_Q4_EXP selects "removal experiment" kernels (no result stores / no operand loads: wrong results by design, for profiles/q4_exp.sh);
-    // they exist only in a profiling build (-DDDP_PROFILE_BUILD, profiles/build_variant.sh) — the production library ignores the switch
-#ifdef DDP_PROFILE_BUILD
-    const char *ex = ddp_env(h, ENV_Q4_EXP);
-    const int exp = ex ? atoi(ex) : 0;
-#else
-    const int exp = 0;
-#endif
     const char *sg = ddp_env(h, ENV_Q4_SINGLE);                  // 1: force the one-step-at-a-time kernel (tests)
-    const bool aligned16 = ((((uintptr_t)fx | (uintptr_t)fu | (uintptr_t)cx | (uintptr_t)cu | (uintptr_t)K | (uintptr_t)k | (uintptr_t)Quu |
-                              (uintptr_t)Vx | (uintptr_t)Vxx | (uintptr_t)(d->has_lims ? u : cu)) & 15) == 0);
+    const bool aligned16 = ((((uintptr_t)c.fx | (uintptr_t)c.fu | (uintptr_t)c.cx | (uintptr_t)c.cu | (uintptr_t)c.K | (uintptr_t)c.k | (uintptr_t)c.Quu |
+                              (uintptr_t)c.Vx | (uintptr_t)c.Vxx | (uintptr_t)(d->has_lims ? c.u : c.cu)) & 15) == 0);
     const bool paired = !d->cost_tv && (d->N % 2 == 0) && d->N >= 4 * Q4_DP && aligned16 && h->sink != nullptr && !(sg && sg[0] == '1');
-#define Q4P(L_, R_, E_) hipLaunchKernelGGL((back_pass_q4p_kernel<L_, R_, E_>), grid, block, 0, h->stream, a)
+#define Q4P(L_, R_) hipLaunchKernelGGL((back_pass_q4p_kernel<L_, R_>), grid, block, 0, h->stream, a)
 #define Q4S(L_, C_, R_) hipLaunchKernelGGL((back_pass_q4_kernel<L_, C_, R_>), grid, block, 0, h->stream, a)
     const bool reg2 = d->regType == 2;
     const char *lv = ddp_env(h, ENV_Q4_LDS);                     // 0 / 1: never / whenever possible the LDS-group kernel (A/B, tests)
     // the LDS-group kernel is the latency kernel: 24 KB of LDS per wave let 6 of them share a CU, and from two waves per SIMD on the
     // pair kernel hides its issue gaps behind the other wave (B = 8192: 0.66 ms against 0.90 ms; B = 6144: 0.61 against 0.53, B = 4096: 0.44 against 0.39)
     const bool few = lv ? (lv[0] == '1' || lv[0] == 'o') : d->B <= 6144;
-    const bool c3exp = exp >= 11 && exp <= 13 && d->has_lims && d->regType == 2;      // DDP_Q4_EXP=11|12|13: removal experiments of the chunked kernel (C3 shape)
-    const bool chunked = paired && d->fx_tv && (d->N % Q4L_CH == 0) && d->N >= 2 * Q4L_CH && (exp == 0 || c3exp) && few;
+    const bool chunked = paired && d->fx_tv && (d->N % Q4L_CH == 0) && d->N >= 2 * Q4L_CH && few;
     a.eta = nullptr; a.Quui = nullptr;
     if (chunked && lv && lv[0] == 'o') {                        // DDP_Q4_LDS=o: the first chunked layout (A/B timing against q4c)
 #define Q4L(L_, R_) hipLaunchKernelGGL((back_pass_q4l_kernel<L_, R_>), grid, block, 0, h->stream, a)
@@ -959,31 +945,11 @@ int ddp_launch_back_pass_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx
 #undef Q4L
     } else if (chunked) {
         const ddp_kl_cost_terms nokl = {};
-#ifdef DDP_PROFILE_BUILD
-        if (c3exp) {
-            if (exp == 11) hipLaunchKernelGGL((back_pass_q4c_kernel<true, true, false, 8, 1>), grid, block, 0, h->stream, a, nokl);
-            else if (exp == 12) hipLaunchKernelGGL((back_pass_q4c_kernel<true, true, false, 8, 2>), grid, block, 0, h->stream, a, nokl);
-            else hipLaunchKernelGGL((back_pass_q4c_kernel<true, true, false, 8, 3>), grid, block, 0, h->stream, a, nokl);
-            DDP_HIP(hipGetLastError());
-            return 0;
-        }
-#endif
 #define Q4C_(L_, R_) hipLaunchKernelGGL((back_pass_q4c_kernel<L_, R_, false, 8>), grid, block, 0, h->stream, a, nokl)
         if (d->has_lims && reg2) Q4C_(true, true); else if (d->has_lims) Q4C_(true, false); else if (reg2) Q4C_(false, true); else Q4C_(false, false);
 #undef Q4C_
     } else if (paired) {
-        if (d->has_lims && reg2) {
-#ifdef DDP_PROFILE_BUILD
-            switch (exp) {
-            case 1: Q4P(true, true, 1); break; case 2: Q4P(true, true, 2); break; case 3: Q4P(true, true, 3); break;
-            case 4: Q4P(true, true, 4); break; case 7: Q4P(true, true, 7); break; default: Q4P(true, true, 0);
-            }
-#else
-            Q4P(true, true, 0);
-#endif
-        } else if (d->has_lims) Q4P(true, false, 0);
-        else if (reg2) Q4P(false, true, 0);
-        else Q4P(false, false, 0);
+        if (d->has_lims && reg2) Q4P(true, true); else if (d->has_lims) Q4P(true, false); else if (reg2) Q4P(false, true); else Q4P(false, false);
     } else {
         const int key = (d->has_lims ? 4 : 0) | (d->cost_tv ? 2 : 0) | (reg2 ? 1 : 0);
         switch (key) {
@@ -1001,12 +967,14 @@ int ddp_launch_back_pass_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx
 
 // back_pass_gps for n = 4, m = 1 with one η per trajectory: prepass (c̃• = c•/η + c•kl into the handle's pad buffer), the matrix-core
 // kernel above with the 1/η factors on the products with V, Quui = 1/Quu.  Returns 1 when the shape is not handled here.
-int ddp_launch_back_pass_gps_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                                const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                                const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                                const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                                double *Vxx, double *dV, int32_t *diverge)
+int ddp_launch_back_pass_gps_q4(ddp_handle h, const BPCall &call)
 {
+    const ddp_bp_desc *d = &call.d;
+    const ddp_kl_cost_terms *kl = call.kl;
+    const double *cx = call.cx, *cu = call.cu, *cxx = call.cxx, *cxu = call.cxu, *cuu = call.cuu, *fx = call.fx, *fu = call.fu, *lims = call.lims, *u = call.u;
+    const int32_t *active = call.active;
+    double *K = call.K, *k = call.k, *Quu = call.Quu, *Quui = call.Quui, *Vx = call.Vx, *Vxx = call.Vxx, *dV = call.dV;
+    int32_t *diverge = call.diverge;
     if (!(d->n == 4 && d->m == 1) || d->N < 2 || !d->fx_tv || !d->cost_tv || kl->eta_tv) return 1;
     const char *q4e = ddp_env(h, ENV_GPS_Q4);                      // 0: never (the lane-per-trajectory kernel instead; A/B timing, tests)
     if (q4e && q4e[0] == '0') return 1;
@@ -1028,14 +996,6 @@ int ddp_launch_back_pass_gps_q4(ddp_handle h, const ddp_bp_desc *d, const double
             a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
             a.eta = kl->eta; a.Quui = Quui; a.sink = (double *)h->sink;
             const dim3 grid((unsigned)((d->B + 3) / 4)), block(DDP_WAVE);
-#ifdef DDP_PROFILE_BUILD
-            const char *ex = ddp_env(h, ENV_Q4_EXP);            // removal experiments (profiles/q4_exp.sh): 1 no result stores, 2 no operand loads after the first two chunks
-            const int exp = ex ? atoi(ex) : 0;
-            if (d->has_lims && exp == 1) hipLaunchKernelGGL((back_pass_q4c_kernel<true, false, true, 4, 1>), grid, block, 0, h->stream, a, *kl);
-            else if (d->has_lims && exp == 2) hipLaunchKernelGGL((back_pass_q4c_kernel<true, false, true, 4, 2>), grid, block, 0, h->stream, a, *kl);
-            else if (d->has_lims && exp == 3) hipLaunchKernelGGL((back_pass_q4c_kernel<true, false, true, 4, 3>), grid, block, 0, h->stream, a, *kl);
-            else
-#endif
             if (d->has_lims) hipLaunchKernelGGL((back_pass_q4c_kernel<true, false, true, 4>), grid, block, 0, h->stream, a, *kl);
             else hipLaunchKernelGGL((back_pass_q4c_kernel<false, false, true, 4>), grid, block, 0, h->stream, a, *kl);
             DDP_HIP(hipGetLastError());
@@ -1079,8 +1039,8 @@ int ddp_launch_back_pass_gps_q4(ddp_handle h, const ddp_bp_desc *d, const double
     const bool chunked = !(le && le[0] == '0') && d->N % Q4L_CH == 0 && d->N >= 2 * Q4L_CH && al16 && h->sink != nullptr && d->B <= 6144;
     if (chunked && d->has_lims) hipLaunchKernelGGL((back_pass_q4l_kernel<true, false, true, true>), grid, block, 0, h->stream, a);
     else if (chunked) hipLaunchKernelGGL((back_pass_q4l_kernel<false, false, true, true>), grid, block, 0, h->stream, a);
-    else if (d->has_lims) hipLaunchKernelGGL((back_pass_q4_kernel<true, true, false, 0, true>), grid, block, 0, h->stream, a);
-    else hipLaunchKernelGGL((back_pass_q4_kernel<false, true, false, 0, true>), grid, block, 0, h->stream, a);
+    else if (d->has_lims) hipLaunchKernelGGL((back_pass_q4_kernel<true, true, false, true>), grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL((back_pass_q4_kernel<false, true, false, true>), grid, block, 0, h->stream, a);
     hipLaunchKernelGGL(gps_quui_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, h->stream, d->N, NB, (const double *)Quu,
                        (const int32_t *)diverge, active, Quui);
     DDP_HIP(hipGetLastError());

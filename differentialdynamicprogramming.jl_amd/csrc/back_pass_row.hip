@@ -410,17 +410,13 @@ int launch_row(ddp_handle h, const ddp_bp_desc *d, const BPRArgs &a)
 #endif
 
 // The padded sizes compiled here: NP in {4, 6, 8, 10, 12, 14}, MP in {1, 2, 4} (3 at NP = 12, 1 at NP = 14: NP + MP + 1 <= 16).
-// returns 1 if the shape has no row kernel (n > 14, m > 4, n + m > 15), 0 launched, < 0 error
+// (back_pass.hip chooses this kernel for n <= 14, m <= 4, n + m <= 15, m <= 3 above n = 10, m = 1 above n = 12, with a sink)
 #if DDP_ROW_PART == 0
 int ddp_launch_back_pass_row_hi(ddp_handle h, const ddp_bp_desc *d, const void *args);
-int ddp_launch_back_pass_row(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge)
+int ddp_launch_back_pass_row(ddp_handle h, const BPCall &c)
 {
+    const ddp_bp_desc *d = &c.d;
     const int n = d->n, m = d->m;
-    if (n < 1 || m < 1 || m > 4 || n > 14 || n + m > 15 || (n > 12 && m > 1) || (n > 10 && m > 3)) return 1;
     const long N = d->N;
     BPRArgs a;
     a.n = n; a.m = m; a.N = d->N; a.B = d->B; a.regType = d->regType;
@@ -430,11 +426,10 @@ int ddp_launch_back_pass_row(ddp_handle h, const ddp_bp_desc *d, const double *c
     a.cxx_t = d->cost_tv ? nn : 0; a.cxx_b = d->cost_batched ? nn * (d->cost_tv ? N : 1) : 0;
     a.cxu_t = d->cost_tv ? nm : 0; a.cxu_b = d->cost_batched ? nm * (d->cost_tv ? N : 1) : 0;
     a.cuu_t = d->cost_tv ? mm : 0; a.cuu_b = d->cost_batched ? mm * (d->cost_tv ? N : 1) : 0;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.lims = lims;
-    a.u = u; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     a.sink = (double *)h->sink;
-    if (!a.sink) return 1;
     const int np = n <= 4 ? 4 : (n + 1) & ~1;
     if (np > 8) return ddp_launch_back_pass_row_hi(h, d, &a);
     const int mp = m <= 2 ? m : 4;
@@ -443,7 +438,7 @@ int ddp_launch_back_pass_row(ddp_handle h, const ddp_bp_desc *d, const double *c
     ROW_CASE(6, 1) ROW_CASE(6, 2) ROW_CASE(6, 4)
     ROW_CASE(8, 1) ROW_CASE(8, 2) ROW_CASE(8, 4)
 #undef ROW_CASE
-    return 1;
+    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", d->n, d->m);
 }
 #else
 // second translation unit (back_pass_row_hi.hip): the larger padded sizes, compiled beside the first
@@ -457,6 +452,6 @@ int ddp_launch_back_pass_row_hi(ddp_handle h, const ddp_bp_desc *d, const void *
     if (np == 12) { if (m == 1) ROW_CASE(12, 1) if (m == 2) ROW_CASE(12, 2) ROW_CASE(12, 3) }
     if (np == 14) { ROW_CASE(14, 1) }
 #undef ROW_CASE
-    return 1;
+    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", d->n, d->m);
 }
 #endif

@@ -42,6 +42,7 @@ namespace {
 constexpr int SH_GMAX = 16;                         // groups per launch
 constexpr int SH_TAB = 64;                          // hash slots for distinct λ values
 constexpr int CH = 8;                               // steps per chunk: chunk c = steps 8c .. 8c + 7 (absolute index)
+static_assert(DDP_SH_MIN_N == 2 * CH, "back_pass.hip chooses this kernel from two chunks of steps on");
 constexpr int GREC = 348;                           // doubles per step of a group's record stream: Vxx 100 | K 20 | Quu 4 | M 16 x 14
 constexpr int G_K = 100, G_QUU = 120, G_M = 124, MLD = 14, G_OUT = 124;
 constexpr int GCHUNK = GREC * CH;                   // 2 784 doubles = 22 272 bytes
@@ -83,6 +84,9 @@ constexpr int C_WAVE = NSB * GCHUNK, C_WSZ = NEI * EIMG + 8;        // per affin
 constexpr int C_FLAGS = C_WAVE + NAFF * C_WSZ;
 constexpr int SH_LDS_DOUBLES = (P_FLAGS > C_FLAGS ? P_FLAGS : C_FLAGS) + 48;
 constexpr size_t SH_LDS_BYTES = (size_t)SH_LDS_DOUBLES * 8;
+// result stores are non-temporal below this batch, plain from it on (profiles/r05_sh_stores.txt: B = 2 048 0.43 ms non-temporal vs
+// 0.53 plain, B = 3 072 0.65 plain vs 0.84 non-temporal)
+constexpr int SH_NT_MAX_B = 3072;
 static_assert(SH_LDS_BYTES <= 160 * 1024, "LDS budget");
 // producer flags (ints behind P_FLAGS): chain -> builder -> publisher
 enum { PF_CREADY = 0, PF_BDONE = 1, PF_BREADY = 2, PF_PDONE = 3, PF_CDIV = 4 };
@@ -1022,17 +1026,12 @@ extern "C" int ddp_sh_max_tiles(int B, int ncu)
     return best > floor_ ? best : floor_;
 }
 
-// Shared-LTI backward pass.  Returns 1 when the shape is not handled here, 0 when launched (the caller then runs the per-trajectory
-// kernels with *fb_active as their activity mask), < 0 on error.
-int ddp_launch_back_pass_sh(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const int32_t *active, double *K,
-                            double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge,
-                            const int32_t **fb_active)
+// Shared-LTI backward pass for n = 10, m = 2, shared LTI operands without limits, N >= 2 CH, 16-byte aligned arrays, with a sink
+// (back_pass.hip tests them).  0 when launched (the caller then runs the per-trajectory kernels with *fb_active as their activity
+// mask), < 0 on error.
+int ddp_launch_back_pass_sh(ddp_handle h, const BPCall &c, const int32_t **fb_active)
 {
-    if (d->has_lims || d->m != 2 || d->n != 10 || d->fx_batched || d->cost_batched || d->fx_tv || d->cost_tv) return 1;
-    if (d->N < 2 * CH || !h->sink) return 1;
-    if ((((uintptr_t)cx | (uintptr_t)cu | (uintptr_t)K | (uintptr_t)k | (uintptr_t)Quu | (uintptr_t)Vx | (uintptr_t)Vxx | (uintptr_t)cxx | (uintptr_t)cuu) & 15) != 0) return 1;
+    const ddp_bp_desc *d = &c.d;
     const int B = d->B, N = d->N;
     if (!h->ncu) { hipDeviceProp_t pr; DDP_HIP(hipGetDeviceProperties(&pr, h->device)); h->ncu = pr.multiProcessorCount; }
     const int Wmax = ddp_sh_max_tiles(B, h->ncu);
@@ -1055,24 +1054,19 @@ int ddp_launch_back_pass_sh(ddp_handle h, const ddp_bp_desc *d, const double *cx
     ShArgs a;
     a.N = N; a.B = B; a.ncu = h->ncu; a.regType = d->regType; a.wmax = Wmax;
     a.test_abort = ddp_env(h, ENV_TEST_SH_ABORT) ? 1 : 0;
-    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.fx = fx; a.fu = fu; a.lambda = lambda; a.active = active;
-    a.K = K; a.k = k; a.Quu = Quu; a.Vx = Vx; a.Vxx = Vxx; a.dV = dV; a.diverge = diverge;
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     a.ctl = (ShCtl *)base; a.items = (int4 *)(base + o_items); a.perm = (int *)(base + o_perm); a.fb_active = (int32_t *)(base + o_fb);
     a.rec = (double *)(base + o_rec);
     a.sink = (double *)h->sink;
     if (a.B <= 8 * 1024) hipLaunchKernelGGL(sh_group_kernel<true>, dim3(1), dim3(1024), 0, h->stream, a);
     else hipLaunchKernelGGL(sh_group_kernel<false>, dim3(1), dim3(1024), 0, h->stream, a);
-    if (!h->sh_attr) {
-        DDP_HIP(hipFuncSetAttribute((const void *)sh_back_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LDS_BYTES));
-        DDP_HIP(hipFuncSetAttribute((const void *)sh_back_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LDS_BYTES));
-        DDP_HIP(hipFuncSetAttribute((const void *)sh_back_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LDS_BYTES));
-        DDP_HIP(hipFuncSetAttribute((const void *)sh_back_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_LDS_BYTES));
-        h->sh_attr = true;
-    }
     const dim3 grid(SH_GMAX + Wmax), block(SH_THREADS);
-    // result stores: non-temporal while the batch is small, plain from DDP_SH_NT_MAX_B trajectories on (default 3 072; store16_res)
-    const char *nte = ddp_env(h, ENV_SH_NT_MAX_B);
-    const bool nts = B < (nte ? atoi(nte) : 3072);
+    for (const void *kern : {(const void *)sh_back_kernel<false, false>, (const void *)sh_back_kernel<true, false>, (const void *)sh_back_kernel<false, true>,
+                             (const void *)sh_back_kernel<true, true>})
+        if (int rc = ddp_raise_lds(h, kern, (int)SH_LDS_BYTES)) return rc;
+    // result stores: non-temporal while the batch is small, plain from SH_NT_MAX_B trajectories on (store16_res)
+    const bool nts = B < SH_NT_MAX_B;
     if (d->regType == 2) { if (nts) hipLaunchKernelGGL((sh_back_kernel<true, true>), grid, block, SH_LDS_BYTES, h->stream, a); else hipLaunchKernelGGL((sh_back_kernel<true, false>), grid, block, SH_LDS_BYTES, h->stream, a); }
     else { if (nts) hipLaunchKernelGGL((sh_back_kernel<false, true>), grid, block, SH_LDS_BYTES, h->stream, a); else hipLaunchKernelGGL((sh_back_kernel<false, false>), grid, block, SH_LDS_BYTES, h->stream, a); }
     DDP_HIP(hipGetLastError());

@@ -24,7 +24,7 @@ extern "C" {
 const char *ddp_last_error(void) { return g_err; }
 const char *ddp_version(void) { return "ddp_amd 0.3.0 (gfx950, fp64)"; }
 
-static const char *const ddp_env_names[ENV_COUNT] = {"DDP_BACKPASS", "DDP_SH_MIN_B", "DDP_MX2", "DDP_DPPW", "DDP_DPPW_EXP", "DDP_MX_LDS", "DDP_Q4_EXP", "DDP_Q4_SINGLE", "DDP_Q4_LDS", "DDP_GPS_Q4", "DDP_GPS_Q4L", "DDP_DF_DENSE", "DDP_FORWARD", "DDP_FORWARD64", "DDP_FORWARD_FAST", "DDP_FORWARD_FUSE", "DDP_FORWARD_LANE", "DDP_FORWARD_PEND", "DDP_FORWARD_PIPE", "DDP_ILQG_COMPACT", "DDP_ILQG_LSGROUPS", "DDP_TEST_COMPACT_ALLOC_FAIL", "DDP_GPS_LANE", "DDP_FCOV_Q4", "DDP_FCOV_Q4L", "DDP_KL_LDS", "DDP_TEST_SH_ABORT", "DDP_SH_NT_MAX_B", "DDP_MXG_COAL", "DDP_FORWARD_MID", "DDP_PEND_CHUNK"};
+static const char *const ddp_env_names[ENV_COUNT] = {"DDP_BACKPASS", "DDP_SH_MIN_B", "DDP_MX2", "DDP_DPPW", "DDP_MX_LDS", "DDP_Q4_SINGLE", "DDP_Q4_LDS", "DDP_GPS_Q4", "DDP_GPS_Q4L", "DDP_DF_DENSE", "DDP_FORWARD", "DDP_FORWARD64", "DDP_FORWARD_FAST", "DDP_FORWARD_FUSE", "DDP_FORWARD_LANE", "DDP_FORWARD_PEND", "DDP_FORWARD_PIPE", "DDP_ILQG_COMPACT", "DDP_ILQG_LSGROUPS", "DDP_TEST_COMPACT_ALLOC_FAIL", "DDP_GPS_LANE", "DDP_FCOV_Q4", "DDP_FCOV_Q4L", "DDP_KL_LDS", "DDP_TEST_SH_ABORT", "DDP_MXG_COAL", "DDP_FORWARD_MID", "DDP_PEND_CHUNK"};
 
 int ddp_reload_env(ddp_handle h)
 {
@@ -67,7 +67,7 @@ static int create_impl(int device, void *ext_stream, bool adopt, ddp_handle *out
     h->device = device;
     h->scratch = nullptr;
     h->scratch_bytes = 0;
-    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->sh_attr = false; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } h->last_kernel[0] = h->last_kernel[1] = nullptr; ddp_reload_env(h);
+    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } h->last_kernel[0] = h->last_kernel[1] = nullptr; ddp_reload_env(h);
     h->h_pinned = nullptr;
     h->timing = nullptr; h->timing_cap = 0; h->tev_ok = false;
     h->owns_stream = !adopt;
@@ -79,9 +79,9 @@ static int create_impl(int device, void *ext_stream, bool adopt, ddp_handle *out
         return -2;
     }
     if (hipHostMalloc((void **)&h->h_pinned, 256) != hipSuccess) h->h_pinned = nullptr;
-    // + a flag word behind it (df.hip) + 1 KB that stays ZERO (offset 4352: loads of padded rows / columns are pointed at it, back_pass_mf2)
-    if (hipMalloc(&h->sink, 4096 + 256 + 1024) != hipSuccess) h->sink = nullptr;
-    else if (hipMemset(h->sink, 0, 4096 + 256 + 1024) != hipSuccess) { hipFree(h->sink); h->sink = nullptr; }
+    // the sink: 4 KB that masked-out lanes may write + a flag word behind it (df.hip)
+    if (hipMalloc(&h->sink, 4096 + 256) != hipSuccess) h->sink = nullptr;
+    else if (hipMemset(h->sink, 0, 4096 + 256) != hipSuccess) { hipFree(h->sink); h->sink = nullptr; }
     *out = h;
     return 0;
 }
@@ -292,6 +292,17 @@ int ddp_event_elapsed_ms(ddp_handle h, void *start, void *stop, float *ms)
 
 }   // extern "C"
 
+int ddp_raise_lds(ddp_handle h, const void *kernel, int bytes)
+{
+    for (const auto &e : h->lds_raised)
+        if (e.first == kernel && e.second >= bytes) return 0;
+    DDP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    for (auto &e : h->lds_raised)
+        if (e.first == kernel) { e.second = bytes; return 0; }
+    h->lds_raised.push_back({kernel, bytes});
+    return 0;
+}
+
 int ddp_scratch(ddp_handle h, size_t bytes, void **out)
 {
     DDP_DEVICE(h);
@@ -324,7 +335,7 @@ int ddp_back_pass_f64_dev(ddp_handle h, const ddp_bp_desc *d, const double *cx, 
     DDP_CHECK(h && d, "back_pass: null handle/descriptor");
     DDP_CHECK(cx && cu && cxx && cxu && cuu && fx && fu && lambda, "back_pass: null input pointer");
     DDP_CHECK(K && k && Quu && Vx && Vxx && dV && diverge, "back_pass: null output pointer");
-    return ddp_launch_back_pass(h, d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge);
+    return ddp_launch_back_pass(h, {*d, cx, cu, cxx, cxu, cuu, fx, fu, lambda, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge});
 }
 
 int ddp_back_pass_f64(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,

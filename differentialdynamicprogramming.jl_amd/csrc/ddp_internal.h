@@ -4,15 +4,18 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <utility>
+#include <vector>
 #include "../../include/ddp_amd.h"
 
 #define DDP_WAVE 64
 #define DDP_MAX_N_GENERIC 32      // run-time-sized kernels: n <= 32, m <= DDP_MAX_M
+#define DDP_SH_MIN_N 16           // the shared-operand backward pass needs two chunks of steps (back_pass_sh.hip)
 
 // The DDP_* switches of the dispatchers (kernel choice for A/B timing and for the tests that force every code path) are read from the
 // environment ONCE per handle (ddp_create) and again on ddp_reload_env(): no launch calls getenv, and a setenv() in another thread
 // cannot race with a launch.  ddp_env() returns the cached value or nullptr.
-enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_DPPW_EXP, ENV_MX_LDS, ENV_Q4_EXP, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_SH_NT_MAX_B, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_COUNT };
+enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_MX_LDS, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_COUNT };
 
 struct ddp_handle_s {
     int          device;
@@ -27,7 +30,6 @@ struct ddp_handle_s {
     void        *sh;              // back_pass_sh.hip: control block, work items, record streams of the shared-LTI backward pass
     size_t       sh_bytes;
     int          sh_timeouts;     // timed-out tiles counted by control blocks that have been freed (ddp_sh_timeouts)
-    bool         sh_attr;         // its dynamic-LDS attribute has been set on this device
     int          ncu;             // compute units of the device (0: not asked yet)
     struct { const void *Q, *R; int n, m, ok; } diag_cache[8];      // verdicts of ddp_check_cost_diag (forward_pass.hip)
     int          diag_next;
@@ -37,7 +39,8 @@ struct ddp_handle_s {
     char         envv[ENV_COUNT][24];
     bool         envset[ENV_COUNT];
     const char  *last_kernel[4];  // what the last backward / forward / user-derivative / user-cost dispatch launched (ddp_last_kernel)
-    void        *sink;            // 4 KB of device memory that masked-out lanes may write (stores without an exec-mask branch)
+    void        *sink;            // 4 KB of device memory that masked-out lanes may write (stores without an exec-mask branch) + a flag word (df.hip)
+    std::vector<std::pair<const void *, int>> lds_raised;   // kernels whose dynamic-LDS limit has been raised on this device, to how many bytes
     double      *timing;          // ddp_ilqg_set_timing: host buffer [3, timing_cap] or NULL
     int          timing_cap;
     hipEvent_t   tev[4];          // created on first use
@@ -110,111 +113,72 @@ int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *
                         const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                         double *Vxx, double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
 
-// kernel launchers (each in its own .hip)
-int ddp_launch_back_pass(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                         const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                         const double *fu, const double *lambda, const double *lims, const double *u,
-                         const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                         double *Vxx, double *dV, int32_t *diverge);
-int ddp_launch_back_pass_gps(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
-// one lane per trajectory (n = 4, m <= 2); returns 1 when the shape is not handled
-int ddp_launch_back_pass_gps_lane(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
-// n=10, m=2, no limits: one wave per trajectory, all matrices of a step in one 16x16 fp64 MFMA tile; 1 = not applicable
-int ddp_launch_back_pass_mx(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const int32_t *active, double *K,
-                            double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge);
-// any n <= 10, m <= 2 without limits inside the same tile (run-time sizes, results straight to global memory); 1 = not applicable
-int ddp_launch_back_pass_mxr(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge);
+// raises the dynamic-LDS limit of `kernel` to at least `bytes`, once per handle (capi.hip; the attribute belongs to the device the handle
+// runs on: a process-wide flag would leave a second handle on another device at the 64 KB default)
+int ddp_raise_lds(ddp_handle h, const void *kernel, int bytes);
 
-// back_pass_mxg.hip: the tile kernel for any n <= 12, m <= 4 (m <= 3 above n = 8), with or without limits; 1 = not applicable
-int ddp_launch_back_pass_mxg(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge);
+// One backward-pass call: the descriptor, operands and results as the C ABI passes them (ddp_back_pass_f64_dev), and for back_pass_gps
+// its KL terms and Quui.  Every backward-pass launcher takes one; back_pass.hip chooses which one runs.
+struct BPCall {
+    ddp_bp_desc d;
+    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
+    const int32_t *active;
+    double *K, *k, *Quu, *Vx, *Vxx, *dV;
+    int32_t *diverge;
+    const ddp_kl_cost_terms *kl = nullptr;      // back_pass_gps only
+    double *Quui = nullptr;                     // back_pass_gps only
+};
 
-// the same tile arithmetic with a chain wave + a write-back wave per trajectory (back_pass_mx2.hip); 1 = not applicable
-int ddp_launch_back_pass_mx2(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const int32_t *active, double *K,
-                             double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge);
-
+// the dispatcher (back_pass.hip) and back_pass_gps (run-time sizes n <= 32, m <= 8)
+int ddp_launch_back_pass(ddp_handle h, const BPCall &c);
+int ddp_launch_back_pass_gps(ddp_handle h, const BPCall &c);
+// Family launchers.  Each launches the kernel of its family for a call back_pass.hip has chosen it for (the shape and alignment tests
+// live there); 0 launched, < 0 error.
+// back_pass_gps for n = 4, m <= 2 and time-varying operands, one lane per trajectory (back_pass_gps_lane.hip); 1 = not applicable
+int ddp_launch_back_pass_gps_lane(ddp_handle h, const BPCall &c);
+// back_pass_gps for n = 4, m = 1 with one η per trajectory on the matrix cores (back_pass_q4.hip); 1 = not applicable
+int ddp_launch_back_pass_gps_q4(ddp_handle h, const BPCall &c);
+// n=10, m=2, no limits: one wave per trajectory, all matrices of a step in one 16x16 fp64 MFMA tile (back_pass_mx.hip)
+int ddp_launch_back_pass_mx(ddp_handle h, const BPCall &c);
+// any n <= 10, m <= 2 without limits inside the same tile (run-time sizes, results straight to global memory)
+int ddp_launch_back_pass_mxr(ddp_handle h, const BPCall &c);
+// the same tile arithmetic with a chain wave + a write-back wave per trajectory (back_pass_mx2.hip)
+int ddp_launch_back_pass_mx2(ddp_handle h, const BPCall &c);
+// the tile kernel for any n <= 12, m <= 4 (m <= 3 above n = 8), with or without limits (back_pass_mxg.hip)
+int ddp_launch_back_pass_mxg(ddp_handle h, const BPCall &c);
+// the 16-lane-row kernel compiled for padded sizes — any n <= 14, m <= 4 with n + m <= 15 (back_pass_row.hip)
+int ddp_launch_back_pass_row(ddp_handle h, const BPCall &c);
+// one wave per trajectory, the products on the fp64 matrix cores with LDS operands — any n <= 32, m <= 8 (back_pass_mid.hip)
+int ddp_launch_back_pass_mid(ddp_handle h, const BPCall &c);
 // shared time-invariant operands (n=10, m=2, no limits): the matrix recursion once per distinct λ, an affine chain per trajectory
-// (back_pass_sh.hip); 1 = not applicable; 0 = launched, the trajectories it left out are flagged in *fb_active
-// back_pass_row.hip: the 16-lane-row kernel compiled for padded sizes — any n <= 14, m <= 4 with n + m <= 15; 1 = not applicable
-int ddp_launch_back_pass_row(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
-// back_pass_mid.hip: one wave per trajectory, the products on the fp64 matrix cores with LDS operands — any n <= 32, m <= 8; 1 = not applicable
-int ddp_launch_back_pass_mid(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
+// (back_pass_sh.hip); the trajectories it left out are flagged in *fb_active
+extern "C" int ddp_sh_max_tiles(int B, int ncu);      // capacity of its work-item list: the most consumer tiles any grouping of B trajectories can make
+int ddp_launch_back_pass_sh(ddp_handle h, const BPCall &c, const int32_t **fb_active);
+// 16-lane DPP-row backward pass, 4 trajectories per wave, (10, 2) and (4, 1) (back_pass_dpp.hip)
+int ddp_launch_back_pass_dpp(ddp_handle h, const BPCall &c);
+// the (10, 2) row kernel with a write-back wave per chain wave (back_pass_dppw.hip)
+int ddp_launch_back_pass_dppw(ddp_handle h, const BPCall &c);
+// n = 4, m = 1 on v_mfma_f64_4x4x4_4b, one trajectory per MFMA block (back_pass_q4.hip)
+int ddp_launch_back_pass_q4(ddp_handle h, const BPCall &c);
+// large states (even n <= 64, even m <= 8): 256-thread work-group per trajectory (back_pass_big.hip)
+int ddp_launch_back_pass_big(ddp_handle h, const BPCall &c);
+// 32 < n <= 64, m <= 8 at run time: every product on the fp64 matrix cores (back_pass_mf2.hip), and the round-5 kernel of the exact
+// n = 64, m = 8 shape (back_pass_mfma.hip).  `lims_active`: has_lims with real limits (lims[1,1] <= lims[1,2]), read by the caller
+int ddp_launch_back_pass_mf2(ddp_handle h, const BPCall &c, bool lims_active);
+int ddp_launch_back_pass_mfma(ddp_handle h, const BPCall &c, bool lims_active);
 // forward_pass_row.hip: the 16-lane-row rollout compiled for padded sizes (LQ problems, n <= 14, m <= 4); 1 = not applicable
 int ddp_launch_forward_row(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
-extern "C" int ddp_sh_max_tiles(int B, int ncu);      // capacity of its work-item list: the most consumer tiles any grouping of B trajectories can make
-int ddp_launch_back_pass_sh(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const int32_t *active, double *K,
-                            double *k, double *Quu, double *Vx, double *Vxx, double *dV, int32_t *diverge,
-                            const int32_t **fb_active);
-
-// 16-lane DPP-row backward pass (4 trajectories per wave); returns 1 when the shape has no such kernel
-int ddp_launch_back_pass_dpp(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
-// n = 4, m = 1 on v_mfma_f64_4x4x4_4b, one trajectory per MFMA block (back_pass_q4.hip); returns 1 for any other shape
-int ddp_launch_back_pass_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                            const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                            const double *fu, const double *lambda, const double *lims, const double *u,
-                            const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                            double *Vxx, double *dV, int32_t *diverge);
-// large states (even n <= 64, even m <= 8): 256-thread work-group per trajectory; returns 1 when not applicable
-int ddp_launch_back_pass_big(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge);
-// n=64, m=8 on the fp64 matrix cores (v_mfma_f64_16x16x4_f64); returns 1 for any other shape
-// 32 < n <= 64, m <= 8 at run time: every product on the fp64 matrix cores (back_pass_mf2.hip); 1 = not applicable, 2 = (64, 8) with real
-// limits and `defer_64x8_lims`: nothing launched, the caller takes the round-5 kernel
-int ddp_launch_back_pass_mf2(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                             const double *fu, const double *lambda, const double *lims, const double *u,
-                             const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                             double *Vxx, double *dV, int32_t *diverge, bool defer_64x8_lims);
-int ddp_launch_back_pass_mfma(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                              const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                              const double *fu, const double *lambda, const double *lims, const double *u,
-                              const int32_t *active, double *K, double *k, double *Quu, double *Vx,
-                              double *Vxx, double *dV, int32_t *diverge);
 // 16-lane DPP-row forward pass + separate cost kernel; returns 1 when the shape has no such kernel
 int ddp_launch_forward_dpp(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
                             const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
                             const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
 
-// LQ n=10/m=2 rollout as a producer/consumer pipeline of one work-group per 4 rollouts (forward_pass_pipe.hip); 1 = not applicable
 struct QPOptsDev;
 int ddp_launch_boxqp_big(ddp_handle h, int m, int count, const double *H, const double *g, const double *lower, const double *upper,
                          const double *x0, const QPOptsDev &o, double *x, int32_t *result, double *Hfree, uint8_t *free_out);   // boxqp_big.hip
+// LQ n=10/m=2 rollout as a producer/consumer pipeline of one work-group per 4 rollouts (forward_pass_pipe.hip); 1 = not applicable
 int ddp_launch_forward_pipe(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
                             const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
                             const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);

@@ -686,8 +686,8 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
                  : ddp_df_f64_dev(h, &pw, ws.x, ws.u, ws.s.dodf, cx, cu, fxw, fuw);                              // STEP 1
         if (rc) return rc;
         if (timed) DDP_HIP(hipEventRecord(h->tev[1], st));
-        rc = ddp_launch_back_pass(h, &d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx,
-                                  dV, div);                                                                  // STEP 2
+        rc = ddp_launch_back_pass(h, {d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx,
+                                      dV, div});                                                             // STEP 2
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, ws.s);
         if (timed) DDP_HIP(hipEventRecord(h->tev[2], st));
@@ -894,7 +894,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
         DDP_HIP(hipEventRecord(h->sched_ev[1], h->sched_aux));
         rc = ddp_df_f64_dev(h, &pw, ws.x, ws.u, s.dodf, cx, cu, fxw, fuw);                                     // STEP 1
         if (rc) return rc;
-        rc = ddp_launch_back_pass(h, &d, cx, cu, p->Q, cxu, p->R, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div);   // STEP 2
+        rc = ddp_launch_back_pass(h, {d, cx, cu, p->Q, cxu, p->R, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div});   // STEP 2
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, s);
         const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};                         // STEP 3

@@ -10,13 +10,6 @@
 #include <type_traits>
 #include "ddp_internal.h"
 
-// back_pass_gps on the matrix-core kernel of back_pass_q4.hip (n = 4, m = 1, one η per trajectory); 1 = shape not handled there
-int ddp_launch_back_pass_gps_q4(ddp_handle h, const ddp_bp_desc *d, const double *cx, const double *cu,
-                                const double *cxx, const double *cxu, const double *cuu, const double *fx,
-                                const double *fu, const ddp_kl_cost_terms *kl, const double *lims, const double *u,
-                                const int32_t *active, double *K, double *k, double *Quu, double *Quui, double *Vx,
-                                double *Vxx, double *dV, int32_t *diverge);
-
 namespace {
 
 constexpr int NMAXK = DDP_MAX_N_GENERIC, MMAXK = DDP_MAX_M;
@@ -664,13 +657,14 @@ int ddp_back_pass_gps_f64_dev(ddp_handle h, const ddp_bp_desc *d,
               "back_pass_gps: null argument");
     DDP_HIP(hipMemsetAsync(Quui, 0, sizeof(double) * (size_t)d->m * d->m * d->N * d->B, h->stream));
     const char *env = ddp_env(h, ENV_GPS_LANE);                     // 0: always the run-time-sized kernel (cross-check in the tests)
+    const BPCall c = {*d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge, kl, Quui};
     if (!(env && env[0] == '0') && kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!d->has_lims || (lims && u))) {
-        const int r4 = ddp_launch_back_pass_gps_q4(h, d, cx, cu, cxx, cxu, cuu, fx, fu, kl, lims, u, active, K, k, Quu, Quui, Vx, Vxx, dV, diverge);
+        const int r4 = ddp_launch_back_pass_gps_q4(h, c);
         if (r4 <= 0) return r4;                                   // n = 4, m = 1, one η per trajectory: the matrix-core kernel (DDP_GPS_Q4=0: not)
-        const int rc = ddp_launch_back_pass_gps_lane(h, d, cx, cu, cxx, cxu, cuu, fx, fu, kl, lims, u, active, K, k, Quu, Quui, Vx, Vxx, dV, diverge);
+        const int rc = ddp_launch_back_pass_gps_lane(h, c);
         if (rc <= 0) return rc;
     }
-    return ddp_launch_back_pass_gps(h, d, cx, cu, cxx, cxu, cuu, fx, fu, kl, lims, u, active, K, k, Quu, Quui, Vx, Vxx, dV, diverge);
+    return ddp_launch_back_pass_gps(h, c);
 }
 
 int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *fx, int fx_batched,
@@ -852,6 +846,7 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
     ddp_bp_desc d;
     d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = 0;
     d.regType = 1; d.has_lims = lims != nullptr;
+    const BPCall gps = {d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, kp, nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
     auto poll = [&](int *out) -> int {
         DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
         DDP_HIP(hipStreamSynchronize(st));
@@ -870,9 +865,9 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
         if ((rc = dual(0, it))) return rc;
         for (int guard = 0;; ++guard) {                    // back passes until the KL-regularised Quu is positive definite everywhere (:95-122)
             DDP_HIP(hipMemsetAsync(Sigma, 0, m * m * NB * 8, st));
-            rc = ddp_launch_back_pass_gps_q4(h, &d, cx, cu, cxx, cxu, cuu, fx, fu, &t, lims, kp, nullptr, K, k, Sigmai, Sigma, Vx, Vxx, dV, div);
-            if (rc > 0) rc = ddp_launch_back_pass_gps_lane(h, &d, cx, cu, cxx, cxu, cuu, fx, fu, &t, lims, kp, nullptr, K, k, Sigmai, Sigma, Vx, Vxx, dV, div);
-            if (rc > 0) rc = ddp_launch_back_pass_gps(h, &d, cx, cu, cxx, cxu, cuu, fx, fu, &t, lims, kp, nullptr, K, k, Sigmai, Sigma, Vx, Vxx, dV, div);
+            rc = ddp_launch_back_pass_gps_q4(h, gps);
+            if (rc > 0) rc = ddp_launch_back_pass_gps_lane(h, gps);
+            if (rc > 0) rc = ddp_launch_back_pass_gps(h, gps);
             if (rc) return rc;
             int pending = 0;
             if ((rc = dual(1, it)) || (rc = poll(&pending))) return rc;                                    // :103-105

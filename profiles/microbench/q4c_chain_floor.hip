@@ -63,9 +63,9 @@ __global__ __launch_bounds__(64) void chain(int steps, double *out, long long *t
                 double *q = rec + 5 * 64 * (i & 1) + lane;
                 q[0] = prev.Vn; q[64] = prev.Kc; q[128] = prev.vx; q[192] = prev.kk; q[256] = prev.Quu;
             };
-            q4_step<LIMS, REG2, 0, decltype(mid), false>(i, o, s, res, par, mid);
+            q4_step<LIMS, REG2, decltype(mid), false>(i, o, s, res, par, mid);
         } else {
-            q4_step<LIMS, REG2, 0, Q4NoMid, false>(i, o, s, res, par);
+            q4_step<LIMS, REG2, Q4NoMid, false>(i, o, s, res, par);
         }
         prev = res;
         if (FETCH) in = nx;
