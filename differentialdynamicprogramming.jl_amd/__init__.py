@@ -158,7 +158,8 @@ _EXAMPLES = _os.path.join(_lib._HERE, "user_examples")
 
 
 def example_source(name):
-    """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``)."""
+    """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``), or the same
+    model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -166,21 +167,23 @@ def example_source(name):
 class DeviceProblem:
     """The user's own ``f``, ``costfun`` and ``df`` (iLQG.jl:143) as HIP device source: ``dynamics``, ``stage_cost``,
     ``derivatives`` and, with ``terminal=True``, ``terminal_cost`` (``const_hessian=True``: ``cost_hessians``) — the contract is in
-    include/ddp_amd.h.  The library compiles the source for gfx950 with hiprtc, once per handle, and runs ``forward_pass``, ``df``,
+    include/ddp_amd.h.  ``autodiff=True`` (DDP_USER_AUTODIFF): ``dynamics``, ``stage_cost`` and ``terminal_cost`` are templates over
+    the scalar type of x and u, ``derivatives`` is not needed, and the library derives df by forward-mode AD on the device.  The library compiles the source for gfx950 with hiprtc, once per handle, and runs ``forward_pass``, ``df``,
     ``costfun`` and the whole ``iLQG`` on the device.  ``params``: ``[nparam]`` shared by the batch or ``[nparam, B]`` per trajectory
     (may be replaced per call through the ``params=`` keyword of the entry points).  ``diff``: ``None`` (``-``) or a ``WrappedDiff``."""
     kind = 2
 
-    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, diff=None):
+    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None):
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
-        self.terminal, self.const_hessian = bool(terminal), bool(const_hessian)
-        self.flags = (1 if self.terminal else 0) | (2 if self.const_hessian else 0)
+        self.terminal, self.const_hessian, self.autodiff = bool(terminal), bool(const_hessian), bool(autodiff)
+        self.flags = (1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0)
         self.diff_mask = _diff_mask(diff, self.n) if self.n <= 32 else 0
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
 
     def check(self, extra_options=None):
-        """Compile for gfx950 without a device (ddp_user_check); returns the compiler log, raises DDPError with it on failure."""
+        """Compile for gfx950 without a device (ddp_user_check), with the problem's flags (``autodiff`` included); returns the
+        compiler log, raises DDPError with it on failure."""
         L = _lib.lib()
         rc = L.ddp_user_check(self.source.encode(), self.n, self.m, self.nparam, self.flags,
                               extra_options.encode() if extra_options else None)

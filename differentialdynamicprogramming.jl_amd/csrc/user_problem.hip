@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "ddp_internal.h"
+#include "user_autodiff.h"
 #include "user_problem_kernels.h"
 
 DDP_USER_ABI
@@ -63,12 +64,19 @@ std::string g_log;                                          // log of the last c
 // dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
 constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024;
 
-struct Layout { int chunk, rlanes, dflanes; };
+struct Layout { int chunk, rlanes, dflanes, adj, adh; };
 
-// chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit
+// chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit.
+// DDP_USER_AUTODIFF: seeds per call of `dynamics` (adj) and per Hessian block (adh) of ddp_user_df_ad, chosen by the kernel's VGPR and
+// scratch counts (-Rpass-analysis=kernel-resource-usage)
 Layout layout_of(int n, int m, int flags)
 {
     Layout L;
+    // nz <= 6 (car, pendcart): one call of `dynamics`, two Hessian blocks (3 block pairs).  lq 10x2 spills with 3-wide blocks or
+    // 6-wide Jacobian chunks next to its 2-wide blocks; beyond nz = 12 the kernel spills anyway and 8-wide blocks halve the compile time
+    const int nz = n + m;
+    L.adj = nz <= 8 ? nz : 4;
+    L.adh = nz <= 6 ? (nz + 1) / 2 : (nz <= 12 ? 2 : 8);
     const int ps = 2 * m + m * n + n;                            // DDP_PS
     L.rlanes = 64;
     L.chunk = (ROLL_LDS / 8 / 64 - 1) / ps;
@@ -104,11 +112,13 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M)", m, DDP_MAX_M);
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
-    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN)) == 0, "user problem: unknown flags 0x%x", flags);
+    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF)) == 0, "user problem: unknown flags 0x%x", flags);
     DDP_CHECK(n >= 32 || (wrap >> n) == 0, "user problem: diff_wrap = 0x%x names coordinates at or above n = %d", wrap, n);
     const std::string src(source);
     const char *need[] = {"dynamics", "stage_cost", "derivatives"};
-    for (const char *f : need) DDP_CHECK(has_identifier(src, f), "user problem: the source defines no `%s` (the contract of ddp_amd.h)", f);
+    const int nneed = (flags & DDP_USER_AUTODIFF) ? 2 : 3;      // DDP_USER_AUTODIFF derives `derivatives`
+    for (int k = 0; k < nneed; ++k)
+        DDP_CHECK(has_identifier(src, need[k]), "user problem: the source defines no `%s` (the contract of ddp_amd.h)", need[k]);
     if (flags & DDP_USER_TERMINAL)
         DDP_CHECK(has_identifier(src, "terminal_cost"), "user problem: DDP_USER_TERMINAL is set but the source defines no `terminal_cost`");
     if (flags & DDP_USER_CONST_HESSIAN)
@@ -125,11 +135,22 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
     char head[512];
     snprintf(head, sizeof head,
              "#define DDP_N %d\n#define DDP_M %d\n#define DDP_NP %d\n#define DDP_TERMINAL %d\n#define DDP_CONST_HESSIAN %d\n"
-             "#define DDP_WRAP 0x%xu\n#define DDP_CHUNK %d\n#define DDP_RLANES %d\n#define DDP_DFLANES %d\n",
-             n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes);
+             "#define DDP_WRAP 0x%xu\n#define DDP_CHUNK %d\n#define DDP_RLANES %d\n#define DDP_DFLANES %d\n"
+             "#define DDP_AUTODIFF %d\n#define DDP_ADJ %d\n#define DDP_ADH %d\n",
+             n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
+             (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh);
     std::string s(head);
+    const bool ad = (flags & DDP_USER_AUTODIFF) != 0;
+    if (ad) {
+        s += "#line 1 \"ddp_user_autodiff\"\n";
+        s += kUserAutodiff;
+    }
     s += "#line 1 \"user_source\"\n";
     s += source;
+    if (ad) {
+        s += "\n#line 1 \"ddp_user_autodiff_derivs\"\n";
+        s += kUserAutodiffDerivs;
+    }
     s += "\n#line 1 \"ddp_user_kernels\"\n";
     s += DDP_USER_ABI_TEXT;
     s += "\n";
@@ -198,6 +219,7 @@ int compile(const char *source, int n, int m, int nparam, int flags, unsigned wr
 struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr;
+    const char *df_name = nullptr;                               // ddp_user_df, or ddp_user_df_ad (DDP_USER_AUTODIFF)
     Layout L{};
 };
 struct Cache { std::map<std::string, Module> mods; };
@@ -223,7 +245,7 @@ struct UserProblem final : ddp_family {
         void *args[] = {&a};
         const long R = (long)N * Bc;
         DDP_HIP(hipModuleLaunchKernel(mod->df, (unsigned)((R + mod->L.dflanes - 1) / mod->L.dflanes), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
-        hh->last_kernel[2] = "ddp_user_df";
+        hh->last_kernel[2] = mod->df_name;
         return 0;
     }
     int hessians(ddp_handle hh, int Bc, const int32_t *map, double *cxx, double *cxu, double *cuu) const override
@@ -369,9 +391,10 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
         if (rc) return rc;
         Module M;
         M.L = layout_of(n, m, flags);
+        M.df_name = (flags & DDP_USER_AUTODIFF) ? "ddp_user_df_ad" : "ddp_user_df";
         DDP_HIP(hipModuleLoadData(&M.mod, code.data()));
         const bool ok = hipModuleGetFunction(&M.roll, M.mod, "ddp_user_rollout") == hipSuccess &&
-                        hipModuleGetFunction(&M.df, M.mod, "ddp_user_df") == hipSuccess &&
+                        hipModuleGetFunction(&M.df, M.mod, M.df_name) == hipSuccess &&
                         hipModuleGetFunction(&M.cost, M.mod, "ddp_user_cost") == hipSuccess &&
                         (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess);
         if (!ok) {

@@ -1,8 +1,8 @@
 // user_problem_kernels.h — the kernel templates of a user problem (user_problem.hip), as program text for hiprtc.
 //
 // The program hiprtc compiles is: the size / flag macros (DDP_N, DDP_M, DDP_NP, DDP_TERMINAL, DDP_CONST_HESSIAN, DDP_WRAP, DDP_CHUNK,
-// DDP_RLANES, DDP_DFLANES), the user's source, DDP_USER_ABI (the argument structs, shared with the host through the macro below) and
-// kUserKernels.  Every size is a compile-time constant there: the state of a rollout stays in VGPRs and every loop over n, m unrolls.
+// DDP_RLANES, DDP_DFLANES, DDP_AUTODIFF, DDP_ADJ, DDP_ADH), the user's source (with DDP_AUTODIFF between the texts of user_autodiff.h),
+// DDP_USER_ABI (the argument structs, shared with the host through the macro below) and kUserKernels.  Every size is a compile-time constant there: the state of a rollout stays in VGPRs and every loop over n, m unrolls.
 //
 //   ddp_user_rollout   one lane per (trajectory, α) rollout, DDP_RLANES rollouts per 64-lane work-group.  The operand streams (u, x, k, K)
 //                      of DDP_CHUNK steps are staged through LDS as one contiguous run per rollout and stream (a rollout's chunk of K is
@@ -11,6 +11,8 @@
 //                      the pattern that tops out at ~1.8 TB/s (profiles/r06_narrow_streams.txt).  The stage cost is fused (csum).
 //   ddp_user_df        one lane per (time step, trajectory), DDP_DFLANES per work-group; `derivatives` writes straight into the lane's
 //                      LDS slot, and each output array leaves as the contiguous run of the work-group's (step, trajectory) pairs.
+//   ddp_user_df_ad     DDP_AUTODIFF (in place of ddp_user_df): the same, with forward-mode AD of the templated model (user_autodiff.h)
+//                      writing the slot.
 //   ddp_user_cost      costfun on given trajectories: one wave per trajectory, lanes over time.
 //   ddp_user_hessians  DDP_CONST_HESSIAN: cost_hessians once per trajectory.
 #pragma once
@@ -192,7 +194,16 @@ __device__ __forceinline__ void ddp_df_store(const double *lds, const int *rb, d
     }
 }
 
-extern "C" __global__ __launch_bounds__(64) void ddp_user_df(UserDfArgs a)
+// ddp_user_df_ad (DDP_AUTODIFF): the same kernel, with the lane's slot written by ddp_ad_derivatives (user_autodiff.h), the derivatives of
+// the user's templated model, instead of the user's `derivatives`
+#if DDP_AUTODIFF
+#define DDP_DF_KERNEL ddp_user_df_ad
+#define DDP_DERIVATIVES ddp_ad_derivatives
+#else
+#define DDP_DF_KERNEL ddp_user_df
+#define DDP_DERIVATIVES derivatives
+#endif
+extern "C" __global__ __launch_bounds__(64) void DDP_DF_KERNEL(UserDfArgs a)
 {
     constexpr int n = DDP_N, m = DDP_M;
     constexpr int OFX = 0, OFU = OFX + n * n, OCX = OFU + n * m, OCU = OCX + n, OXX = OCU + m, OXU = OXX + n * n, OUU = OXU + n * m;
@@ -219,9 +230,9 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_df(UserDfArgs a)
             // the Hessians `derivatives` writes are not used (cost_hessians supplies them): lane-private arrays that are never read,
             // so the compiler drops the stores
             double nxx[n * n], nxu[n * m], nuu[m * m];
-            derivatives(x, u, i, N, p, L + OFX, L + OFU, L + OCX, L + OCU, nxx, nxu, nuu);
+            DDP_DERIVATIVES(x, u, i, N, p, L + OFX, L + OFU, L + OCX, L + OCU, nxx, nxu, nuu);
 #else
-            derivatives(x, u, i, N, p, L + OFX, L + OFU, L + OCX, L + OCU, L + OXX, L + OXU, L + OUU);
+            DDP_DERIVATIVES(x, u, i, N, p, L + OFX, L + OFU, L + OCX, L + OCU, L + OXX, L + OXU, L + OUU);
 #endif
         }
     }

@@ -914,8 +914,10 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
 end
 
 # ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
-# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, diff) holds the source; it is compiled with hiprtc for the
-# handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff) holds the source; it is compiled with hiprtc for
+# the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
+# autodiff=true (DDP_USER_AUTODIFF): dynamics / stage_cost / terminal_cost are templates over the scalar type of x and u, the source
+# needs no `derivatives`, and df is derived on the device by forward-mode AD.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -927,9 +929,9 @@ mutable struct DeviceProblem
     made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
-                       const_hessian::Bool=false, diff=-)
+                       const_hessian::Bool=false, autodiff::Bool=false, diff=-)
     wrap = Int(_diff_mask(diff, n))
-    p = DeviceProblem(String(source), n, m, nparam, (terminal ? 1 : 0) | (const_hessian ? 2 : 0), wrap, _f64(params),
+    p = DeviceProblem(String(source), n, m, nparam, (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0), wrap, _f64(params),
                       Dict{Ptr{Cvoid},Ptr{Cvoid}}())
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p

@@ -467,10 +467,31 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * made); diff_wrap is the bit mask of ddp_problem::diff_wrap.  Limits: n <= DDP_MAX_N_USER, m <= DDP_MAX_M, nparam <= DDP_USER_MAX_NPARAM;
  * anything else is refused before compiling.  A problem is compiled once per (source, n, m, nparam, flags) and handle: the handle keeps
  * the module until ddp_destroy.  Kernel names (rocprofv3, ddp_last_kernel): ddp_user_rollout, ddp_user_df, ddp_user_cost,
- * ddp_user_hessians. */
+ * ddp_user_hessians.
+ *
+ * The terminal cost at the last step: `derivatives` at i == N-1 adds the gradient and Hessian in x of terminal_cost(x[:,N-1]) to cx
+ * and cxx (the backward pass has no separate terminal term; user_examples/pendcart.hip's w = 2 and car.hip follow this).
+ *
+ * DDP_USER_AUTODIFF: df by forward-mode automatic differentiation on the device.  The model functions are templates over the scalar
+ * type T of x and u, and `derivatives` is neither required nor called (a definition is ignored):
+ *
+ *   template <class T> __device__ void dynamics(const T *x, const T *u, int i, const double *p, T *xnext);
+ *   template <class T> __device__ T    stage_cost(const T *x, const T *u, int i, const double *p);
+ *   template <class T> __device__ T    terminal_cost(const T *x, const double *p);                       with DDP_USER_TERMINAL
+ *
+ * p, i and N stay plain; every intermediate that depends on x or u must be a T.  T = double in the rollout and cost kernels (the
+ * same code as a non-template model) and a dual number in ddp_user_df_ad, which writes what `derivatives` would: fx = ∂f/∂x,
+ * fu = ∂f/∂u at (x_i, u_i, i); cx, cu, cxx, cxu, cuu of stage_cost, plus, with DDP_USER_TERMINAL at i == N-1, the gradient and
+ * Hessian of terminal_cost in x.  cxx and cuu are exactly symmetric (one triangle is evaluated and mirrored).  With
+ * DDP_USER_AUTODIFF | DDP_USER_CONST_HESSIAN only fx, fu, cx, cu are derived (first-order passes) and cost_hessians stays.  A T
+ * supports + - * / (with T, double or int on either side), unary -, += -= *= /=, comparisons on the value, and
+ *   sin cos tan exp log sqrt pow (T^double, T^int, T^T, double^T) tanh sinh cosh atan atan2 asin acos fabs fmin fmax hypot
+ *   expm1 log1p, and rint floor (derivative 0);
+ * any other function of a T fails to compile, with its name in ddp_user_compile_log().  Kernel name: ddp_user_df_ad, in place of
+ * ddp_user_df. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
-enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2 };
+enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4 };
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
