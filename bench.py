@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — iLQG backward+forward pass throughput on MI355X (the BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,9 +13,17 @@ data-path exchange); the only collective is one all-reduce (RCCL) of a 4-double 
 step (Σ new cost, Σ expected-reduction terms, #diverged) — the line-search cost reduction of SURVEY.md §8(e).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) including
-  roofline     — dominant kernel (the back_pass kernel): algorithmic bytes / HIP-event time vs 8 TB/s
-  cpu_baseline — the CPU oracle (C restatement of the reference, single thread) on a bounded sample
-  machine_filling — the same pass at a batch that fills the GPU (outside the timed region, informational)
+  roofline     — dominant kernel (the back_pass kernel): algorithmic bytes / HIP-event time vs 8 TB/s; its `traffic` is the
+                 committed figure of profiles/pmc_traffic.json for this kernel and batch
+A plain run does only what that line needs: set-up, preheat, warm-up, the timed steps, --dump-outputs.  With --full, rank 0 of a
+single-GPU run then also measures, after the timed region (--no-traffic, --no-cpu-baseline, --no-other-configs and --fill-batch 0
+switch single legs off again):
+  roofline.traffic  — measured by two rocprofv3 --pmc child runs instead of replayed
+  cpu_baseline      — the CPU oracle (C restatement of the reference, single thread) on a bounded sample
+  full_line_search  — one back_pass + the rollouts of all 11 step sizes
+  machine_filling   — the same pass at a batch that fills the GPU
+  other_configs     — pass lines of BASELINE configs 3 and 4 and the off-shape lines (profiles/bench_configs.py in a child process)
+Without --full those keys are null.
 """
 import argparse
 import ctypes as C
@@ -257,12 +265,15 @@ def main():
                          "communicator (ddp_allreduce_stats_f64_dev; torch.distributed then only ships the 128-byte id)")
     ap.add_argument("--preheat", type=int, default=200, help="untimed passes BEFORE the warmup so that the GPU clocks have settled (a pass is "
                     "0.7 ms; a cold device ramps its clocks over the first ~50 ms); 0 = none")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure what the headline does not need (single GPU, "
+                    "rank 0): live PMC traffic, the CPU baseline, the full line search, the machine-filling batch and the other "
+                    "configurations; the --no-* options and --fill-batch 0 switch single legs off again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic (two rocprofv3 --pmc child runs of a 3-step "
                     "bench after the timed region); the committed figure of profiles/pmc_traffic.json is replayed instead")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the C3 / C4 pass lines (profiles/bench_configs.py in a child process)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="trajectories for the CPU baseline (0 = auto ~10-20 s)")
-    ap.add_argument("--fill-batch", type=int, default=32768, help="machine-filling batch reported next to the headline (0 = skip)")
+    ap.add_argument("--fill-batch", type=int, default=32768, help="machine-filling batch reported next to the headline with --full (0 = skip)")
     ap.add_argument("--dry-run", action="store_true", help="no device work: the ranks rendezvous (gloo), build their shard of the workload on "
                     "the host and share the statistics vector exactly as the timed run does; rank 0 prints the launch-contract line "
                     "(n_ranks_seen, per-rank seeds and input digests).  What a CPU-only host can check of `--gpus N` (tests/test_sharding_gloo.py)")
@@ -333,12 +344,13 @@ def main():
         elapsed = float(t.item())
     roofline = pb.roofline(bp_ms, fp_ms)
     stats_vec = pb.stats.cpu().numpy() if use_dist else None
-    # HBM traffic per launch: measured after the timed region by two rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE: separate passes)
-    # of a 3-step bench of the same workload (rank 0, single GPU); where that is not possible (rocprofv3 missing, multi-rank run,
-    # --no-traffic) the committed figure for THIS kernel at THIS batch is replayed — never a number of another batch or kernel
+    # HBM traffic per launch: with --full measured after the timed region by two rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE:
+    # separate passes) of a 3-step bench of the same workload (rank 0, single GPU); otherwise, or where that is not possible (rocprofv3
+    # missing, multi-rank run, --no-traffic), the committed figure for THIS kernel at THIS batch is replayed — never a number of another
+    # batch or kernel
     roofline["traffic_source"] = None
     profiled = "rocprofiler" in os.environ.get("LD_PRELOAD", "") or bool(os.environ.get("ROCP_TOOL_LIBRARIES"))     # already under rocprofv3
-    if rank == 0 and world == 1 and not args.no_traffic and not profiled and os.environ.get("DDP_BENCH_CHILD") != "1":
+    if args.full and rank == 0 and world == 1 and not args.no_traffic and not profiled and os.environ.get("DDP_BENCH_CHILD") != "1":
         try:
             tr, src = measure_traffic(roofline["kernel"].split("<")[0], B, N)
             roofline["traffic"], roofline["traffic_source"] = tr, src
@@ -369,17 +381,18 @@ def main():
 
     out = None
     if rank == 0:
+        extras = args.full and world == 1                       # the informational legs: outside the timed region, never in a plain run
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             cpu = cpu_baseline(pb, args.cpu_sample)
         ls = None
-        if world == 1 and not args.no_other_configs:
+        if extras and not args.no_other_configs:
             try:
                 ls = pb.line_search_variant(fence)
             except Exception as exc:                            # informational: never in the way of the headline
                 ls = {"error": str(exc)[-200:]}
         fill = None
-        if world == 1 and args.fill_batch and args.fill_batch != B:
+        if extras and args.fill_batch and args.fill_batch != B:
             A_, Bm_, Q_, R_, x0_ = pb.host
             del pb
             torch.cuda.empty_cache()
@@ -391,7 +404,7 @@ def main():
                     "back_pass_roofline_frac": r2["frac"], "forward_ms": r2["forward_kernels"]["avg_launch_ms"]}
             del pf
         other = None
-        if world == 1 and not args.no_other_configs:
+        if extras and not args.no_other_configs:
             other = other_configs()
         value = B * world * args.steps / elapsed
         out = {"metric": "iLQG iterations/sec (backward+forward, n=10 m=2 T=1000)", "value": round(value, 1),

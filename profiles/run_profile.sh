@@ -8,7 +8,7 @@ TAG=${1:-r01}
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT $OUT/profiles
-python bench.py --steps 50 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 50 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 for B in 1024 32768; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_b$B -o stats -- python $REPO/bench.py --steps 50 --warmup 5 --batch $B --no-cpu-baseline --no-other-configs --no-traffic --fill-batch 0 > $OUT/stats_b$B.log 2>&1

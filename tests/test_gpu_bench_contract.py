@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_has_the_contract_fields():
     env = dict(os.environ, DDP_BENCH_REHEARSALS="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--preheat", "10", "--cpu-sample", "2",
-                        "--no-other-configs", "--fill-batch", "0"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--no-other-configs", "--fill-batch", "0", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -41,6 +41,27 @@ def test_bench_line_has_the_contract_fields():
         assert "timed out" in rf["traffic_source"], rf["traffic_source"]
         pytest.skip("rocprofv3 child ran past its time limit on this box: traffic replayed from profiles/pmc_traffic.json, bounds not checked (%s)" % rf["traffic_source"][:120])
     assert 0.95 * rf["bytes_per_launch"] < rf["traffic"] < 1.5 * rf["bytes_per_launch"]
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the line carries the headline and the event-timed roofline, and nothing that takes a run of its own: no CPU
+    baseline, line search, machine-filling batch, other configurations or rocprofv3 children (traffic is the committed figure)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "f64" and d["higher_is_better"] is True and d["unit"] == "iterations/s"
+    assert abs(d["value"] - 1024 * 6 / (d["ms_per_step"] * 6e-3)) < 1e-3 * d["value"]
+    assert d.get("sh_timeouts") == 0, (d.get("sh_timeouts"), d.get("sh_timeout_info"))
+    for k in ("cpu_baseline", "machine_filling", "full_line_search", "other_configs"):
+        assert d[k] is None, (k, d[k])
+    rf = d["roofline"]
+    assert rf["avg_launch_ms"] > 0 and rf["forward_kernels"]["avg_launch_ms"] > 0
+    src = rf["traffic_source"] or ""
+    assert "replayed from the committed profile" in src or "no PMC profile committed" in src, src
 
 
 def _torchrun_bench(collective, port):
