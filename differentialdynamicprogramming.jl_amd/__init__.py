@@ -159,7 +159,8 @@ _EXAMPLES = _os.path.join(_lib._HERE, "user_examples")
 
 def example_source(name):
     """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``), or the same
-    model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``."""
+    model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``; ``"car_plant"``: the car with a plant for the
+    closed loop (``plant=True``)."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -170,13 +171,16 @@ class DeviceProblem:
     include/ddp_amd.h.  ``autodiff=True`` (DDP_USER_AUTODIFF): ``dynamics``, ``stage_cost`` and ``terminal_cost`` are templates over
     the scalar type of x and u, ``derivatives`` is not needed, and the library derives df by forward-mode AD on the device.  The library compiles the source for gfx950 with hiprtc, once per handle, and runs ``forward_pass``, ``df``,
     ``costfun`` and the whole ``iLQG`` on the device.  ``params``: ``[nparam]`` shared by the batch or ``[nparam, B]`` per trajectory
-    (may be replaced per call through the ``params=`` keyword of the entry points).  ``diff``: ``None`` (``-``) or a ``WrappedDiff``."""
+    (may be replaced per call through the ``params=`` keyword of the entry points).  ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
+    ``plant=True`` (DDP_USER_PLANT): the source also defines ``plant``, the true system that ``iLQG_mpc`` advances its trajectories
+    with instead of the model."""
     kind = 2
 
-    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None):
+    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False):
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
-        self.terminal, self.const_hessian, self.autodiff = bool(terminal), bool(const_hessian), bool(autodiff)
-        self.flags = (1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0)
+        self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
+        self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
+                      (8 if self.plant else 0))
         self.diff_mask = _diff_mask(diff, self.n) if self.n <= 32 else 0
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -723,58 +727,93 @@ def _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin,
     return o
 
 
+def _user_sched_args(problem, x0, u0, L, params, diff_fun):
+    """a DeviceProblem in iLQG_queue / iLQG_mpc: extents against the compiled n, m and the parameters, before any launch"""
+    (n, B), m = x0.shape, u0.shape[0]
+    _user_shapes(problem, n, m)
+    if u0.shape[2] != B:
+        raise DDPError("x0[n,B] and u0[m,N,B] have different B: %s, %s" % (x0.shape, u0.shape))
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    if diff_fun is not None and _diff_mask(diff_fun, n) != problem.diff_mask:
+        raise DDPError("DeviceProblem: diff_fun is compiled into the problem (DeviceProblem(..., diff=...))")
+    return problem._params(B, params)
+
+
 def iLQG_queue(problem, x0, u0, *, slots=0, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
-               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None):
+               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None):
     """``P = u0.shape[2]`` independent solves of ``iLQG`` through ``slots`` resident trajectories (``ddp_ilqg_queue_f64``): a slot whose
     solve has ended is flushed and armed with the next problem on the device, instead of idling until the slowest trajectory of a
     lock-step batch has ended.  Every solve is the solve ``iLQG`` performs at batch size ``slots``.
+    A ``DeviceProblem`` takes ``params`` (default: its own), ``(nparam,)`` shared or ``(nparam, P)`` one column per problem.
     Returns ``(x, u, traj_new, Vx, Vxx, cost, trace)`` with P columns; ``trace`` holds ``stats[8,P]``, ``status``, ``iter``, ``global_iters``."""
-    h = handle or default_handle()
     u0, x0 = _lib.f64(u0), _lib.f64(x0)
     if u0.ndim != 3 or x0.ndim != 2:
         raise ValueError("iLQG_queue: x0[n,P], u0[m,N,P]")
     m, N, P = u0.shape
     n = x0.shape[0]
-    _check_problem(problem, n, m, N, P)
-    dp = _DevProblem(problem, N, P, diff_fun)
-    o = _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    user = isinstance(problem, DeviceProblem)
     L = _lims(lims)
-    CL = dp.cost_len
+    if user:
+        prm, pb = _user_sched_args(problem, x0, u0, L, params, diff_fun)
+        CL = problem.cost_len(N)
+    else:
+        _check_problem(problem, n, m, N, P)
+        dp = _DevProblem(problem, N, P, diff_fun)
+        CL = dp.cost_len
+    o = _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
     x = _lib.result_array((n, N, P)); u = _lib.result_array((m, N, P))
     K = _lib.result_array((m, n, N, P)); k = _lib.result_array((m, N, P)); Quu = _lib.result_array((m, m, N, P))
     Vx = _lib.result_array((n, N, P)); Vxx = _lib.result_array((n, n, N, P)); cost = _lib.result_array((CL, P))
     stats = np.zeros((8, P), order="F")
     git = _C.c_int(0)
+    h = handle or default_handle()
     t0 = _time.time()
-    _lib.check(_lib.lib().ddp_ilqg_queue_f64(h.raw, _C.byref(dp.struct), _C.byref(o), int(slots), _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L),
-                                             *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), _C.byref(git)))
+    outs = tuple(map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)))
+    if user:
+        _lib.check(_lib.lib().ddp_user_ilqg_queue_f64(h.raw, problem._ptr(h), N, P, _lib.ptr(prm), pb, _C.byref(o), int(slots), _lib.ptr(x0),
+                                                      _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
+    else:
+        _lib.check(_lib.lib().ddp_ilqg_queue_f64(h.raw, _C.byref(dp.struct), _C.byref(o), int(slots), _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L),
+                                                 *outs, _C.byref(git)))
     trace = dict(stats=stats, status=stats[0].astype(int), iter=stats[1].astype(int), λ=stats[5], grad_norm=stats[6],
                  global_iters=git.value, time_total=_time.time() - t0)
     return x, u, GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, P)), Quu), Vx, Vxx, cost, trace
 
 
 def iLQG_mpc(problem, x0, u0, steps, *, zero_tail=False, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0,
-             dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None):
+             dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None):
     """Closed loop on the device (``ddp_ilqg_mpc_f64``): every trajectory of the batch is solved ``steps`` times; after each solve the
     first control is applied (model = plant: the next initial state is ``x[:,1]`` of the solution), the control sequence is shifted by
     one step (``mpc_shift``) and the problem is solved again without returning to the host.
+    A ``DeviceProblem`` takes ``params`` (default: its own), ``(nparam,)`` or ``(nparam, B)`` per trajectory; built with
+    ``plant=True`` its ``plant`` is the true system: ``xcl[:,t+1] = plant(xcl[:,t], ucl[:,t], t, p)`` starts the next solve.
     Returns ``(xcl[n,steps+1,B], ucl[m,steps,B], stats[8,steps,B], x_plan[n,N,B], u_plan[m,N,B], global_iters)``."""
-    h = handle or default_handle()
     u0, x0 = _lib.f64(u0), _lib.f64(x0)
     if u0.ndim != 3 or x0.ndim != 2:
         raise ValueError("iLQG_mpc: x0[n,B], u0[m,N,B]")
     m, N, B = u0.shape
     n = x0.shape[0]
-    _check_problem(problem, n, m, N, B)
-    dp = _DevProblem(problem, N, B, diff_fun)
-    o = _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    user = isinstance(problem, DeviceProblem)
     L = _lims(lims)
+    if user:
+        prm, pb = _user_sched_args(problem, x0, u0, L, params, diff_fun)
+    else:
+        _check_problem(problem, n, m, N, B)
+        dp = _DevProblem(problem, N, B, diff_fun)
+    o = _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
     steps = int(steps)
     xcl = np.zeros((n, steps + 1, B), order="F"); ucl = np.zeros((m, steps, B), order="F"); scl = np.zeros((8, steps, B), order="F")
     x = _lib.result_array((n, N, B)); u = _lib.result_array((m, N, B))
     git = _C.c_int(0)
-    _lib.check(_lib.lib().ddp_ilqg_mpc_f64(h.raw, _C.byref(dp.struct), _C.byref(o), steps, int(bool(zero_tail)), _lib.ptr(x0), _lib.ptr(u0),
-                                           _lib.ptr(L), *map(_lib.ptr, (xcl, ucl, scl, x, u)), _C.byref(git)))
+    h = handle or default_handle()
+    outs = tuple(map(_lib.ptr, (xcl, ucl, scl, x, u)))
+    if user:
+        _lib.check(_lib.lib().ddp_user_ilqg_mpc_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm), pb, _C.byref(o), steps, int(bool(zero_tail)),
+                                                    _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
+    else:
+        _lib.check(_lib.lib().ddp_ilqg_mpc_f64(h.raw, _C.byref(dp.struct), _C.byref(o), steps, int(bool(zero_tail)), _lib.ptr(x0), _lib.ptr(u0),
+                                               _lib.ptr(L), *outs, _C.byref(git)))
     return xcl, ucl, scl, x, u, git.value
 
 

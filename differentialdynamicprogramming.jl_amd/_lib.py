@@ -32,7 +32,8 @@ EXPORTS = [
     "ddp_comm_rccl_info", "ddp_comm_unique_id", "ddp_comm_create", "ddp_comm_destroy", "ddp_allreduce_stats_f64_dev",
     "ddp_user_check", "ddp_user_compile_log", "ddp_user_create", "ddp_user_destroy", "ddp_user_df_f64_dev", "ddp_user_df_f64",
     "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
-    "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64",
+    "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64", "ddp_user_ilqg_queue_f64_dev", "ddp_user_ilqg_queue_f64", "ddp_user_ilqg_mpc_f64_dev",
+    "ddp_user_ilqg_mpc_f64",
 ]
 
 

@@ -43,7 +43,7 @@ int ddp_reload_env(ddp_handle h)
 
 const char *ddp_last_kernel(ddp_handle h, int which)
 {
-    if (!h || which < 0 || which > 3 || !h->last_kernel[which]) return "";
+    if (!h || which < 0 || which > 4 || !h->last_kernel[which]) return "";
     return h->last_kernel[which];
 }
 

@@ -38,7 +38,7 @@ struct ddp_handle_s {
     hipEvent_t   sched_ev[2];
     char         envv[ENV_COUNT][24];
     bool         envset[ENV_COUNT];
-    const char  *last_kernel[4];  // what the last backward / forward / user-derivative / user-cost dispatch launched (ddp_last_kernel)
+    const char  *last_kernel[5];  // what the last backward / forward / user-derivative / user-cost / user-plant dispatch launched (ddp_last_kernel)
     void        *sink;            // 4 KB of device memory that masked-out lanes may write (stores without an exec-mask branch) + a flag word (df.hip)
     std::vector<std::pair<const void *, int>> lds_raised;   // kernels whose dynamic-LDS limit has been raised on this device, to how many bytes
     double      *timing;          // ddp_ilqg_set_timing: host buffer [3, timing_cap] or NULL
@@ -94,24 +94,36 @@ void ddp_user_release(ddp_handle h);
 // A problem family the iLQG driver (ilqg.hip) runs besides the registered ddp_problem kinds: the user's compiled problems
 // (user_problem.hip).  `map` (may be NULL) is the slot -> trajectory map of a compacted working set; the family reads what it keeps
 // per trajectory (its parameters) through it.  Derivatives are time-varying and per trajectory (fx[n,n,N,B] ...); the cost Hessians
-// too, or, with const_hessian, one set per trajectory written by hessians() (cxx[n,n,B] ...).
+// too, or, with const_hessian, one set per trajectory written by hessians() (cxx[n,n,B] ...) for the slots `active` names (NULL: all).
+// The slot scheduler's map also holds -1 (empty slot) and -2 (resting slot): the family never reads parameters through those.
+// has_plant: the closed loop of ddp_ilqg_sched_family_dev advances its trajectories with plant() instead of x_1 of the plan.
 struct ddp_family {
     int n, m, N, B, CL;
-    bool const_hessian;
+    bool const_hessian, has_plant;
     virtual ~ddp_family() {}
     virtual int df(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx,
                    double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu) const = 0;
-    virtual int hessians(ddp_handle h, int B, const int32_t *map, double *cxx, double *cxu, double *cuu) const = 0;
+    virtual int hessians(ddp_handle h, int B, const int32_t *map, const int32_t *active, double *cxx, double *cxu, double *cuu) const = 0;
     virtual int rollout(ddp_handle h, int B, const int32_t *map, const double *K, const double *k, const double *x0, const double *u,
                         const double *x, const double *alpha, int nalpha, const double *lims, const int32_t *active, double *xnew,
                         double *unew, double *cnew, double *csum) const = 0;
     virtual int costfun(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *cost,
                         double *csum) const = 0;
+    // closed loop, S slots: for every slot with adv[b] = t + 1 > 0 (its solve t of trajectory advp[b] has just ended)
+    // xcl[:, t+1, advp[b]] = plant(xcl[:, t, .], ucl[:, t, .], t, params of advp[b]), and x0s[:, b] the same when the slot was re-armed
+    // for that trajectory (map[b] == advp[b]).  xcl[n, steps+1, P], ucl[m, steps, P].
+    virtual int plant(ddp_handle h, int S, int steps, const int32_t *adv, const int32_t *advp, const int32_t *map, const double *ucl,
+                      double *xcl, double *x0s) const = 0;
 };
 // the device-resident iLQG of ilqg.hip for such a family (arguments as ddp_ilqg_ex_f64_dev)
 int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *o, const double *x0, int x0_prerolled, const double *u0,
                         const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                         double *Vxx, double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
+// the slot scheduler of ilqg.hip for such a family: the queue (steps == 0; arguments as ddp_ilqg_queue_f64_dev, f->B = P problems) or
+// the closed loop (steps >= 1; as ddp_ilqg_mpc_f64_dev, f->B = trajectories)
+int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *o, int slots, int steps, int zero_tail, const double *x0,
+                              const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
+                              double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters);
 
 // raises the dynamic-LDS limit of `kernel` to at least `bytes`, once per handle (capi.hip; the attribute belongs to the device the handle
 // runs on: a process-wide flag would leave a second handle on another device at the 64 KB default)

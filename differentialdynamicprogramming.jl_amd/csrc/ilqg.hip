@@ -330,7 +330,8 @@ __global__ void stats_kernel(int B, Traj s, const int32_t *map, int only_finishe
 
 
 // ---- slot scheduler (ddp_ilqg_queue_f64_dev, ddp_ilqg_mpc_f64_dev): S resident slots work through P >= S problems (queue), or every
-// slot re-solves its own problem `steps` times in closed loop (MPC: apply u_0, the model is the plant, shift, solve again).  A slot
+// slot re-solves its own problem `steps` times in closed loop (MPC: apply u_0, the model is the plant — or a user family's plant() —,
+// shift, solve again).  A slot
 // whose solve has ended is flushed and re-armed ON THE DEVICE at the end of the global iteration in which it ended; the host only
 // polls the number of busy slots.  The state machine of a solve is the one of ilqg_impl (same kernels, same launches per global
 // iteration), so a solve does the arithmetic of its stand-alone solve at the same batch size.
@@ -345,6 +346,7 @@ struct Sched {
     // results per problem (queue) / last plan per trajectory (MPC)
     double *x, *u, *cost, *K, *k, *Quu, *Vx, *Vxx, *stats;
     double *xcl, *ucl, *stats_cl;       // MPC: closed-loop states [n,steps+1,P], controls [m,steps,P], summaries [8,steps,P]
+    int32_t *adv, *advp;                // MPC with a plant (else NULL): step + 1 of the solve that ended in the last sched_take_kernel (0: none), its trajectory
 };
 
 // end of a global iteration (and once before the first): flush the slots whose solve has ended, re-arm them — one wave per slot
@@ -356,6 +358,7 @@ __global__ __launch_bounds__(TAKE_T) void sched_take_kernel(int n, int m, int N,
     // the slot's state as every thread of the work-group sees it BEFORE anybody changes it
     const int ready = q.ready[b], running = s.run[b], arming = q.initm[b], prob = q.map[b], left0 = q.left[b], nofl = q.noflush[b];
     __syncthreads();
+    if (q.adv && lane == 0) q.adv[b] = 0;
     if (ready) {                                                   // its initial rollout (on the side stream) passed: the solve starts with
         if (lane == 0) { q.ready[b] = 0; q.initm[b] = 0; s.run[b] = 1; s.dodf[b] = 1; atomicAdd(counter, 1); }     // the next global iteration
         return;
@@ -393,6 +396,7 @@ __global__ __launch_bounds__(TAKE_T) void sched_take_kernel(int n, int m, int N,
                 r[7] = s.csum[b];
             }
             if (valid) {
+                if (q.adv && lane == 0) { q.adv[b] = step + 1; q.advp[b] = prob; }      // the plant (launched next) overwrites xcl[:, step + 1]
                 for (int e = lane; e < n; e += TAKE_T) q.xcl[(size_t)n * ((size_t)(q.mpc_steps + 1) * t + step) + e] = xb[e];
                 for (int e = lane; e < m; e += TAKE_T) q.ucl[(size_t)m * ((size_t)q.mpc_steps * t + step) + e] = ub[e];
                 for (int e = lane; e < n; e += TAKE_T) q.xcl[(size_t)n * ((size_t)(q.mpc_steps + 1) * t + step + 1) + e] = xb[(N > 1 ? n : 0) + e];
@@ -588,7 +592,7 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     const double *fx = own_fx ? fxw : p->A, *fu = own_fx ? fuw : p->Bm;
     const double *cxx = fam ? hxx : p->Q, *cxu_ = fam ? hxu : cxu, *cuu = fam ? huu : p->R;
     if (chess) {                                           // the constant cost Hessians: once per trajectory (again after a compaction)
-        rc = fam->hessians(h, (int)B, nullptr, hxx, hxu, huu);
+        rc = fam->hessians(h, (int)B, nullptr, nullptr, hxx, hxu, huu);
         if (rc) return rc;
     }
 
@@ -675,7 +679,7 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
             Bw = R;
             pw.B = (int)R; d.B = (int)R;
             if (chess) {
-                rc = fam->hessians(h, (int)R, ws.map, hxx, hxu, huu);
+                rc = fam->hessians(h, (int)R, ws.map, nullptr, hxx, hxu, huu);
                 if (rc) return rc;
             }
         }
@@ -775,18 +779,22 @@ int ddp_ilqg_warm_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opt
 }
 
 // ---- the slot scheduler (kernels above).  S slots, P problems (queue: P >= S; MPC: S == P, `steps` solves per trajectory).
+// fam: a user family (ddp_ilqg_sched_family_dev) in place of the registered kind of `p`, as in ilqg_impl; every family call reads the
+// parameters of a slot's problem through the slot map.
 static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo, int slots, int mpc_steps, int zero_tail,
                            const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
                            double *Quu, double *Vx, double *Vxx, double *cost, double *stats, double *xcl, double *ucl,
-                           double *stats_cl, int *global_iters)
+                           double *stats_cl, int *global_iters, const ddp_family *fam = nullptr)
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && p && x0 && u0 && x && u, "ilqg_sched: null argument");
     ddp_ilqg_opts od;
     if (!oo) { ddp_ilqg_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->n_alpha >= 1 && oo->n_alpha <= 16, "ilqg_sched: n_alpha=%d out of [1,16]", oo->n_alpha);
-    const size_t n = p->n, m = p->m, N = p->N, P = p->B, na = oo->n_alpha, CL = ddp_cost_len(p);
+    const size_t n = p->n, m = p->m, N = p->N, P = p->B, na = oo->n_alpha, CL = fam ? fam->CL : ddp_cost_len(p);
     const bool pend = p->kind == DDP_PROBLEM_PENDCART, mpc = mpc_steps > 0;
+    // a user family: own time-varying fx, fu and cost Hessians (per step, or one set per slot with const_hessian), as in ilqg_impl
+    const bool own_fx = pend || fam, chess = fam && fam->const_hessian, plant = mpc && fam && fam->has_plant;
     DDP_CHECK(N >= 2, "ilqg_sched: N=%d (at least two time steps)", (int)N);
     if (mpc) slots = (int)P;                                            // every trajectory keeps its slot
     if (slots <= 0 || (size_t)slots > P) slots = (int)(P < 4096 ? P : 4096);
@@ -797,11 +805,13 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     // ---- one block: working set of S slots, derivative / candidate workspace, scheduler state
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t f_x = al(n * N * S * 8), f_u = al(m * N * S * 8), f_c = al(CL * S * 8), f_K = al(m * n * N * S * 8), f_Q = al(m * m * N * S * 8),
-                 f_V = al(n * n * N * S * 8), f_fx = pend ? al(n * n * N * S * 8) : 0, f_fu = pend ? al(n * m * N * S * 8) : 0,
-                 f_d = al(S * 8), f_i = al(S * 4);
+                 f_V = al(n * n * N * S * 8), f_fx = own_fx ? al(n * n * N * S * 8) : 0, f_fu = own_fx ? al(n * m * N * S * 8) : 0,
+                 hT = chess ? 1 : N, f_hxx = fam ? al(n * n * hT * S * 8) : 0, f_hxu = fam ? al(n * m * hT * S * 8) : 0,
+                 f_huu = fam ? al(m * m * hT * S * 8) : 0, f_d = al(S * 8), f_i = al(S * 4);
     const size_t bytes = 2 * f_x /* x, Vx */ + 2 * f_u /* u, k */ + f_c + f_K + f_Q + f_V + al(n * S * 8) /* x0s */ + 2 * f_u /* u0s, us */ +
                          f_x + f_u /* cx, cu */ + f_fx + f_fu + na * (f_x + f_u + f_c + f_d) /* candidates */ + (f_x + f_u + f_c + f_d) /* initial rollout */ +
-                         al(2 * S * 8) + f_i /* dV, div */ + al(n * m * 8) + 4 * f_d + 10 * f_i /* Traj */ + 6 * f_i /* scheduler */ + 2 * f_i /* more */ + 512;
+                         al(2 * S * 8) + f_i /* dV, div */ + al(n * m * 8) + 4 * f_d + 10 * f_i /* Traj */ + 6 * f_i /* scheduler */ + 2 * f_i /* more */ + 512 +
+                         f_hxx + f_hxu + f_huu + (plant ? 2 * f_i : 0) /* adv, advp */;
     void *blk = nullptr;
     DDP_HIP(hipMalloc(&blk, bytes));
     struct Free { void *q; ~Free() { hipFree(q); } } free_blk{blk};
@@ -811,7 +821,8 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     ws.x = (double *)take(f_x); ws.Vx = (double *)take(f_x); ws.u = (double *)take(f_u); ws.k = (double *)take(f_u); ws.cost = (double *)take(f_c);
     ws.K = (double *)take(f_K); ws.Quu = (double *)take(f_Q); ws.Vxx = (double *)take(f_V); ws.x0 = (double *)take(al(n * S * 8));
     double *u0s = (double *)take(f_u), *us = (double *)take(f_u);
-    double *cx = (double *)take(f_x), *cu = (double *)take(f_u), *fxw = pend ? (double *)take(f_fx) : nullptr, *fuw = pend ? (double *)take(f_fu) : nullptr;
+    double *cx = (double *)take(f_x), *cu = (double *)take(f_u), *fxw = own_fx ? (double *)take(f_fx) : nullptr, *fuw = own_fx ? (double *)take(f_fu) : nullptr;
+    double *hxx = fam ? (double *)take(f_hxx) : nullptr, *hxu = fam ? (double *)take(f_hxu) : nullptr, *huu = fam ? (double *)take(f_huu) : nullptr;
     double *xn = (double *)take(na * f_x), *un = (double *)take(na * f_u), *cn = (double *)take(na * f_c), *cs = (double *)take(na * f_d);
     double *xi = (double *)take(f_x), *ui = (double *)take(f_u), *ci = (double *)take(f_c), *csi = (double *)take(f_d);
     double *dV = (double *)take(al(2 * S * 8));
@@ -832,6 +843,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     int *counter = (int *)take(256);
     q.qhead = (int *)take(256);
     q.x = x; q.u = u; q.cost = cost; q.K = K; q.k = k; q.Quu = Quu; q.Vx = Vx; q.Vxx = Vxx; q.stats = stats; q.xcl = xcl; q.ucl = ucl; q.stats_cl = stats_cl;
+    q.adv = plant ? (int32_t *)take(f_i) : nullptr; q.advp = plant ? (int32_t *)take(f_i) : nullptr;
     ws.map = q.map;
     DDP_CHECK(h->h_pinned, "ilqg_sched: pinned poll buffer missing");
 
@@ -865,9 +877,10 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     pw.B = (int)S;
     ddp_bp_desc d;
     d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)S;
-    d.fx_tv = pend ? 1 : p->dyn_tv; d.fx_batched = pend ? 1 : p->dyn_batched;
-    d.cost_tv = 0; d.cost_batched = 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
-    const double *fx = pend ? fxw : p->A, *fu = pend ? fuw : p->Bm;
+    d.fx_tv = own_fx ? 1 : p->dyn_tv; d.fx_batched = own_fx ? 1 : p->dyn_batched;
+    d.cost_tv = (fam && !chess) ? 1 : 0; d.cost_batched = fam ? 1 : 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
+    const double *fx = own_fx ? fxw : p->A, *fu = own_fx ? fuw : p->Bm;
+    const double *cxx = fam ? hxx : p->Q, *cxu_ = fam ? hxu : cxu, *cuu = fam ? huu : p->R;
     // the line search in the groups ilqg_impl uses at this batch size (same launches -> same kernels -> same bits per solve)
     const char *genv = ddp_env(h, ENV_ILQG_LSGROUPS);
     const double rpw = pend ? 64.0 : (n <= 16 ? 4.0 : 1.0);
@@ -886,15 +899,21 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
         DDP_HIP(hipEventRecord(h->sched_ev[0], st));
         DDP_HIP(hipStreamWaitEvent(h->sched_aux, h->sched_ev[0], 0));
         h->stream = h->sched_aux;
-        rc = ddp_forward_pass_f64_dev(h, &pw, nullptr, nullptr, ws.x0, us, nullptr, &one, 1, lims, q.initm, xi, ui, ci, csi);
+        // const_hessian: the Hessians of the problem an armed slot has just taken, before it joins (the running slots keep theirs)
+        if (chess) rc = fam->hessians(h, (int)S, q.map, q.initm, hxx, hxu, huu);
+        if (!rc)
+            rc = fam ? fam->rollout(h, (int)S, q.map, nullptr, nullptr, ws.x0, us, nullptr, &one, 1, lims, q.initm, xi, ui, ci, csi)
+                     : ddp_forward_pass_f64_dev(h, &pw, nullptr, nullptr, ws.x0, us, nullptr, &one, 1, lims, q.initm, xi, ui, ci, csi);
         h->stream = st;
         if (rc) return rc;
         hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)S), dim3(64), 0, h->sched_aux, (int)n, (int)m, (int)N, (int)CL, xi, ui, ci, csi, s, ws.x, ws.u, ws.cost);
         hipLaunchKernelGGL(sched_init_advance_kernel, dim3((unsigned)S), dim3(64), 0, h->sched_aux, (int)m, (int)N, q, s);
         DDP_HIP(hipEventRecord(h->sched_ev[1], h->sched_aux));
-        rc = ddp_df_f64_dev(h, &pw, ws.x, ws.u, s.dodf, cx, cu, fxw, fuw);                                     // STEP 1
+        rc = fam ? fam->df(h, (int)S, q.map, ws.x, ws.u, s.dodf, fxw, fuw, cx, cu, chess ? nullptr : hxx, chess ? nullptr : hxu,
+                           chess ? nullptr : huu)
+                 : ddp_df_f64_dev(h, &pw, ws.x, ws.u, s.dodf, cx, cu, fxw, fuw);                                 // STEP 1
         if (rc) return rc;
-        rc = ddp_launch_back_pass(h, {d, cx, cu, p->Q, cxu, p->R, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div});   // STEP 2
+        rc = ddp_launch_back_pass(h, {d, cx, cu, cxx, cxu_, cuu, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div});   // STEP 2
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, s);
         const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};                         // STEP 3
@@ -908,8 +927,10 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
                                    gi == 1 ? (const int32_t *)nullptr : (const int32_t *)more, mk);
                 mask = mk;
             }
-            rc = ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * S * a0,
-                                          un + m * N * S * a0, cn + CL * S * a0, cs + S * a0);
+            rc = fam ? fam->rollout(h, (int)S, q.map, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * S * a0,
+                                    un + m * N * S * a0, cn + CL * S * a0, cs + S * a0)
+                     : ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * S * a0,
+                                                un + m * N * S * a0, cn + CL * S * a0, cs + S * a0);
             if (rc) return rc;
         }
         const int slot = git % POLL;
@@ -918,6 +939,10 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
                            ws.x, ws.u, ws.cost, ws.k, 0, (double *)nullptr, (double *)nullptr, (const int32_t *)nullptr, counter + 32);      // STEP 4
         DDP_HIP(hipStreamWaitEvent(st, h->sched_ev[1], 0));
         hipLaunchKernelGGL(sched_take_kernel, dim3((unsigned)S), dim3(TAKE_T), 0, st, (int)n, (int)m, (int)N, (int)CL, q, ws, counter + slot);
+        if (plant) {                 // the true system replaces x_1 of the plan, before the next initial rollout reads x0s
+            rc = fam->plant(h, (int)S, mpc_steps, q.adv, q.advp, q.map, ucl, xcl, ws.x0);
+            if (rc) return rc;
+        }
         ++git;
         if (slot == POLL - 1 || git >= hard_cap) {
             DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4 * (slot + 1), hipMemcpyDeviceToHost, st));
@@ -933,6 +958,23 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     if (global_iters) *global_iters = git;
     return 0;
 }
+
+}   // extern "C"
+
+// the scheduler for a family of ddp_family (user_problem.hip), with a problem struct that carries the sizes only (B = problems)
+int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *oo, int slots, int steps, int zero_tail, const double *x0,
+                              const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
+                              double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters)
+{
+    DDP_CHECK(f, "ilqg_sched: null family");
+    DDP_CHECK(steps >= 0, "ilqg_mpc: steps=%d", steps);
+    ddp_problem pf = {};
+    pf.kind = -1; pf.n = f->n; pf.m = f->m; pf.N = f->N; pf.B = f->B;
+    return ilqg_sched_impl(h, &pf, oo, slots, steps, zero_tail, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, xcl, ucl, stats_cl,
+                           global_iters, f);
+}
+
+extern "C" {
 
 int ddp_ilqg_queue_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o, int slots, const double *x0, const double *u0,
                            const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,

@@ -112,7 +112,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M)", m, DDP_MAX_M);
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
-    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF)) == 0, "user problem: unknown flags 0x%x", flags);
+    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT)) == 0, "user problem: unknown flags 0x%x",
+              flags);
     DDP_CHECK(n >= 32 || (wrap >> n) == 0, "user problem: diff_wrap = 0x%x names coordinates at or above n = %d", wrap, n);
     const std::string src(source);
     const char *need[] = {"dynamics", "stage_cost", "derivatives"};
@@ -123,6 +124,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
         DDP_CHECK(has_identifier(src, "terminal_cost"), "user problem: DDP_USER_TERMINAL is set but the source defines no `terminal_cost`");
     if (flags & DDP_USER_CONST_HESSIAN)
         DDP_CHECK(has_identifier(src, "cost_hessians"), "user problem: DDP_USER_CONST_HESSIAN is set but the source defines no `cost_hessians`");
+    if (flags & DDP_USER_PLANT)
+        DDP_CHECK(has_identifier(src, "plant"), "user problem: DDP_USER_PLANT is set but the source defines no `plant`");
     const Layout L = layout_of(n, m, flags);
     const int ps = 2 * m + m * n + n;
     DDP_CHECK((size_t)L.rlanes * ((L.chunk * ps) | 1) * 8 <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the rollout's LDS", n, m);
@@ -136,9 +139,9 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
     snprintf(head, sizeof head,
              "#define DDP_N %d\n#define DDP_M %d\n#define DDP_NP %d\n#define DDP_TERMINAL %d\n#define DDP_CONST_HESSIAN %d\n"
              "#define DDP_WRAP 0x%xu\n#define DDP_CHUNK %d\n#define DDP_RLANES %d\n#define DDP_DFLANES %d\n"
-             "#define DDP_AUTODIFF %d\n#define DDP_ADJ %d\n#define DDP_ADH %d\n",
+             "#define DDP_AUTODIFF %d\n#define DDP_ADJ %d\n#define DDP_ADH %d\n#define DDP_PLANT %d\n",
              n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
-             (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh);
+             (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh, (flags & DDP_USER_PLANT) ? 1 : 0);
     std::string s(head);
     const bool ad = (flags & DDP_USER_AUTODIFF) != 0;
     if (ad) {
@@ -218,7 +221,7 @@ int compile(const char *source, int n, int m, int nparam, int flags, unsigned wr
 
 struct Module {
     hipModule_t mod = nullptr;
-    hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr;
+    hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr;
     const char *df_name = nullptr;                               // ddp_user_df, or ddp_user_df_ad (DDP_USER_AUTODIFF)
     Layout L{};
 };
@@ -248,11 +251,11 @@ struct UserProblem final : ddp_family {
         hh->last_kernel[2] = mod->df_name;
         return 0;
     }
-    int hessians(ddp_handle hh, int Bc, const int32_t *map, double *cxx, double *cxu, double *cuu) const override
+    int hessians(ddp_handle hh, int Bc, const int32_t *map, const int32_t *active, double *cxx, double *cxu, double *cuu) const override
     {
         DDP_CHECK(mod->hess, "user problem: compiled without DDP_USER_CONST_HESSIAN");
         UserHessArgs a;
-        a.B = Bc; a.params_batched = params_batched; a.params = params; a.map = map; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu;
+        a.B = Bc; a.params_batched = params_batched; a.params = params; a.map = map; a.active = active; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu;
         void *args[] = {&a};
         DDP_HIP(hipModuleLaunchKernel(mod->hess, (unsigned)((Bc + 63) / 64), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
         hh->last_kernel[2] = "ddp_user_hessians";
@@ -288,6 +291,18 @@ struct UserProblem final : ddp_family {
         hh->last_kernel[3] = "ddp_user_cost";
         return 0;
     }
+    int plant(ddp_handle hh, int S, int steps, const int32_t *adv, const int32_t *advp, const int32_t *map, const double *ucl, double *xcl,
+              double *x0s) const override
+    {
+        DDP_CHECK(mod->plant, "user problem: compiled without DDP_USER_PLANT");
+        UserPlantArgs a;
+        a.S = S; a.steps = steps; a.params_batched = params_batched; a.pad_ = 0;
+        a.params = params; a.ucl = ucl; a.adv = adv; a.advp = advp; a.map = map; a.xcl = xcl; a.x0s = x0s;
+        void *args[] = {&a};
+        DDP_HIP(hipModuleLaunchKernel(mod->plant, (unsigned)((S + 63) / 64), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
+        hh->last_kernel[4] = "ddp_user_plant";
+        return 0;
+    }
 };
 
 void ddp_user_release(ddp_handle h)
@@ -318,6 +333,7 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
     DDP_CHECK(P->nparam == 0 || params, "user problem: nparam = %d but params is NULL", P->nparam);
     P->N = N; P->B = B; P->CL = (P->flags & DDP_USER_TERMINAL) ? N + 1 : N;
     P->params = P->nparam ? params : nullptr; P->params_batched = params_batched;
+    P->has_plant = false;
     return 0;
 }
 
@@ -396,7 +412,8 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
         const bool ok = hipModuleGetFunction(&M.roll, M.mod, "ddp_user_rollout") == hipSuccess &&
                         hipModuleGetFunction(&M.df, M.mod, M.df_name) == hipSuccess &&
                         hipModuleGetFunction(&M.cost, M.mod, "ddp_user_cost") == hipSuccess &&
-                        (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess);
+                        (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess) &&
+                        (!(flags & DDP_USER_PLANT) || hipModuleGetFunction(&M.plant, M.mod, "ddp_user_plant") == hipSuccess);
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -406,6 +423,7 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
     }
     UserProblem *P = new UserProblem();
     P->h = h; P->n = n; P->m = m; P->N = 0; P->B = 0; P->CL = 0; P->const_hessian = (flags & DDP_USER_CONST_HESSIAN) != 0;
+    P->has_plant = false;                                        // set by the closed-loop entry points only
     P->nparam = nparam; P->flags = flags; P->wrap = wrap; P->mod = &it->second;
     *out = P;
     return 0;
@@ -429,7 +447,7 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
     rc = P->df(h, B, nullptr, x, u, active, fx, fu, cx, cu, P->const_hessian ? nullptr : cxx, P->const_hessian ? nullptr : cxu,
                P->const_hessian ? nullptr : cuu);
     if (rc) return rc;
-    if (P->const_hessian && cxx && cxu && cuu) return P->hessians(h, B, nullptr, cxx, cxu, cuu);
+    if (P->const_hessian && cxx && cxu && cuu) return P->hessians(h, B, nullptr, nullptr, cxx, cxu, cuu);
     return 0;
 }
 
@@ -552,6 +570,81 @@ int ddp_user_ilqg_f64(ddp_handle h, void *up, int N, int B, const double *params
     DDP_STAGED(S);
     return S.finish(ddp_user_ilqg_f64_dev(h, up, N, B, dp, params_batched, o, dx0, x0_prerolled, du0, dc0, dl, dx, du, dK, dk, dQ, dVx, dVxx,
                                           dc, ds, trace_cap, dt7, global_iters));
+}
+
+int ddp_user_ilqg_queue_f64_dev(ddp_handle h, void *up, int N, int P, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                                int slots, const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
+                                double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, P, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
+    return ddp_ilqg_sched_family_dev(h, U, o, slots, 0, 0, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, nullptr, nullptr, nullptr,
+                                     global_iters);
+}
+
+int ddp_user_ilqg_queue_f64(ddp_handle h, void *up, int N, int P, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                            int slots, const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
+                            double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, P, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
+    const size_t n = U->n, m = U->m, T = (size_t)N * P, CL = U->CL;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? P : 1)), *dx0 = S.in(x0, n * P), *du0 = S.in(u0, m * T),
+           *dl = S.in(lims, 2 * m);
+    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T),
+           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * P), *ds = S.out(stats, (size_t)DDP_ILQG_NSTATS * P);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_ilqg_queue_f64_dev(h, up, N, P, dp, params_batched, o, slots, dx0, du0, dl, dx, du, dK, dk, dQ, dVx, dVxx, dc, ds,
+                                                global_iters));
+}
+
+int ddp_user_ilqg_mpc_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                              int steps, int zero_tail, const double *x0, const double *u0, const double *lims, double *xcl, double *ucl,
+                              double *stats_cl, double *x, double *u, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
+    DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
+    U->has_plant = (U->flags & DDP_USER_PLANT) != 0;           // the plant acts in the closed loop only
+    rc = ddp_ilqg_sched_family_dev(h, U, o, 0, steps, zero_tail, x0, u0, lims, x, u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, xcl, ucl, stats_cl, global_iters);
+    U->has_plant = false;
+    return rc;
+}
+
+int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                          int steps, int zero_tail, const double *x0, const double *u0, const double *lims, double *xcl, double *ucl,
+                          double *stats_cl, double *x, double *u, int *global_iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
+    DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
+    const size_t n = U->n, m = U->m, T = (size_t)N * B;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * B), *du0 = S.in(u0, m * T),
+           *dl = S.in(lims, 2 * m);
+    double *dxcl = S.out(xcl, n * (size_t)(steps + 1) * B), *ducl = S.out(ucl, m * (size_t)steps * B),
+           *dscl = S.out(stats_cl, (size_t)DDP_ILQG_NSTATS * steps * B), *dx = S.out(x, n * T), *du = S.out(u, m * T);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_ilqg_mpc_f64_dev(h, up, N, B, dp, params_batched, o, steps, zero_tail, dx0, du0, dl, dxcl, ducl, dscl, dx, du,
+                                              global_iters));
 }
 
 }   // extern "C"

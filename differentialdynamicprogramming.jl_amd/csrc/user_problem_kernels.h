@@ -1,7 +1,7 @@
 // user_problem_kernels.h — the kernel templates of a user problem (user_problem.hip), as program text for hiprtc.
 //
 // The program hiprtc compiles is: the size / flag macros (DDP_N, DDP_M, DDP_NP, DDP_TERMINAL, DDP_CONST_HESSIAN, DDP_WRAP, DDP_CHUNK,
-// DDP_RLANES, DDP_DFLANES, DDP_AUTODIFF, DDP_ADJ, DDP_ADH), the user's source (with DDP_AUTODIFF between the texts of user_autodiff.h),
+// DDP_RLANES, DDP_DFLANES, DDP_AUTODIFF, DDP_ADJ, DDP_ADH, DDP_PLANT), the user's source (with DDP_AUTODIFF between the texts of user_autodiff.h),
 // DDP_USER_ABI (the argument structs, shared with the host through the macro below) and kUserKernels.  Every size is a compile-time constant there: the state of a rollout stays in VGPRs and every loop over n, m unrolls.
 //
 //   ddp_user_rollout   one lane per (trajectory, α) rollout, DDP_RLANES rollouts per 64-lane work-group.  The operand streams (u, x, k, K)
@@ -14,10 +14,12 @@
 //   ddp_user_df_ad     DDP_AUTODIFF (in place of ddp_user_df): the same, with forward-mode AD of the templated model (user_autodiff.h)
 //                      writing the slot.
 //   ddp_user_cost      costfun on given trajectories: one wave per trajectory, lanes over time.
-//   ddp_user_hessians  DDP_CONST_HESSIAN: cost_hessians once per trajectory.
+//   ddp_user_hessians  DDP_CONST_HESSIAN: cost_hessians once per trajectory (per armed slot in the slot scheduler: `active`).
+//   ddp_user_plant     DDP_PLANT: one lane per slot of the closed loop; the user's plant advances the trajectories whose solve has just
+//                      ended (xcl[:, t+1], and the next solve's initial state).
 #pragma once
 
-// argument structs of the four kernels: compiled into the host library and, as text (DDP_USER_ABI_TEXT), into every user program.
+// argument structs of the kernels: compiled into the host library and, as text (DDP_USER_ABI_TEXT), into every user program.
 // Only int / pointer / double members, so that both compilers lay them out alike.
 #define DDP_USER_ABI                                                                                                                  \
     struct UserRollArgs {                                                                                                            \
@@ -42,8 +44,14 @@
     struct UserHessArgs {                                                                                                            \
         int B, params_batched;                                                                                                       \
         const double *params;                                                                                                        \
-        const int *map;                                                                                                              \
+        const int *map, *active;                                                                                                     \
         double *cxx, *cxu, *cuu;                                                                                                     \
+    };                                                                                                                               \
+    struct UserPlantArgs {                                                                                                           \
+        int S, steps, params_batched, pad_;                                                                                          \
+        const double *params, *ucl;                                                                                                  \
+        const int *adv, *advp, *map;                                                                                                 \
+        double *xcl, *x0s;                                                                                                           \
     };
 #define DDP_USER_STR_(...) #__VA_ARGS__
 #define DDP_USER_STR(x) DDP_USER_STR_(x)
@@ -68,10 +76,13 @@ __device__ __forceinline__ double ddp_wrap_pi(double d)     // rem2pi(d, RoundNe
     return fma(-q, 0x1.1a62633145c07p-52, fma(-q, 0x1.921fb54442d18p+2, d));
 }
 
+// the parameters of slot b; NULL for an empty (-1) or resting (-2) slot of the scheduler's map, whose lanes never run the model
 __device__ __forceinline__ const double *ddp_params(const double *P, int batched, const int *map, int b)
 {
     if (!P) return nullptr;
-    return batched ? P + (size_t)DDP_NP * (size_t)(map ? map[b] : b) : P;
+    if (!batched) return P;
+    const int j = map ? map[b] : b;
+    return j >= 0 ? P + (size_t)DDP_NP * (size_t)j : nullptr;
 }
 
 // chunk [i0, i0 + cs) of one operand stream (W doubles per step) of every rollout of the work-group into its LDS slots
@@ -280,12 +291,39 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_hessians(UserHessArgs 
 {
     constexpr int n = DDP_N, m = DDP_M;
     const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= a.B) return;
+    if (b >= a.B || (a.active && a.active[b] == 0)) return;
     double hxx[n * n], hxu[n * m], huu[m * m];
     cost_hessians(ddp_params(a.params, a.params_batched, a.map, b), hxx, hxu, huu);
     for (int e = 0; e < n * n; ++e) a.cxx[(size_t)n * n * b + e] = hxx[e];
     for (int e = 0; e < n * m; ++e) a.cxu[(size_t)n * m * b + e] = hxu[e];
     for (int e = 0; e < m * m; ++e) a.cuu[(size_t)m * m * b + e] = huu[e];
+}
+#endif
+
+#if DDP_PLANT
+// xcl[n, steps+1, P], ucl[m, steps, P]; adv[b] = t + 1 when solve t of trajectory advp[b] has just ended on slot b (0: nothing to do)
+extern "C" __global__ __launch_bounds__(64) void ddp_user_plant(UserPlantArgs a)
+{
+    constexpr int n = DDP_N, m = DDP_M;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.S) return;
+    const int t1 = a.adv[b];
+    if (t1 <= 0) return;
+    const int t = t1 - 1, j = a.advp[b];
+    double *xc = a.xcl + (size_t)n * ((size_t)(a.steps + 1) * j + t);
+    const double *uc = a.ucl + (size_t)m * ((size_t)a.steps * j + t);
+    double x[n], u[m], xn[n];
+#pragma unroll
+    for (int l = 0; l < n; ++l) x[l] = xc[l];
+#pragma unroll
+    for (int q = 0; q < m; ++q) u[q] = uc[q];
+    plant(x, u, t, ddp_params(a.params, a.params_batched, a.advp, b), xn);
+#pragma unroll
+    for (int l = 0; l < n; ++l) xc[n + l] = xn[l];
+    if (a.map[b] == j) {                                       // the slot goes on with this trajectory: its next initial state
+#pragma unroll
+        for (int l = 0; l < n; ++l) a.x0s[(size_t)n * b + l] = xn[l];
+    }
 }
 #endif
 )DDPK";

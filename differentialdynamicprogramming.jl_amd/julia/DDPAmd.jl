@@ -914,10 +914,11 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
 end
 
 # ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
-# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff) holds the source; it is compiled with hiprtc for
-# the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant) holds the source; it is compiled with hiprtc
+# for the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
 # autodiff=true (DDP_USER_AUTODIFF): dynamics / stage_cost / terminal_cost are templates over the scalar type of x and u, the source
 # needs no `derivatives`, and df is derived on the device by forward-mode AD.
+# plant=true (DDP_USER_PLANT): the source also defines `plant`, the true system the closed loop of iLQG_mpc advances its trajectories with.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -929,10 +930,10 @@ mutable struct DeviceProblem
     made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
-                       const_hessian::Bool=false, autodiff::Bool=false, diff=-)
+                       const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false)
     wrap = Int(_diff_mask(diff, n))
-    p = DeviceProblem(String(source), n, m, nparam, (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0), wrap, _f64(params),
-                      Dict{Ptr{Cvoid},Ptr{Cvoid}}())
+    flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0)
+    p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}())
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
 end
@@ -1058,6 +1059,56 @@ function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun
     return x, u, policy(N, n, m, K, k, zeros(m, m, N, bt...), Quu), Vx, Vxx, costo, trace
 end
 
+# iLQG_queue / iLQG_mpc with the user's closures: as the methods for registered problems; `params` [nparam] or [nparam, P] (queue: one
+# column per problem; MPC: per trajectory)
+function _user_sched_check(problem::DeviceProblem, x0, u0)
+    n, B = size(x0); m = size(u0, 1)
+    (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
+    size(u0, 3) == B || throw(DDPError(-1, "x0[n,B] and u0[m,N,B] have different B"))
+    return n, m, size(u0, 2), B
+end
+
+function iLQG_queue(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{<:Real,3}; slots::Integer=0, lims=[], α=DEFAULT_ALPHA,
+                    tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1,
+                    reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing, policy=GaussianPolicy{Float64})
+    n, m, N, P_ = _user_sched_check(problem, x0, u0)
+    P, pb = _user_params(problem, P_, params)
+    CL = cost_len(problem, N)
+    o = _opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    x = result_array(n, N, P_); u = result_array(m, N, P_); K = result_array(m, n, N, P_); k = result_array(m, N, P_)
+    Quu = result_array(m, m, N, P_); Vx = result_array(n, N, P_); Vxx = result_array(n, n, N, P_); costo = result_array(CL, P_)
+    stats = zeros(8, P_); git = Ref{Cint}(0)
+    x0h = _f64(x0); u0h = _f64(u0); limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x0h u0h limsp x u K k Quu Vx Vxx costo stats begin
+        check(@ccall libddp.ddp_user_ilqg_queue_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, P_::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, Ref(o)::Ptr{ILQGOpts}, slots::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64},
+            x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+            costo::Ptr{Float64}, stats::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    end
+    trace = Dict{Symbol,Any}(:stats => stats, :status => Int.(stats[1, :]), :iter => Int.(stats[2, :]), :global_iters => Int(git[]))
+    return x, u, policy(N, n, m, K, k, zeros(m, m, N, P_), Quu), Vx, Vxx, costo, trace
+end
+
+function iLQG_mpc(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{<:Real,3}, steps::Integer; zero_tail::Bool=false, lims=[],
+                  α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1,
+                  reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing)
+    n, m, N, B = _user_sched_check(problem, x0, u0)
+    P, pb = _user_params(problem, B, params)
+    o = _opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    xcl = zeros(n, steps + 1, B); ucl = zeros(m, steps, B); scl = zeros(8, steps, B)
+    x = result_array(n, N, B); u = result_array(m, N, B); git = Ref{Cint}(0)
+    x0h = _f64(x0); u0h = _f64(u0); limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x0h u0h limsp xcl ucl scl x u begin
+        check(@ccall libddp.ddp_user_ilqg_mpc_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, Ref(o)::Ptr{ILQGOpts}, steps::Cint, (zero_tail ? 1 : 0)::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64},
+            _ptr_or_null(limsp)::Ptr{Float64}, xcl::Ptr{Float64}, ucl::Ptr{Float64}, scl::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64},
+            git::Ptr{Cint})::Cint)
+    end
+    return xcl, ucl, scl, x, u
+end
+
 # device-pointer flavours (arrays already on the handle's device, e.g. from ddp_malloc): thin wrappers over the C entries
 user_df_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, x, u, active, fx, fu, cx, cu, cxx, cxu, cuu; handle::Handle=default_handle()) =
     check(@ccall libddp.ddp_user_df_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint, params::Ptr{Float64},
@@ -1079,6 +1130,24 @@ function user_ilqg_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQ
         pb::Cint, Ref(o)::Ptr{ILQGOpts}, x0::Ptr{Float64}, prerolled::Cint, u0::Ptr{Float64}, cost0::Ptr{Float64}, lims::Ptr{Float64},
         x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
         cost::Ptr{Float64}, stats::Ptr{Float64}, cap::Cint, trace7::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    return Int(git[])
+end
+function user_ilqg_queue_dev!(p::DeviceProblem, N, P, params::Ptr{Float64}, pb, o::ILQGOpts, slots, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx,
+                              cost, stats; handle::Handle=default_handle())
+    git = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqg_queue_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, P::Cint,
+        params::Ptr{Float64}, pb::Cint, Ref(o)::Ptr{ILQGOpts}, slots::Cint, x0::Ptr{Float64}, u0::Ptr{Float64}, lims::Ptr{Float64},
+        x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+        cost::Ptr{Float64}, stats::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    return Int(git[])
+end
+function user_ilqg_mpc_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQGOpts, steps, zero_tail, x0, u0, lims, xcl, ucl,
+                            stats_cl, x, u; handle::Handle=default_handle())
+    git = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqg_mpc_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, Ref(o)::Ptr{ILQGOpts}, steps::Cint, zero_tail::Cint, x0::Ptr{Float64}, u0::Ptr{Float64},
+        lims::Ptr{Float64}, xcl::Ptr{Float64}, ucl::Ptr{Float64}, stats_cl::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64},
+        git::Ptr{Cint})::Cint)
     return Int(git[])
 end
 

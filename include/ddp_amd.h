@@ -44,7 +44,8 @@ int  ddp_sync(ddp_handle h);
 int  ddp_reload_env(ddp_handle h);
 /* name of the kernel the last back_pass (which = 0) / forward_pass (which = 1) dispatch of this handle launched ("" before the first
  * one): a debug query — the tests assert through it that the timed path is the one they checked.  which = 2 / 3: the last derivative /
- * cost kernel of a user problem (ddp_user_df*, ddp_user_costfun*; the hessians of DDP_USER_CONST_HESSIAN count as derivatives).     */
+ * cost kernel of a user problem (ddp_user_df*, ddp_user_costfun*; the hessians of DDP_USER_CONST_HESSIAN count as derivatives);
+ * which = 4: the plant kernel of a user problem's closed loop (ddp_user_plant).                                                    */
 const char *ddp_last_kernel(ddp_handle h, int which);
 /* The shared-operand backward pass (one fx, fu, cxx, cxu, cuu for the batch) hands work between work-groups of one launch; every such
  * wait is time-bounded (4 s).  A tile whose wait ran out gives its trajectories to the per-trajectory kernels launched behind it — the
@@ -488,10 +489,22 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  *   sin cos tan exp log sqrt pow (T^double, T^int, T^T, double^T) tanh sinh cosh atan atan2 asin acos fabs fmin fmax hypot
  *   expm1 log1p, and rint floor (derivative 0);
  * any other function of a T fails to compile, with its name in ddp_user_compile_log().  Kernel name: ddp_user_df_ad, in place of
- * ddp_user_df. */
+ * ddp_user_df.
+ *
+ * DDP_USER_PLANT: the true system of the closed loop (ddp_user_ilqg_mpc_*; every other entry point ignores the flag), for a solver that
+ * plans with the model while the system it controls differs (mass, actuator gain, drift, a known disturbance sequence):
+ *
+ *   __device__ void   plant(const double *x, const double *u, int t, const double *p, double *xnext);
+ *
+ * t is the 0-based closed-loop step and p the trajectory's parameter column, the one the model sees: plant-only parameters go into the
+ * same params (after the model's, for instance; a disturbance sequence indexed by t included).  plant is a plain double function, also
+ * with DDP_USER_AUTODIFF (it may call dynamics<double>).  After every solve t of a trajectory that did not diverge at its start (the
+ * last one included) xcl[:,t+1] = plant(xcl[:,t], ucl[:,t], t, p) replaces x_1 of the plan, and is the next solve's initial state.  A
+ * plant that leaves the state non-finite or beyond the bound of the initial rollout ends the trajectory's loop through the initial-
+ * divergence exit of the next solve.  Kernel name: ddp_user_plant (one lane per slot; ddp_last_kernel(h, 4)). */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
-enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4 };
+enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8 };
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
@@ -531,6 +544,26 @@ int ddp_user_ilqg_f64(ddp_handle h, void *up, int N, int B, const double *params
                       const double *x0, int x0_prerolled, const double *u0, const double *cost0, const double *lims,
                       double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
                       double *cost, double *stats, int trace_cap, double *trace7, int *global_iters);
+/* The slot scheduler with the user's closures: P solves through `slots` resident trajectories, arguments and outputs as
+ * ddp_ilqg_queue_f64(_dev) (x0[n,P], u0[m,N,P]; every solve is the one ddp_user_ilqg_f64 performs at batch size `slots`).  params:
+ * [nparam] shared or [nparam,P] one column per problem (params_batched = 1), read through the slot -> problem map.  With
+ * DDP_USER_CONST_HESSIAN the Hessians of a slot are evaluated when it takes a problem (ddp_user_hessians on the armed slots).        */
+int ddp_user_ilqg_queue_f64_dev(ddp_handle h, void *up, int N, int P, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                                int slots, const double *x0, const double *u0, const double *lims,
+                                double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                                double *cost, double *stats, int *global_iters);
+int ddp_user_ilqg_queue_f64(ddp_handle h, void *up, int N, int P, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                            int slots, const double *x0, const double *u0, const double *lims,
+                            double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
+                            double *cost, double *stats, int *global_iters);
+/* The closed loop with the user's closures: arguments and outputs as ddp_ilqg_mpc_f64(_dev); params [nparam] or [nparam,B] per
+ * trajectory.  Without DDP_USER_PLANT the model is the plant (x_1 of the plan is the next state); with it, the user's plant.        */
+int ddp_user_ilqg_mpc_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                              int steps, int zero_tail, const double *x0, const double *u0, const double *lims,
+                              double *xcl, double *ucl, double *stats_cl, double *x, double *u, int *global_iters);
+int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                          int steps, int zero_tail, const double *x0, const double *u0, const double *lims,
+                          double *xcl, double *ucl, double *stats_cl, double *x, double *u, int *global_iters);
 
 #ifdef __cplusplus
 }
