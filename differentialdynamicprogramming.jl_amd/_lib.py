@@ -33,7 +33,7 @@ EXPORTS = [
     "ddp_user_check", "ddp_user_compile_log", "ddp_user_create", "ddp_user_destroy", "ddp_user_df_f64_dev", "ddp_user_df_f64",
     "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
     "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64", "ddp_user_ilqg_queue_f64_dev", "ddp_user_ilqg_queue_f64", "ddp_user_ilqg_mpc_f64_dev",
-    "ddp_user_ilqg_mpc_f64",
+    "ddp_user_ilqg_mpc_f64", "ddp_user_ilqgkl_f64_dev", "ddp_user_ilqgkl_f64",
 ]
 
 

@@ -43,6 +43,9 @@ struct BPMidArgs {
     const int32_t *active;
     double *K, *k, *Quu, *Vx, *Vxx, *dV;
     int32_t *diverge;
+    const double *eta;                                                          // GPS: η [B] or [N,B] (eta_tv)
+    const double *kcx, *kcu, *kcxx, *kcxu, *kcuu;                               // GPS_FUSED: ∇kl [n,N,B] [m,N,B] [n,n,N,B] [m,n,N,B] [m,m,N,B]
+    int eta_tv;
 };
 
 __device__ __forceinline__ d4 mf(double x, double y, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, c, 0, 0, 0); }
@@ -58,10 +61,16 @@ struct MidLds {
 };
 
 // MMX: the size the m x m system is compiled for (4 for m <= 4: a quarter of the registers of the 8 x 8 arrays)
-template <int NTR, int PT, int MMX, bool LIMS, bool CTV>
+// GPS: back_pass_gps (backward_pass.jl:259-350).  The kernel scales the products with V by 1/η, G = F'[W | Vx]/η + [H̃ | c̃], symmetrises
+// Quu before the gains (:301), and runs without λ; Quui = inv(Quu) is a post-kernel (gps_mid_quui_kernel).  GPS_PRE: on operands a prepass
+// has combined into c̃• = c•/η + c•kl (every step but the last, where only cuu is).  GPS_FUSED: on the raw operands, the KL terms
+// requested beside the cost Hessians in the step's one load batch and folded in as the cost image is formed, H̃ = H/η + Hkl, c̃ = c/η + ckl
+enum { GPS_OFF = 0, GPS_PRE = 1, GPS_FUSED = 2 };
+template <int NTR, int PT, int MMX, bool LIMS, bool CTV, int GPSK = GPS_OFF>
 __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
 {
     using L = MidLds<NTR, PT, MMX>;
+    constexpr bool GPS = GPSK != GPS_OFF, FUSED = GPSK == GPS_FUSED;
     constexpr int NR = L::NR, PC = L::PC, LDV = L::LDV, LDF = L::LDF, LDW = L::LDW, MM = L::MM, MK = L::MK, KT = NR / 4;
     const int b = blockIdx.x, lane = threadIdx.x, l15 = lane & 15, l4 = lane >> 4;
     if (a.active && a.active[b] == 0) return;
@@ -76,8 +85,10 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
     const double *cxx = a.cxx + a.cxx_b * b, *cxu = a.cxu + a.cxu_b * b, *cuu = a.cuu + a.cuu_b * b;
     double *Kg = a.K + nm * N * b, *kg = a.k + (size_t)m * N * b, *Quug = a.Quu + mm * N * b,
            *Vxg = a.Vx + (size_t)n * N * b, *Vxxg = a.Vxx + nn * N * b;
-    const double lam = a.lambda[b];
-    const int regType = a.regType;
+    const double lam = GPS ? 0.0 : a.lambda[b];
+    const int regType = GPS ? 1 : a.regType;
+    const double *const etag = GPS ? a.eta + (a.eta_tv ? (size_t)N * b : (size_t)b) : nullptr;
+    const int eta_st = GPS && a.eta_tv ? 1 : 0;
     bool nolims = true;
     double limlo[MM], limhi[MM];
 #pragma unroll
@@ -95,7 +106,11 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         const size_t tl = (size_t)(N - 1);
         for (int e = lane; e < (int)nn; e += DDP_WAVE) { const double v = cxx[a.cxx_t * tl + e]; Vs[(e % n) + LDV * (e / n)] = v; Vxxg[nn * tl + e] = v; }
         if (lane < n) { const double v = cx[(size_t)n * tl + lane]; vxs[lane] = v; Vxg[(size_t)n * tl + lane] = v; }
-        if (lane < (int)mm) Quug[mm * tl + lane] = cuu[a.cuu_t * tl + lane];
+        if (lane < (int)mm) {
+            double v = cuu[a.cuu_t * tl + lane];
+            if constexpr (FUSED) v = v / etag[eta_st * tl] + a.kcuu[mm * ((size_t)N * b + tl) + lane];     // Quu[:,:,N] = cuu/η + cuukl (:282)
+            Quug[mm * tl + lane] = v;
+        }
         for (int e = lane; e < (int)nm; e += DDP_WAVE) Kg[nm * tl + e] = 0.0;
         if (lane < m) kg[(size_t)m * tl + lane] = 0.0;
     }
@@ -138,7 +153,9 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         s_a[r] = (ee % n) + LDV * (ee / n);
     }
     const int quu_src = lane < (int)mm ? (lane % m) * PC + n + lane / m : 0;      // (no division by a run-time m inside the loop)
-    double pfA[RA], pfB[RB], pg, pu = 0.0;                        // F, the gradients (and, with limits, u) of the next step, requested a step ahead
+    double pfA[RA], pfB[RB], pg, pu = 0.0, pe = 1.0, pk = 0.0;    // F, the gradients (and, with limits, u; GPS: η, fused: ∇kl) of the next step, requested a step ahead
+    const double *const kgrad = FUSED ? (lane < n ? a.kcx + (size_t)n * N * b + lane : a.kcu + (size_t)m * N * b + (lane < p ? lane - n : 0)) : nullptr;
+    const int kgs = lane < n ? n : m;
     double *const uvec = lds + L::oUv;
     auto load_F = [&](int i) {
         const char *fxi = (const char *)(fx + a.fx_t * i), *fui = (const char *)(fu + a.fu_t * i);
@@ -148,13 +165,15 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         for (int r = 0; r < RB; ++r) pfB[r] = *(const double *)(fui + gB[r]);
         pg = *(const double *)(gptr + (size_t)gstride * i);
         if constexpr (LIMS) pu = ug[(size_t)m * i + (lane < m ? lane : 0)];
+        if constexpr (GPS) pe = etag[eta_st * i];
+        if constexpr (FUSED) pk = kgrad[(size_t)kgs * i];
     };
     auto store_F = [&]() {
 #pragma unroll
         for (int r = 0; r < RA; ++r) FsA[LDF * CPI * r] = pfA[r];
 #pragma unroll
         for (int r = 0; r < RB; ++r) lds[lB[r]] = pfB[r];
-        gv[lane] = lane < p ? pg : 0.0;
+        gv[lane] = lane < p ? (FUSED ? pg / pe + pk : pg) : 0.0;                 // fused: c̃ = c/η + ckl (:295, :298)
         if constexpr (LIMS) { if (lane < 8) uvec[lane] = lane < m ? pu : 0.0; }
     };
     // Vxx_i from the LDS image, in memory order: all reads first (under a condition the compiler sank each read into its store's branch: 16
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         cmask[ti] = (16 * ti + l15 < n) ? 1.0 : 0.0;
     }
     // cost Hessians of this lane's tile elements: registers while they do not vary with time
-    double hc[PT][PT][4];
+    double hc[PT][PT][4], hk[FUSED ? PT : 1][FUSED ? PT : 1][4];   // fused: Hkl of this lane's tile elements beside H
     auto load_H = [&](int i) {
         const double *cxxi = cxx + a.cxx_t * i, *cxui = cxu + a.cxu_t * i, *cuui = cuu + a.cuu_t * i;
 #pragma unroll
@@ -203,6 +222,13 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
                     if (row < n) { if (col < n) c = cxxi[row + n * col]; else if (col < p) c = cxui[row + n * (col - n)]; }       // (:244), Qxu = Qux'
                     else if (row < p) { if (col < n) c = cxui[col + n * (row - n)]; else if (col < p) c = cuui[(row - n) + m * (col - n)]; }   // (:242-243)
                     hc[ti][cj][r] = c;
+                    if constexpr (FUSED) {                  // cxukl is [m,n] (∇kl's layout): Qux[q][j] gets cxukl[q + m j], Qxu[j][q] the same
+                        const size_t tb = (size_t)N * b + i;
+                        double k2 = 0.0;
+                        if (row < n) { if (col < n) k2 = a.kcxx[nn * tb + row + n * col]; else if (col < p) k2 = a.kcxu[nm * tb + (col - n) + m * row]; }
+                        else if (row < p) { if (col < n) k2 = a.kcxu[nm * tb + (row - n) + m * col]; else if (col < p) k2 = a.kcuu[mm * tb + (row - n) + m * (col - n)]; }
+                        hk[FUSED ? ti : 0][FUSED ? cj : 0][r] = k2;
+                    }
                 }
     };
     // the gradient column (Qx, Qu: column p of G): the lanes l15 == p % 16 of tile column p / 16 add gv[row]; the others read zeros
@@ -214,6 +240,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         MP(7)
         // ---- F_i = [fx fu] into the LDS (k fastest; the memory order of both arrays); the next one is requested behind the products
         store_F();
+        const double ie = GPS ? 1.0 / pe : 1.0;                   // (:295-299)
         wave_sync();
         MP(0)
         // ================= W = Vxx F ==============================================================================
@@ -291,8 +318,12 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
 #pragma unroll
                 for (int cj = 0; cj < PT; ++cj) {
                     double v[4] = {g[ti][cj].x, g[ti][cj].y, g[ti][cj].z, g[ti][cj].w};
+                    if constexpr (GPS) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] += hc[ti][cj][r];
+                        for (int r = 0; r < 4; ++r) v[r] *= ie;                      // F'[W | Vx] / η
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] += FUSED ? hc[ti][cj][r] * ie + hk[FUSED ? ti : 0][FUSED ? cj : 0][r] : hc[ti][cj][r];
                     if (cj == cjp) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] += gsel[16 * ti + 4 * r];       // (zeros outside the lanes of column p; hc is zero in them)
@@ -317,6 +348,14 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
         load_F(i > 0 ? i - 1 : 0);
         if (CTV) load_H(i > 0 ? i - 1 : 0);
         wave_sync();
+        if constexpr (GPS) {                                       // Quu = ½(Quu + Quu') (:301): the matrix factorised, stored and used below
+            const int r2 = lane & 7, c2 = lane >> 3;
+            const bool in_m = r2 < m && c2 < m;
+            const double sv = in_m ? 0.5 * (Gu[r2 * PC + n + c2] + Gu[c2 * PC + n + r2]) : 0.0;
+            wave_sync();
+            if (in_m) Gu[r2 * PC + n + c2] = sv;
+            wave_sync();
+        }
         MP(2)
         // ================= gains (backward_pass.jl:30-62) ==============================================================================
         if constexpr (MM == 8) {
@@ -610,15 +649,115 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_mid_kernel(BPMidArgs a)
     if (lane == 0) { a.dV[2 * b] = dV0; a.dV[2 * b + 1] = dV1; a.diverge[b] = diverge; }
 }
 
-template <int NTR, int PT, int MMX, bool LIMS, bool CTV>
+template <int NTR, int PT, int MMX, bool LIMS, bool CTV, int GPS = GPS_OFF>
 int launch_mid2(ddp_handle h, const ddp_bp_desc *d, const BPMidArgs &a)
 {
-    const size_t bytes = ((size_t)MidLds<NTR, PT, MMX>::oTot + ((MMX == 8 && a.regType == 2) ? 8 * MidLds<NTR, PT, MMX>::PC : 0)) * sizeof(double);
+    const size_t bytes = ((size_t)MidLds<NTR, PT, MMX>::oTot + ((MMX == 8 && a.regType == 2 && !GPS) ? 8 * MidLds<NTR, PT, MMX>::PC : 0)) * sizeof(double);
     const dim3 grid((unsigned)d->B), block(DDP_WAVE);
-    if (int rc = ddp_raise_lds(h, (const void *)back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV>, (int)bytes)) return rc;
-    hipLaunchKernelGGL((back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV>), grid, block, bytes, h->stream, a);
+    if (int rc = ddp_raise_lds(h, (const void *)back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV, GPS>, (int)bytes)) return rc;
+    hipLaunchKernelGGL((back_pass_mid_kernel<NTR, PT, MMX, LIMS, CTV, GPS>), grid, block, bytes, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
+}
+
+template <int NTR, int PT, int MMX>
+int launch_mid_gps(ddp_handle h, const ddp_bp_desc *d, const BPMidArgs &a)
+{
+    constexpr int K = NTR == 1 ? GPS_FUSED : GPS_PRE;            // (fused at NTR = 2 spills: DESIGN §3.5)
+    return d->has_lims ? launch_mid2<NTR, PT, MMX, true, true, K>(h, d, a) : launch_mid2<NTR, PT, MMX, false, true, K>(h, d, a);
+}
+
+// back_pass_gps prepass: c̃• = c•/η + c•kl into [.,.,N,B] arrays, except cx and cxx at the last step (:281-283: Vx[:,N] = cx[:,N],
+// Vxx[:,:,N] = cxx[:,:,N]); cuu there is cuu/η + cuukl, which is Quu[:,:,N].  cxukl is [m,n] (∇kl's layout), cxu [n,m].  Cost Hessians
+// with any time / trajectory stride (0: shared), so the constant Hessians of a user problem need no repeated copy.
+struct GpsMidCombine {
+    int n, m, N, B, eta_tv;
+    long cxx_t, cxx_b, cxu_t, cxu_b, cuu_t, cuu_b;
+    const double *cx, *cu, *cxx, *cxu, *cuu, *kcx, *kcu, *kcxx, *kcxu, *kcuu, *eta;
+    double *ox, *ou, *oxx, *oxu, *ouu;
+};
+// One launch per array (`which`, a kernel argument: every launch's grid is its own array's size).  `chunks` blocks per step: block
+// blockIdx.x covers step t = blockIdx.x / chunks (one division per block) and elements q of that step over the trajectories.
+__global__ __launch_bounds__(256) void gps_mid_combine_kernel(GpsMidCombine a, int which, unsigned chunks)
+{
+    const int n = a.n, m = a.m;                                 // which: 0 cx (n), 1 cu (m), 2 cxx (n n), 3 cxu (n m), 4 cuu (m m)
+    const int len = which == 0 ? n : which == 1 ? m : which == 2 ? n * n : which == 3 ? n * m : m * m;
+    const int t = (int)(blockIdx.x / chunks);
+    const unsigned q = (blockIdx.x - (unsigned)t * chunks) * 256u + threadIdx.x;        // trajectory q / len, element q % len (32-bit)
+    if (q >= (unsigned)len * (unsigned)a.B) return;
+    const int b = (int)(q / (unsigned)len), e = (int)(q - (unsigned)b * (unsigned)len);
+    const long tb = (long)a.N * b + t, g = tb * len + e;
+    const bool last = t == a.N - 1;
+    const double ie = 1.0 / a.eta[a.eta_tv ? tb : (long)b];
+    switch (which) {
+    case 0: a.ox[g] = last ? a.cx[g] : a.cx[g] * ie + a.kcx[g]; break;
+    case 1: a.ou[g] = a.cu[g] * ie + a.kcu[g]; break;
+    case 2: { const double c = a.cxx[a.cxx_b * b + a.cxx_t * t + e]; a.oxx[g] = last ? c : c * ie + a.kcxx[g]; } break;
+    case 3: { const int j = e % n, c = e / n; a.oxu[g] = a.cxu[a.cxu_b * b + a.cxu_t * t + e] * ie + a.kcxu[tb * len + c + m * j]; } break;
+    default: a.ouu[g] = a.cuu[a.cuu_b * b + a.cuu_t * t + e] * ie + a.kcuu[g]; break;
+    }
+}
+
+// Quui[:,:,t] = inv(Quu[:,:,t]) (:283, :344) for the steps the pass completed (every step without a failure, the steps after the failing
+// one otherwise; zeros at and before it), one lane per (step, trajectory).  The inverse of the full matrix, also where limits clamp
+// coordinates: column by column, Gaussian elimination with partial pivoting on a fresh copy of Quu (registers: one m x m array + a column)
+template <int MM>
+__global__ __launch_bounds__(256) void gps_mid_quui_kernel(int m, int N, long NB, const double *__restrict__ Quu, const int32_t *__restrict__ diverge,
+                                                           const int32_t *__restrict__ active, double *__restrict__ Quui)
+{
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= NB) return;
+    const long b = g / N;
+    if (active && active[b] == 0) return;
+    const int t = (int)(g % N), dv = diverge[b];
+    const size_t mm = (size_t)m * m;
+    const double *Q = Quu + mm * g;
+    double *out = Quui + mm * g;
+    if (!(dv == 0 || t > dv - 1)) {
+        for (size_t e = 0; e < mm; ++e) out[e] = 0.0;
+        return;
+    }
+    for (int c = 0; c < m; ++c) {
+        double A[MM * MM], x[MM];
+#pragma unroll
+        for (int cc = 0; cc < MM; ++cc)
+#pragma unroll
+            for (int r = 0; r < MM; ++r) A[r + MM * cc] = (r < m && cc < m) ? Q[r + m * cc] : (r == cc ? 1.0 : 0.0);
+#pragma unroll
+        for (int r = 0; r < MM; ++r) x[r] = r == c ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < MM; ++k) {
+            int pr = k;
+            double best = fabs(A[k + MM * k]);
+#pragma unroll
+            for (int r = k + 1; r < MM; ++r) { const double v = fabs(A[r + MM * k]); if (v > best) { best = v; pr = r; } }
+#pragma unroll
+            for (int r = k + 1; r < MM; ++r) {
+                if (r == pr) {
+#pragma unroll
+                    for (int j = 0; j < MM; ++j) { const double tt = A[k + MM * j]; A[k + MM * j] = A[r + MM * j]; A[r + MM * j] = tt; }
+                    const double tt = x[k]; x[k] = x[r]; x[r] = tt;
+                }
+            }
+            const double piv = 1.0 / A[k + MM * k];
+#pragma unroll
+            for (int r = k + 1; r < MM; ++r) {
+                const double f = A[r + MM * k] * piv;
+#pragma unroll
+                for (int j = k; j < MM; ++j) A[r + MM * j] -= f * A[k + MM * j];
+                x[r] -= f * x[k];
+            }
+        }
+#pragma unroll
+        for (int k = MM - 1; k >= 0; --k) {
+            double sum = x[k];
+#pragma unroll
+            for (int j = k + 1; j < MM; ++j) sum -= A[k + MM * j] * x[j];
+            x[k] = sum / A[k + MM * k];
+        }
+#pragma unroll
+        for (int r = 0; r < MM; ++r) if (r < m) out[r + (size_t)m * c] = x[r];
+    }
 }
 
 template <int NTR, int PT, int MMX>
@@ -655,4 +794,74 @@ int ddp_launch_back_pass_mid(ddp_handle h, const BPCall &c)
     }
     if (ntr == 1) return launch_mid<1, 2, 8>(h, d, a);
     return pt <= 2 ? launch_mid<2, 2, 8>(h, d, a) : launch_mid<2, 3, 8>(h, d, a);
+}
+
+// back_pass_gps for any n <= 32, m <= 8 (backward_pass.jl:259-350).  n <= 16: back_pass_mid_kernel<..., GPS_FUSED> on the raw operands.
+// 16 < n: the prepass gps_mid_combine_kernel writes c̃• into the handle's pad buffer and back_pass_mid_kernel<..., GPS_PRE> runs on them
+// (fused, those instantiations spill: DESIGN §3.5).  Then gps_mid_quui_kernel forms Quui.  Returns 1 for shapes it does not take.
+int ddp_launch_back_pass_gps_mid(ddp_handle h, const BPCall &c)
+{
+    const ddp_bp_desc *d = &c.d;
+    const ddp_kl_cost_terms *kl = c.kl;
+    const int n = d->n, m = d->m;
+    if (n < 1 || m < 1 || n > DDP_MAX_N_GENERIC || m > 8 || !kl || !c.Quui) return 1;
+    const long N = d->N, B = d->B, NB = N * B;
+    const long nn = (long)n * n, nm = (long)n * m, mm = (long)m * m;
+    BPMidArgs a;
+    a.n = n; a.m = m; a.N = d->N; a.B = d->B; a.regType = 1;
+    a.fx_t = d->fx_tv ? nn : 0; a.fx_b = d->fx_batched ? nn * (d->fx_tv ? N : 1) : 0;
+    a.fu_t = d->fx_tv ? nm : 0; a.fu_b = d->fx_batched ? nm * (d->fx_tv ? N : 1) : 0;
+    a.fx = c.fx; a.fu = c.fu; a.lambda = nullptr; a.lims = c.lims; a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    a.eta = kl->eta; a.eta_tv = kl->eta_tv;
+    a.kcx = kl->cx; a.kcu = kl->cu; a.kcxx = kl->cxx; a.kcxu = kl->cxu; a.kcuu = kl->cuu;
+    const int ntr = n <= 16 ? 1 : 2, pt = (n + m + 1 + 15) / 16;
+    int rc;
+    if (ntr == 1) {     // fused: the raw operands with their own strides, the KL terms folded in by the kernel (no prepass)
+        a.cxx_t = d->cost_tv ? nn : 0; a.cxx_b = d->cost_batched ? nn * (d->cost_tv ? N : 1) : 0;
+        a.cxu_t = d->cost_tv ? nm : 0; a.cxu_b = d->cost_batched ? nm * (d->cost_tv ? N : 1) : 0;
+        a.cuu_t = d->cost_tv ? mm : 0; a.cuu_b = d->cost_batched ? mm * (d->cost_tv ? N : 1) : 0;
+        a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu;
+        rc = m <= 4 ? launch_mid_gps<1, 2, 4>(h, d, a) : launch_mid_gps<1, 2, 8>(h, d, a);
+    } else {            // the prepass into the handle's pad buffer, then the kernel on the combined operands
+    auto al = [](size_t b_) { return (b_ + 255) & ~(size_t)255; };
+    const size_t sx = al((size_t)n * NB * 8), su = al((size_t)m * NB * 8), sxx = al((size_t)nn * NB * 8), sxu = al((size_t)nm * NB * 8),
+                 suu = al((size_t)mm * NB * 8), bytes = sx + su + sxx + sxu + suu;
+    if (bytes > h->pad_bytes) {
+        DDP_HIP(hipStreamSynchronize(h->stream));
+        if (h->pad) DDP_HIP(hipFree(h->pad));
+        h->pad = nullptr; h->pad_bytes = 0;
+        DDP_HIP(hipMalloc(&h->pad, bytes));
+        h->pad_bytes = bytes;
+    }
+    char *q = (char *)h->pad;
+    auto tk = [&](size_t b_) { double *r_ = (double *)q; q += b_; return r_; };
+    GpsMidCombine g;
+    g.n = n; g.m = m; g.N = d->N; g.B = d->B; g.eta_tv = kl->eta_tv;
+    g.cxx_t = d->cost_tv ? nn : 0; g.cxx_b = d->cost_batched ? nn * (d->cost_tv ? N : 1) : 0;
+    g.cxu_t = d->cost_tv ? nm : 0; g.cxu_b = d->cost_batched ? nm * (d->cost_tv ? N : 1) : 0;
+    g.cuu_t = d->cost_tv ? mm : 0; g.cuu_b = d->cost_batched ? mm * (d->cost_tv ? N : 1) : 0;
+    g.cx = c.cx; g.cu = c.cu; g.cxx = c.cxx; g.cxu = c.cxu; g.cuu = c.cuu;
+    g.kcx = kl->cx; g.kcu = kl->cu; g.kcxx = kl->cxx; g.kcxu = kl->cxu; g.kcuu = kl->cuu; g.eta = kl->eta;
+    g.ox = tk(sx); g.ou = tk(su); g.oxx = tk(sxx); g.oxu = tk(sxu); g.ouu = tk(suu);
+    const long lens[5] = {n, m, nn, nm, mm};
+    for (int w = 0; w < 5; ++w) {
+        const unsigned chunks = (unsigned)((lens[w] * B + 255) / 256);
+        DDP_CHECK((unsigned long)chunks * N < (1ul << 32) && (unsigned long)lens[w] * B < (1ul << 32), "back_pass_gps: N, B too large for the combine grid");
+        hipLaunchKernelGGL(gps_mid_combine_kernel, dim3(chunks * (unsigned)N), dim3(256), 0, h->stream, g, w, chunks);
+    }
+    DDP_HIP(hipGetLastError());
+    a.cxx_t = nn; a.cxx_b = nn * N; a.cxu_t = nm; a.cxu_b = nm * N; a.cuu_t = mm; a.cuu_b = mm * N;
+    a.cx = g.ox; a.cu = g.ou; a.cxx = g.oxx; a.cxu = g.oxu; a.cuu = g.ouu;
+    if (m <= 4) rc = pt <= 2 ? launch_mid_gps<2, 2, 4>(h, d, a) : launch_mid_gps<2, 3, 4>(h, d, a);
+    else rc = pt <= 2 ? launch_mid_gps<2, 2, 8>(h, d, a) : launch_mid_gps<2, 3, 8>(h, d, a);
+    }
+    if (rc) return rc;
+    const dim3 qg((unsigned)((NB + 255) / 256));
+    if (m <= 4) hipLaunchKernelGGL(gps_mid_quui_kernel<4>, qg, dim3(256), 0, h->stream, m, d->N, NB, (const double *)c.Quu, (const int32_t *)c.diverge,
+                                   c.active, c.Quui);
+    else hipLaunchKernelGGL(gps_mid_quui_kernel<8>, qg, dim3(256), 0, h->stream, m, d->N, NB, (const double *)c.Quu, (const int32_t *)c.diverge,
+                            c.active, c.Quui);
+    DDP_HIP(hipGetLastError());
+    return 0;
 }

@@ -15,7 +15,7 @@
 // The DDP_* switches of the dispatchers (kernel choice for A/B timing and for the tests that force every code path) are read from the
 // environment ONCE per handle (ddp_create) and again on ddp_reload_env(): no launch calls getenv, and a setenv() in another thread
 // cannot race with a launch.  ddp_env() returns the cached value or nullptr.
-enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_MX_LDS, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_COUNT };
+enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_MX_LDS, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_GPS_MID, ENV_COUNT };
 
 struct ddp_handle_s {
     int          device;
@@ -125,6 +125,12 @@ int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_
                               const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                               double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters);
 
+// the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev; model_fx == NULL: the family's own fx of STEP 1)
+int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
+                          const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
+                          int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
+                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters);
+
 // raises the dynamic-LDS limit of `kernel` to at least `bytes`, once per handle (capi.hip; the attribute belongs to the device the handle
 // runs on: a process-wide flag would leave a second handle on another device at the 64 KB default)
 int ddp_raise_lds(ddp_handle h, const void *kernel, int bytes);
@@ -162,6 +168,11 @@ int ddp_launch_back_pass_mxg(ddp_handle h, const BPCall &c);
 int ddp_launch_back_pass_row(ddp_handle h, const BPCall &c);
 // one wave per trajectory, the products on the fp64 matrix cores with LDS operands — any n <= 32, m <= 8 (back_pass_mid.hip)
 int ddp_launch_back_pass_mid(ddp_handle h, const BPCall &c);
+// back_pass_gps on the same kernel (GPS instantiations, KL terms combined by a prepass) — any n <= 32, m <= 8; 1 = not applicable
+int ddp_launch_back_pass_gps_mid(ddp_handle h, const BPCall &c);
+// back_pass_gps dispatch (kl.hip): the user-problem KL driver (`user`) tries q4, lane, mid, generic; every other call q4, lane, generic.
+// DDP_GPS_MID=1 puts mid first for every call, =0 keeps it out.  Records the kernel in ddp_last_kernel(h, 0).
+int ddp_dispatch_back_pass_gps(ddp_handle h, const BPCall &c, bool user);
 // shared time-invariant operands (n=10, m=2, no limits): the matrix recursion once per distinct λ, an affine chain per trajectory
 // (back_pass_sh.hip); the trajectories it left out are flagged in *fb_active
 extern "C" int ddp_sh_max_tiles(int B, int ncu);      // capacity of its work-item list: the most consumer tiles any grouping of B trajectories can make

@@ -2,7 +2,9 @@
 //   ∇kl                src/klutils.jl:8-23       one lane per (time step, trajectory)
 //   forward_covariance src/forward_pass.jl:37-56 one wave per trajectory, the discrete Lyapunov chain Σ⁺ = fx Σ fx' + R1
 //   kl_div_wiki        src/klutils.jl:70-103     one wave per trajectory, lanes over time, mean over time in the wave
-// plus the C-ABI entry points of the four KL calls (the back_pass_gps kernel itself is the GPS variant of back_pass.hip).
+// plus the C-ABI entry points of the four KL calls (the back_pass_gps kernels: the GPS variants of back_pass.hip and back_pass_mid.hip,
+// the n = 4 ones of back_pass_q4.hip and back_pass_gps_lane.hip; gps_dispatch below chooses) and the iLQGkl driver for registered and
+// user problems.
 // None of this is on the benchmarked path; the kernels are written for clarity and coalescing, not tuned.
 #include "arena.h"
 #include <stdlib.h>
@@ -629,7 +631,49 @@ __global__ __launch_bounds__(DDP_WAVE) void kl_summary_kernel(int m, int N, ddp_
 
 size_t fcov_lds(int n, int m) { return ((size_t)3 * n * n + 2 * (size_t)n * m) * sizeof(double); }
 
+// ---- back_pass_gps kernel choice.  q4: n = 4, m = 1, one η per trajectory (back_pass_q4.hip); lane: n = 4, m <= 2 (back_pass_gps_lane.hip);
+// mid: any n <= 32, m <= 8 on the matrix cores behind a combine prepass (back_pass_mid.hip); generic: the 64-lane run-time-sized kernel
+// (back_pass.hip).  The user-problem KL driver takes q4, lane, mid, generic; the stand-alone call and the registered families' driver
+// q4, lane, generic as before.  DDP_GPS_MID=1 puts mid first in every call, =0 keeps it out of all of them (A/B timing, tests).
+enum GpsKernel { GPS_Q4, GPS_LANE, GPS_MID, GPS_GENERIC };
+const char *const gps_kernel_name[] = {"back_pass_gps_q4", "back_pass_gps_lane", "back_pass_gps_mid", "back_pass_gps"};
+enum GpsCaller { GPS_STANDALONE = 0, GPS_REGISTERED = 1, GPS_USER = 2 };
+
+// host facts only (the same tests the launchers make before they return 1)
+GpsKernel gps_choose(const ddp_bp_desc &d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane)
+{
+    const char mid = gps_mid ? gps_mid[0] : 0;
+    const bool mid_ok = d.n >= 1 && d.n <= NMAXK && d.m >= 1 && d.m <= 8;
+    if (mid == '1' && mid_ok) return GPS_MID;
+    const bool fast = caller != GPS_STANDALONE || !(gps_lane && gps_lane[0] == '0');    // stand-alone DDP_GPS_LANE=0: the generic kernel
+    const bool tv = d.N >= 2 && d.fx_tv && d.cost_tv;
+    if (fast && tv && d.n == 4 && d.m == 1 && !eta_tv && !(gps_q4 && gps_q4[0] == '0')) return GPS_Q4;
+    if (fast && tv && d.n == 4 && (d.m == 1 || d.m == 2)) return GPS_LANE;
+    if (caller == GPS_USER && mid != '0' && mid_ok) return GPS_MID;
+    return GPS_GENERIC;
+}
+
+int gps_dispatch(ddp_handle h, const BPCall &c, int caller)
+{
+    const ddp_kl_cost_terms *kl = c.kl;
+    const bool complete = kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!c.d.has_lims || (c.lims && c.u));
+    GpsKernel k = complete ? gps_choose(c.d, kl->eta_tv, caller, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE))
+                           : GPS_GENERIC;
+    int rc = 1;
+    if (k == GPS_MID) rc = ddp_launch_back_pass_gps_mid(h, c);
+    if (k == GPS_Q4) {
+        rc = ddp_launch_back_pass_gps_q4(h, c);
+        if (rc > 0) k = GPS_LANE;
+    }
+    if (k == GPS_LANE) rc = ddp_launch_back_pass_gps_lane(h, c);
+    if (rc > 0) { k = GPS_GENERIC; rc = ddp_launch_back_pass_gps(h, c); }
+    h->last_kernel[0] = gps_kernel_name[k];
+    return rc;
+}
+
 }   // namespace
+
+int ddp_dispatch_back_pass_gps(ddp_handle h, const BPCall &c, bool user) { return gps_dispatch(h, c, user ? GPS_USER : GPS_REGISTERED); }
 
 extern "C" {
 
@@ -656,15 +700,18 @@ int ddp_back_pass_gps_f64_dev(ddp_handle h, const ddp_bp_desc *d,
     DDP_CHECK(h && d && cx && cu && cxx && cxu && cuu && fx && fu && kl && K && k && Quu && Quui && Vx && Vxx && dV && diverge,
               "back_pass_gps: null argument");
     DDP_HIP(hipMemsetAsync(Quui, 0, sizeof(double) * (size_t)d->m * d->m * d->N * d->B, h->stream));
-    const char *env = ddp_env(h, ENV_GPS_LANE);                     // 0: always the run-time-sized kernel (cross-check in the tests)
+    // q4 (n = 4, m = 1, one η per trajectory; DDP_GPS_Q4=0: not), lane (n = 4, m <= 2), generic; DDP_GPS_LANE=0: always the run-time-sized
+    // kernel (cross-check in the tests); DDP_GPS_MID=1: the mid kernel for every shape it takes
     const BPCall c = {*d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge, kl, Quui};
-    if (!(env && env[0] == '0') && kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!d->has_lims || (lims && u))) {
-        const int r4 = ddp_launch_back_pass_gps_q4(h, c);
-        if (r4 <= 0) return r4;                                   // n = 4, m = 1, one η per trajectory: the matrix-core kernel (DDP_GPS_Q4=0: not)
-        const int rc = ddp_launch_back_pass_gps_lane(h, c);
-        if (rc <= 0) return rc;
-    }
-    return ddp_launch_back_pass_gps(h, c);
+    return gps_dispatch(h, c, GPS_STANDALONE);
+}
+
+// Unlisted debug hook (not in ddp_amd.h): the name ddp_last_kernel(h, 0) reports after a back_pass_gps with these facts — the choice of
+// gps_dispatch, callable without a GPU.  caller: 0 stand-alone ddp_back_pass_gps_*, 1 ddp_ilqgkl_* (registered problems), 2 ddp_user_ilqgkl_*;
+// the switches DDP_GPS_MID, DDP_GPS_Q4, DDP_GPS_LANE as strings (NULL: unset)
+const char *ddp_gps_choice(const ddp_bp_desc *d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane)
+{
+    return gps_kernel_name[gps_choose(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane)];
 }
 
 int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *fx, int fx_batched,
@@ -768,34 +815,46 @@ void ddp_ilqgkl_default_opts(ddp_ilqgkl_opts *o)
     o->kl_step = 1.0; o->max_iter = 50; o->etabracket[0] = 1e-8; o->etabracket[1] = 1.0; o->etabracket[2] = 1e16; o->del0 = 1e-4;
 }
 
-int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *oo, const double *x0, const double *cost0,
-                       const double *Kp, const double *kp, const double *Sp, const double *Sip,
+// The body of ddp_ilqgkl_f64_dev and ddp_user_ilqgkl_f64_dev: the registered problem `p`, or the family `f` (a user problem) with its
+// derivatives [.,.,N,B] (constant Hessians [.,.,B]), its costfun and its rollout.  model_fx == NULL (family only): the model is the
+// problem itself, forward_covariance takes the fx of STEP 1.
+static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, const ddp_ilqgkl_opts *oo, const double *x0,
+                       const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
                        const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
                        double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
                        double *dV, double *stats, int *iters_out)
 {
-    DDP_DEVICE(h);
-    DDP_CHECK(p && x0 && Kp && kp && Sp && Sip && model_fx && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats,
-              "ilqgkl: null argument");
+    DDP_CHECK((p || f) && x0 && Kp && kp && Sp && Sip && (model_fx || f) && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV &&
+              stats, "ilqgkl: null argument");
     ddp_ilqgkl_opts od;
     if (!oo) { ddp_ilqgkl_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->max_iter >= 1, "ilqgkl: max_iter=%d (the reference returns undefined arrays without an iteration)", oo->max_iter);
     DDP_CHECK(x0 != x && kp != u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
-    const size_t n = p->n, m = p->m, N = p->N, B = p->B, CL = ddp_cost_len(p), NB = N * B, P2 = (n + m) * (n + m);
-    const bool pend = p->kind == DDP_PROBLEM_PENDCART;
+    const size_t n = f ? f->n : p->n, m = f ? f->m : p->m, N = f ? f->N : p->N, B = f ? f->B : p->B, NB = N * B, P2 = (n + m) * (n + m);
+    const bool pend = !f && p->kind == DDP_PROBLEM_PENDCART;
     DDP_CHECK(n <= (size_t)NMAXK && m <= (size_t)MMAXK, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d)", n, m, NMAXK, MMAXK);
     // dynamics as back_pass_gps wants them: [n,n,N] or [n,n,N,B]
-    const bool fx_b = pend || p->dyn_batched, fx_rep = !pend && !p->dyn_tv;
+    const bool fx_b = f || pend || p->dyn_batched, fx_rep = !f && !pend && !p->dyn_tv, fx_own = f || pend || fx_rep;
+    // cost Hessians: [.,.,N] of the registered problem, [.,.,N,B] of a family; constant Hessians of a family [.,.,B], repeated along time
+    // for every kernel but mid (the others want time-varying operands)
+    const bool cst = f && f->const_hessian;
+    ddp_bp_desc d;
+    d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = f != nullptr;
+    d.regType = 1; d.has_lims = lims != nullptr;
+    const bool hrep = cst && gps_choose(d, 0, GPS_USER, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE)) != GPS_MID;
+    if (cst && !hrep) d.cost_tv = 0;
+    const size_t hc = f ? (cst && !hrep ? B : NB) : N;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t fxc = N * (fx_b ? B : 1);
-    const size_t s_fx = (pend || fx_rep) ? al(n * n * fxc * 8) : 0, s_fu = (pend || fx_rep) ? al(n * m * fxc * 8) : 0;
+    const size_t s_fx = fx_own ? al(n * n * fxc * 8) : 0, s_fu = fx_own ? al(n * m * fxc * 8) : 0;
+    const size_t s_h = hrep ? al(n * n * B * 8) + al(n * m * B * 8) + al(m * m * B * 8) : 0;
     const size_t sz[] = {al(n * NB * 8), al(m * NB * 8),                                       // cx, cu
-                         al(n * n * N * 8), al(n * m * N * 8), al(m * m * N * 8),              // cxx, cxu, cuu [.,.,N]
+                         al(n * n * hc * 8), al(n * m * hc * 8), al(m * m * hc * 8),           // cxx, cxu, cuu
                          al(n * NB * 8), al(m * NB * 8), al(n * n * NB * 8), al(m * n * NB * 8), al(m * m * NB * 8),   // ∇kl
                          al(m * NB * 8), al(m * NB * 8),                                       // k (new policy), zeros (traj_prev.k *= 0)
                          al(P2 * NB * 8), al(NB * 8), al(B * 8), al(B * 8), al(n * B * 8),     // sigmanew, kldiv, klmean, csum, x0[:,1]
                          al(3 * B * 8), 4 * al(B * 8), 6 * al(B * 4), al(B * 4), 256};         // dual state (+ sum(cost0)), diverge, counters
-    size_t bytes = s_fx + s_fu;
+    size_t bytes = s_fx + s_fu + s_h;
     for (size_t v : sz) bytes += v;
     void *base;
     int rc = ddp_scratch(h, bytes, &base);
@@ -803,8 +862,8 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
     char *q = (char *)base;
     auto take = [&](size_t b) { void *r = q; q += al(b); return r; };
     int32_t *counter = (int32_t *)take(256);               // first: the stand-alone ddp_kl_dual_* entry points keep theirs at the scratch base
-    double *cx = (double *)take(n * NB * 8), *cu = (double *)take(m * NB * 8), *cxx = (double *)take(n * n * N * 8),
-           *cxu = (double *)take(n * m * N * 8), *cuu = (double *)take(m * m * N * 8);
+    double *cx = (double *)take(n * NB * 8), *cu = (double *)take(m * NB * 8), *cxx = (double *)take(n * n * hc * 8),
+           *cxu = (double *)take(n * m * hc * 8), *cuu = (double *)take(m * m * hc * 8);
     ddp_kl_cost_terms t;
     double *kcx = (double *)take(n * NB * 8), *kcu = (double *)take(m * NB * 8), *kcxx = (double *)take(n * n * NB * 8),
            *kcxu = (double *)take(m * n * NB * 8), *kcuu = (double *)take(m * m * NB * 8);
@@ -818,7 +877,9 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
     s.pend = (int32_t *)take(B * 4); s.iters = (int32_t *)take(B * 4); s.nback = (int32_t *)take(B * 4);
     int32_t *div = (int32_t *)take(B * 4);
     double *c0buf = (double *)take(B * 8);
-    double *fxw = (pend || fx_rep) ? (double *)take(n * n * fxc * 8) : nullptr, *fuw = (pend || fx_rep) ? (double *)take(n * m * fxc * 8) : nullptr;
+    double *fxw = fx_own ? (double *)take(n * n * fxc * 8) : nullptr, *fuw = fx_own ? (double *)take(n * m * fxc * 8) : nullptr;
+    double *hxx = hrep ? (double *)take(n * n * B * 8) : nullptr, *hxu = hrep ? (double *)take(n * m * B * 8) : nullptr,
+           *huu = hrep ? (double *)take(m * m * B * 8) : nullptr;
     t.cx = kcx; t.cu = kcu; t.cxx = kcxx; t.cxu = kcxu; t.cuu = kcuu; t.eta = s.eta; t.eta_tv = 0;
 
     hipStream_t st = h->stream;
@@ -828,24 +889,36 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
                        oo->del0, etab ? 0 : 1, s);
     DDP_HIP(hipMemsetAsync(kzero, 0, m * NB * 8, st));
     hipLaunchKernelGGL(kl_first_col_kernel, grid(n * B), dim3(256), 0, st, (int)n, (int)N, (int)B, x0, x0c);
-    // STEP 1 (:86): derivs(x, u) with u = copy(traj_prev.k) (:45)
-    if ((rc = ddp_df_f64_dev(h, p, x0, kp, nullptr, cx, cu, pend ? fxw : nullptr, pend ? fuw : nullptr))) return rc;
-    if (fx_rep) {
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
+    // STEP 1 (:86): derivs(x, u) with u = copy(traj_prev.k) (:45); a family evaluates every trajectory (no slot map: the loop recomputes all)
+    if (f) {
+        if ((rc = f->df(h, (int)B, nullptr, x0, kp, nullptr, fxw, fuw, cx, cu, cst ? nullptr : cxx, cst ? nullptr : cxu, cst ? nullptr : cuu)))
+            return rc;
+        if (cst && (rc = f->hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;
+        if (hrep) {
+            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * NB), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * NB), 1, (const double *)hxx, cxx);
+            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * NB), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * NB), 1, (const double *)hxu, cxu);
+            hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * NB), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * NB), 1, (const double *)huu, cuu);
+        }
+    } else {
+        if ((rc = ddp_df_f64_dev(h, p, x0, kp, nullptr, cx, cu, pend ? fxw : nullptr, pend ? fuw : nullptr))) return rc;
+        if (fx_rep) {
+            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
+            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
+        }
     }
-    const double *fx = (pend || fx_rep) ? fxw : p->A, *fu = (pend || fx_rep) ? fuw : p->Bm;
-    hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * N), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * N), 0, p->Q, cxx);
-    hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * N), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * N), 0, (const double *)nullptr, cxu);
-    hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * N), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * N), 0, p->R, cuu);
+    const double *fx = fx_own ? fxw : p->A, *fu = fx_own ? fuw : p->Bm;
+    if (!f) {
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * N), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * N), 0, p->Q, cxx);
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * N), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * N), 0, (const double *)nullptr, cxu);
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * N), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * N), 0, p->R, cuu);
+    }
     if ((rc = ddp_kl_terms_f64_dev(h, (int)n, (int)m, (int)N, (int)B, Kp, kzero, Sip, kcx, kcu, kcxx, kcxu, kcuu))) return rc;   // :90
     if (!cost0) {                                          // the reference insists on `cost` (:69); a C caller may leave it to costfun(x0, u)
-        if ((rc = ddp_costfun_f64_dev(h, p, x0, kp, nullptr, cost, c0buf))) return rc;
+        if ((rc = f ? f->costfun(h, (int)B, nullptr, x0, kp, nullptr, cost, c0buf) : ddp_costfun_f64_dev(h, p, x0, kp, nullptr, cost, c0buf)))
+            return rc;
         cost0 = c0buf;
     }
-    ddp_bp_desc d;
-    d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = 0;
-    d.regType = 1; d.has_lims = lims != nullptr;
+    if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56)
     const BPCall gps = {d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, kp, nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
     auto poll = [&](int *out) -> int {
         DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
@@ -865,16 +938,15 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
         if ((rc = dual(0, it))) return rc;
         for (int guard = 0;; ++guard) {                    // back passes until the KL-regularised Quu is positive definite everywhere (:95-122)
             DDP_HIP(hipMemsetAsync(Sigma, 0, m * m * NB * 8, st));
-            rc = ddp_launch_back_pass_gps_q4(h, gps);
-            if (rc > 0) rc = ddp_launch_back_pass_gps_lane(h, gps);
-            if (rc > 0) rc = ddp_launch_back_pass_gps(h, gps);
-            if (rc) return rc;
+            if ((rc = gps_dispatch(h, gps, f ? GPS_USER : GPS_REGISTERED))) return rc;
             int pending = 0;
             if ((rc = dual(1, it)) || (rc = poll(&pending))) return rc;                                    // :103-105
             if (!pending) break;
             DDP_CHECK(guard < 200, "ilqgkl: back_pass_gps keeps diverging (the reference would loop forever)");
         }
-        if ((rc = ddp_forward_pass_f64_dev(h, p, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs))) return rc;                  // :132
+        rc = f ? f->rollout(h, (int)B, nullptr, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs)
+               : ddp_forward_pass_f64_dev(h, p, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs);                                // :132
+        if (rc) return rc;
         if ((rc = ddp_forward_covariance_f64_dev(h, (int)n, (int)m, (int)N, (int)B, model_fx, model_fx_batched, R1, K, Sigma, sig))) return rc;   // :133
         if ((rc = ddp_kl_div_f64_dev(h, (int)n, (int)m, (int)N, (int)B, x, x0, sig, K, k, Sigma, Kp, kzero, Sp, Sip, kld, klm))) return rc;
         if ((rc = dual(2, it)) || (rc = poll(&live))) return rc;                                           // :141, :169-177
@@ -886,6 +958,33 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
     if (iters_out) *iters_out = it - 1;
     return 0;
 }
+
+int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *oo, const double *x0, const double *cost0,
+                       const double *Kp, const double *kp, const double *Sp, const double *Sip,
+                       const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
+                       double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
+                       double *dV, double *stats, int *iters_out)
+{
+    DDP_DEVICE(h);
+    DDP_CHECK(p && model_fx, "ilqgkl: null argument");
+    return ilqgkl_impl(h, p, nullptr, oo, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
+                       Vxx, cost, dV, stats, iters_out);
+}
+
+}   // extern "C"
+
+int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
+                          const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
+                          int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
+                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters)
+{
+    DDP_DEVICE(h);
+    DDP_CHECK(f, "ilqgkl: null problem");
+    return ilqgkl_impl(h, nullptr, f, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
+                       Vxx, cost, dV, stats, iters);
+}
+
+extern "C" {
 
 
 // host-pointer flavour of the driver: separate device allocations (the driver owns the handle's scratch), one upload, one download

@@ -647,4 +647,45 @@ int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *pa
                                               global_iters));
 }
 
+int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                            const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
+                            const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
+                            double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                            double *cost, double *dV, double *stats, int *iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, B, params, params_batched);
+    if (rc) return rc;
+    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
+                                 Vxx, cost, dV, stats, iters);
+}
+
+int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                        const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
+                        const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
+                        double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                        double *cost, double *dV, double *stats, int *iters)
+{
+    DDP_DEVICE(h);
+    UserProblem *U = as_problem(h, up);
+    if (!U) return -1;
+    int rc = bind(U, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl: null argument");
+    const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * T), *dc0 = S.in(cost0, (size_t)B),
+           *dKp = S.in(Kp, m * n * T), *dkp = S.in(kp, m * T), *dSp = S.in(Sp, m * m * T), *dSip = S.in(Sip, m * m * T),
+           *dmf = S.in(model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)), *dR1 = S.in(R1, n * n), *dl = S.in(lims, 2 * m);
+    double *det = etab ? (double *)S.put(etab, etab, (size_t)3 * B * 8) : nullptr;
+    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dS = S.out(Sigma, m * m * T), *dSi = S.out(Sigmai, m * m * T),
+           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * B), *ddV = S.out(dV, (size_t)2 * B),
+           *ds = S.out(stats, (size_t)DDP_ILQGKL_NSTATS * B);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_ilqgkl_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
+                                            det, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters));
+}
+
 }   // extern "C"

@@ -14,7 +14,8 @@
 #     DDPAmd.boxQP(H,g,lower,upper,x0)                                    ↔ src/boxQP.jl:29-188
 #     DDPAmd.forward_pass(traj_new,x0,u,x,α,problem,lims)                 ↔ src/forward_pass.jl:9-33
 #     DDPAmd.∇kl / back_pass_gps / forward_covariance / kl_div_wiki       ↔ src/klutils.jl, backward_pass.jl:259-350, forward_pass.jl:37-56
-#     DDPAmd.iLQGkl(problem, x0, traj_prev, fx_model, R1; ...)            ↔ src/iLQGkl.jl:25-178 (single KL constraint, one library call)
+#     DDPAmd.iLQGkl(problem, x0, traj_prev, fx_model, R1; ...)            ↔ src/iLQGkl.jl:25-178 (single KL constraint, one library call;
+#                                                                           a DeviceProblem with params=, fx_model = nothing: its own fx)
 #   device-resident (`DevArray`, or any array type whose `pointer` is a device pointer, e.g. AMDGPU.ROCArray)
 #     back_pass_dev!, forward_pass_dev!, df_dev!, iLQG_dev!
 module DDPAmd
@@ -1109,6 +1110,53 @@ function iLQG_mpc(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{
     return xcl, ucl, scl, x, u
 end
 
+# iLQGkl with the user's closures (`ddp_user_ilqgkl_f64`): as the method for registered problems; `fx_model = nothing` means the
+# problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B]
+function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
+                ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64})
+    constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
+    isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
+    batched = ndims(x0) == 3
+    n, N = size(x0, 1), size(x0, 2)
+    u0 = _f64(traj_prev.k)
+    m = size(u0, 1)
+    (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
+    size(u0, 2) == N || error("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")     # :72
+    B = batched ? size(x0, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    CL = cost_len(problem, N)
+    x0 = _f64(x0); Kp = _f64(traj_prev.K); Sp = _f64(traj_prev.Σ); Sip = _f64(traj_prev.Σi); R1 = _f64(R1)
+    fxm = fx_model === nothing ? Float64[] : _f64(fx_model)                  # empty: NULL, the problem's own fx
+    isempty(fxm) || size(fxm) in ((n, n, N), (n, n, N, B)) || throw(DDPError(-1, "fx_model must be [n,n,N] or [n,n,N,B]"))
+    size(R1) == (n, n) || throw(DDPError(-1, "R1 must be [n,n]"))
+    c0 = batched ? (ndims(cost) == 2 ? vec(sum(cost, dims=1)) : _f64(vec(cost))) : [Float64(sum(cost))]      # only sum(cost) enters (:74,135)
+    length(c0) == B || error("cost must hold one entry (or one column) per trajectory")
+    etab = ndims(ηbracket) == 2 ? _f64(copy(ηbracket)) : repeat(_f64(ηbracket), 1, B)                        # copy (:52)
+    size(etab) == (3, B) || error("ηbracket must be a 3-vector or 3×B")
+    limsp = _lims(lims)
+    o = ILQGKLOpts(kl_step, max_iter, (1e-8, 1.0, 1e16), del0)
+    bt = batched ? (B,) : ()
+    x, x_r = result_pair((n, N, B), (n, N, bt...)); u, u_r = result_pair((m, N, B), (m, N, bt...)); K, K_r = result_pair((m, n, N, B), (m, n, N, bt...))
+    S, S_r = result_pair((m, m, N, B), (m, m, N, bt...)); Si, Si_r = result_pair((m, m, N, B), (m, m, N, bt...))
+    Vx, Vx_r = result_pair((n, N, B), (n, N, bt...)); Vxx, Vxx_r = result_pair((n, n, N, B), (n, n, N, bt...))
+    cnew, cnew_r = result_pair((CL, B), (CL, bt...)); dV = zeros(2, B); st = zeros(12, B)
+    its = Ref{Cint}(0)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
+        check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
+            Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
+            R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+            S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
+            its::Ptr{Cint})::Cint)
+    end
+    trace = Dict{Symbol,Any}(:status => Int.(st[1, :]), :iter => Int.(st[2, :]), :n_backpass => Int.(st[3, :]), :satisfied => st[4, :] .!= 0,
+                             :η => etab, :divergence => st[8, :], :cost => st[9, :], :improvement => st[10, :],
+                             :expected_reduction => st[11, :], :grad_norm => st[12, :], :dV => dV, :batch_iterations => Int(its[]))
+    traj_new = policy(N, n, m, K_r, copy(u_r), S_r, Si_r)                                                     # traj_new.k = copy(u) (:239)
+    return x_r, u_r, traj_new, Vx_r, Vxx_r, cnew_r, trace
+end
+
 # device-pointer flavours (arrays already on the handle's device, e.g. from ddp_malloc): thin wrappers over the C entries
 user_df_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, x, u, active, fx, fu, cx, cu, cxx, cxu, cuu; handle::Handle=default_handle()) =
     check(@ccall libddp.ddp_user_df_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint, params::Ptr{Float64},
@@ -1149,6 +1197,17 @@ function user_ilqg_mpc_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o:
         lims::Ptr{Float64}, xcl::Ptr{Float64}, ucl::Ptr{Float64}, stats_cl::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64},
         git::Ptr{Cint})::Cint)
     return Int(git[])
+end
+
+function user_ilqgkl_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQGKLOpts, x0, cost0, Kp, kp, Sp, Sip, model_fx,
+                          model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats; handle::Handle=default_handle())
+    its = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqgkl_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, cost0::Ptr{Float64}, Kp::Ptr{Float64}, kp::Ptr{Float64},
+        Sp::Ptr{Float64}, Sip::Ptr{Float64}, model_fx::Ptr{Float64}, model_fx_batched::Cint, R1::Ptr{Float64}, lims::Ptr{Float64},
+        etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, Sigma::Ptr{Float64}, Sigmai::Ptr{Float64}, Vx::Ptr{Float64},
+        Vxx::Ptr{Float64}, cost::Ptr{Float64}, dV::Ptr{Float64}, stats::Ptr{Float64}, its::Ptr{Cint})::Cint)
+    return Int(its[])
 end
 
 end # module

@@ -12,7 +12,8 @@ outer loop of iLQGkl with its per-trajectory η bracket (``ddp_ilqgkl_f64``).  A
 axis is the batch of independent trajectories.  No CPU fallback.
 
 `model`: the reference calls `df(model,x,u)` and `covariance(model,x,u)` of the un-vendored LinearTimeVaryingModelsBase;
-here the model is ``Model(fx[n,n,N(,B)], fu[n,m,N(,B)], R1[n,n])`` — the arrays those calls would return — and
+here the model is ``Model(fx[n,n,N(,B)], fu[n,m,N(,B)], R1[n,n])`` — the arrays those calls would return (with a
+``DeviceProblem``, ``Model(None, None, R1)``: the problem's own linearisation at x0, traj_prev.k) — and
 ``model_covariance`` is this build's documented choice for `covariance` (empirical covariance of the one-step
 prediction residuals, the inline comment at forward_pass.jl:42).  The per-time-step branch (`constrain_per_step`,
 iLQGkl.jl:180-232) is not offloaded.
@@ -25,7 +26,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from . import GaussianPolicy, _DevProblem, _lims, default_handle, df, forward_pass
+from . import DDPError, DeviceProblem, GaussianPolicy, _DevProblem, _lims, _user_shapes, default_handle, df, forward_pass
 
 __all__ = ["Model", "grad_kl", "∇kl", "back_pass_gps", "forward_covariance", "kl_div_wiki", "calc_η", "geom", "iLQGkl",
            "model_covariance", "demo_linear_kl"]
@@ -168,10 +169,12 @@ def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, ha
 
 
 def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50, cost=None, ηbracket=(1e-8, 1.0, 1e16),
-           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None):
+           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None):
     """``iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step, lims, max_iter, cost, ηbracket, del0)`` with a registered
-    ``problem`` standing in for the three closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the
-    pre-rolled trajectory (the reference errors otherwise, :71-72) and ``cost`` its cost (:69).
+    ``problem`` or a ``DeviceProblem`` (the user's closures as device source; ``params`` as in ``iLQG``) standing in for the three
+    closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the pre-rolled trajectory (the reference errors otherwise,
+    :71-72) and ``cost`` its cost (:69).  With a ``DeviceProblem``, ``model = Model(None, None, R1)`` means the problem's own
+    linearisation (the fx of STEP 1).
     Returns ``(x, u, traj_new, Vx, Vxx, cost, trace)``; ``trace`` is a dict of per-trajectory arrays
     (status 1 SUCCESS :169 / 2 η > ηmax :174 / 3 max_iter :234, iter, η bracket, divergence, n_backpass).
     The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead."""
@@ -189,18 +192,27 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     if x.shape[1] != u.shape[1]:
         raise ValueError("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")            # :72
     prev0 = GaussianPolicy(N, n, m, _b(traj_prev.K, 3), np.zeros_like(u), _b(traj_prev.Σ, 3), _b(traj_prev.Σi, 3))   # k *= 0 (:51)
+    user = isinstance(problem, DeviceProblem)
+    prm = _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched) if user else None
     etab = np.asarray(ηbracket, dtype=np.float64)
     etab = etab.copy() if etab.shape == (3, B) else np.repeat(etab.reshape(3)[:, None], B, 1)                    # copy (:52); [3,B]: one bracket per trajectory
     del0 = np.full(B, float(del0))
     import os as _os
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
-        return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun)
+        return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm)
     # ---- DDP_KL_HOSTLOOP=1: the loop of the reference on host arrays, one library call per array operation (cross-check in the tests)
     # STEP 1 (:86): the KL demos hand 3-D arrays to back_pass_gps (demo_linear.jl:91-101)
-    fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h)
-    dynb = bool(getattr(problem, "dyn_batched", False))
-    fx, fu = _tv(fx, N, dynb), _tv(fu, N, dynb)
-    cxx, cxu, cuu = _tv(cxx, N), _tv(cxu, N), _tv(cuu, N)
+    if user:
+        fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h, params=prm[0])
+        hb = problem.const_hessian                             # constant Hessians [.,.,B]: the time axis back_pass_gps wants
+        cxx, cxu, cuu = _tv(cxx, N, hb), _tv(cxu, N, hb), _tv(cuu, N, hb)
+        if model.fx is None:
+            model = Model(fx, fu, model.R1)
+    else:
+        fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h)
+        dynb = bool(getattr(problem, "dyn_batched", False))
+        fx, fu = _tv(fx, N, dynb), _tv(fu, N, dynb)
+        cxx, cxu, cuu = _tv(cxx, N), _tv(cxu, N), _tv(cuu, N)
     kl = grad_kl(prev0, handle=h)                                                                               # :90
     status = np.zeros(B, dtype=int); iters = np.zeros(B, dtype=int); nback = np.zeros(B, dtype=int)
     divergence = np.zeros(B); satisfied = np.zeros(B, dtype=bool)
@@ -244,9 +256,10 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
                 raise RuntimeError("back_pass_gps keeps diverging (the reference would loop forever)")
         new = GaussianPolicy(N, n, m, acc[0], acc[1], acc[2], acc[3])
         sel = (lambda a: a) if allB else (lambda a: a[..., idx])                                                # noqa: E731
-        pb = problem if allB else _SubProblem(problem, idx, B)
+        pb = _SubProblem(problem, idx, B, prm[0]) if user else (problem if allB else _SubProblem(problem, idx, B))
         xs = sel(x)
         xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h)                  # :132
+        del pb                                                 # (a DeviceProblem slice frees its compiled-problem pointer here)
         mdl = Model(model.fx if (np.ndim(model.fx) == 3 or allB) else model.fx[..., idx], model.fu, model.R1)
         sig = forward_covariance(mdl, xs, sel(u), new, handle=h)                                                # :133
         pv = prev0 if allB else GaussianPolicy(N, n, m, sel(prev0.K), sel(prev0.k), sel(prev0.Σ), sel(prev0.Σi))
@@ -281,16 +294,42 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
 
 
 
-def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None):
-    """the whole loop of iLQGkl (iLQGkl.jl:91-178) as ONE library call: ``ddp_ilqgkl_f64`` (csrc/kl.hip)"""
+def _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched):
+    """a DeviceProblem in iLQGkl: extents against the compiled n, m, the parameters, model.fx and cost, before any launch"""
+    from . import _diff_mask
     n, N, B = x.shape
     m = u.shape[0]
-    dp = _DevProblem(problem, N, B, diff_fun)
-    CL = dp.cost_len
+    _user_shapes(problem, n, m)
+    tb = (B,)
+    if prev0.K.shape != (m, n, N) + tb or prev0.Σ.shape != (m, m, N) + tb or prev0.Σi.shape != (m, m, N) + tb:
+        raise DDPError("traj_prev.K, Σ, Σi should be (m,n,N), (m,m,N), (m,m,N) [+ batch axis]")
+    if model.fx is not None and np.shape(model.fx) not in ((n, n, N), (n, n, N, B)):
+        raise DDPError("model.fx should be (n,n,N) or (n,n,N,B) (None: the problem's own linearisation), got %s" % (np.shape(model.fx),))
+    if np.shape(model.R1) != (n, n):
+        raise DDPError("model.R1 should be (n, n), got %s" % (np.shape(model.R1),))
+    CL = problem.cost_len(N)
+    cs = np.shape(cost)
+    if cs not in (((CL, B), (B,)) if batched else ((CL,), (), (1,))):
+        raise DDPError("cost should be %s, got %s" % ("(CL=%d, B) or (B,)" % CL if batched else "(CL=%d,)" % CL, cs))
+    L = _lims(lims)
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    if diff_fun is not None and _diff_mask(diff_fun, n) != problem.diff_mask:
+        raise DDPError("DeviceProblem: diff_fun is compiled into the problem (DeviceProblem(..., diff=...))")
+    return problem._params(B, params)
+
+
+def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None, prm=None):
+    """the whole loop of iLQGkl (iLQGkl.jl:91-178) as ONE library call: ``ddp_ilqgkl_f64`` / ``ddp_user_ilqgkl_f64`` (csrc/kl.hip)"""
+    n, N, B = x.shape
+    m = u.shape[0]
+    user = prm is not None
+    dp = None if user else _DevProblem(problem, N, B, diff_fun)
+    CL = problem.cost_len(N) if user else dp.cost_len
     c0 = np.asarray(cost, dtype=np.float64)                                                      # only sum(cost) enters (:74,135)
     c0 = (c0.sum(axis=0) if c0.ndim == 2 else c0.reshape(-1)) if batched else np.array([c0.sum()])   # batch: [CL,B] per-step costs or [B] sums
     c0 = np.ascontiguousarray(np.broadcast_to(c0, (B,)))
-    mfx, R1 = _lib.f64(model.fx), _lib.f64(model.R1)
+    mfx, R1 = (None if model.fx is None else _lib.f64(model.fx)), _lib.f64(model.R1)
     Kp, Sp, Sip = _lib.f64(prev0.K), _lib.f64(prev0.Σ), _lib.f64(prev0.Σi)
     Lh = _lims(lims)
     o = _lib.ILQGKLOpts()
@@ -301,9 +340,15 @@ def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, 
     S = _lib.result_array((m, m, N, B)); Si = _lib.result_array((m, m, N, B)); Vx = _lib.result_array((n, N, B))
     Vxx = _lib.result_array((n, n, N, B)); co = _lib.result_array((CL, B)); dV = np.zeros((2, B), order="F")
     st = np.zeros((_lib.ILQGKL_NSTATS, B), order="F")
-    _lib.check(_lib.lib().ddp_ilqgkl_f64(h.raw, _C.byref(dp.struct), _C.byref(o), _lib.ptr(x), _lib.ptr(c0), _lib.ptr(Kp), _lib.ptr(u),
-                                         _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), int(mfx.ndim == 4), _lib.ptr(R1), _lib.ptr(Lh), _lib.ptr(eb),
-                                         *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None))
+    mb = int(mfx is not None and mfx.ndim == 4)
+    if user:
+        _lib.check(_lib.lib().ddp_user_ilqgkl_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm[0]), prm[1], _C.byref(o), _lib.ptr(x), _lib.ptr(c0),
+                                                  _lib.ptr(Kp), _lib.ptr(u), _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1),
+                                                  _lib.ptr(Lh), _lib.ptr(eb), *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None))
+    else:
+        _lib.check(_lib.lib().ddp_ilqgkl_f64(h.raw, _C.byref(dp.struct), _C.byref(o), _lib.ptr(x), _lib.ptr(c0), _lib.ptr(Kp), _lib.ptr(u),
+                                             _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1), _lib.ptr(Lh), _lib.ptr(eb),
+                                             *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None))
     trace = dict(status=st[0].astype(int), iter=st[1].astype(int), η=eb, divergence=st[7].copy(), satisfied=st[3] != 0,
                  n_backpass=st[2].astype(int), dV=dV, cost=st[8].copy(), improvement=st[9].copy(), expected_reduction=st[10].copy(),
                  grad_norm=st[11].copy())
@@ -325,11 +370,19 @@ def _tv(a, N, batched=False):
 
 
 class _SubProblem:
-    """a registered problem restricted to a subset of the batch (per-trajectory dynamics are sliced)"""
+    """a registered problem restricted to a subset of the batch (per-trajectory dynamics are sliced); a DeviceProblem with its
+    per-trajectory params[:, idx] (and a compiled-problem pointer of its own: the cached module is shared)"""
 
-    def __new__(cls, problem, idx, B):
+    def __new__(cls, problem, idx, B, params=None):
         import copy
         p = copy.copy(problem)
+        if isinstance(problem, DeviceProblem):
+            p._made = {}
+            P = problem.params if params is None else params
+            if P is not None and np.ndim(P) == 2 and np.shape(P)[1] == B:
+                P = _lib.f64(np.asarray(P)[:, idx])
+            p.params = P
+            return p
         for name in ("A", "B"):
             a = getattr(p, name, None)
             if isinstance(a, np.ndarray) and getattr(p, "dyn_batched", False) and a.shape[-1] == B:

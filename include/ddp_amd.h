@@ -564,6 +564,23 @@ int ddp_user_ilqg_mpc_f64_dev(ddp_handle h, void *up, int N, int B, const double
 int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
                           int steps, int zero_tail, const double *x0, const double *u0, const double *lims,
                           double *xcl, double *ucl, double *stats_cl, double *x, double *u, int *global_iters);
+/* iLQGkl with the user's closures: arguments, outputs, stats[DDP_ILQGKL_NSTATS,B] and exit codes as ddp_ilqgkl_f64(_dev), with the
+ * user problem in place of dynamics / costfun / derivs and params [nparam] shared or [nparam,B] per trajectory (params_batched = 1);
+ * cost[CL,B] uses the problem's CL (N+1 with DDP_USER_TERMINAL).  STEP 1 evaluates `derivatives` (or its forward-mode AD) once at
+ * (x0, kp) for every trajectory; DDP_USER_CONST_HESSIAN and the compiled diff_wrap apply, DDP_USER_PLANT is ignored.  model_fx == NULL:
+ * the model is the problem itself — forward_covariance takes the fx of STEP 1 [n,n,N,B], which is df(model, x, u) of the reference's
+ * forward_covariance (the loop never moves x0, kp); R1 is still required.  The backward pass is back_pass_gps on q4 (n = 4, m = 1),
+ * lane (n = 4, m = 2) or the mid kernel (every other n <= 32, m <= 8); ddp_last_kernel(h, 0) names it.                            */
+int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                            const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
+                            const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
+                            double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                            double *cost, double *dV, double *stats, int *iters);
+int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                        const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
+                        const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
+                        double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                        double *cost, double *dV, double *stats, int *iters);
 
 #ifdef __cplusplus
 }
