@@ -225,7 +225,8 @@ def test_forward_row_kernel_every_shape_vs_oracle(ddp, n, m):
 
 @pytest.mark.parametrize("n,m", [(5, 2), (12, 3)])
 def test_forward_row_kernel_agrees_with_the_group_kernel(ddp, n, m):
-    """the run-time-sized kernel (DDP_FORWARD=group) on the same rollouts, per-trajectory time-varying dynamics, inactive trajectories"""
+    """the run-time-sized kernel (DDP_FORWARD=group) on the same rollouts, per-trajectory time-varying dynamics (the host-pointer entry
+    takes no `active` mask: inactive trajectories are tests/test_gpu_forward_contract.py's)"""
     from ddp_amd import _lib
     rng = np.random.default_rng(5 * n + m)
     N, B = 33, 9
