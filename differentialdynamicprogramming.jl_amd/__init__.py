@@ -29,7 +29,7 @@ from . import _lib
 from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
-           "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source"]
+           "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -160,7 +160,8 @@ _EXAMPLES = _os.path.join(_lib._HERE, "user_examples")
 def example_source(name):
     """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``), or the same
     model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``; ``"car_plant"``: the car with a plant for the
-    closed loop (``plant=True``)."""
+    closed loop (``plant=True``); ``"bicycle_ad"``: a kinematic bicycle whose dynamics have mixed and control curvature, for
+    ``second_order=True``."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -173,14 +174,18 @@ class DeviceProblem:
     ``costfun`` and the whole ``iLQG`` on the device.  ``params``: ``[nparam]`` shared by the batch or ``[nparam, B]`` per trajectory
     (may be replaced per call through the ``params=`` keyword of the entry points).  ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
     ``plant=True`` (DDP_USER_PLANT): the source also defines ``plant``, the true system that ``iLQG_mpc`` advances its trajectories
-    with instead of the model."""
+    with instead of the model.  ``second_order=True`` (DDP_USER_SECOND_ORDER, needs ``autodiff=True``): full DDP — ``iLQG``,
+    ``iLQG_queue`` and ``iLQG_mpc`` run the backward pass with the curvature of the dynamics (backward_pass.jl:81-160), derived on the
+    device from the same templates; ``vhess`` and ``back_pass_ddp`` are its array-level pieces.  ``iLQGkl`` refuses such a problem."""
     kind = 2
 
-    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False):
+    def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
+                 second_order=False):
+        self.second_order = bool(second_order)
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
-                      (8 if self.plant else 0))
+                      (8 if self.plant else 0) | (16 if self.second_order else 0))
         self.diff_mask = _diff_mask(diff, self.n) if self.n <= 32 else 0
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -555,6 +560,56 @@ def _user_df(problem, x, u, *, handle=None, params=None):
         fx, fu, cx, cu, cxx, cxu, cuu = (a[..., 0] for a in (fx, fu, cx, cu, cxx, cxu, cuu))
     e = np.zeros((0,))
     return fx, fu, e, e, e, cx, cu, cxx, cxu, cuu
+
+
+def vhess(problem, x, u, v, *, handle=None, params=None):
+    """``H[n+m, n+m, N(, B)] = Σ_k v[k, i] ∂²f_k/∂z∂z`` at ``(x[:, i], u[:, i], i)``, ``z = [x; u]``, of a ``DeviceProblem`` made with
+    ``second_order=True``: the ``vectens(v, fxx)`` / ``fxu`` / ``fuu`` blocks of backward_pass.jl:106-123 without the tensors,
+    exactly symmetric."""
+    if not isinstance(problem, DeviceProblem):
+        raise TypeError("vhess: a DeviceProblem is needed")
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x, u, problem)
+    x, v = _lib.f64(x), _lib.f64(v)
+    if x.shape != ((n, N, B) if batched else (n, N)) or v.shape != x.shape:
+        raise DDPError("x and v should be (n, N) — (n, N, B) with a batched u")
+    P, pb = problem._params(B, params)
+    H = _lib.result_array((n + m, n + m, N, B))
+    _lib.check(_lib.lib().ddp_user_vhess_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(v), _lib.ptr(H)))
+    return H if batched else H[..., 0]
+
+
+def back_pass_ddp(problem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, u, *, handle=None, params=None):
+    """The second-order backward pass (backward_pass.jl:81-160) of a ``DeviceProblem`` made with ``second_order=True``: arguments as
+    ``back_pass`` with the arrays ``df(problem, x, u)`` returns (time-varying, a trailing batch axis with a batched ``u``; with
+    ``const_hessian`` the Hessians carry no time axis), the curvature terms derived on the device at ``(x, u)``.  Returns what
+    ``back_pass`` returns: ``(diverge, GaussianPolicy, Vx, Vxx, dV)``."""
+    if not isinstance(problem, DeviceProblem):
+        raise TypeError("back_pass_ddp: a DeviceProblem is needed")
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x, u, problem)
+    tb = (B,) if batched else ()
+    ht = () if problem.const_hessian else (N,)
+    x, cx, cu, cxx, cxu, cuu, fx, fu = map(_lib.f64, (x, cx, cu, cxx, cxu, cuu, fx, fu))
+    want = {"x": (x, (n, N)), "cx": (cx, (n, N)), "cu": (cu, (m, N)), "fx": (fx, (n, n, N)), "fu": (fu, (n, m, N)),
+            "cxx": (cxx, (n, n) + ht), "cxu": (cxu, (n, m) + ht), "cuu": (cuu, (m, m) + ht)}
+    for name, (arr, shp) in want.items():
+        if arr.shape != shp + tb:
+            raise DDPError("back_pass_ddp: %s should be %s, got %s" % (name, shp + tb, arr.shape))
+    L = _lims(lims)
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    P, pb = problem._params(B, params)
+    lam = np.ascontiguousarray(np.broadcast_to(np.asarray(λ, dtype=np.float64), (B,)))
+    K = _lib.result_array((m, n, N, B)); k = _lib.result_array((m, N, B)); Quu = _lib.result_array((m, m, N, B))
+    Vx = _lib.result_array((n, N, B)); Vxx = _lib.result_array((n, n, N, B)); dV = np.zeros((2, B), order="F")
+    div = np.zeros(B, dtype=np.int32)
+    _lib.check(_lib.lib().ddp_user_back_pass_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb,
+                                                 *map(_lib.ptr, (x, u, fx, fu, cx, cu, cxx, cxu, cuu, lam)), int(regType), _lib.ptr(L),
+                                                 *map(_lib.ptr, (K, k, Quu, Vx, Vxx, dV)), div.ctypes.data_as(_lib.vp)))
+    if not batched:
+        return int(div[0]), GaussianPolicy(N, n, m, K[..., 0], k[..., 0], np.zeros((m, m, N)), Quu[..., 0]), Vx[..., 0], Vxx[..., 0], dV[:, 0]
+    return div, GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, B)), Quu), Vx, Vxx, dV
 
 
 def costfun(problem, x, u, *, handle=None, params=None):

@@ -34,6 +34,7 @@ EXPORTS = [
     "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
     "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64", "ddp_user_ilqg_queue_f64_dev", "ddp_user_ilqg_queue_f64", "ddp_user_ilqg_mpc_f64_dev",
     "ddp_user_ilqg_mpc_f64", "ddp_user_ilqgkl_f64_dev", "ddp_user_ilqgkl_f64",
+    "ddp_user_vhess_f64_dev", "ddp_user_vhess_f64", "ddp_user_back_pass_f64_dev", "ddp_user_back_pass_f64",
 ]
 
 
@@ -154,6 +155,14 @@ def lib():
         L.ddp_user_check.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
         L.ddp_user_create.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.ddp_user_destroy.argtypes = [vp]
+        ci, cd = C.c_int, vp
+        L.ddp_user_vhess_f64.argtypes = [vp, vp, ci, ci, cd, ci, cd, cd, cd, cd]
+        L.ddp_user_vhess_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci, cd, cd, cd, vp, cd]
+        L.ddp_user_back_pass_f64.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 10 + [ci, cd] + [cd] * 6 + [vp]
+        L.ddp_user_back_pass_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 10 + [ci, cd, vp] + [cd] * 6 + [vp]
+        if hasattr(L, "ddp_user_program_text"):               # unlisted debug hook (tests); absent from older A/B builds of the library
+            L.ddp_user_program_text.restype = C.c_char_p
+            L.ddp_user_program_text.argtypes = [C.c_char_p, ci, ci, ci, ci, ci]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

@@ -30,12 +30,27 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_q4.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_mf2.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "back_pass_mf2_lims.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+               "back_pass_mf2_lims.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "user_problem.hip": ["-I", OBJ]}                  # build/boxqp_dev_text.h (_boxqp_text)
 
 
 EXTRA_DEPS = {"user_problem.hip": ["user_problem_kernels.h", "user_autodiff.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
               "forward_pass_dpp.hip": ["pend_math.h"]}
+
+
+def _boxqp_text():
+    """csrc/boxqp_dev.h as program text for hiprtc -> build/boxqp_dev_text.h (kBoxqpDevText).  ddp_user_back_pass2, compiled at run time
+    (user_problem_kernels.h), factorises and solves with the routines the precompiled backward kernels include: one definition for both
+    compilers.  The header's own #include lines and #pragma once are left out (hiprtc has no include path to them; ddp_rsqrt, the one
+    thing boxqp_dev.h takes from ddp_internal.h, is part of the program text)."""
+    src = open(os.path.join(CSRC, "boxqp_dev.h")).read()
+    body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
+    assert ')DDPQ"' not in body
+    text = "// written by build.py from csrc/boxqp_dev.h\nstatic const char *kBoxqpDevText = R\"DDPQ(\n" + body + ")DDPQ\";\n"
+    out = os.path.join(OBJ, "boxqp_dev_text.h")
+    if not os.path.exists(out) or open(out).read() != text:
+        open(out, "w").write(text)
 
 
 def _stale(target, deps):
@@ -98,6 +113,7 @@ def build(force=False, verbose=True):
     if force:
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
+    _boxqp_text()
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         results = list(ex.map(_compile, srcs))

@@ -97,10 +97,14 @@ void ddp_user_release(ddp_handle h);
 // too, or, with const_hessian, one set per trajectory written by hessians() (cxx[n,n,B] ...) for the slots `active` names (NULL: all).
 // The slot scheduler's map also holds -1 (empty slot) and -2 (resting slot): the family never reads parameters through those.
 // has_plant: the closed loop of ddp_ilqg_sched_family_dev advances its trajectories with plant() instead of x_1 of the plan.
+// second_order (DDP_USER_SECOND_ORDER): STEP 2 of the iLQG drivers calls back_pass() — the family's own backward pass, with the
+// curvature of its dynamics — instead of the dispatcher of back_pass.hip; the call carries x and the slot map besides the operands.
+struct BPCall;
 struct ddp_family {
     int n, m, N, B, CL;
-    bool const_hessian, has_plant;
+    bool const_hessian, has_plant, second_order = false;
     virtual ~ddp_family() {}
+    virtual int back_pass(ddp_handle h, const BPCall &c) const { ddp_set_error("back_pass: the family has no backward pass of its own"); return -1; }
     virtual int df(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx,
                    double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu) const = 0;
     virtual int hessians(ddp_handle h, int B, const int32_t *map, const int32_t *active, double *cxx, double *cxu, double *cuu) const = 0;
@@ -145,6 +149,8 @@ struct BPCall {
     int32_t *diverge;
     const ddp_kl_cost_terms *kl = nullptr;      // back_pass_gps only
     double *Quui = nullptr;                     // back_pass_gps only
+    const double *x = nullptr;                  // ddp_family::back_pass only: the nominal states x[n,N,B]
+    const int32_t *map = nullptr;               // ddp_family::back_pass only: slot -> trajectory map of the working set (may be NULL)
 };
 
 // the dispatcher (back_pass.hip) and back_pass_gps (run-time sizes n <= 32, m <= 8)

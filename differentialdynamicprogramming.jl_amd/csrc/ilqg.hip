@@ -690,8 +690,11 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
                  : ddp_df_f64_dev(h, &pw, ws.x, ws.u, ws.s.dodf, cx, cu, fxw, fuw);                              // STEP 1
         if (rc) return rc;
         if (timed) DDP_HIP(hipEventRecord(h->tev[1], st));
-        rc = ddp_launch_back_pass(h, {d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx,
-                                      dV, div});                                                             // STEP 2
+        {
+            BPCall bc = {d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div};
+            if (fam && fam->second_order) { bc.x = ws.x; bc.map = ws.map; rc = fam->back_pass(h, bc); }
+            else rc = ddp_launch_back_pass(h, bc);                                                               // STEP 2
+        }
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, ws.s);
         if (timed) DDP_HIP(hipEventRecord(h->tev[2], st));
@@ -913,7 +916,11 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
                            chess ? nullptr : huu)
                  : ddp_df_f64_dev(h, &pw, ws.x, ws.u, s.dodf, cx, cu, fxw, fuw);                                 // STEP 1
         if (rc) return rc;
-        rc = ddp_launch_back_pass(h, {d, cx, cu, cxx, cxu_, cuu, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div});   // STEP 2
+        {
+            BPCall bc = {d, cx, cu, cxx, cxu_, cuu, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div};
+            if (fam && fam->second_order) { bc.x = ws.x; bc.map = q.map; rc = fam->back_pass(h, bc); }
+            else rc = ddp_launch_back_pass(h, bc);                                                               // STEP 2
+        }
         if (rc) return rc;
         hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, s);
         const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};                         // STEP 3

@@ -980,6 +980,8 @@ int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_op
 {
     DDP_DEVICE(h);
     DDP_CHECK(f, "ilqgkl: null problem");
+    DDP_CHECK(!f->second_order, "ilqgkl: a DDP_USER_SECOND_ORDER problem is refused (back_pass_gps has no second-order variant); make the "
+                                "problem without the flag for the KL loop");
     return ilqgkl_impl(h, nullptr, f, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
                        Vxx, cost, dV, stats, iters);
 }

@@ -10,6 +10,7 @@
 //                        written once, as a chain rule on V, and nests by itself.
 //   kUserAutodiffDerivs  ddp_ad_derivatives: fx, fu by DDP_ADJ seeds per call of `dynamics`; cx, cu, cxx, cxu, cuu by the
 //                        second-order type over the block upper triangle of z = [x; u] (DDP_ADH seeds per block), mirrored.
+//   kUserAutodiffVhess   ddp_ad_vhess: one entry of the Hessian of v·f(z) (DDP_USER_SECOND_ORDER), the pair (a, b) a run-time value.
 //
 // Neither text uses a device builtin or include: with DDP_AD_FN defined as `inline` (and __device__ as nothing for the user's
 // source), both compile as host C++, which is how tests/test_user_autodiff_cpu.py checks the arithmetic without a GPU.  Every loop
@@ -342,5 +343,34 @@ DDP_AD_FN void ddp_ad_derivatives(const double *x, const double *u, int i, int N
 #if !DDP_CONST_HESSIAN
     ddp_ad_hessian<0, 0>(x, u, i, N, p, o);
 #endif
+}
+)DDPA";
+
+// DDP_USER_SECOND_ORDER only (a program without the flag does not contain it)
+static const char *kUserAutodiffVhess = R"DDPA(
+// Σ_k v[k] · ∂²f_k/∂z_a∂z_b at (x, u, i), z = [x; u]: the (a, b) entry of the Hessian of the scalar v·f(z), from ONE call of `dynamics`
+// on a dual over a dual with one partial each, the inner number seeded in direction min(a, b), the outer in max(a, b) (so the value
+// does not depend on the order of a and b).  a and b are run-time values: the seeds come from compares in the unrolled loop over z, no
+// array is indexed by them, and every lane of a wave may ask for its own pair while all of them run the same code
+// (ddp_user_back_pass2, ddp_user_vhess), which the template recursion over blocks above cannot offer.
+DDP_AD_FN double ddp_ad_vhess(const double *x, const double *u, int i, const double *p, const double *v, int a, int b)
+{
+    constexpr int n = DDP_N, m = DDP_M;
+    typedef ddp_dual<ddp_dual<double, 1>, 1> D2;
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    D2 xd[n], ud[m], xn[n];
+#pragma unroll
+    for (int k = 0; k < n + m; ++k) {
+        D2 &z = k < n ? xd[k] : ud[k - n];
+        z = D2(k < n ? x[k] : u[k - n]);
+        z.v.d[0] = k == lo ? 1.0 : 0.0;
+        z.d[0].v = k == hi ? 1.0 : 0.0;
+    }
+    DDP_AD_FRESH(p);
+    dynamics(xd, ud, i, p, xn);
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < n; ++r) s += v[r] * xn[r].d[0].d[0];
+    return s;
 }
 )DDPA";

@@ -15,8 +15,10 @@
 #include "ddp_internal.h"
 #include "user_autodiff.h"
 #include "user_problem_kernels.h"
+#include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 
 DDP_USER_ABI
+DDP_USER_ABI2
 
 namespace {
 
@@ -112,8 +114,10 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M)", m, DDP_MAX_M);
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
-    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT)) == 0, "user problem: unknown flags 0x%x",
-              flags);
+    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER)) == 0,
+              "user problem: unknown flags 0x%x", flags);
+    DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER) || (flags & DDP_USER_AUTODIFF),
+              "user problem: DDP_USER_SECOND_ORDER needs DDP_USER_AUTODIFF (the curvature of the dynamics is derived from the templated model)");
     DDP_CHECK(n >= 32 || (wrap >> n) == 0, "user problem: diff_wrap = 0x%x names coordinates at or above n = %d", wrap, n);
     const std::string src(source);
     const char *need[] = {"dynamics", "stage_cost", "derivatives"};
@@ -158,6 +162,17 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
     s += DDP_USER_ABI_TEXT;
     s += "\n";
     s += kUserKernels;
+    if (flags & DDP_USER_SECOND_ORDER) {                         // a problem without the flag: the text above, nothing more
+        s += "\n#define DDP_SECOND_ORDER 1\n#line 1 \"ddp_user_autodiff_vhess\"\n";
+        s += kUserAutodiffVhess;
+        s += "\n#line 1 \"ddp_boxqp_dev\"\n";
+        s += kUserRsqrt;
+        s += kBoxqpDevText;
+        s += "\n#line 1 \"ddp_user_kernels2\"\n";
+        s += DDP_USER_ABI2_TEXT;
+        s += "\n";
+        s += kUserKernels2;
+    }
     return s;
 }
 
@@ -221,7 +236,7 @@ int compile(const char *source, int n, int m, int nparam, int flags, unsigned wr
 
 struct Module {
     hipModule_t mod = nullptr;
-    hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr;
+    hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
     const char *df_name = nullptr;                               // ddp_user_df, or ddp_user_df_ad (DDP_USER_AUTODIFF)
     Layout L{};
 };
@@ -301,6 +316,27 @@ struct UserProblem final : ddp_family {
         void *args[] = {&a};
         DDP_HIP(hipModuleLaunchKernel(mod->plant, (unsigned)((S + 63) / 64), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
         hh->last_kernel[4] = "ddp_user_plant";
+        return 0;
+    }
+    // DDP_USER_SECOND_ORDER: the backward pass with the curvature of the dynamics (ddp_user_back_pass2); c.x and c.map are read
+    int back_pass(ddp_handle hh, const BPCall &c) const override
+    {
+        DDP_CHECK(mod->bp2, "user problem: compiled without DDP_USER_SECOND_ORDER");
+        const ddp_bp_desc &d = c.d;
+        DDP_CHECK(d.n == n && d.m == m && d.N == N && d.B >= 1, "back_pass: sizes n=%d m=%d N=%d B=%d do not match the problem", d.n, d.m, d.N, d.B);
+        DDP_CHECK(d.regType == 1 || d.regType == 2, "back_pass: regType must be 1 or 2 (got %d)", d.regType);
+        DDP_CHECK(d.fx_tv && d.fx_batched && d.cost_batched && (d.cost_tv != 0) == !const_hessian,
+                  "back_pass: a second-order pass takes the derivative arrays as ddp_user_df writes them");
+        DDP_CHECK(c.x && c.u, "back_pass: a second-order pass needs x and u");
+        DDP_CHECK(!d.has_lims || c.lims, "back_pass: has_lims needs lims");
+        UserBp2Args a;
+        a.N = N; a.B = d.B; a.regType = d.regType; a.has_lims = d.has_lims; a.params_batched = params_batched; a.pad_ = 0;
+        a.params = params; a.x = c.x; a.u = c.u; a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu;
+        a.lambda = c.lambda; a.lims = c.lims; a.active = c.active; a.map = c.map;
+        a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+        void *args[] = {&a};
+        DDP_HIP(hipModuleLaunchKernel(mod->bp2, (unsigned)d.B, 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
+        hh->last_kernel[0] = "ddp_user_back_pass2";
         return 0;
     }
 };
@@ -413,7 +449,9 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
                         hipModuleGetFunction(&M.df, M.mod, M.df_name) == hipSuccess &&
                         hipModuleGetFunction(&M.cost, M.mod, "ddp_user_cost") == hipSuccess &&
                         (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess) &&
-                        (!(flags & DDP_USER_PLANT) || hipModuleGetFunction(&M.plant, M.mod, "ddp_user_plant") == hipSuccess);
+                        (!(flags & DDP_USER_PLANT) || hipModuleGetFunction(&M.plant, M.mod, "ddp_user_plant") == hipSuccess) &&
+                        (!(flags & DDP_USER_SECOND_ORDER) || (hipModuleGetFunction(&M.bp2, M.mod, "ddp_user_back_pass2") == hipSuccess &&
+                                                              hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess));
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -424,6 +462,7 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
     UserProblem *P = new UserProblem();
     P->h = h; P->n = n; P->m = m; P->N = 0; P->B = 0; P->CL = 0; P->const_hessian = (flags & DDP_USER_CONST_HESSIAN) != 0;
     P->has_plant = false;                                        // set by the closed-loop entry points only
+    P->second_order = (flags & DDP_USER_SECOND_ORDER) != 0;
     P->nparam = nparam; P->flags = flags; P->wrap = wrap; P->mod = &it->second;
     *out = P;
     return 0;
@@ -467,6 +506,103 @@ int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, 
            *dxx = S.out(cxx, n * n * HT), *dxu = S.out(cxu, n * m * HT), *duu = S.out(cuu, m * m * HT);
     DDP_STAGED(S);
     return S.finish(ddp_user_df_f64_dev(h, up, N, B, dp, params_batched, dx, du, nullptr, dfx, dfu, dcx, dcu, dxx, dxu, duu));
+}
+
+int ddp_user_vhess_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                           const double *v, const int32_t *active, double *H)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->vhess, "vhess: the problem was made without DDP_USER_SECOND_ORDER");
+    DDP_CHECK(x && u && v && H, "vhess: null argument");
+    UserVhessArgs a;
+    a.N = N; a.B = B; a.params_batched = params_batched; a.pad_ = 0;
+    a.params = P->params; a.x = x; a.u = u; a.v = v; a.active = active; a.map = nullptr; a.H = H;
+    void *args[] = {&a};
+    const int nz = P->n + P->m;
+    const long total = (long)(nz * (nz + 1) / 2) * N * B;
+    DDP_CHECK(total <= 64L * 0x7fffffffL, "vhess: N = %d, B = %d is too large for one launch", N, B);
+    DDP_HIP(hipModuleLaunchKernel(P->mod->vhess, (unsigned)((total + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    h->last_kernel[2] = "ddp_user_vhess";
+    return 0;
+}
+
+int ddp_user_vhess_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                       const double *v, double *H)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    DDP_CHECK(x && u && v && H, "vhess: null argument");
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    const size_t n = P->n, m = P->m, T = (size_t)N * B;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T), *dv = S.in(v, n * T);
+    double *dH = S.out(H, (n + m) * (n + m) * T);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_vhess_f64_dev(h, up, N, B, dp, params_batched, dx, du, dv, nullptr, dH));
+}
+
+int ddp_user_back_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                               const double *u, const double *fx, const double *fu, const double *cx, const double *cu, const double *cxx,
+                               const double *cxu, const double *cuu, const double *lambda, int regType, const double *lims,
+                               const int32_t *active, double *K, double *k, double *Quu, double *Vx, double *Vxx, double *dV,
+                               int32_t *diverge)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(P->second_order, "back_pass: the problem was made without DDP_USER_SECOND_ORDER; a first-order pass is ddp_back_pass_f64 "
+                               "on the arrays of ddp_user_df");
+    DDP_CHECK(x && u && fx && fu && cx && cu && cxx && cxu && cuu && lambda && K && k && Quu && Vx && Vxx && dV && diverge,
+              "back_pass: null argument");
+    BPCall c = {};
+    c.d.n = P->n; c.d.m = P->m; c.d.N = N; c.d.B = B; c.d.fx_tv = 1; c.d.fx_batched = 1; c.d.cost_tv = P->const_hessian ? 0 : 1;
+    c.d.cost_batched = 1; c.d.regType = regType; c.d.has_lims = lims != nullptr;
+    c.cx = cx; c.cu = cu; c.cxx = cxx; c.cxu = cxu; c.cuu = cuu; c.fx = fx; c.fu = fu; c.lambda = lambda; c.lims = lims; c.u = u; c.x = x;
+    c.active = active; c.K = K; c.k = k; c.Quu = Quu; c.Vx = Vx; c.Vxx = Vxx; c.dV = dV; c.diverge = diverge;
+    return P->back_pass(h, c);
+}
+
+int ddp_user_back_pass_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                           const double *fx, const double *fu, const double *cx, const double *cu, const double *cxx, const double *cxu,
+                           const double *cuu, const double *lambda, int regType, const double *lims, double *K, double *k, double *Quu,
+                           double *Vx, double *Vxx, double *dV, int32_t *diverge)
+{
+    DDP_DEVICE(h);
+    UserProblem *P = as_problem(h, up);
+    if (!P) return -1;
+    int rc = bind(P, N, B, params, params_batched);
+    if (rc) return rc;
+    DDP_CHECK(x && u && fx && fu && cx && cu && cxx && cxu && cuu && lambda && K && k && Quu && Vx && Vxx && dV && diverge,
+              "back_pass: null argument");
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, HT = P->const_hessian ? (size_t)B : T;
+    Staging S(h);
+    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T),
+           *dfx = S.in(fx, n * n * T), *dfu = S.in(fu, n * m * T), *dcx = S.in(cx, n * T), *dcu = S.in(cu, m * T), *dxx = S.in(cxx, n * n * HT),
+           *dxu = S.in(cxu, n * m * HT), *duu = S.in(cuu, m * m * HT), *dlam = S.in(lambda, (size_t)B), *dl = S.in(lims, 2 * m);
+    double *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T), *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T),
+           *ddV = S.out(dV, (size_t)2 * B);
+    int32_t *ddiv = (int32_t *)S.put(nullptr, diverge, (size_t)B * 4);
+    DDP_STAGED(S);
+    return S.finish(ddp_user_back_pass_f64_dev(h, up, N, B, dp, params_batched, dx, du, dfx, dfu, dcx, dcu, dxx, dxu, duu, dlam, regType, dl,
+                                               nullptr, dK, dk, dQ, dVx, dVxx, ddV, ddiv));
+}
+
+// Unlisted debug hook (not in ddp_amd.h): the program text hiprtc compiles for these arguments (tests: a problem without
+// DDP_USER_SECOND_ORDER compiles the text it compiled before the flag existed).  NULL if the arguments are refused.
+const char *ddp_user_program_text(const char *source, int n, int m, int nparam, int flags, int diff_wrap)
+{
+    static thread_local std::string text;
+    if (validate(source, n, m, nparam, flags, (unsigned)diff_wrap)) return nullptr;
+    text = program_text(source, n, m, nparam, flags, (unsigned)diff_wrap);
+    return text.c_str();
 }
 
 int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,

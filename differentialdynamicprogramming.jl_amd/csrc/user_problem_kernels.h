@@ -327,3 +327,447 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_plant(UserPlantArgs a)
 }
 #endif
 )DDPK";
+
+// ---- DDP_USER_SECOND_ORDER: appended to the program of a problem with the flag only (a problem without it compiles the text above,
+// unchanged).  The program then is: the macros (+ DDP_SECOND_ORDER 1), user_autodiff.h's texts around the user's source, DDP_USER_ABI,
+// kUserKernels, ddp_rsqrt + the text of boxqp_dev.h (kBoxqpDevText, written by build.py from the header the precompiled backward
+// kernels include: one definition of the Cholesky and the box-QP for both compilers), DDP_USER_ABI2, kUserKernels2.
+//
+//   ddp_user_back_pass2  the backward pass of backward_pass.jl:81-160 (the reference's second-order variant): Qxx += Vx⁺·fxx,
+//                        Qux += Vx⁺·fxu, Quu += Vx⁺·fuu, and the same Hux, Huu in Qux_reg and QuuF.  One wave per trajectory, the step
+//                        as in back_pass.hip (P1-P4, operands and intermediates in LDS, fx/fu and the cost Hessians one step ahead in
+//                        registers, cx|cu|x|u in chunks of DDP_TC steps) with every size a compile-time constant.  The curvature
+//                        H_i = ∇²_z (Vx_{i+1}·f(z)) needs no tensor: the (n+m)(n+m+1)/2 pairs a <= b are dealt over the 64 lanes, each
+//                        lane calls ddp_ad_vhess for its pair and adds the value into the LDS image of the step's cost Hessians at
+//                        (a, b) and (b, a) before the Q-expansion reads it.  The phase reads Vx_{i+1}, x_i, u_i and the parameters
+//                        only, so it runs after the step's prefetch loads are issued, in their shadow.
+//   ddp_user_vhess       H[n+m, n+m, N, B] = Σ_k v[k, i, b] ∂²f_k/∂z∂z at (x, u): one lane per (pair, step, trajectory).
+#define DDP_USER_ABI2                                                                                                                 \
+    struct UserBp2Args {                                                                                                             \
+        int N, B, regType, has_lims, params_batched, pad_;                                                                           \
+        const double *params, *x, *u, *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims;                                          \
+        const int *active, *map;                                                                                                     \
+        double *K, *k, *Quu, *Vx, *Vxx, *dV;                                                                                         \
+        int *diverge;                                                                                                                \
+    };                                                                                                                               \
+    struct UserVhessArgs {                                                                                                           \
+        int N, B, params_batched, pad_;                                                                                              \
+        const double *params, *x, *u, *v;                                                                                            \
+        const int *active, *map;                                                                                                     \
+        double *H;                                                                                                                   \
+    };
+#define DDP_USER_ABI2_TEXT DDP_USER_STR(DDP_USER_ABI2)
+
+// 1/sqrt(x) of ddp_internal.h (which hiprtc cannot include), for the text of boxqp_dev.h
+static const char *kUserRsqrt = R"DDPK(
+__device__ __forceinline__ double ddp_rsqrt(double x)
+{
+    double y = __builtin_amdgcn_rsq(x);
+    double e = fma(-(x * y), y, 1.0);
+    y = fma(0.5 * y, e, y);
+    e = fma(-(x * y), y, 1.0);
+    y = fma(0.5 * y, e, y);
+    return y;
+}
+)DDPK";
+
+static const char *kUserKernels2 = R"DDPK(
+#if DDP_SECOND_ORDER
+#define DDP_NZ (DDP_N + DDP_M)
+#define DDP_NPAIR (DDP_NZ * (DDP_NZ + 1) / 2)
+#define DDP_TC 8                                              // time steps per cx | cu | x | u chunk
+
+// Hand-off between the lanes of the one wave of a work-group through LDS.  Wavefront scope: LDS operations of a wave execute in issue
+// order, the compiler must not move them across the hand-off, and nothing here may wait for the step's outstanding global loads and
+// stores (a wider scope may: the prefetch of the next step would then land on the critical path)
+__device__ __forceinline__ void ddp_bp2_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__host__ __device__ constexpr int ddp_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// element e of the upper triangle stored by columns: e = j (j + 1) / 2 + i, i <= j
+__device__ __forceinline__ void ddp_tri(int e, int &i, int &j)
+{
+    int c = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+    while (c * (c + 1) / 2 > e) --c;
+    while ((c + 1) * (c + 2) / 2 <= e) ++c;
+    j = c;
+    i = e - c * (c + 1) / 2;
+}
+
+extern "C" __global__ __launch_bounds__(64) void ddp_user_back_pass2(UserBp2Args a)
+{
+    constexpr int n = DDP_N, m = DDP_M, p = DDP_NZ, TC = DDP_TC, HS = DDP_CONST_HESSIAN ? 0 : 1;
+    constexpr int nn = n * n, nm = n * m, mm = m * m, ntri = n * (n + 1) / 2;
+    constexpr int R1 = ddp_cdiv(n * p, 64), RT = ddp_cdiv(ntri, 64), RU = ddp_cdiv(m * p, 64), RN = ddp_cdiv(nn, 64), RX = ddp_cdiv(nm, 64);
+    constexpr int CLEN = 2 * p, RC = ddp_cdiv(TC * CLEN, 64), RP = ddp_cdiv(DDP_NPAIR, 64);
+    // LDS carve-up (doubles)
+    constexpr int oF = 0, oV = oF + n * p, ov = oV + nn, oW = ov + n, oQ = oW + n * p, oxx = oQ + p, oxu = oxx + nn, ouu = oxu + nm,
+                  oQux = ouu + mm, oQuxr = oQux + nm, oQuu = oQuxr + nm, oQuuF = oQuu + mm, oK = oQuuF + mm, ok = oK + nm, oT = ok + m,
+                  oQuuk = oT + nm, oC = (oQuuk + m + 1) & ~1, TOTAL = oC + 2 * TC * CLEN;
+    static_assert(TOTAL * 8 <= 64 * 1024, "ddp_user_back_pass2: the step does not fit 64 KB of LDS");
+    __shared__ double lds[TOTAL];
+    double *Fs = lds + oF, *Vs = lds + oV, *vs = lds + ov, *Ws = lds + oW, *Qs = lds + oQ, *cxxs = lds + oxx, *cxus = lds + oxu,
+           *cuus = lds + ouu, *Quxs = lds + oQux, *Quxrs = lds + oQuxr, *Quus = lds + oQuu, *QuuFs = lds + oQuuF, *Ks = lds + oK,
+           *ks = lds + ok, *Ts = lds + oT, *Quuks = lds + oQuuk, *cbuf = lds + oC;
+
+    const int b = blockIdx.x, lane = threadIdx.x, N = a.N;
+    if (b >= a.B || (a.active && a.active[b] == 0)) return;
+    const double *pp = ddp_params(a.params, a.params_batched, a.map, b);
+    const double *cx = a.cx + (size_t)n * N * b, *cu = a.cu + (size_t)m * N * b, *xg = a.x + (size_t)n * N * b, *ug = a.u + (size_t)m * N * b;
+    const double *fx = a.fx + (size_t)nn * N * b, *fu = a.fu + (size_t)nm * N * b;
+    const double *cxx = a.cxx + (size_t)nn * (HS ? N : 1) * b, *cxu = a.cxu + (size_t)nm * (HS ? N : 1) * b,
+                 *cuu = a.cuu + (size_t)mm * (HS ? N : 1) * b;
+    double *Kg = a.K + (size_t)nm * N * b, *kg = a.k + (size_t)m * N * b, *Quug = a.Quu + (size_t)mm * N * b,
+           *Vxg = a.Vx + (size_t)n * N * b, *Vxxg = a.Vxx + (size_t)nn * N * b;
+    const double lam = a.lambda[b];
+    const int regType = a.regType;
+    bool nolims = true;
+    double limlo[m], limhi[m];
+#pragma unroll
+    for (int q = 0; q < m; ++q) { limlo[q] = 0.0; limhi[q] = 0.0; }
+    if (a.has_lims) {
+        nolims = a.lims[0] > a.lims[m];                          // backward_pass.jl:31
+#pragma unroll
+        for (int q = 0; q < m; ++q) { limlo[q] = a.lims[q]; limhi[q] = a.lims[q + m]; }
+    }
+    const QPOptsDev qpo = {100, 1e-8, 1e-8, 0.6, 1e-22, 0.1};    // boxQP.jl:30-35
+
+    // ---- per-lane element assignments (loop invariant)
+    int t_i[RT], t_j[RT];                                        // P2 / P4: (i <= j) of the Qxx / Vxx upper-triangle element
+#pragma unroll
+    for (int r = 0; r < RT; ++r) ddp_tri(lane + 64 * r, t_i[r], t_j[r]);
+    int h_a[RP], h_b[RP];                                        // curvature phase: the lane's pairs a <= b of z = [x; u]
+#pragma unroll
+    for (int r = 0; r < RP; ++r) ddp_tri(lane + 64 * r, h_a[r], h_b[r]);
+
+    // chunk c holds the time steps [c TC, c TC + TC) of cx | cu | x | u, time-major per stream
+    auto chunk_elem = [&](int c, int e) -> double {              // e in [0, TC * CLEN)
+        const int t0 = c * TC;
+        if (e < TC * n) return t0 + e / n < N ? cx[(size_t)t0 * n + e] : 0.0;
+        e -= TC * n;
+        if (e < TC * m) return t0 + e / m < N ? cu[(size_t)t0 * m + e] : 0.0;
+        e -= TC * m;
+        if (e < TC * n) return t0 + e / n < N ? xg[(size_t)t0 * n + e] : 0.0;
+        e -= TC * n;
+        return t0 + e / m < N ? ug[(size_t)t0 * m + e] : 0.0;
+    };
+
+    // ---- the last step has no dynamics (backward_pass.jl:93-95): Vx = cx, Vxx = cxx, Quu = cuu
+    for (int e = lane; e < nn; e += 64) {
+        const double v = cxx[(size_t)nn * (N - 1) * HS + e];
+        Vs[e] = v;
+        Vxxg[(size_t)nn * (N - 1) + e] = v;
+    }
+    for (int e = lane; e < n; e += 64) {
+        const double v = cx[(size_t)n * (N - 1) + e];
+        vs[e] = v;
+        Vxg[(size_t)n * (N - 1) + e] = v;
+    }
+    for (int e = lane; e < mm; e += 64) Quug[(size_t)mm * (N - 1) + e] = cuu[(size_t)mm * (N - 1) * HS + e];
+    for (int e = lane; e < nm; e += 64) Kg[(size_t)nm * (N - 1) + e] = 0.0;
+    for (int e = lane; e < m; e += 64) { kg[(size_t)m * (N - 1) + e] = 0.0; ks[e] = 0.0; }
+    double dV0 = 0.0, dV1 = 0.0;
+    if (N < 2) {
+        if (lane == 0) { a.dV[2 * b] = 0.0; a.dV[2 * b + 1] = 0.0; a.diverge[b] = 0; }
+        return;
+    }
+    // the first step's operands straight to LDS, the next chunk into registers
+    double pfc[RC];
+    {
+        const int c0 = (N - 2) / TC;
+        for (int e = lane; e < TC * CLEN; e += 64) cbuf[(c0 & 1) * TC * CLEN + e] = chunk_elem(c0, e);
+#pragma unroll
+        for (int r = 0; r < RC; ++r) {
+            const int e = lane + 64 * r;
+            pfc[r] = (c0 > 0 && e < TC * CLEN) ? chunk_elem(c0 - 1, e) : 0.0;
+        }
+    }
+    double pfF[R1], pfxx[RN], pfxu[RX], pfuu = 0.0;
+    {
+        const int i0 = N - 2;
+        for (int e = lane; e < nn; e += 64) { Fs[e] = fx[(size_t)nn * i0 + e]; cxxs[e] = cxx[(size_t)nn * i0 * HS + e]; }
+        for (int e = lane; e < nm; e += 64) { Fs[nn + e] = fu[(size_t)nm * i0 + e]; cxus[e] = cxu[(size_t)nm * i0 * HS + e]; }
+        for (int e = lane; e < mm; e += 64) cuus[e] = cuu[(size_t)mm * i0 * HS + e];
+    }
+    ddp_bp2_sync();
+
+    int diverge = 0;
+    for (int i = N - 2; i >= 0; --i) {
+        const int cc = i / TC;
+        const double *cb = cbuf + (cc & 1) * TC * CLEN;
+        const double *cxi = cb + (i - cc * TC) * n;
+        const double *cui = cb + TC * n + (i - cc * TC) * m;
+        const double *xi = cb + TC * p + (i - cc * TC) * n;
+        const double *ui = cb + TC * (p + n) + (i - cc * TC) * m;
+
+        // ---- issue the next step's operands (they land while this step computes)
+        if (i > 0) {
+#pragma unroll
+            for (int r = 0; r < R1; ++r) {
+                const int e = lane + 64 * r;
+                if (e < n * p) pfF[r] = (e < nn) ? fx[(size_t)nn * (i - 1) + e] : fu[(size_t)nm * (i - 1) + (e - nn)];
+            }
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int e = lane + 64 * r;
+                if (e < nn) pfxx[r] = cxx[(size_t)nn * (i - 1) * HS + e];
+            }
+#pragma unroll
+            for (int r = 0; r < RX; ++r) {
+                const int e = lane + 64 * r;
+                if (e < nm) pfxu[r] = cxu[(size_t)nm * (i - 1) * HS + e];
+            }
+            if (lane < mm) pfuu = cuu[(size_t)mm * (i - 1) * HS + lane];
+        }
+
+        // ================= P0: H = ∇²_z (Vx_{i+1}·f)(x_i, u_i) into the cost Hessians of the step (:106-123) =================
+        // every pair belongs to one lane and is written to (a, b) and (b, a): cxx + Hxx and cuu + Huu stay exactly symmetric
+#ifndef DDP_BP2_NO_CURVATURE                                      // (a source that defines it: the pass without P0, for bench/user_second_order.py)
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            if (lane + 64 * r < DDP_NPAIR) {
+                const int pa = h_a[r], pb = h_b[r];
+                const double hv = ddp_ad_vhess(xi, ui, i, pp, vs, pa, pb);
+                if (pb < n) {
+                    cxxs[pa + n * pb] += hv;
+                    if (pa != pb) cxxs[pb + n * pa] += hv;
+                } else if (pa < n) {
+                    cxus[pa + n * (pb - n)] += hv;
+                } else {
+                    cuus[(pa - n) + m * (pb - n)] += hv;
+                    if (pa != pb) cuus[(pb - n) + m * (pa - n)] += hv;
+                }
+            }
+        }
+#endif
+
+        // ================= P1: W = Vxx·F,  Qs = [cx; cu] + F'Vx =================
+#pragma unroll
+        for (int r = 0; r < R1; ++r) {
+            const int e = lane + 64 * r;
+            if (e < n * p) {
+                const double *vc = Vs + (e % n) * n, *fc = Fs + (e / n) * n;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < n; ++l) s += vc[l] * fc[l];
+                Ws[e] = s;
+            }
+        }
+        for (int j = 63 - lane; j < p; j += 64) {                // high lanes: idle in the last W round
+            const double *fc = Fs + j * n;
+            double s = 0.0;
+#pragma unroll
+            for (int l = 0; l < n; ++l) s += fc[l] * vs[l];
+            Qs[j] = (j < n ? cxi[j] : cui[j - n]) + s;
+        }
+        ddp_bp2_sync();
+
+        // ================= P2: Qxx (registers), Qux, Quu and the regularised variants =================
+        double qxx[RT];
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const int e = lane + 64 * r;
+            qxx[r] = 0.0;
+            if (e < ntri) {
+                const double *fc = Fs + t_i[r] * n, *wc = Ws + t_j[r] * n;
+                double s = 0.0;
+#pragma unroll
+                for (int l = 0; l < n; ++l) s += fc[l] * wc[l];
+                qxx[r] = cxxs[t_i[r] + n * t_j[r]] + s;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RU; ++r) {
+            const int e = (63 - lane) + 64 * r;
+            if (e < m * p) {
+                const int q = e % m, j = e / m;
+                const double *fc = Fs + (n + q) * n, *wc = Ws + j * n, *fj = Fs + j * n;
+                double s = 0.0, sr = 0.0;
+#pragma unroll
+                for (int l = 0; l < n; ++l) { s += fc[l] * wc[l]; sr += fc[l] * fj[l]; }
+                if (j < n) {                                     // Qux, Qux_reg
+                    const double c = cxus[j + n * q];
+                    Quxs[q + m * j] = c + s;
+                    Quxrs[q + m * j] = c + (regType == 2 ? s + lam * sr : s);
+                } else {                                         // Quu, QuuF
+                    const int bb = j - n;
+                    const double c = cuus[q + m * bb];
+                    Quus[q + m * bb] = c + s;
+                    QuuFs[q + m * bb] = c + (regType == 2 ? s + lam * sr : s) + ((regType == 1 && q == bb) ? lam : 0.0);
+                }
+            }
+        }
+        ddp_bp2_sync();
+
+        // ================= P3: gains (backward_pass.jl:30-62), every lane the same solve =================
+        double H[mm], R[mm], kk[m], ri[m];
+        unsigned clamped = 0u;
+#pragma unroll
+        for (int e = 0; e < mm; ++e) H[e] = QuuFs[e];
+        int fail;
+        if (nolims) {
+            fail = chol_masked_ri<m>(m, H, 0u, R, ri);
+#pragma unroll
+            for (int q = 0; q < m; ++q) kk[q] = Qs[n + q];
+            chol_solve_ri<m>(m, R, ri, kk);
+#pragma unroll
+            for (int q = 0; q < m; ++q) kk[q] = -kk[q];
+        } else {
+            double g[m], lo[m], up[m], x0[m];
+#pragma unroll
+            for (int q = 0; q < m; ++q) {
+                const double uq = ui[q];
+                g[q] = Qs[n + q];
+                lo[q] = limlo[q] - uq;
+                up[q] = limhi[q] - uq;
+                x0[q] = ks[q];                                   // k[:, min(i+1, N-1)]
+            }
+            int iters;
+            const int result = boxqp_dev_ri<m>(m, H, g, lo, up, x0, qpo, kk, R, ri, clamped, iters);
+            fail = (result < 1);
+        }
+        if (fail) {                                              // wave-uniform: diverge = i (1-based)
+            diverge = i + 1;
+            for (int e = lane; e < mm; e += 64) Quug[(size_t)mm * i + e] = Quus[e];   // the reference has stored Quu[:,:,i] already
+            for (size_t e = lane; e < (size_t)nm * (i + 1); e += 64) Kg[e] = 0.0;
+            for (size_t e = lane; e < (size_t)m * (i + 1); e += 64) kg[e] = 0.0;
+            for (size_t e = lane; e < (size_t)n * (i + 1); e += 64) Vxg[e] = 0.0;
+            for (size_t e = lane; e < (size_t)nn * (i + 1); e += 64) Vxxg[e] = 0.0;
+            for (size_t e = lane; e < (size_t)mm * i; e += 64) Quug[e] = 0.0;
+            break;
+        }
+        if (lane < n) {                                          // column `lane` of K_i
+            double col[m];
+#pragma unroll
+            for (int q = 0; q < m; ++q) col[q] = ((clamped >> q) & 1u) ? 0.0 : Quxrs[q + m * lane];
+            chol_solve<m>(m, R, col);
+#pragma unroll
+            for (int q = 0; q < m; ++q) col[q] = ((clamped >> q) & 1u) ? 0.0 : -col[q];
+#pragma unroll
+            for (int q = 0; q < m; ++q) {
+                double t = Quxs[q + m * lane];                   // T = Quu·K + Qux
+#pragma unroll
+                for (int q2 = 0; q2 < m; ++q2) t += Quus[q + m * q2] * col[q2];
+                Ks[q + m * lane] = col[q];
+                Ts[q + m * lane] = t;
+            }
+        } else if (lane == n) {                                  // k_i, Quu·k, dV
+            double kQu = 0.0, kQuuk = 0.0;
+#pragma unroll
+            for (int q = 0; q < m; ++q) {
+                double t = 0.0;
+#pragma unroll
+                for (int q2 = 0; q2 < m; ++q2) t += Quus[q + m * q2] * kk[q2];
+                Quuks[q] = t;
+                ks[q] = kk[q];
+                kQu += kk[q] * Qs[n + q];
+                kQuuk += kk[q] * t;
+            }
+            dV0 += kQu;
+            dV1 += 0.5 * kQuuk;
+        }
+        ddp_bp2_sync();
+
+        // ================= P4: value update, stores, operand hand-over =================
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+            const int e = lane + 64 * r;
+            if (e < ntri) {
+                const int ii = t_i[r], jj = t_j[r];
+                double mij = qxx[r], mji = qxx[r];
+#pragma unroll
+                for (int q = 0; q < m; ++q) {
+                    const double Ki = Ks[q + m * ii], Kj = Ks[q + m * jj];
+                    mij += Ki * Ts[q + m * jj] + Quxs[q + m * ii] * Kj;
+                    mji += Kj * Ts[q + m * ii] + Quxs[q + m * jj] * Ki;
+                }
+                const double v = (mij + mji) / 2;
+                Vs[ii + n * jj] = v;
+                Vs[jj + n * ii] = v;
+                Vxxg[(size_t)nn * i + ii + n * jj] = v;
+                Vxxg[(size_t)nn * i + jj + n * ii] = v;
+            }
+        }
+        for (int j = 63 - lane; j < n; j += 64) {                // Vx_i
+            double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll
+            for (int q = 0; q < m; ++q) {
+                s1 += Ks[q + m * j] * Quuks[q];
+                s2 += Ks[q + m * j] * Qs[n + q];
+                s3 += Quxs[q + m * j] * ks[q];
+            }
+            const double v = ((Qs[j] + s1) + s2) + s3;
+            vs[j] = v;
+            Vxg[(size_t)n * i + j] = v;
+        }
+        for (int e = lane; e < nm; e += 64) Kg[(size_t)nm * i + e] = Ks[e];
+        if (lane < m) kg[(size_t)m * i + lane] = ks[lane];
+        if (lane < mm) Quug[(size_t)mm * i + lane] = Quus[lane];
+        // the prefetched operands of step i-1 into LDS (their last readers were P1 / P2)
+        if (i > 0) {
+#pragma unroll
+            for (int r = 0; r < R1; ++r) {
+                const int e = lane + 64 * r;
+                if (e < n * p) Fs[e] = pfF[r];
+            }
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int e = lane + 64 * r;
+                if (e < nn) cxxs[e] = pfxx[r];
+            }
+#pragma unroll
+            for (int r = 0; r < RX; ++r) {
+                const int e = lane + 64 * r;
+                if (e < nm) cxus[e] = pfxu[r];
+            }
+            if (lane < mm) cuus[lane] = pfuu;
+        }
+        if (i > 0 && i == cc * TC) {                             // leaving chunk cc: publish cc-1, fetch cc-2
+            double *nb = cbuf + ((cc - 1) & 1) * TC * CLEN;
+#pragma unroll
+            for (int r = 0; r < RC; ++r) {
+                const int e = lane + 64 * r;
+                if (e < TC * CLEN) nb[e] = pfc[r];
+            }
+            if (cc >= 2) {
+#pragma unroll
+                for (int r = 0; r < RC; ++r) {
+                    const int e = lane + 64 * r;
+                    if (e < TC * CLEN) pfc[r] = chunk_elem(cc - 2, e);
+                }
+            }
+        }
+        ddp_bp2_sync();
+    }
+    if (lane == n) { a.dV[2 * b] = dV0; a.dV[2 * b + 1] = dV1; }
+    if (lane == 0) a.diverge[b] = diverge;
+}
+
+extern "C" __global__ __launch_bounds__(64) void ddp_user_vhess(UserVhessArgs a)
+{
+    constexpr int n = DDP_N, m = DDP_M, nz = DDP_NZ;
+    const long total = (long)DDP_NPAIR * a.N * a.B, g = (long)blockIdx.x * 64 + threadIdx.x;
+    if (g >= total) return;
+    const int e = (int)(g % DDP_NPAIR);
+    const long r = g / DDP_NPAIR;                                // (step, trajectory)
+    const int b = (int)(r / a.N), i = (int)(r - (long)b * a.N);
+    if (a.active && a.active[b] == 0) return;
+    int pa, pb;
+    ddp_tri(e, pa, pb);
+    double x[n], u[m], v[n];
+#pragma unroll
+    for (int l = 0; l < n; ++l) { x[l] = a.x[(size_t)n * r + l]; v[l] = a.v[(size_t)n * r + l]; }
+#pragma unroll
+    for (int q = 0; q < m; ++q) u[q] = a.u[(size_t)m * r + q];
+    const double hv = ddp_ad_vhess(x, u, i, ddp_params(a.params, a.params_batched, a.map, b), v, pa, pb);
+    double *H = a.H + (size_t)nz * nz * r;
+    H[pa + nz * pb] = hv;
+    H[pb + nz * pa] = hv;
+}
+#endif
+)DDPK";

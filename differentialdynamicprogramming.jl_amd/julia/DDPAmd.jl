@@ -915,11 +915,13 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
 end
 
 # ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
-# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant) holds the source; it is compiled with hiprtc
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant, second_order) holds the source; it is compiled with hiprtc
 # for the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
 # autodiff=true (DDP_USER_AUTODIFF): dynamics / stage_cost / terminal_cost are templates over the scalar type of x and u, the source
 # needs no `derivatives`, and df is derived on the device by forward-mode AD.
 # plant=true (DDP_USER_PLANT): the source also defines `plant`, the true system the closed loop of iLQG_mpc advances its trajectories with.
+# second_order=true (DDP_USER_SECOND_ORDER, needs autodiff=true): full DDP — iLQG, iLQG_queue and iLQG_mpc run the second-order backward
+# pass (backward_pass.jl:81-160), the curvature of the dynamics derived on the device; vhess and back_pass_ddp are its array-level pieces.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -931,9 +933,9 @@ mutable struct DeviceProblem
     made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
-                       const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false)
+                       const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false)
     wrap = Int(_diff_mask(diff, n))
-    flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0)
+    flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}())
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1008,6 +1010,50 @@ function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), param
             cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64})::Cint)
     end
     return fx, fu, Float64[], Float64[], Float64[], cx, cu, cxx, cxu, cuu
+end
+
+# vhess(problem, x, u, v) -> H[n+m, n+m, N(, B)] = Σ_k v[k, i] ∂²f_k/∂z∂z at (x[:, i], u[:, i]), z = [x; u] (second_order=true problems)
+function vhess(problem::DeviceProblem, x, u, v; handle::Handle=default_handle(), params=nothing)
+    batched = ndims(u) == 3
+    m, N = size(u, 1), size(u, 2)
+    n = size(x, 1)
+    B = batched ? size(u, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    H = result_array(n + m, n + m, N, (batched ? (B,) : ())...)
+    x = _f64(x); u = _f64(u); v = _f64(v)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x u v H begin
+        check(@ccall libddp.ddp_user_vhess_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
+            x::Ptr{Float64}, u::Ptr{Float64}, v::Ptr{Float64}, H::Ptr{Float64})::Cint)
+    end
+    return H
+end
+
+# back_pass_ddp(problem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, u): the second-order backward pass on the arrays df returns;
+# -> (diverge, K, k, Quu, Vx, Vxx, dV), a trailing batch axis with a batched u
+function back_pass_ddp(problem::DeviceProblem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, u; handle::Handle=default_handle(),
+                       params=nothing)
+    batched = ndims(u) == 3
+    m, N = size(u, 1), size(u, 2)
+    n = size(x, 1)
+    B = batched ? size(u, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    bt = batched ? (B,) : ()
+    K = result_array(m, n, N, bt...); k = result_array(m, N, bt...); Quu = result_array(m, m, N, bt...)
+    Vx = result_array(n, N, bt...); Vxx = result_array(n, n, N, bt...); dV = zeros(2, bt...)
+    div = zeros(Int32, B)
+    lam = λ isa Number ? fill(Float64(λ), B) : _f64(λ)
+    x = _f64(x); u = _f64(u); cx = _f64(cx); cu = _f64(cu); cxx = _f64(cxx); cxu = _f64(cxu); cuu = _f64(cuu); fx = _f64(fx); fu = _f64(fu)
+    limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x u fx fu cx cu cxx cxu cuu lam limsp K k Quu Vx Vxx dV div begin
+        check(@ccall libddp.ddp_user_back_pass_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64},
+            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, lam::Ptr{Float64}, regType::Cint, _ptr_or_null(limsp)::Ptr{Float64},
+            K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, dV::Ptr{Float64},
+            div::Ptr{Int32})::Cint)
+    end
+    return (batched ? div : Int(div[1])), K, k, Quu, Vx, Vxx, dV
 end
 
 function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)

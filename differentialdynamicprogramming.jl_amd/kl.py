@@ -180,6 +180,9 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead."""
     if constrain_per_step:
         raise NotImplementedError("constrain_per_step (iLQGkl.jl:180-232) is not offloaded")
+    if isinstance(problem, DeviceProblem) and problem.second_order:
+        raise DDPError("iLQGkl: a DeviceProblem made with second_order=True is refused (back_pass_gps has no second-order variant); "
+                       "make the problem without the flag for the KL loop")
     if cost is None or np.size(cost) == 0:
         raise ValueError("Initial trajectory supplied, initial cost must also be supplied")                     # :69
     h = handle or default_handle()

@@ -501,10 +501,21 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * with DDP_USER_AUTODIFF (it may call dynamics<double>).  After every solve t of a trajectory that did not diverge at its start (the
  * last one included) xcl[:,t+1] = plant(xcl[:,t], ucl[:,t], t, p) replaces x_1 of the plan, and is the next solve's initial state.  A
  * plant that leaves the state non-finite or beyond the bound of the initial rollout ends the trajectory's loop through the initial-
- * divergence exit of the next solve.  Kernel name: ddp_user_plant (one lane per slot; ddp_last_kernel(h, 4)). */
+ * divergence exit of the next solve.  Kernel name: ddp_user_plant (one lane per slot; ddp_last_kernel(h, 4)).
+ *
+ * DDP_USER_SECOND_ORDER: full DDP, the second-order backward pass of the reference (backward_pass.jl:81-160) in every iLQG-type solve
+ * of the problem (ddp_user_ilqg_*, ddp_user_ilqg_queue_*, ddp_user_ilqg_mpc_*).  It needs DDP_USER_AUTODIFF (the templates; refused
+ * otherwise) and nothing else from the user.  With T_i[k,a,b] = ∂²f_k/∂z_a∂z_b at (x_i, u_i, i), z = [x; u], and
+ * H_i = Σ_k Vx_{i+1}[k] T_i[k] split as Hxx, Hux, Huu:  Qxx += Hxx, Qux += Hux, Quu[:,:,i] += Huu, and the same Hux, Huu go into
+ * Qux_reg and QuuF (:106-123); everything after that is the shared tail (:28-79) — the first-order pass with the cost Hessians of step
+ * i replaced by cxx + Hxx, cxu + Hux', cuu + Huu; the stored Quu includes Huu; the last step has no dynamics (Vx = cx, Vxx = cxx).
+ * The λ schedule, line search and exits of the driver are untouched: an indefinite QuuF is a `diverge` like any other.  No tensor is
+ * formed: H_i is the Hessian of the scalar Vx_{i+1}·f(z), one call of `dynamics` per pair a <= b on a dual over a dual, inside the
+ * recursion (kernel ddp_user_back_pass2, one wave per trajectory; ddp_last_kernel(h, 0)).  ddp_user_ilqgkl_* refuses such a problem
+ * (back_pass_gps has no second-order variant).  A problem without the flag compiles and runs exactly as before. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
-enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8 };
+enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16 };
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
@@ -519,6 +530,24 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
                         const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
 int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                     double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
+/* DDP_USER_SECOND_ORDER problems only.  vhess: x[n,N,B] u[m,N,B] v[n,N,B] -> H[n+m,n+m,N,B] = Σ_k v[k,i,b] ∂²f_k/∂z∂z at (x_i, u_i, i),
+ * exactly symmetric (kernel ddp_user_vhess, one lane per pair, step and trajectory): the `vectens` terms for a caller of the array API. */
+int ddp_user_vhess_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                           const double *v, const int32_t *active, double *H);
+int ddp_user_vhess_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                       const double *v, double *H);
+/* One second-order backward pass: x, u and the seven derivative arrays as ddp_user_df writes them (Hessians [.,.,B] with
+ * DDP_USER_CONST_HESSIAN), lambda[B], regType 1 | 2, lims[m,2] or NULL, `active` -> K, k, Quu, Vx, Vxx, dV[2,B], diverge[B] shaped as
+ * ddp_back_pass_f64_dev.  A problem without the flag is refused: its backward pass is ddp_back_pass_f64 on the same arrays.      */
+int ddp_user_back_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                               const double *u, const double *fx, const double *fu, const double *cx, const double *cu, const double *cxx,
+                               const double *cxu, const double *cuu, const double *lambda, int regType, const double *lims,
+                               const int32_t *active, double *K, double *k, double *Quu, double *Vx, double *Vxx, double *dV,
+                               int32_t *diverge);
+int ddp_user_back_pass_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
+                           const double *fx, const double *fu, const double *cx, const double *cu, const double *cxx, const double *cxu,
+                           const double *cuu, const double *lambda, int regType, const double *lims, double *K, double *k, double *Quu,
+                           double *Vx, double *Vxx, double *dV, int32_t *diverge);
 /* forward_pass: arguments and outputs as ddp_forward_pass_f64_dev; cnew[CL,B,nalpha]                                           */
 int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
                                   const double *K, const double *k, const double *x0, const double *u, const double *x,
