@@ -745,12 +745,14 @@ static int launch_back_pass_padded(ddp_handle h, const BPCall &c, int np_, int m
 //   mid     one wave per trajectory with LDS operands (back_pass_mid.hip): n <= 32, m <= 8;
 //   mf2     32 < n <= 64, m <= 8 on the matrix cores with run-time sizes (back_pass_mf2.hip); mfma: the round-5 kernel of the exact
 //           (64, 8) shape (back_pass_mfma.hip); big: the 256-thread vector kernel of even sizes (back_pass_big.hip), padded: big on the
-//           next even sizes.
-enum BPKernel { BP_NONE, BP_SH, BP_MX2, BP_MX, BP_Q4, BP_DPPW, BP_MXG, BP_DPP, BP_MXR, BP_ROW, BP_MID, BP_GENERAL, BP_MFMA, BP_MF2, BP_BIG, BP_PADDED };
+//           next even sizes;
+//   wide    8 < m <= 32 with any n <= 64: one work-group of four waves per trajectory, products on the matrix cores, Cholesky and
+//           box-QP across the lanes of a wave (back_pass_wide.hip).
+enum BPKernel { BP_NONE, BP_SH, BP_MX2, BP_MX, BP_Q4, BP_DPPW, BP_MXG, BP_DPP, BP_MXR, BP_ROW, BP_MID, BP_GENERAL, BP_MFMA, BP_MF2, BP_BIG, BP_PADDED, BP_WIDE };
 static const char *const bp_kernel_name[] = {"", "sh_back_kernel", "back_pass_mx2_kernel", "back_pass_mx_kernel", "back_pass_q4", "back_pass_dppw_kernel",
                                              "back_pass_mxg_kernel", "back_pass_dpp_kernel", "back_pass_mx_kernel<RT>", "back_pass_row_kernel",
                                              "back_pass_mid_kernel", "back_pass_kernel", "back_pass_mfma_kernel", "back_pass_mf2_kernel",
-                                             "back_pass_big_kernel", "back_pass_big_kernel"};
+                                             "back_pass_big_kernel", "back_pass_big_kernel", "back_pass_wide_kernel"};
 
 enum { BP_AL_IN = 1, BP_AL_COST = 2, BP_AL_OUT = 4 };      // 16-byte aligned: cx, cu | cxx, cuu | K, k, Quu, Vx, Vxx
 
@@ -764,7 +766,7 @@ struct BPChoiceIn {
 
 constexpr int MXG_LIMS_MAX_B = 2048;             // (measured cross-over with the row kernels: profiles/r05_lims_sweep.sh)
 
-// DDP_BACKPASS=x|q|dpp|general|big|s|row|tile|wtile|mid|old|new forces one family by its first letter (A/B timing, tests of every code
+// DDP_BACKPASS=x|q|dpp|general|big|s|row|tile|wtile|mid|old|new|controls forces one family by its first letter (A/B timing, tests of every code
 // path); a forced family that cannot take the shape falls through to the general kernel.  `shared`: whether the shared-operand kernel
 // may be chosen (not for the trajectories it leaves to the others).
 static BPKernel bp_choose(const ddp_bp_desc &d, const BPChoiceIn &q, bool shared)
@@ -773,6 +775,9 @@ static BPKernel bp_choose(const ddp_bp_desc &d, const BPChoiceIn &q, bool shared
     const int n = d.n, m = d.m, B = d.B;
     const bool lti_shared = !d.fx_tv && !d.cost_tv && !d.fx_batched && !d.cost_batched;
     const bool n10m2 = n == 10 && m == 2 && !d.has_lims;
+    // wide controls, 8 < m <= 32 (no other family holds them), and DDP_BACKPASS=controls at any m <= 32 (A/B timing against the
+    // specialised kernels, tests of the same arithmetic on the shapes they share)
+    if (m > DDP_MAX_M || force == 'c') return (n <= 64 && m <= DDP_MAX_M_WIDE) ? BP_WIDE : BP_NONE;
     // Operands shared by the batch (the reference's LTI method with ONE fx, fu, cxx, cxu, cuu): the matrix recursion once per distinct
     // λ (back_pass_sh.hip).  What it leaves out (λ values that occur once, more distinct values than it has groups) comes back as the
     // activity mask of the per-trajectory kernels, which are launched behind it and exit at once when there is nothing for them.
@@ -866,9 +871,10 @@ static int launch_family(ddp_handle h, BPKernel k, const BPCall &c, bool lims_ac
     case BP_MF2: return ddp_launch_back_pass_mf2(h, c, lims_active);
     case BP_BIG: return ddp_launch_back_pass_big(h, c);
     case BP_PADDED: return launch_back_pass_padded(h, c, c.d.n + (c.d.n & 1), c.d.m + (c.d.m & 1));
+    case BP_WIDE: return ddp_launch_back_pass_wide(h, c);
     default: break;
     }
-    DDP_CHECK(false, "back_pass: n=%d m=%d has no kernel (n <= %d with m <= %d, or n <= 64)", c.d.n, c.d.m, DDP_MAX_N_GENERIC, DDP_MAX_M);
+    DDP_CHECK(false, "back_pass: n=%d m=%d has no kernel (n <= 64, m <= %d)", c.d.n, c.d.m, DDP_MAX_M_WIDE);
 }
 
 int ddp_launch_back_pass(ddp_handle h, const BPCall &c)
@@ -878,7 +884,7 @@ int ddp_launch_back_pass(ddp_handle h, const BPCall &c)
     DDP_CHECK(d.n >= 1 && d.m >= 1 && d.N >= 1 && d.B >= 1, "back_pass: bad sizes n=%d m=%d N=%d B=%d", d.n, d.m, d.N, d.B);
     DDP_CHECK(d.regType == 1 || d.regType == 2, "back_pass: regType must be 1 or 2 (got %d)", d.regType);
     DDP_CHECK(!d.has_lims || (c.lims && c.u), "back_pass: has_lims needs lims and u");
-    DDP_CHECK(d.m <= DDP_MAX_M, "back_pass: m=%d exceeds DDP_MAX_M=%d", d.m, DDP_MAX_M);
+    DDP_CHECK(d.m <= DDP_MAX_M_WIDE, "back_pass: m=%d exceeds DDP_MAX_M_WIDE=%d", d.m, DDP_MAX_M_WIDE);
     BPChoiceIn q = bp_choice_in(h, c);
     BPKernel k = bp_choose(d, q, true);
     if ((k == BP_MF2 || k == BP_MFMA) && d.has_lims) {

@@ -195,12 +195,19 @@ int ddp_launch_back_pass_big(ddp_handle h, const BPCall &c);
 // n = 64, m = 8 shape (back_pass_mfma.hip).  `lims_active`: has_lims with real limits (lims[1,1] <= lims[1,2]), read by the caller
 int ddp_launch_back_pass_mf2(ddp_handle h, const BPCall &c, bool lims_active);
 int ddp_launch_back_pass_mfma(ddp_handle h, const BPCall &c, bool lims_active);
+// wide controls, any n <= 64 with m <= DDP_MAX_M_WIDE at run time: one work-group of four waves per trajectory (back_pass_wide.hip)
+int ddp_launch_back_pass_wide(ddp_handle h, const BPCall &c);
 // forward_pass_row.hip: the 16-lane-row rollout compiled for padded sizes (LQ problems, n <= 14, m <= 4); 1 = not applicable
 int ddp_launch_forward_row(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
 // 16-lane DPP-row forward pass + separate cost kernel; returns 1 when the shape has no such kernel
 int ddp_launch_forward_dpp(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
+                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
+                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
+
+// one wave per rollout for wide controls (LQ family, n <= 64, 8 < m <= DDP_MAX_M_WIDE; forward_pass_wide.hip)
+int ddp_launch_forward_wide(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
                             const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
                             const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
 

@@ -294,7 +294,7 @@ int ddp_forward_pass_f64_dev(ddp_handle h, const ddp_problem *p, const double *K
     DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
     DDP_CHECK((K == nullptr) == (k == nullptr), "forward_pass: K and k must both be given or both NULL");
     DDP_CHECK(!K || x, "forward_pass: a non-empty policy needs the nominal trajectory x");
-    DDP_CHECK(p->m <= DDP_MAX_M && p->n <= 64, "forward_pass: n=%d m=%d unsupported (n<=64, m<=%d)", p->n, p->m, DDP_MAX_M);
+    DDP_CHECK(p->m <= DDP_MAX_M_WIDE && p->n <= 64, "forward_pass: n=%d m=%d unsupported (n<=64, m<=%d)", p->n, p->m, DDP_MAX_M_WIDE);
     // the trailing field of ddp_problem (library 0.2.0): a caller built against the older layout, or one that does not zero the struct,
     // hands over garbage here — anything but 0 / 1 is refused instead of silently selecting the diagonal-cost rollout
     DDP_CHECK(p->cost_diag == 0 || p->cost_diag == 1, "forward_pass: ddp_problem.cost_diag = %d (0 or 1; zero-initialise the struct)", p->cost_diag);
@@ -302,6 +302,10 @@ int ddp_forward_pass_f64_dev(ddp_handle h, const ddp_problem *p, const double *K
     // diff_fun with wrapped coordinates: the pendulum's row / lane kernels and the run-time-sized kernel below implement it
     DDP_CHECK(p->diff_wrap == 0 || (p->n <= DDP_MAX_N_GENERIC && (p->n >= 32 || (p->diff_wrap >> p->n) == 0)),
               "forward_pass: ddp_problem.diff_wrap = 0x%x needs n <= %d and no bits at or above n = %d (zero-initialise the struct)", p->diff_wrap, DDP_MAX_N_GENERIC, p->n);
+    if (p->m > DDP_MAX_M) {                                      // wide controls (8 < m <= 32): forward_pass_wide.hip, LQ family only
+        DDP_CHECK(p->kind == DDP_PROBLEM_LQ, "forward_pass: m=%d needs the LQ family (problem kind %d)", p->m, p->kind);
+        return ddp_launch_forward_wide(h, p, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
+    }
     if (p->n > DDP_MAX_N_GENERIC || (p->diff_wrap == 0 && ddp_env(h, ENV_FORWARD) && ddp_env(h, ENV_FORWARD)[0] == 'b')) {   // large states
         const int rc = ddp_launch_forward_big(h, p, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
         if (rc <= 0) return rc;                             // (the launcher names the kernel)

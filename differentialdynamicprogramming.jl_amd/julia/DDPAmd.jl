@@ -543,8 +543,9 @@ end
 # ---- the drop-in entry point ------------------------------------------------------------------------------------------
 const _ref = Ref{Any}(nothing)         # the reference module once `install!` has added the GPU methods to its back_pass
 const _installed = Method[]            # the methods `install!` added (what `uninstall!` deletes)
-const MAX_N = 64                       # include/ddp_amd.h: the backward kernels take n <= 64, m <= 8
-const MAX_M = 8
+const MAX_N = 64                       # include/ddp_amd.h: the backward kernels take n <= 64, m <= 32
+const MAX_M = 8                        # DDP_MAX_M: user problems, the KL functions, the lane-per-problem boxQP
+const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
 # What the GPU methods accept: dense Float64 arrays (and the `Diagonal` / vector cost terms of the reference's demos).  Everything else —
 # Float32, BigFloat, dual numbers, views, sparse or static arrays — stays on the reference's own `AbstractArray{T}` methods, which
@@ -560,7 +561,7 @@ _ref_sig(::Val{:lti})    = Tuple{Any,Any,AbstractArray{Float64,2},Any,Any,Abstra
 # true when the C library takes this call (sizes in range, every operand a Float64 array)
 function _gpu_takes(cx, cu, cxu, cuu, fu, x, u)
     n, m = size(cx, 1), size(cu, 1)
-    (1 <= n <= MAX_N && 1 <= m <= MAX_M) || return false
+    (1 <= n <= MAX_N && 1 <= m <= MAX_M_WIDE) || return false
     return all(a -> a isa AbstractArray{Float64}, (cx, cu, cxu, cuu, fu, x, u))
 end
 
@@ -572,7 +573,7 @@ ADDS three methods to the loaded reference package's `back_pass`, on signatures 
 `Diagonal{Float64}` / `Array{Float64,3}`), so that the reference's own `iLQG(f,costfun,df,x0,u0; ...)` — arbitrary Julia closures, its own
 line search, trace and printing — runs STEP 2 (iLQG.jl:235-251) on the GPU.  The reference's methods are NOT overwritten: they remain the
 fallback, reached by dispatch for every other element or array type and by `invoke` from the GPU methods when the problem is outside
-the kernels' range (n > $MAX_N, m > $MAX_M, a non-`Float64` operand) or the library refuses the shape (`DDPError`).  The second-order
+the kernels' range (n > $MAX_N, m > $MAX_M_WIDE, a non-`Float64` operand) or the library refuses the shape (`DDPError`).  The second-order
 methods (`fxx, fxu, fuu`, :81,:132) have another arity and are untouched.  Returns policies of the reference's own `GaussianPolicy` type.
 `uninstall!` removes the three methods again.
 """

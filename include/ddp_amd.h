@@ -100,10 +100,14 @@ typedef struct {
  * outputs: K[m,n,N,B] k[m,N,B] Quu[m,m,N,B] Vx[n,N,B] Vxx[n,n,N,B] dV[2,B] diverge int32[B]
  *          (diverge: 0 ok, else the 1-based failing time index; outputs earlier in time than the
  *          failing step are zero like the reference's zero-initialised arrays)
- * shapes : m <= DDP_MAX_M (8); n <= 64 (kernel families by size: n = 10/m = 2, n = 4/m = 1, any n <= 12/m <= 4, n <= 14/m <= 4, n <= 32/m <= 8,
- *          32 < n <= 64 with m <= 8 at run time on the matrix-core kernel back_pass_mf2: padded to 16-row tiles and 8 controls inside the LDS
- *          only, no scratch on the handle).  Larger n or m: return code < 0.
- *          back_pass_gps: n <= 32.                                                                     */
+ * shapes : any 1 <= n <= 64 with 1 <= m <= DDP_MAX_M_WIDE (32).  Kernel families by size, for m <= DDP_MAX_M (8): n = 10/m = 2,
+ *          n = 4/m = 1, any n <= 12/m <= 4, n <= 14/m <= 4, n <= 32/m <= 8, 32 < n <= 64 with m <= 8 at run time on the matrix-core kernel
+ *          back_pass_mf2 (padded to 16-row tiles and 8 controls inside the LDS only, no scratch on the handle).  Wide controls,
+ *          8 < m <= 32 with any n <= 64: back_pass_wide_kernel, one work-group of four waves per trajectory, run-time sizes, every
+ *          operand layout, limits by a box-QP across the lanes of a wave; operands are read from the caller's arrays (no padded
+ *          copies, no scratch on the handle).  n > 64 or m > 32: return code < 0.
+ *          back_pass_gps: n <= 32, m <= DDP_MAX_M.  User problems (ddp_user_*), the KL functions and the lane-per-problem boxQP
+ *          stop at m = DDP_MAX_M.                                                                                          */
 int ddp_back_pass_f64_dev(ddp_handle h, const ddp_bp_desc *d,
                           const double *cx, const double *cu, const double *cxx, const double *cxu,
                           const double *cuu, const double *fx, const double *fu,
@@ -126,6 +130,7 @@ int ddp_back_pass_f64(ddp_handle h, const ddp_bp_desc *d,
  * Hfree[m,m,count] (leading nfree x nfree block = upper Cholesky factor of H[free,free], zero elsewhere)
  * free uint8[m,count].                                                                             */
 #define DDP_MAX_M 8
+#define DDP_MAX_M_WIDE 32   /* back_pass, forward_pass, df, costfun and the iLQG drivers of DDP_PROBLEM_LQ: 8 < m <= 32 on the wide-control kernels */
 #define DDP_QP_MAX_M 1024
 typedef struct {
     int    maxIter;        /* 100   */
@@ -185,6 +190,9 @@ typedef struct {
 int ddp_cost_len(const ddp_problem *p);
 
 /* All `nalpha` step sizes are rolled out concurrently (one work-group slice per (trajectory, α)).
+ * shapes : DDP_PROBLEM_LQ: any n <= 64 with m <= DDP_MAX_M_WIDE (32); 8 < m <= 32 runs in forward_wide_kernel (one wave per
+ *          (trajectory, α), every dyn_tv / dyn_batched layout, limits, diff_wrap for n <= 32 as below).  DDP_PROBLEM_PENDCART:
+ *          n = 4, m = 1.  Anything else: return code < 0.
  * inputs : K[m,n,N,B], k[m,N,B] (both NULL = empty policy, forward_pass.jl:17), x0[n,B], u[m,N,B],
  *          x[n,N,B] (may be NULL with an empty policy), alpha[nalpha] (HOST pointer, <= 16 values),
  *          lims[m,2] or NULL, active int32[B] or NULL
