@@ -161,7 +161,8 @@ def example_source(name):
     """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``), or the same
     model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``; ``"car_plant"``: the car with a plant for the
     closed loop (``plant=True``); ``"bicycle_ad"``: a kinematic bicycle whose dynamics have mixed and control curvature, for
-    ``second_order=True``."""
+    ``second_order=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
+    for ``wave=True``."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -176,17 +177,21 @@ class DeviceProblem:
     ``plant=True`` (DDP_USER_PLANT): the source also defines ``plant``, the true system that ``iLQG_mpc`` advances its trajectories
     with instead of the model.  ``second_order=True`` (DDP_USER_SECOND_ORDER, needs ``autodiff=True``): full DDP — ``iLQG``,
     ``iLQG_queue`` and ``iLQG_mpc`` run the backward pass with the curvature of the dynamics (backward_pass.jl:81-160), derived on the
-    device from the same templates; ``vhess`` and ``back_pass_ddp`` are its array-level pieces.  ``iLQGkl`` refuses such a problem."""
+    device from the same templates; ``vhess`` and ``back_pass_ddp`` are its array-level pieces.  ``iLQGkl`` refuses such a problem.
+    ``wave=True`` (DDP_USER_WAVE): large problems, ``n <= 64`` and ``m <= 32`` (without it ``n <= 32``, ``m <= 8``): the rollout runs on a
+    group of lanes per rollout (``ddp_user_rollout_wave``) and, with ``autodiff=True``, df on one wave per time step and trajectory
+    (``ddp_user_df_wave``).  Legal at every shape; not with ``second_order=True``; ``iLQGkl`` takes such a problem up to ``n = 32``,
+    ``m = 8``."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False):
-        self.second_order = bool(second_order)
+                 second_order=False, wave=False):
+        self.second_order, self.wave = bool(second_order), bool(wave)
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
-                      (8 if self.plant else 0) | (16 if self.second_order else 0))
-        self.diff_mask = _diff_mask(diff, self.n) if self.n <= 32 else 0
+                      (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0))
+        self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
 

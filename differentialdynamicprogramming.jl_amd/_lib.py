@@ -75,6 +75,8 @@ class ILQGKLOpts(C.Structure):
 
 
 ILQGKL_NSTATS = 12
+USER_WAVE = 32                 # DDP_USER_WAVE: the flag of DeviceProblem(..., wave=True)
+MAX_N_USER_WAVE = 64           # DDP_MAX_N_USER_WAVE: n of a user problem with the flag (m <= 32)
 
 _lib = None
 hip_runtime_note = "library not loaded yet"

@@ -15,6 +15,7 @@
 #include "ddp_internal.h"
 #include "user_autodiff.h"
 #include "user_problem_kernels.h"
+#include "user_problem_wave_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 
 DDP_USER_ABI
@@ -66,9 +67,10 @@ std::string g_log;                                          // log of the last c
 // dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
 constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024;
 
-struct Layout { int chunk, rlanes, dflanes, adj, adh; };
+struct Layout { int chunk, rlanes, dflanes, adj, adh, wg; };
 
 // chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit.
+// DDP_USER_WAVE: rlanes and dflanes are the same two counts of the wave kernels (the launch geometry reads nothing else), wg the group.
 // DDP_USER_AUTODIFF: seeds per call of `dynamics` (adj) and per Hessian block (adh) of ddp_user_df_ad, chosen by the kernel's VGPR and
 // scratch counts (-Rpass-analysis=kernel-resource-usage)
 Layout layout_of(int n, int m, int flags)
@@ -90,6 +92,15 @@ Layout layout_of(int n, int m, int flags)
     const int dt = n * n + n * m + n + m + ((flags & DDP_USER_CONST_HESSIAN) ? 0 : n * n + n * m + m * m);
     L.dflanes = 64;
     while (L.dflanes > 1 && (size_t)L.dflanes * (dt | 1) * 8 > (size_t)DF_LDS) L.dflanes /= 2;
+    L.wg = 0;
+    if (flags & DDP_USER_WAVE) {
+        // ddp_user_rollout_wave: a group of wg lanes (the power of two >= m, 8 at least) per rollout, 64 / wg rollouts per work-group;
+        // ddp_user_df_wave: one (step, trajectory) per work-group; the hand-written ddp_user_df under the flag: 64 of them
+        L.wg = m <= 8 ? 8 : (m <= 16 ? 16 : 32);
+        L.chunk = 1;
+        L.rlanes = 64 / L.wg;
+        L.dflanes = (flags & DDP_USER_AUTODIFF) ? 1 : 64;
+    }
     return L;
 }
 
@@ -110,12 +121,24 @@ bool has_identifier(const std::string &src, const char *name)
 int validate(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
 {
     DDP_CHECK(source, "user problem: null source");
-    DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER, "user problem: n = %d out of [1, %d] (DDP_MAX_N_USER)", n, DDP_MAX_N_USER);
-    DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M)", m, DDP_MAX_M);
+    const bool wave = (flags & DDP_USER_WAVE) != 0;
+    if (wave) {
+        DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER_WAVE, "user problem: n = %d out of [1, %d] (DDP_MAX_N_USER_WAVE)", n, DDP_MAX_N_USER_WAVE);
+        DDP_CHECK(m >= 1 && m <= DDP_MAX_M_WIDE, "user problem: m = %d out of [1, %d] (DDP_MAX_M_WIDE)", m, DDP_MAX_M_WIDE);
+    } else {
+        DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER, "user problem: n = %d out of [1, %d] (DDP_MAX_N_USER; DDP_USER_WAVE takes n <= %d)", n,
+                  DDP_MAX_N_USER, DDP_MAX_N_USER_WAVE);
+        DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "user problem: m = %d out of [1, %d] (DDP_MAX_M; DDP_USER_WAVE takes m <= %d)", m, DDP_MAX_M,
+                  DDP_MAX_M_WIDE);
+    }
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
-    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER)) == 0,
+    DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
+                         DDP_USER_WAVE)) == 0,
               "user problem: unknown flags 0x%x", flags);
+    DDP_CHECK(!(wave && (flags & DDP_USER_SECOND_ORDER)),
+              "user problem: DDP_USER_SECOND_ORDER | DDP_USER_WAVE is refused (ddp_user_back_pass2 is sized for n <= %d, m <= %d)",
+              DDP_MAX_N_USER, DDP_MAX_M);
     DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER) || (flags & DDP_USER_AUTODIFF),
               "user problem: DDP_USER_SECOND_ORDER needs DDP_USER_AUTODIFF (the curvature of the dynamics is derived from the templated model)");
     DDP_CHECK(n >= 32 || (wrap >> n) == 0, "user problem: diff_wrap = 0x%x names coordinates at or above n = %d", wrap, n);
@@ -130,6 +153,7 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
         DDP_CHECK(has_identifier(src, "cost_hessians"), "user problem: DDP_USER_CONST_HESSIAN is set but the source defines no `cost_hessians`");
     if (flags & DDP_USER_PLANT)
         DDP_CHECK(has_identifier(src, "plant"), "user problem: DDP_USER_PLANT is set but the source defines no `plant`");
+    if (wave) return 0;                                          // (the wave kernels check their LDS with a static_assert: it fits at every shape)
     const Layout L = layout_of(n, m, flags);
     const int ps = 2 * m + m * n + n;
     DDP_CHECK((size_t)L.rlanes * ((L.chunk * ps) | 1) * 8 <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the rollout's LDS", n, m);
@@ -147,7 +171,11 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
              n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
              (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh, (flags & DDP_USER_PLANT) ? 1 : 0);
     std::string s(head);
-    const bool ad = (flags & DDP_USER_AUTODIFF) != 0;
+    const bool ad = (flags & DDP_USER_AUTODIFF) != 0, wave = (flags & DDP_USER_WAVE) != 0;
+    if (wave) {                                                  // a problem without the flag: not a byte of its text changes
+        snprintf(head, sizeof head, "#define DDP_WAVE 1\n#define DDP_WG %d\n", L.wg);
+        s += head;
+    }
     if (ad) {
         s += "#line 1 \"ddp_user_autodiff\"\n";
         s += kUserAutodiff;
@@ -161,7 +189,18 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
     s += "\n#line 1 \"ddp_user_kernels\"\n";
     s += DDP_USER_ABI_TEXT;
     s += "\n";
-    s += kUserKernels;
+    s += kUserKernelsHead;
+    if (wave) {
+        s += "\n#line 1 \"ddp_user_wave_kernels\"\n";
+        s += kUserWaveKernels;
+        s += "\n#line 1 \"ddp_user_kernels_shared\"\n";
+        s += kUserKernelsCost;
+    } else {
+        s += kUserKernelsLane;
+        s += kUserKernelsCost;
+        s += kUserKernelsHessians;
+    }
+    s += kUserKernelsPlant;
     if (flags & DDP_USER_SECOND_ORDER) {                         // a problem without the flag: the text above, nothing more
         s += "\n#define DDP_SECOND_ORDER 1\n#line 1 \"ddp_user_autodiff_vhess\"\n";
         s += kUserAutodiffVhess;
@@ -237,7 +276,8 @@ int compile(const char *source, int n, int m, int nparam, int flags, unsigned wr
 struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
-    const char *df_name = nullptr;                               // ddp_user_df, or ddp_user_df_ad (DDP_USER_AUTODIFF)
+    const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
+    const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
     Layout L{};
 };
 struct Cache { std::map<std::string, Module> mods; };
@@ -292,7 +332,7 @@ struct UserProblem final : ddp_family {
         const long total = (long)Bc * nalpha;
         DDP_HIP(hipModuleLaunchKernel(mod->roll, (unsigned)((total + mod->L.rlanes - 1) / mod->L.rlanes), 1, 1, 64, 1, 1, 0, hh->stream, args,
                                       nullptr));
-        hh->last_kernel[1] = "ddp_user_rollout";
+        hh->last_kernel[1] = mod->roll_name;
         return 0;
     }
     int costfun(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *cost,
@@ -443,9 +483,11 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
         if (rc) return rc;
         Module M;
         M.L = layout_of(n, m, flags);
-        M.df_name = (flags & DDP_USER_AUTODIFF) ? "ddp_user_df_ad" : "ddp_user_df";
+        const bool wave = (flags & DDP_USER_WAVE) != 0;
+        M.df_name = (flags & DDP_USER_AUTODIFF) ? (wave ? "ddp_user_df_wave" : "ddp_user_df_ad") : "ddp_user_df";
+        M.roll_name = wave ? "ddp_user_rollout_wave" : "ddp_user_rollout";
         DDP_HIP(hipModuleLoadData(&M.mod, code.data()));
-        const bool ok = hipModuleGetFunction(&M.roll, M.mod, "ddp_user_rollout") == hipSuccess &&
+        const bool ok = hipModuleGetFunction(&M.roll, M.mod, M.roll_name) == hipSuccess &&
                         hipModuleGetFunction(&M.df, M.mod, M.df_name) == hipSuccess &&
                         hipModuleGetFunction(&M.cost, M.mod, "ddp_user_cost") == hipSuccess &&
                         (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess) &&

@@ -2,7 +2,7 @@
 //
 // The program hiprtc compiles is: the size / flag macros (DDP_N, DDP_M, DDP_NP, DDP_TERMINAL, DDP_CONST_HESSIAN, DDP_WRAP, DDP_CHUNK,
 // DDP_RLANES, DDP_DFLANES, DDP_AUTODIFF, DDP_ADJ, DDP_ADH, DDP_PLANT), the user's source (with DDP_AUTODIFF between the texts of user_autodiff.h),
-// DDP_USER_ABI (the argument structs, shared with the host through the macro below) and kUserKernels.  Every size is a compile-time constant there: the state of a rollout stays in VGPRs and every loop over n, m unrolls.
+// DDP_USER_ABI (the argument structs, shared with the host through the macro below) and kUserKernels (five pieces, below).  Every size is a compile-time constant there: the state of a rollout stays in VGPRs and every loop over n, m unrolls.
 //
 //   ddp_user_rollout   one lane per (trajectory, α) rollout, DDP_RLANES rollouts per 64-lane work-group.  The operand streams (u, x, k, K)
 //                      of DDP_CHUNK steps are staged through LDS as one contiguous run per rollout and stream (a rollout's chunk of K is
@@ -17,6 +17,8 @@
 //   ddp_user_hessians  DDP_CONST_HESSIAN: cost_hessians once per trajectory (per armed slot in the slot scheduler: `active`).
 //   ddp_user_plant     DDP_PLANT: one lane per slot of the closed loop; the user's plant advances the trajectories whose solve has just
 //                      ended (xcl[:, t+1], and the next solve's initial state).
+// DDP_USER_WAVE (n <= 64, m <= 32): ddp_user_rollout_wave, ddp_user_df_wave and the direct-store ddp_user_df / ddp_user_hessians of
+// user_problem_wave_kernels.h take the place of the rollout, derivative and Hessian kernels here; ddp_user_cost and ddp_user_plant stay.
 #pragma once
 
 // argument structs of the kernels: compiled into the host library and, as text (DDP_USER_ABI_TEXT), into every user program.
@@ -57,7 +59,9 @@
 #define DDP_USER_STR(x) DDP_USER_STR_(x)
 #define DDP_USER_ABI_TEXT DDP_USER_STR(DDP_USER_ABI)
 
-static const char *kUserKernels = R"DDPK(
+// kUserKernels in five pieces: a problem without DDP_USER_WAVE compiles Head + Lane + Cost + Hessians + Plant (the same bytes as ever), one
+// with the flag Head + kUserWaveKernels (user_problem_wave_kernels.h) + Cost + Plant
+static const char *kUserKernelsHead = R"DDPK(
 #define DDP_PS (2 * DDP_M + DDP_M * DDP_N + DDP_N)            // doubles per rollout step in LDS: u, x, k, K
 #define DDP_RS ((DDP_CHUNK * DDP_PS) | 1)                     // per-rollout stride (odd: 8-byte accesses of a wave spread over the banks)
 #define DDP_DT (DDP_N * DDP_N + DDP_N * DDP_M + DDP_N + DDP_M + (DDP_CONST_HESSIAN ? 0 : DDP_N * DDP_N + DDP_N * DDP_M + DDP_M * DDP_M))
@@ -85,7 +89,9 @@ __device__ __forceinline__ const double *ddp_params(const double *P, int batched
     return j >= 0 ? P + (size_t)DDP_NP * (size_t)j : nullptr;
 }
 
-// chunk [i0, i0 + cs) of one operand stream (W doubles per step) of every rollout of the work-group into its LDS slots
+)DDPK";
+
+static const char *kUserKernelsLane = R"DDPK(// chunk [i0, i0 + cs) of one operand stream (W doubles per step) of every rollout of the work-group into its LDS slots
 template <int W, int OFF>
 __device__ __forceinline__ void ddp_roll_load(double *lds, const int *rb, const double *src, int N, int i0, int cs, int lane)
 {
@@ -259,7 +265,9 @@ extern "C" __global__ __launch_bounds__(64) void DDP_DF_KERNEL(UserDfArgs a)
 #endif
 }
 
-extern "C" __global__ __launch_bounds__(64) void ddp_user_cost(UserCostArgs a)
+)DDPK";
+
+static const char *kUserKernelsCost = R"DDPK(extern "C" __global__ __launch_bounds__(64) void ddp_user_cost(UserCostArgs a)
 {
     constexpr int n = DDP_N, m = DDP_M;
     const int b = blockIdx.x, lane = threadIdx.x, N = a.N, CL = DDP_TERMINAL ? N + 1 : N;
@@ -286,7 +294,9 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_cost(UserCostArgs a)
     if (lane == 0 && a.csum) a.csum[b] = acc;
 }
 
-#if DDP_CONST_HESSIAN
+)DDPK";
+
+static const char *kUserKernelsHessians = R"DDPK(#if DDP_CONST_HESSIAN
 extern "C" __global__ __launch_bounds__(64) void ddp_user_hessians(UserHessArgs a)
 {
     constexpr int n = DDP_N, m = DDP_M;
@@ -300,7 +310,9 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_hessians(UserHessArgs 
 }
 #endif
 
-#if DDP_PLANT
+)DDPK";
+
+static const char *kUserKernelsPlant = R"DDPK(#if DDP_PLANT
 // xcl[n, steps+1, P], ucl[m, steps, P]; adv[b] = t + 1 when solve t of trajectory advp[b] has just ended on slot b (0: nothing to do)
 extern "C" __global__ __launch_bounds__(64) void ddp_user_plant(UserPlantArgs a)
 {

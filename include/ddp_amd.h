@@ -473,7 +473,8 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * `p` points at the trajectory's parameters: params[nparam] shared by the batch (params_batched = 0) or its column of
  * params[nparam,B] (params_batched = 1); NULL when nparam = 0.  Semantics of the rollout: src/forward_pass.jl:9-33 (u + α k +
  * K diff(x̂, x), clamp to lims[m,2], x̂_{i+1} = f(x̂_i, û_i, i) for i < N-1 — the reference's last call of f is discarded, so it is not
- * made); diff_wrap is the bit mask of ddp_problem::diff_wrap.  Limits: n <= DDP_MAX_N_USER, m <= DDP_MAX_M, nparam <= DDP_USER_MAX_NPARAM;
+ * made); diff_wrap is the bit mask of ddp_problem::diff_wrap.  Limits: n <= DDP_MAX_N_USER, m <= DDP_MAX_M (with DDP_USER_WAVE:
+ * n <= DDP_MAX_N_USER_WAVE, m <= DDP_MAX_M_WIDE), nparam <= DDP_USER_MAX_NPARAM;
  * anything else is refused before compiling.  A problem is compiled once per (source, n, m, nparam, flags) and handle: the handle keeps
  * the module until ddp_destroy.  Kernel names (rocprofv3, ddp_last_kernel): ddp_user_rollout, ddp_user_df, ddp_user_cost,
  * ddp_user_hessians.
@@ -520,10 +521,35 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * The λ schedule, line search and exits of the driver are untouched: an indefinite QuuF is a `diverge` like any other.  No tensor is
  * formed: H_i is the Hessian of the scalar Vx_{i+1}·f(z), one call of `dynamics` per pair a <= b on a dual over a dual, inside the
  * recursion (kernel ddp_user_back_pass2, one wave per trajectory; ddp_last_kernel(h, 0)).  ddp_user_ilqgkl_* refuses such a problem
- * (back_pass_gps has no second-order variant).  A problem without the flag compiles and runs exactly as before. */
+ * (back_pass_gps has no second-order variant).  A problem without the flag compiles and runs exactly as before.
+ *
+ * DDP_USER_WAVE: large problems, 1 <= n <= DDP_MAX_N_USER_WAVE (64) and 1 <= m <= DDP_MAX_M_WIDE (32), the shapes the backward-pass
+ * kernels hold.  The user's functions and the argument lists do not change; the library compiles other kernels around them, in which no
+ * lane holds a vector of n or a matrix of m x n doubles of the library's own:
+ *   ddp_user_rollout_wave   a group of 8, 16 or 32 lanes (the power of two >= m) per (trajectory, alpha) rollout; the state, diff(x^, x),
+ *                           the control and the successor state live in LDS, lane q of the group streams row q of K_i from memory, one
+ *                           lane of the group calls stage_cost and dynamics (their x, u and xnext then point into LDS).  Semantics and
+ *                           the order of every sum are those of ddp_user_rollout (ddp_last_kernel(h, 1)).
+ *   ddp_user_df_wave        with DDP_USER_AUTODIFF: one wave per (step, trajectory), one seed direction of z = [x; u] per lane and round
+ *                           (ceil((n + m) / 64) rounds; `dynamics` is instantiated once); cx, cu from the same pass of stage_cost; the
+ *                           Hessians from one call of stage_cost per pair a <= b on a dual over a dual, dealt over the lanes, each
+ *                           value stored to (a, b) and (b, a): cxx and cuu are exactly symmetric.  DDP_USER_CONST_HESSIAN skips the
+ *                           pairs: the fast path for quadratic costs (ddp_last_kernel(h, 2)).
+ *   ddp_user_df             hand-written `derivatives` under the flag: one lane per (step, trajectory), writing straight into the
+ *                           output arrays in memory (discarded Hessians go to a dump area in LDS).  At large shapes this is slower
+ *                           than ddp_user_df_wave: prefer DDP_USER_AUTODIFF there.
+ *   ddp_user_hessians       cost_hessians writes straight into cxx, cxu, cuu in memory.
+ * The flag is legal at every shape (n <= 32, m <= 8 included: the same arithmetic on the other kernels) and with DDP_USER_TERMINAL,
+ * DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF and DDP_USER_PLANT.  DDP_USER_SECOND_ORDER | DDP_USER_WAVE is refused (ddp_user_back_pass2
+ * is sized for n <= 32, m <= 8), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch (back_pass_gps has no
+ * kernel there).  diff_wrap names coordinates below 32 only.  The backward pass of a solve is the one ddp_back_pass_f64 chooses for
+ * the shape (32 < n <= 64, m <= 8: the MFMA kernels; m > 8: back_pass_wide).  user_examples/chain_ad.hip is a model with 7 parameters
+ * at every size.  A problem without the flag compiles the text it always did and refuses n > 32, m > 8. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
-enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16 };
+#define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
+enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
+       DDP_USER_WAVE = 32 };
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
