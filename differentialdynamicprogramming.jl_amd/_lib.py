@@ -28,7 +28,7 @@ EXPORTS = [
     "ddp_kl_terms_f64_dev", "ddp_kl_terms_f64", "ddp_back_pass_gps_f64_dev", "ddp_back_pass_gps_f64",
     "ddp_forward_covariance_f64_dev", "ddp_forward_covariance_f64", "ddp_kl_div_f64_dev", "ddp_kl_div_f64",
     "ddp_kl_dual_begin_f64_dev", "ddp_kl_dual_retry_f64_dev", "ddp_kl_dual_update_f64_dev",
-    "ddp_ilqgkl_default_opts", "ddp_ilqgkl_f64_dev", "ddp_ilqgkl_f64",
+    "ddp_ilqgkl_default_opts", "ddp_ilqgkl_f64_dev", "ddp_ilqgkl_f64", "ddp_kl_set_wide",
     "ddp_comm_rccl_info", "ddp_comm_unique_id", "ddp_comm_create", "ddp_comm_destroy", "ddp_allreduce_stats_f64_dev",
     "ddp_user_check", "ddp_user_compile_log", "ddp_user_create", "ddp_user_destroy", "ddp_user_df_f64_dev", "ddp_user_df_f64",
     "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
@@ -153,6 +153,7 @@ def lib():
         L.ddp_stream.argtypes = [vp]
         L.ddp_last_kernel.restype = C.c_char_p
         L.ddp_last_kernel.argtypes = [vp, C.c_int]
+        L.ddp_kl_set_wide.argtypes = [vp, C.c_int]
         L.ddp_user_compile_log.restype = C.c_char_p
         L.ddp_user_check.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p]
         L.ddp_user_create.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -221,6 +222,13 @@ class Handle:
     def last_kernel(self, which=0):
         """kernel of the last back_pass (0) / forward_pass (1) dispatch, or user-problem derivative (2) / cost (3) kernel (ddp_last_kernel)"""
         return lib().ddp_last_kernel(self._h, int(which)).decode()
+
+    def set_kl_wide(self, on):
+        """the handle's switch for the large shapes of the KL functions, n <= 64 and m <= 32 (ddp_kl_set_wide); returns the previous value"""
+        was = lib().ddp_kl_set_wide(self._h, int(bool(on)))
+        if was < 0:
+            check(was)
+        return bool(was)
 
     def sh_timeouts(self):
         """tiles of the shared-operand backward pass that gave their trajectories to the per-trajectory kernels after a timed-out wait"""

@@ -21,10 +21,9 @@
 #include <stdlib.h>
 #include "ddp_internal.h"
 #include "boxqp_dev.h"      // QPOptsDev, ddp_clamp
+#include "wide_tile.h"      // xty, inv_wave
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int WT = 256;                 // threads per work-group (four waves)
 constexpr int NWAVE = WT / DDP_WAVE;
@@ -38,20 +37,20 @@ struct BPWArgs {
     const int32_t *active;
     double *K, *k, *Quu, *Vx, *Vxx, *dV;
     int32_t *diverge;
+    // back_pass_gps only: the KL terms [., N, B], η [B] or [N, B], and inv(Quu)
+    const double *cxkl, *cukl, *cxxkl, *cxukl, *cuukl, *eta;
+    int eta_tv;
+    double *Quui;
 };
-
-__host__ __device__ constexpr int cdivw(int a, int b) { return (a + b - 1) / b; }
-// leading dimension for r rows: the smallest ld >= r with ld = 2 (mod 4)
-__host__ __device__ constexpr int ld4(int r) { return ((r + 1) & ~3) + 2; }
-__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
-__host__ __device__ constexpr int even(int a) { return (a + 1) & ~1; }
 
 // LDS map (doubles).  Two regions change hands inside a step:
 //   V : Vxx_{i+1} (ldn x n) for P1;  then H = QuuF (ldm x m) | Kx = Qux_reg -> K in place (ldm x n) for P2-P4;  then M, Vxx_i (P4)
 //   G : Gt (ldn x (n+m)) for P1-P2;  then R = the Cholesky factor (ldm x m) | T (ldm x n) for P3-P4
+// back_pass_gps adds the [Quu | inv(Quu) | pivot column] image of inv_wave: behind R | T in the G region where that has the room (at
+// (64, 32) it has, and nothing else would fit under the 160 KB), else a region of its own.
 struct WLds {
-    int ldn, ldm, F, V, G, Qux, Quu, Qs, vs, ks, Quuk, xb, sb, flags, total;
-    __host__ __device__ WLds(int n, int m)
+    int ldn, ldm, F, V, G, Qux, Quu, Qs, vs, ks, Quuk, xb, sb, flags, inv, total;
+    __host__ __device__ WLds(int n, int m, bool gps = false)
     {
         const int p = n + m;
         ldn = ld4(n); ldm = ld4(m);
@@ -68,32 +67,14 @@ struct WLds {
         xb = o; o += even(m);           // box-QP: the vector a matrix-vector product reads
         sb = o; o += even(m);           // box-QP: the terms of a sum
         flags = o; o += 2;              // two ints: failure, free mask
+        inv = 0;
+        if (gps) {
+            if (ldm * p + inv_wave_len(ldm, m) <= imax(ldn * p, ldm * p)) inv = G + ldm * p;
+            else { inv = o; o += even(inv_wave_len(ldm, m)); }
+        }
         total = o;
     }
 };
-
-__device__ __forceinline__ d4 mf(double x, double y, d4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, c, 0, 0, 0); }
-
-// acc[i][j] += sum_{k < kn} X(k, i) Y(k, j) on one 16 x 16 tile, i = r0 + (lane & 15) < nr, j = c0 + (lane & 15) < nc; X(k, i) is
-// X[k xk + i xi], Y(k, j) is Y[k yk + j yj].  Rows, columns and k outside the ranges contribute exact zeros (their addresses are
-// clamped to entries that exist).  Result: component r of lane l is row (l >> 4) + 4 r, column l & 15 of the tile.
-__device__ __forceinline__ d4 xty(const double *X, int xk, int xi, int r0, int nr, const double *Y, int yk, int yj, int c0, int nc, int kn,
-                                  d4 acc, int l15, int l4)
-{
-    const int i = r0 + l15, j = c0 + l15;
-    const bool iv = i < nr, jv = j < nc;
-    const double *xp = X + (iv ? i : 0) * xi, *yp = Y + (jv ? j : 0) * yj;
-    for (int k0 = 0; k0 < kn; k0 += 4) {
-        const int k = k0 + l4;
-        const bool kv = k < kn;
-        const int kc = kv ? k : 0;
-        const double av = xp[kc * xk], bv = yp[kc * yk];
-        acc = mf((iv && kv) ? av : 0.0, (jv && kv) ? bv : 0.0, acc);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ double comp(const d4 &v, int r) { return r == 0 ? v.x : (r == 1 ? v.y : (r == 2 ? v.z : v.w)); }
 
 // ---- wave-level pieces of P3 (wave 0; `lane` is the coordinate)
 // every lane gets sum_{i < m} v_i, added in index order (the order of the reference's loops)
@@ -242,6 +223,9 @@ __device__ __forceinline__ void solve_col(double *b, const double *R, int ldm, i
     for (int i = 0; i < m; ++i) b[i] = ((freem >> i) & 1u) ? -b[i] : 0.0;
 }
 
+// GPS: back_pass_gps (backward_pass.jl:259-350) on the same phases — every Q• is Q•/η + c•kl, no λ; Quu is symmetrised and is the
+// matrix that is factorised; wave 1 inverts it in P3 (Gauss-Jordan across its lanes) while wave 0 solves for the gains.
+template <bool GPS>
 __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
 {
     const int b = blockIdx.x, t = threadIdx.x;
@@ -255,7 +239,7 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
     constexpr int RV = cdivw(WIDE_MAX_N * WIDE_MAX_N, WT);                                                                // Vxx entries per thread
 
     extern __shared__ double lds[];
-    const WLds L(n, m);
+    const WLds L(n, m, GPS);
     const int ldn = L.ldn, ldm = L.ldm;
     double *Fs = lds + L.F, *Vs = lds + L.V, *Gt = lds + L.G, *Quxs = lds + L.Qux, *Quus = lds + L.Quu, *Qs = lds + L.Qs, *vs = lds + L.vs,
            *ks = lds + L.ks, *Quuks = lds + L.Quuk, *xb = lds + L.xb, *sb = lds + L.sb;
@@ -271,8 +255,13 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
     const double *cxx = a.cxx + a.cxx_b * b, *cxu = a.cxu + a.cxu_b * b, *cuu = a.cuu + a.cuu_b * b;
     double *Kg = a.K + nm * N * b, *kg = a.k + (size_t)m * N * b, *Quug = a.Quu + mm * N * b, *Vxg = a.Vx + (size_t)n * N * b,
            *Vxxg = a.Vxx + nn * N * b;
-    const double lam = a.lambda[b];
-    const int regType = a.regType;
+    const double lam = GPS ? 0.0 : a.lambda[b];
+    const int regType = GPS ? 0 : a.regType;
+    const double *cxkl = GPS ? a.cxkl + (size_t)n * N * b : nullptr, *cukl = GPS ? a.cukl + (size_t)m * N * b : nullptr,
+                 *cxxkl = GPS ? a.cxxkl + nn * N * b : nullptr, *cxukl = GPS ? a.cxukl + nm * N * b : nullptr,
+                 *cuukl = GPS ? a.cuukl + mm * N * b : nullptr, *etag = GPS ? a.eta + (a.eta_tv ? (size_t)N * b : b) : nullptr;
+    double *Quuig = GPS ? a.Quui + mm * N * b : nullptr;
+    double *img = lds + L.inv;                  // GPS: [Quu | inv(Quu) | pivot column]
     const bool nolims = !a.has_lims || a.lims[0] > a.lims[m];           // backward_pass.jl:31, read on the device
     const unsigned full = m >= 32 ? 0xffffffffu : ((1u << m) - 1u);
     double limlo = 0.0, limhi = 0.0;
@@ -299,7 +288,17 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
             vs[e] = v;
             Vxg[(size_t)n * (N - 1) + e] = v;
         }
-        for (int e = t; e < m * m; e += WT) Quug[mm * (N - 1) + e] = cuuN[e];
+        for (int e = t; e < m * m; e += WT) {
+            double v = cuuN[e];
+            if (GPS) { v = v / etag[a.eta_tv ? N - 1 : 0] + cuukl[mm * (N - 1) + e]; img[(e % m) + ldm * (e / m)] = v; }   // :282
+            Quug[mm * (N - 1) + e] = v;
+        }
+        if (GPS) {                                                      // Quui[:,:,N] = inv(Quu[:,:,N])  (:283)
+            __syncthreads();
+            if (w == 0) inv_wave(img, ldm, m, lane);
+            __syncthreads();
+            for (int e = t; e < m * m; e += WT) Quuig[mm * (N - 1) + e] = img[(e % m) + ldm * (m + e / m)];
+        }
         for (int e = t; e < m * n; e += WT) Kg[nm * (N - 1) + e] = 0.0;
         for (int e = t; e < m; e += WT) { kg[(size_t)m * (N - 1) + e] = 0.0; ks[e] = 0.0; }
     }
@@ -327,7 +326,9 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
             const double *fc = Fs + ldn * t;
             double s = 0.0;
             for (int l = 0; l < n; ++l) s += fc[l] * vs[l];
-            Qs[t] = (t < n ? cx[(size_t)n * i + t] : cu[(size_t)m * i + (t - n)]) + s;         // :240-241
+            double qv = (t < n ? cx[(size_t)n * i + t] : cu[(size_t)m * i + (t - n)]) + s;     // :240-241
+            if (GPS) qv = qv / etag[a.eta_tv ? i : 0] + (t < n ? cxkl[(size_t)n * i + t] : cukl[(size_t)m * i + (t - n)]);   // :295,298
+            Qs[t] = qv;
         }
         __syncthreads();
 
@@ -347,6 +348,18 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
                     sd.z = (r0 + l4 + 8 < n && col < n) ? cxxi[(r0 + l4 + 8) + n * col] : 0.0;
                     sd.w = (r0 + l4 + 12 < n && col < n) ? cxxi[(r0 + l4 + 12) + n * col] : 0.0;
                     qacc[s] = xty(Gt, 1, ldn, r0, n, Fs, 1, ldn, c0, n, n, sd, l15, l4);       // :244
+                    if (GPS) {                                          // :299; only the symmetric part of cxxkl survives :341
+                        const double et = etag[a.eta_tv ? i : 0];
+                        const double *kx = cxxkl + nn * i;
+                        d4 kd = d4{0.0, 0.0, 0.0, 0.0};
+                        if (col < n) {
+                            if (r0 + l4 < n) kd.x = 0.5 * (kx[(r0 + l4) + n * col] + kx[col + n * (r0 + l4)]);
+                            if (r0 + l4 + 4 < n) kd.y = 0.5 * (kx[(r0 + l4 + 4) + n * col] + kx[col + n * (r0 + l4 + 4)]);
+                            if (r0 + l4 + 8 < n) kd.z = 0.5 * (kx[(r0 + l4 + 8) + n * col] + kx[col + n * (r0 + l4 + 8)]);
+                            if (r0 + l4 + 12 < n) kd.w = 0.5 * (kx[(r0 + l4 + 12) + n * col] + kx[col + n * (r0 + l4 + 12)]);
+                        }
+                        qacc[s] = qacc[s] / et + kd;
+                    }
                 }
             }
             const double *cxui = cxu + a.cxu_t * i, *cuui = cuu + a.cuu_t * i;
@@ -369,7 +382,18 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
                     }
                     const d4 acc = xty(Gu, 1, ldn, r0, m, Y, 1, ldn, c0, nc, n, sd, l15, l4);  // :242-243
                     d4 reg = acc;
-                    if (regType == 2) {                                 // Vxx_reg = Vxx + λI (:245): + λ fu'[fx fu]
+                    if (GPS) {                                          // Q• <- Q•/η + c•kl, no λ  (:296-297)
+                        const double et = etag[a.eta_tv ? i : 0];
+                        const double *kp = xcols ? cxukl + nm * i : cuukl + mm * i;     // both m rows: cxukl[q + m j], cuukl[q + m b]
+                        d4 kd = d4{0.0, 0.0, 0.0, 0.0};
+                        if (col < nc) {
+                            if (r0 + l4 < m) kd.x = kp[(r0 + l4) + m * col];
+                            if (r0 + l4 + 4 < m) kd.y = kp[(r0 + l4 + 4) + m * col];
+                            if (r0 + l4 + 8 < m) kd.z = kp[(r0 + l4 + 8) + m * col];
+                            if (r0 + l4 + 12 < m) kd.w = kp[(r0 + l4 + 12) + m * col];
+                        }
+                        reg = acc / et + kd;
+                    } else if (regType == 2) {                                 // Vxx_reg = Vxx + λI (:245): + λ fu'[fx fu]
                         const d4 sr = xty(Fu, 1, ldn, r0, m, Y, 1, ldn, c0, nc, n, d4{0.0, 0.0, 0.0, 0.0}, l15, l4);
                         reg = acc + lam * sr;
                     }
@@ -378,10 +402,10 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
                         const int row = r0 + l4 + 4 * r;
                         if (row < m && col < nc) {
                             if (xcols) {                                // Qux, Qux_reg (:242,246)
-                                Quxs[row + ldm * col] = comp(acc, r);
+                                Quxs[row + ldm * col] = comp(GPS ? reg : acc, r);
                                 Kx[row + ldm * col] = comp(reg, r);
                             } else {                                    // Quu, QuuF (:243,247)
-                                Quus[row + ldm * col] = comp(acc, r);
+                                Quus[row + ldm * col] = comp(GPS ? reg : acc, r);
                                 Hs[row + ldm * col] = comp(reg, r) + ((regType == 1 && row == col) ? lam : 0.0);
                             }
                         }
@@ -390,6 +414,22 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
             }
         }
         __syncthreads();
+        if (GPS) {                                                      // Quu = .5(Quu + Quu')  (:301); it is also the matrix factorised
+            constexpr int RQ = cdivw(WIDE_MAX_M * WIDE_MAX_M, WT);
+            double sv[RQ];
+#pragma unroll
+            for (int r = 0; r < RQ; ++r) {
+                const int e = t + WT * r, ii = e % m, jj = e / m;
+                sv[r] = e < m * m ? 0.5 * (Quus[ii + ldm * jj] + Quus[jj + ldm * ii]) : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < RQ; ++r) {
+                const int e = t + WT * r, ii = e % m, jj = e / m;
+                if (e < m * m) { Quus[ii + ldm * jj] = sv[r]; Hs[ii + ldm * jj] = sv[r]; img[ii + ldm * jj] = sv[r]; }
+            }
+            __syncthreads();
+        }
 
         // ================= P3: gains (backward_pass.jl:30-62) =======================================
         if (w == 0) {
@@ -407,8 +447,11 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
                 if (lane < m) ks[lane] = xq;
             }
             if (lane == 0) { flags[0] = fail; flags[1] = (int)freem; }
+        } else if (GPS && w == 1) {
+            inv_wave(img, ldm, m, lane);                                // Quui[:,:,i] = inv(Quu[:,:,i])  (:346), off the chain
         } else if (a.fx_t != 0 && i > 0) {
-            load_F(i - 1, t - DDP_WAVE, WT - DDP_WAVE);                  // (Fs: last read in P2)
+            if (GPS) load_F(i - 1, t - 2 * DDP_WAVE, WT - 2 * DDP_WAVE);
+            else load_F(i - 1, t - DDP_WAVE, WT - DDP_WAVE);             // (Fs: last read in P2)
         }
         __syncthreads();
         if (flags[0]) {                                                 // uniform: diverge = i (:37-38, :54-55)
@@ -459,6 +502,8 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
         }
         for (int e = t; e < m * n; e += WT) Kg[nm * i + e] = Kx[(e % m) + ldm * (e / m)];       // :76
         for (int e = t; e < m * m; e += WT) Quug[mm * i + e] = Quus[(e % m) + ldm * (e / m)];
+        if (GPS)
+            for (int e = t; e < m * m; e += WT) Quuig[mm * i + e] = img[(e % m) + ldm * (m + e / m)];
         __syncthreads();
 
 #pragma unroll
@@ -528,12 +573,12 @@ __global__ __launch_bounds__(WT) void back_pass_wide_kernel(BPWArgs a)
 
 }   // namespace
 
-// any n <= 64, m <= 32 (the dispatcher has checked the shape)
-int ddp_launch_back_pass_wide(ddp_handle h, const BPCall &c)
+static int launch_wide(ddp_handle h, const BPCall &c, bool gps)
 {
     const ddp_bp_desc *d = &c.d;
-    DDP_CHECK(d->n >= 1 && d->n <= WIDE_MAX_N && d->m >= 1 && d->m <= WIDE_MAX_M, "back_pass: n=%d m=%d outside the wide-control kernel (n <= %d, m <= %d)",
-              d->n, d->m, WIDE_MAX_N, WIDE_MAX_M);
+    const char *who = gps ? "back_pass_gps" : "back_pass";
+    DDP_CHECK(d->n >= 1 && d->n <= WIDE_MAX_N && d->m >= 1 && d->m <= WIDE_MAX_M, "%s: n=%d m=%d outside the wide-control kernel (n <= %d, m <= %d)",
+              who, d->n, d->m, WIDE_MAX_N, WIDE_MAX_M);
     const long n = d->n, m = d->m, N = d->N;
     BPWArgs a;
     a.n = d->n; a.m = d->m; a.N = d->N; a.B = d->B; a.regType = d->regType; a.has_lims = d->has_lims;
@@ -545,11 +590,27 @@ int ddp_launch_back_pass_wide(ddp_handle h, const BPCall &c)
     a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda;
     a.lims = c.lims; a.u = c.u; a.active = c.active;
     a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
-    const WLds L(d->n, d->m);
+    a.cxkl = a.cukl = a.cxxkl = a.cxukl = a.cuukl = a.eta = nullptr; a.eta_tv = 0; a.Quui = nullptr;
+    if (gps) {
+        const ddp_kl_cost_terms *kl = c.kl;
+        DDP_CHECK(kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && c.Quui, "back_pass_gps: null KL terms / Quui");
+        DDP_CHECK(!d->has_lims || (c.lims && c.u), "back_pass_gps: has_lims without lims / u");
+        a.cxkl = kl->cx; a.cukl = kl->cu; a.cxxkl = kl->cxx; a.cxukl = kl->cxu; a.cuukl = kl->cuu; a.eta = kl->eta; a.eta_tv = kl->eta_tv;
+        a.Quui = c.Quui;
+        a.regType = 0;
+    }
+    const WLds L(d->n, d->m, gps);
     const size_t bytes = (size_t)L.total * sizeof(double);
-    DDP_CHECK(bytes <= (size_t)WIDE_LDS_BYTES, "back_pass: n=%d m=%d needs %zu bytes of LDS (limit %d)", d->n, d->m, bytes, WIDE_LDS_BYTES);
-    if (int rc = ddp_raise_lds(h, (const void *)back_pass_wide_kernel, WIDE_LDS_BYTES)) return rc;    // per handle, not per process
-    hipLaunchKernelGGL(back_pass_wide_kernel, dim3(d->B), dim3(WT), bytes, h->stream, a);
+    DDP_CHECK(bytes <= (size_t)WIDE_LDS_BYTES, "%s: n=%d m=%d needs %zu bytes of LDS (limit %d)", who, d->n, d->m, bytes, WIDE_LDS_BYTES);
+    const void *kern = gps ? (const void *)back_pass_wide_kernel<true> : (const void *)back_pass_wide_kernel<false>;
+    if (int rc = ddp_raise_lds(h, kern, WIDE_LDS_BYTES)) return rc;    // per handle, not per process
+    if (gps) hipLaunchKernelGGL(back_pass_wide_kernel<true>, dim3(d->B), dim3(WT), bytes, h->stream, a);
+    else hipLaunchKernelGGL(back_pass_wide_kernel<false>, dim3(d->B), dim3(WT), bytes, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }
+
+// any n <= 64, m <= 32 (the dispatcher has checked the shape)
+int ddp_launch_back_pass_wide(ddp_handle h, const BPCall &c) { return launch_wide(h, c, false); }
+// back_pass_gps on the same kernel (the GPS instantiation)
+int ddp_launch_back_pass_gps_wide(ddp_handle h, const BPCall &c) { return launch_wide(h, c, true); }

@@ -15,7 +15,7 @@
 // The DDP_* switches of the dispatchers (kernel choice for A/B timing and for the tests that force every code path) are read from the
 // environment ONCE per handle (ddp_create) and again on ddp_reload_env(): no launch calls getenv, and a setenv() in another thread
 // cannot race with a launch.  ddp_env() returns the cached value or nullptr.
-enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_MX_LDS, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_GPS_MID, ENV_COUNT };
+enum ddp_env_id { ENV_BACKPASS, ENV_SH_MIN_B, ENV_MX2, ENV_DPPW, ENV_MX_LDS, ENV_Q4_SINGLE, ENV_Q4_LDS, ENV_GPS_Q4, ENV_GPS_Q4L, ENV_DF_DENSE, ENV_FORWARD, ENV_FORWARD64, ENV_FORWARD_FAST, ENV_FORWARD_FUSE, ENV_FORWARD_LANE, ENV_FORWARD_PEND, ENV_FORWARD_PIPE, ENV_ILQG_COMPACT, ENV_ILQG_LSGROUPS, ENV_TEST_COMPACT_ALLOC_FAIL, ENV_GPS_LANE, ENV_FCOV_Q4, ENV_FCOV_Q4L, ENV_KL_LDS, ENV_TEST_SH_ABORT, ENV_MXG_COAL, ENV_FORWARD_MID, ENV_PEND_CHUNK, ENV_GPS_MID, ENV_GPS_WIDE, ENV_COUNT };
 
 struct ddp_handle_s {
     int          device;
@@ -45,6 +45,7 @@ struct ddp_handle_s {
     int          timing_cap;
     hipEvent_t   tev[4];          // created on first use
     bool         tev_ok;
+    int          kl_wide;         // ddp_kl_set_wide: the KL functions take n <= 64, m <= DDP_MAX_M_WIDE
     void        *user_cache;      // user_problem.hip: the modules of the user problems compiled for this handle (unloaded by ddp_destroy)
 };
 
@@ -176,6 +177,16 @@ int ddp_launch_back_pass_row(ddp_handle h, const BPCall &c);
 int ddp_launch_back_pass_mid(ddp_handle h, const BPCall &c);
 // back_pass_gps on the same kernel (GPS instantiations, KL terms combined by a prepass) — any n <= 32, m <= 8; 1 = not applicable
 int ddp_launch_back_pass_gps_mid(ddp_handle h, const BPCall &c);
+// back_pass_gps on the wide-control kernel (the GPS instantiation of back_pass_wide.hip) — any n <= 64, m <= DDP_MAX_M_WIDE
+int ddp_launch_back_pass_gps_wide(ddp_handle h, const BPCall &c);
+// the KL kernels of the same shapes (kl_wide.hip): ∇kl, forward_covariance, kl_div_wiki; the entry points of kl.hip choose them
+int ddp_launch_kl_terms_wide(ddp_handle h, int n, int m, int N, int B, const double *K, const double *k, const double *Sigmai,
+                             double *cx, double *cu, double *cxx, double *cxu, double *cuu);
+int ddp_launch_fcov_wide(ddp_handle h, int n, int m, int N, int B, const double *fx, int fx_batched, const double *R1, const double *K,
+                         const double *Sigma, double *sigmanew);
+int ddp_launch_kl_div_wide(ddp_handle h, int n, int m, int N, int B, const double *xnew, const double *xold, const double *sigmanew,
+                           const double *Kn, const double *kn, const double *Sn, const double *Kp, const double *kp, const double *Sp,
+                           const double *Sip, double *kldiv, double *klmean);
 // back_pass_gps dispatch (kl.hip): the user-problem KL driver (`user`) tries q4, lane, mid, generic; every other call q4, lane, generic.
 // DDP_GPS_MID=1 puts mid first for every call, =0 keeps it out.  Records the kernel in ddp_last_kernel(h, 0).
 int ddp_dispatch_back_pass_gps(ddp_handle h, const BPCall &c, bool user);

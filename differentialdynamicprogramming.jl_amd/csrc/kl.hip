@@ -15,6 +15,7 @@
 namespace {
 
 constexpr int NMAXK = DDP_MAX_N_GENERIC, MMAXK = DDP_MAX_M;
+constexpr int KL_WIDE_MAX_N = 64;        // with ddp_kl_set_wide: n <= 64, m <= DDP_MAX_M_WIDE (kl_wide.hip, back_pass_wide.hip)
 
 // ------------------------------------------------------------------------------------------------ ∇kl
 __global__ void kl_terms_kernel(int n, int m, long NB, const double *__restrict__ K, const double *__restrict__ k,
@@ -635,8 +636,10 @@ size_t fcov_lds(int n, int m) { return ((size_t)3 * n * n + 2 * (size_t)n * m) *
 // mid: any n <= 32, m <= 8 on the matrix cores behind a combine prepass (back_pass_mid.hip); generic: the 64-lane run-time-sized kernel
 // (back_pass.hip).  The user-problem KL driver takes q4, lane, mid, generic; the stand-alone call and the registered families' driver
 // q4, lane, generic as before.  DDP_GPS_MID=1 puts mid first in every call, =0 keeps it out of all of them (A/B timing, tests).
-enum GpsKernel { GPS_Q4, GPS_LANE, GPS_MID, GPS_GENERIC };
-const char *const gps_kernel_name[] = {"back_pass_gps_q4", "back_pass_gps_lane", "back_pass_gps_mid", "back_pass_gps"};
+// wide: any n <= 64, m <= DDP_MAX_M_WIDE on the GPS instantiation of back_pass_wide.hip — the shapes beyond n <= 32, m <= 8 when the
+// handle's ddp_kl_set_wide switch is on, every shape with DDP_GPS_WIDE=1 (gps_choose2).
+enum GpsKernel { GPS_Q4, GPS_LANE, GPS_MID, GPS_GENERIC, GPS_WIDE, GPS_NONE };
+const char *const gps_kernel_name[] = {"back_pass_gps_q4", "back_pass_gps_lane", "back_pass_gps_mid", "back_pass_gps", "back_pass_gps_wide", "none"};
 enum GpsCaller { GPS_STANDALONE = 0, GPS_REGISTERED = 1, GPS_USER = 2 };
 
 // host facts only (the same tests the launchers make before they return 1)
@@ -653,12 +656,39 @@ GpsKernel gps_choose(const ddp_bp_desc &d, int eta_tv, int caller, const char *g
     return GPS_GENERIC;
 }
 
+// The KL shape box: 0 the kernels of n <= 32, m <= 8; 1 the wide kernels (the switch is on and the shape is beyond the box, or
+// DDP_GPS_WIDE=1); -1 no kernel.  Host facts only.
+int kl_shape(int n, int m, int wide_on, const char *gps_wide)
+{
+    const bool small = n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK, wide_ok = n >= 1 && n <= KL_WIDE_MAX_N && m >= 1 && m <= DDP_MAX_M_WIDE;
+    if (small) return (gps_wide && gps_wide[0] == '1') ? 1 : 0;
+    return (wide_on && wide_ok) ? 1 : -1;
+}
+int kl_shape(ddp_handle h, int n, int m) { return kl_shape(n, m, h->kl_wide, ddp_env(h, ENV_GPS_WIDE)); }
+#define DDP_KL_SHAPE(h, who, n, m)                                                                                                   \
+    DDP_CHECK(kl_shape(h, n, m) >= 0, "%s: n=%d m=%d has no kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", who, n, \
+              m, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE)
+
+GpsKernel gps_choose2(const ddp_bp_desc &d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane, int wide_on,
+                      const char *gps_wide)
+{
+    const int sh = kl_shape(d.n, d.m, wide_on, gps_wide);
+    if (sh < 0) return GPS_NONE;
+    return sh ? GPS_WIDE : gps_choose(d, eta_tv, caller, gps_mid, gps_q4, gps_lane);
+}
+
 int gps_dispatch(ddp_handle h, const BPCall &c, int caller)
 {
     const ddp_kl_cost_terms *kl = c.kl;
     const bool complete = kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!c.d.has_lims || (c.lims && c.u));
     GpsKernel k = complete ? gps_choose(c.d, kl->eta_tv, caller, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE))
                            : GPS_GENERIC;
+    if (complete && kl_shape(h, c.d.n, c.d.m) == 1) {
+        DDP_DEVICE(h);
+        const int rcw = ddp_launch_back_pass_gps_wide(h, c);
+        if (!rcw) h->last_kernel[0] = gps_kernel_name[GPS_WIDE];
+        return rcw;
+    }
     int rc = 1;
     if (k == GPS_MID) rc = ddp_launch_back_pass_gps_mid(h, c);
     if (k == GPS_Q4) {
@@ -682,7 +712,9 @@ int ddp_kl_terms_f64_dev(ddp_handle h, int n, int m, int N, int B, const double 
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && K && k && Sigmai && cx && cu && cxx && cxu && cuu, "kl_terms: null argument");
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_terms: bad sizes n=%d m=%d N=%d B=%d", n, m, N, B);
+    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1) return ddp_launch_kl_terms_wide(h, n, m, N, B, K, k, Sigmai, cx, cu, cxx, cxu, cuu);
+    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_terms: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
+              "after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     const long NB = (long)N * B;
     hipLaunchKernelGGL(kl_terms_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, h->stream, n, m, NB, K, k, Sigmai, cx, cu, cxx, cxu, cuu);
     DDP_HIP(hipGetLastError());
@@ -699,6 +731,8 @@ int ddp_back_pass_gps_f64_dev(ddp_handle h, const ddp_bp_desc *d,
     DDP_DEVICE(h);
     DDP_CHECK(h && d && cx && cu && cxx && cxu && cuu && fx && fu && kl && K && k && Quu && Quui && Vx && Vxx && dV && diverge,
               "back_pass_gps: null argument");
+    DDP_CHECK(d->n >= 1 && d->m >= 1 && d->N >= 1 && d->B >= 1, "back_pass_gps: bad sizes n=%d m=%d N=%d B=%d", d->n, d->m, d->N, d->B);
+    DDP_KL_SHAPE(h, "back_pass_gps", d->n, d->m);
     DDP_HIP(hipMemsetAsync(Quui, 0, sizeof(double) * (size_t)d->m * d->m * d->N * d->B, h->stream));
     // q4 (n = 4, m = 1, one η per trajectory; DDP_GPS_Q4=0: not), lane (n = 4, m <= 2), generic; DDP_GPS_LANE=0: always the run-time-sized
     // kernel (cross-check in the tests); DDP_GPS_MID=1: the mid kernel for every shape it takes
@@ -713,13 +747,29 @@ const char *ddp_gps_choice(const ddp_bp_desc *d, int eta_tv, int caller, const c
 {
     return gps_kernel_name[gps_choose(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane)];
 }
+// Its twin with the two facts of the large shapes: the handle's ddp_kl_set_wide switch and DDP_GPS_WIDE.  "none": the call is refused.
+const char *ddp_gps_choice2(const ddp_bp_desc *d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane,
+                            int wide_on, const char *gps_wide)
+{
+    return gps_kernel_name[gps_choose2(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane, wide_on, gps_wide)];
+}
+
+int ddp_kl_set_wide(ddp_handle h, int on)
+{
+    if (!h) { ddp_set_error("null handle"); return -1; }
+    const int was = h->kl_wide;
+    h->kl_wide = on ? 1 : 0;
+    return was;
+}
 
 int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *fx, int fx_batched,
                                    const double *R1, const double *K, const double *Sigma, double *sigmanew)
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && fx && R1 && K && Sigma && sigmanew, "forward_covariance: null argument");
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "forward_covariance: bad sizes n=%d m=%d N=%d B=%d", n, m, N, B);
+    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1) return ddp_launch_fcov_wide(h, n, m, N, B, fx, fx_batched, R1, K, Sigma, sigmanew);
+    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "forward_covariance: bad sizes n=%d m=%d N=%d B=%d (n <= %d, "
+              "m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     const char *q4env = ddp_env(h, ENV_FCOV_Q4);                     // 0: the run-time-sized kernel for every shape (cross-check in the tests)
     if (n == 4 && (m == 1 || m == 2) && h->sink && !(q4env && q4env[0] == '0')) {
         const dim3 grid((unsigned)((B + 3) / 4)), block(DDP_WAVE);
@@ -744,7 +794,10 @@ int ddp_kl_div_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *x
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && xnew && xold && sigmanew && Kn && kn && Sn && Kp && kp && Sp && Sip && kldiv && klmean, "kl_div: null argument");
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_div: bad sizes n=%d m=%d N=%d B=%d", n, m, N, B);
+    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1)
+        return ddp_launch_kl_div_wide(h, n, m, N, B, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip, kldiv, klmean);
+    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_div: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
+              "after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     // operands through an LDS image of 64 steps when that fits (DDP_KL_LDS=0: the direct kernel, cross-check in the tests)
     const int lens[10] = {n, n, (n + m) * (n + m), n * m, m, m * m, n * m, m, m * m, m * m};
     size_t image = 0;
@@ -832,7 +885,9 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     DDP_CHECK(x0 != x && kp != u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
     const size_t n = f ? f->n : p->n, m = f ? f->m : p->m, N = f ? f->N : p->N, B = f ? f->B : p->B, NB = N * B, P2 = (n + m) * (n + m);
     const bool pend = !f && p->kind == DDP_PROBLEM_PENDCART;
-    DDP_CHECK(n <= (size_t)NMAXK && m <= (size_t)MMAXK, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d)", n, m, NMAXK, MMAXK);
+    const int wide = kl_shape(h, (int)n, (int)m);          // 1: back_pass_gps, ∇kl, forward_covariance and kl_div_wiki on the wide kernels
+    DDP_CHECK(wide >= 0, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m,
+              NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     // dynamics as back_pass_gps wants them: [n,n,N] or [n,n,N,B]
     const bool fx_b = f || pend || p->dyn_batched, fx_rep = !f && !pend && !p->dyn_tv, fx_own = f || pend || fx_rep;
     // cost Hessians: [.,.,N] of the registered problem, [.,.,N,B] of a family; constant Hessians of a family [.,.,B], repeated along time
@@ -841,7 +896,8 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     ddp_bp_desc d;
     d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = f != nullptr;
     d.regType = 1; d.has_lims = lims != nullptr;
-    const bool hrep = cst && gps_choose(d, 0, GPS_USER, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE)) != GPS_MID;
+    // (the wide kernel reads every operand layout too)
+    const bool hrep = cst && !wide && gps_choose(d, 0, GPS_USER, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE)) != GPS_MID;
     if (cst && !hrep) d.cost_tv = 0;
     const size_t hc = f ? (cst && !hrep ? B : NB) : N;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };

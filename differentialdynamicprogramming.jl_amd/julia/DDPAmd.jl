@@ -742,20 +742,46 @@ function mpc_shift_dev!(dst, src, d::Integer, N::Integer, B::Integer, shift::Int
 end
 
 # ======================================================================================= KL-constrained path
+# Shapes: n ≤ 32, m ≤ 8.  `wide=true` on ∇kl, back_pass_gps, forward_covariance, kl_div_wiki and iLQGkl opens n ≤ 64, m ≤ 32
+# (`ddp_kl_set_wide`: the shapes beyond the small box run on kernels of their own, smaller ones keep theirs).  The keyword sets the
+# handle's switch for the duration of the call and puts the previous value back; extents are checked before anything is launched.
+const KL_MAX_N, KL_MAX_M, KL_MAX_N_WIDE, KL_MAX_M_WIDE = 32, 8, 64, 32
+
+function _kl_box(who, n, m, wide::Bool)
+    nmax, mmax = wide ? (KL_MAX_N_WIDE, KL_MAX_M_WIDE) : (KL_MAX_N, KL_MAX_M)
+    (1 <= n <= nmax && 1 <= m <= mmax) || throw(DDPError(-1, "$who: n=$n m=$m has no back_pass_gps kernel (n <= $KL_MAX_N, m <= $KL_MAX_M; wide=true: n <= $KL_MAX_N_WIDE, m <= $KL_MAX_M_WIDE)"))
+    return nothing
+end
+
+"`f()` with the handle's switch for the large KL shapes on (`ddp_kl_set_wide`); the previous value comes back in any case"
+function _with_kl_wide(f, handle::Handle, wide::Bool)
+    wide || return f()
+    was = @ccall libddp.ddp_kl_set_wide(handle.ptr::Ptr{Cvoid}, 1::Cint)::Cint
+    was < 0 && check(was)
+    try
+        return f()
+    finally
+        @ccall libddp.ddp_kl_set_wide(handle.ptr::Ptr{Cvoid}, was::Cint)::Cint
+    end
+end
+
 """
     ∇kl(traj_prev) -> cx, cu, cxx, cxu, cuu          (klutils.jl:8-23; cxu is m×n×T like the reference; batch axis allowed)
 """
-function ∇kl(traj_prev; handle::Handle=default_handle())
+function ∇kl(traj_prev; handle::Handle=default_handle(), wide::Bool=false)
     _isempty_policy(traj_prev) && return (0, 0, 0, 0, 0)
     m, n, T = traj_prev.m, traj_prev.n, traj_prev.T
+    _kl_box("∇kl", n, m, wide)
     K, k, Σi = _f64(traj_prev.K), _f64(traj_prev.k), _f64(traj_prev.Σi)
     B = ndims(k) == 3 ? size(k, 3) : 1
     bt = ndims(k) == 3 ? (B,) : ()
     cx, cu, cxx, cxu, cuu = zeros(n, T, bt...), zeros(m, T, bt...), zeros(n, n, T, bt...), zeros(m, n, T, bt...), zeros(m, m, T, bt...)
-    GC.@preserve K k Σi cx cu cxx cxu cuu begin
-        check(@ccall libddp.ddp_kl_terms_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, T::Cint, B::Cint, K::Ptr{Float64},
-            k::Ptr{Float64}, Σi::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64}, cxx::Ptr{Float64}, cxu::Ptr{Float64},
-            cuu::Ptr{Float64})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve K k Σi cx cu cxx cxu cuu begin
+            check(@ccall libddp.ddp_kl_terms_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, T::Cint, B::Cint, K::Ptr{Float64},
+                k::Ptr{Float64}, Σi::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64}, cxx::Ptr{Float64}, cxu::Ptr{Float64},
+                cuu::Ptr{Float64})::Cint)
+        end
     end
     return cx, cu, cxx, cxu, cuu
 end
@@ -765,10 +791,11 @@ end
 
 Same signature and return values as backward_pass.jl:259; `kl_cost_terms = (∇kl(traj_prev), ηbracket)` with `ηbracket` a 3-vector
 or a 3×N matrix.  One trajectory (a batch goes through `iLQGkl` below / `ddp_back_pass_gps_f64_dev`).  Shapes: n ≤ 32, m ≤ 8 (the library
-returns an error beyond; the plain `back_pass` reaches n ≤ 64).
+returns an error beyond; the plain `back_pass` reaches n ≤ 64); `wide=true`: n ≤ 64, m ≤ 32.
 """
-function back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms; handle::Handle=default_handle(), policy=GaussianPolicy{Float64})
+function back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms; handle::Handle=default_handle(), policy=GaussianPolicy{Float64}, wide::Bool=false)
     n, N = size(cx); m = size(cu, 1)
+    _kl_box("back_pass_gps", n, m, wide)
     cx, cu, cxx, cxu, cuu, fx, fu, u = map(_f64, (cx, cu, cxx, cxu, cuu, fx, fu, u))
     cxkl, cukl, cxxkl, cxukl, cuukl = map(_f64, kl_cost_terms[1])
     ηb = kl_cost_terms[2]
@@ -778,13 +805,15 @@ function back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms;
     d = BPDesc(n, m, N, 1, 1, 0, 1, 0, 1, has_lims)
     K = zeros(m, n, N); k = zeros(m, N); Quu = zeros(m, m, N); Quui = zeros(m, m, N); Vx = zeros(n, N); Vxx = zeros(n, n, N)
     dV = zeros(2); diverge = zeros(Int32, 1)
-    GC.@preserve cx cu cxx cxu cuu fx fu u cxkl cukl cxxkl cxukl cuukl η limsp K k Quu Quui Vx Vxx dV diverge begin
-        t = KLCostTerms(pointer(cxkl), pointer(cukl), pointer(cxxkl), pointer(cxukl), pointer(cuukl), pointer(η), isa(ηb, AbstractMatrix))
-        check(@ccall libddp.ddp_back_pass_gps_f64(handle.ptr::Ptr{Cvoid}, Ref(d)::Ptr{BPDesc}, cx::Ptr{Float64}, cu::Ptr{Float64},
-            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, Ref(t)::Ptr{KLCostTerms},
-            _ptr_or_null(limsp)::Ptr{Float64}, (has_lims ? pointer(u) : NULLF)::Ptr{Float64},
-            K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Quui::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
-            dV::Ptr{Float64}, diverge::Ptr{Int32})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve cx cu cxx cxu cuu fx fu u cxkl cukl cxxkl cxukl cuukl η limsp K k Quu Quui Vx Vxx dV diverge begin
+            t = KLCostTerms(pointer(cxkl), pointer(cukl), pointer(cxxkl), pointer(cxukl), pointer(cuukl), pointer(η), isa(ηb, AbstractMatrix))
+            check(@ccall libddp.ddp_back_pass_gps_f64(handle.ptr::Ptr{Cvoid}, Ref(d)::Ptr{BPDesc}, cx::Ptr{Float64}, cu::Ptr{Float64},
+                cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, Ref(t)::Ptr{KLCostTerms},
+                _ptr_or_null(limsp)::Ptr{Float64}, (has_lims ? pointer(u) : NULLF)::Ptr{Float64},
+                K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Quui::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+                dV::Ptr{Float64}, diverge::Ptr{Int32})::Cint)
+        end
     end
     return Int(diverge[1]), policy(N, n, m, K, k, Quui, Quu), Vx, Vxx, dV
 end
@@ -792,12 +821,15 @@ end
 """
     forward_covariance(fx, R1, traj) -> sigmanew       (forward_pass.jl:37-56 with `df(model,·)[1]`, `covariance(model,·)` passed in)
 """
-function forward_covariance(fx::Array{Float64,3}, R1::Matrix{Float64}, traj; handle::Handle=default_handle())
+function forward_covariance(fx::Array{Float64,3}, R1::Matrix{Float64}, traj; handle::Handle=default_handle(), wide::Bool=false)
     n, m, N = traj.n, traj.m, traj.T
+    _kl_box("forward_covariance", n, m, wide)
     S = zeros(n + m, n + m, N); K, Σ = _f64(traj.K), _f64(traj.Σ)
-    GC.@preserve fx R1 K Σ S begin
-        check(@ccall libddp.ddp_forward_covariance_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, 1::Cint, fx::Ptr{Float64},
-            0::Cint, R1::Ptr{Float64}, K::Ptr{Float64}, Σ::Ptr{Float64}, S::Ptr{Float64})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve fx R1 K Σ S begin
+            check(@ccall libddp.ddp_forward_covariance_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, 1::Cint, fx::Ptr{Float64},
+                0::Cint, R1::Ptr{Float64}, K::Ptr{Float64}, Σ::Ptr{Float64}, S::Ptr{Float64})::Cint)
+        end
     end
     return S
 end
@@ -805,15 +837,18 @@ end
 """
     kl_div_wiki(xnew, xold, Σ_new, traj_new, traj_prev) -> kldiv (or Inf)      (klutils.jl:70-103)
 """
-function kl_div_wiki(xnew, xold, Σ_new, traj_new, traj_prev; handle::Handle=default_handle())
+function kl_div_wiki(xnew, xold, Σ_new, traj_new, traj_prev; handle::Handle=default_handle(), wide::Bool=false)
     n, m, T = traj_new.n, traj_new.m, traj_new.T
+    _kl_box("kl_div_wiki", n, m, wide)
     kld = zeros(T); mean_ = zeros(1)
     xnew, xold, Σ_new = map(_f64, (xnew, xold, Σ_new))
     Kn, kn, Σn, Kp, kp, Σp, Σip = map(_f64, (traj_new.K, traj_new.k, traj_new.Σ, traj_prev.K, traj_prev.k, traj_prev.Σ, traj_prev.Σi))
-    GC.@preserve xnew xold Σ_new Kn kn Σn Kp kp Σp Σip kld mean_ begin
-        check(@ccall libddp.ddp_kl_div_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, T::Cint, 1::Cint, xnew::Ptr{Float64},
-            xold::Ptr{Float64}, Σ_new::Ptr{Float64}, Kn::Ptr{Float64}, kn::Ptr{Float64}, Σn::Ptr{Float64}, Kp::Ptr{Float64},
-            kp::Ptr{Float64}, Σp::Ptr{Float64}, Σip::Ptr{Float64}, kld::Ptr{Float64}, mean_::Ptr{Float64})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve xnew xold Σ_new Kn kn Σn Kp kp Σp Σip kld mean_ begin
+            check(@ccall libddp.ddp_kl_div_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, T::Cint, 1::Cint, xnew::Ptr{Float64},
+                xold::Ptr{Float64}, Σ_new::Ptr{Float64}, Kn::Ptr{Float64}, kn::Ptr{Float64}, Σn::Ptr{Float64}, Kp::Ptr{Float64},
+                kp::Ptr{Float64}, Σp::Ptr{Float64}, Σip::Ptr{Float64}, kld::Ptr{Float64}, mean_::Ptr{Float64})::Cint)
+        end
     end
     return isinf(mean_[1]) && all(isfinite, kld) ? Inf : kld
 end
@@ -878,7 +913,8 @@ closures, `fx_model[n,n,N(,B)]` / `R1[n,n]` are what `df(model,·)` / `covarianc
 :cost, :improvement, :expected_reduction, :grad_norm, :dV.  `traj_prev.k` is left untouched (the reference zeroes and restores it, :51,247).
 """
 function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step=1.0, lims=[], max_iter=50, cost=[],
-                ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, diff_fun=-, handle::Handle=default_handle(), policy=GaussianPolicy{Float64})
+                ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, diff_fun=-, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
+                wide::Bool=false)
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
     isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
     batched = ndims(x0) == 3
@@ -886,6 +922,7 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
     u0 = _f64(traj_prev.k)
     m = size(u0, 1)
     size(u0, 2) == N || error("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")     # :72
+    _kl_box("iLQGkl", n, m, wide)
     B = batched ? size(x0, 3) : 1
     P = cproblem(problem, N, B; diff=diff_fun)
     CL = cost_len(problem, N)
@@ -902,12 +939,14 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
     Vx, Vx_r = result_pair((n, N, B), (n, N, bt...)); Vxx, Vxx_r = result_pair((n, n, N, B), (n, n, N, bt...))
     cnew, cnew_r = result_pair((CL, B), (CL, bt...)); dV = zeros(2, B); st = zeros(12, B)
     its = Ref{Cint}(0)
-    GC.@preserve problem x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
-        check(@ccall libddp.ddp_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, Ref(P)::Ptr{CProblem}, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64},
-            c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64}, Sip::Ptr{Float64}, fxm::Ptr{Float64},
-            (ndims(fxm) == 4)::Cint, R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64},
-            x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
-            cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64}, its::Ptr{Cint})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve problem x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
+            check(@ccall libddp.ddp_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, Ref(P)::Ptr{CProblem}, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64},
+                c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64}, Sip::Ptr{Float64}, fxm::Ptr{Float64},
+                (ndims(fxm) == 4)::Cint, R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64},
+                x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+                cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64}, its::Ptr{Cint})::Cint)
+        end
     end
     trace = Dict{Symbol,Any}(:status => Int.(st[1, :]), :iter => Int.(st[2, :]), :n_backpass => Int.(st[3, :]), :satisfied => st[4, :] .!= 0,
                              :η => etab, :divergence => st[8, :], :cost => st[9, :], :improvement => st[10, :],
@@ -1163,7 +1202,8 @@ end
 # iLQGkl with the user's closures (`ddp_user_ilqgkl_f64`): as the method for registered problems; `fx_model = nothing` means the
 # problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B]
 function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
-                ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64})
+                ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
+                wide::Bool=false)
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
     isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
     batched = ndims(x0) == 3
@@ -1172,6 +1212,7 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
     m = size(u0, 1)
     (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
     size(u0, 2) == N || error("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")     # :72
+    _kl_box("iLQGkl", n, m, wide)
     B = batched ? size(x0, 3) : 1
     P, pb = _user_params(problem, B, params)
     CL = cost_len(problem, N)
@@ -1192,13 +1233,15 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
     cnew, cnew_r = result_pair((CL, B), (CL, bt...)); dV = zeros(2, B); st = zeros(12, B)
     its = Ref{Cint}(0)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
-        check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
-            pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
-            Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
-            R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
-            S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
-            its::Ptr{Cint})::Cint)
+    _with_kl_wide(handle, wide) do
+        GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
+            check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
+                Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
+                R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+                S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
+                its::Ptr{Cint})::Cint)
+        end
     end
     trace = Dict{Symbol,Any}(:status => Int.(st[1, :]), :iter => Int.(st[2, :]), :n_backpass => Int.(st[3, :]), :satisfied => st[4, :] .!= 0,
                              :η => etab, :divergence => st[8, :], :cost => st[9, :], :improvement => st[10, :],

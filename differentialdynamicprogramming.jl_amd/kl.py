@@ -17,9 +17,15 @@ here the model is ``Model(fx[n,n,N(,B)], fu[n,m,N(,B)], R1[n,n])`` — the array
 ``model_covariance`` is this build's documented choice for `covariance` (empirical covariance of the one-step
 prediction residuals, the inline comment at forward_pass.jl:42).  The per-time-step branch (`constrain_per_step`,
 iLQGkl.jl:180-232) is not offloaded.
+
+Shapes: n <= 32, m <= 8.  ``wide=True`` on ``grad_kl``, ``back_pass_gps``, ``forward_covariance``, ``kl_div_wiki``, ``calc_η``,
+``iLQGkl`` and ``demo_linear_kl`` opens n <= 64, m <= 32 (``ddp_kl_set_wide``: the shapes beyond the small box run on the kernels of
+csrc/kl_wide.hip and the GPS instantiation of csrc/back_pass_wide.hip; smaller shapes keep their kernels).  The keyword sets the
+handle's switch for the duration of the call and puts the previous value back.  Extents are checked before anything is launched.
 """
 from __future__ import annotations
 
+import contextlib as _contextlib
 import ctypes as _C
 from dataclasses import dataclass
 
@@ -39,13 +45,37 @@ class Model:
     R1: np.ndarray          # [n,n]
 
 
+MAX_N, MAX_M, MAX_N_WIDE, MAX_M_WIDE = 32, 8, 64, 32      # DDP_MAX_N_GENERIC, DDP_MAX_M; with the switch: 64, DDP_MAX_M_WIDE
+
+
+def _kl_box(who, n, m, wide):
+    """the shape box of the KL functions, checked before any launch (and before the handle is touched)"""
+    nmax, mmax = (MAX_N_WIDE, MAX_M_WIDE) if wide else (MAX_N, MAX_M)
+    if not (1 <= n <= nmax and 1 <= m <= mmax):
+        raise DDPError("%s: n=%d m=%d has no back_pass_gps kernel (n <= %d, m <= %d; wide=True: n <= %d, m <= %d)"
+                       % (who, n, m, MAX_N, MAX_M, MAX_N_WIDE, MAX_M_WIDE))
+
+
+@_contextlib.contextmanager
+def _wide(h, on):
+    """``wide=True``: the handle's ddp_kl_set_wide switch is on inside the block; the previous value comes back in any case"""
+    if not on:
+        yield
+        return
+    was = h.set_kl_wide(True)
+    try:
+        yield
+    finally:
+        h.set_kl_wide(was)
+
+
 def _b(a, nd):
     """append a unit batch axis to an unbatched array of rank nd"""
     a = _lib.f64(a)
     return a.reshape(a.shape + (1,)) if a.ndim == nd else a
 
 
-def grad_kl(traj_prev, *, handle=None):
+def grad_kl(traj_prev, *, handle=None, wide=False):
     """``∇kl(traj_prev)`` -> ``(cx,cu,cxx,cxu,cuu)`` with ``cxu`` of shape [m,n,T] like the reference (klutils.jl:20);
     ``(0,0,0,0,0)`` for an empty policy (:9)."""
     if traj_prev is None or traj_prev.isempty():
@@ -54,9 +84,11 @@ def grad_kl(traj_prev, *, handle=None):
     batched = np.ndim(traj_prev.K) == 4
     K, k, Si = _b(traj_prev.K, 3), _b(traj_prev.k, 2), _b(traj_prev.Σi, 3)
     m, n, T, B = K.shape
+    _kl_box("∇kl", n, m, wide)
     cx = _lib.result_array((n, T, B)); cu = _lib.result_array((m, T, B)); cxx = _lib.result_array((n, n, T, B))
     cxu = _lib.result_array((m, n, T, B)); cuu = _lib.result_array((m, m, T, B))
-    _lib.check(_lib.lib().ddp_kl_terms_f64(h.raw, n, m, T, B, *map(_lib.ptr, (K, k, Si, cx, cu, cxx, cxu, cuu))))
+    with _wide(h, wide):
+        _lib.check(_lib.lib().ddp_kl_terms_f64(h.raw, n, m, T, B, *map(_lib.ptr, (K, k, Si, cx, cu, cxx, cxu, cuu))))
     out = (cx, cu, cxx, cxu, cuu)
     return out if batched else tuple(a[..., 0] for a in out)
 
@@ -64,7 +96,7 @@ def grad_kl(traj_prev, *, handle=None):
 globals()["∇kl"] = grad_kl
 
 
-def back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms, *, handle=None):
+def back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms, *, handle=None, wide=False):
     """Drop-in for ``back_pass_gps(cx,cu,cxx,cxu,cuu,fx,fu,lims,x,u,kl_cost_terms)`` (backward_pass.jl:259).
     ``kl_cost_terms = ((cxkl,cukl,cxxkl,cxukl,cuukl), ηbracket)``; ``ηbracket`` is a 3-vector, a [3,N] matrix (per-step η),
     or with a batch [3,B] / [3,N,B].  Returns ``(diverge, GaussianPolicy(N,n,m,K,k,Quui,Quu), Vx, Vxx, dV)``."""
@@ -74,6 +106,7 @@ def back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms, *, h
     cx, cu, u = _b(cx, 2), _b(cu, 2), _b(u, 2)
     n, N, B = cx.shape
     m = cu.shape[0]
+    _kl_box("back_pass_gps", n, m, wide)
     fx, fu, cxx, cxu, cuu = map(_lib.f64, (fx, fu, cxx, cxu, cuu))
     assert fx.ndim in (3, 4) and cxx.ndim in (3, 4), "back_pass_gps needs 3-D fx/fu and cxx/cxu/cuu (backward_pass.jl:259)"
     assert cx.shape[:2] == (n, N) and cu.shape[:2] == (m, N) and cxx.shape[:3] == (n, n, N) and cxu.shape[:3] == (n, m, N)
@@ -97,25 +130,28 @@ def back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, lims, x, u, kl_cost_terms, *, h
     K = _lib.result_array((m, n, N, B)); k = _lib.result_array((m, N, B)); Quu = _lib.result_array((m, m, N, B))
     Quui = _lib.result_array((m, m, N, B)); Vx = _lib.result_array((n, N, B)); Vxx = _lib.result_array((n, n, N, B))
     dV = np.zeros((2, B), order="F"); div = np.zeros(B, dtype=np.int32)
-    _lib.check(_lib.lib().ddp_back_pass_gps_f64(h.raw, _C.byref(d), *map(_lib.ptr, (cx, cu, cxx, cxu, cuu, fx, fu)), _C.byref(t),
-                                                _lib.ptr(L), _lib.ptr(u), *map(_lib.ptr, (K, k, Quu, Quui, Vx, Vxx, dV)),
-                                                div.ctypes.data_as(_lib.i32p)))
+    with _wide(h, wide):
+        _lib.check(_lib.lib().ddp_back_pass_gps_f64(h.raw, _C.byref(d), *map(_lib.ptr, (cx, cu, cxx, cxu, cuu, fx, fu)), _C.byref(t),
+                                                    _lib.ptr(L), _lib.ptr(u), *map(_lib.ptr, (K, k, Quu, Quui, Vx, Vxx, dV)),
+                                                    div.ctypes.data_as(_lib.i32p)))
     if not batched:
         return int(div[0]), GaussianPolicy(N, n, m, K[..., 0], k[..., 0], Quui[..., 0], Quu[..., 0]), Vx[..., 0], Vxx[..., 0], dV[:, 0]
     return div, GaussianPolicy(N, n, m, K, k, Quui, Quu), Vx, Vxx, dV
 
 
-def forward_covariance(model, x, u, traj, *, handle=None):
+def forward_covariance(model, x, u, traj, *, handle=None, wide=False):
     """``forward_covariance(model,x,u,traj)`` -> ``sigmanew[(n+m),(n+m),N(,B)]`` (forward_pass.jl:37-56); ``x``,``u`` are
     only what the reference hands to `df(model,·)`/`covariance(model,·)` — the model here already holds those arrays."""
     h = handle or default_handle()
     batched = np.ndim(traj.K) == 4
     K, Sg = _b(traj.K, 3), _b(traj.Σ, 3)
     m, n, N, B = K.shape
+    _kl_box("forward_covariance", n, m, wide)
     fx, R1 = _lib.f64(model.fx), _lib.f64(model.R1)
     S = _lib.result_array((n + m, n + m, N, B))
-    _lib.check(_lib.lib().ddp_forward_covariance_f64(h.raw, n, m, N, B, _lib.ptr(fx), int(fx.ndim == 4), _lib.ptr(R1), _lib.ptr(K),
-                                                     _lib.ptr(Sg), _lib.ptr(S)))
+    with _wide(h, wide):
+        _lib.check(_lib.lib().ddp_forward_covariance_f64(h.raw, n, m, N, B, _lib.ptr(fx), int(fx.ndim == 4), _lib.ptr(R1), _lib.ptr(K),
+                                                         _lib.ptr(Sg), _lib.ptr(S)))
     return S if batched else S[..., 0]
 
 
@@ -126,21 +162,23 @@ def model_covariance(model, x, u):
     return np.atleast_2d(np.cov(E))
 
 
-def _kl_div(xnew, xold, Σ_new, traj_new, traj_prev, handle=None):
+def _kl_div(xnew, xold, Σ_new, traj_new, traj_prev, handle=None, wide=False):
     h = handle or default_handle()
     batched = np.ndim(traj_new.K) == 4
     Kn, kn, Sn = _b(traj_new.K, 3), _b(traj_new.k, 2), _b(traj_new.Σ, 3)
     Kp, kp, Sp, Sip = _b(traj_prev.K, 3), _b(traj_prev.k, 2), _b(traj_prev.Σ, 3), _b(traj_prev.Σi, 3)
     xnew, xold, S = _b(xnew, 2), _b(xold, 2), _b(Σ_new, 3)
     m, n, T, B = Kn.shape
+    _kl_box("kl_div_wiki", n, m, wide)
     kld = np.zeros((T, B), order="F"); mean = np.zeros(B)
-    _lib.check(_lib.lib().ddp_kl_div_f64(h.raw, n, m, T, B, *map(_lib.ptr, (xnew, xold, S, Kn, kn, Sn, Kp, kp, Sp, Sip, kld, mean))))
+    with _wide(h, wide):
+        _lib.check(_lib.lib().ddp_kl_div_f64(h.raw, n, m, T, B, *map(_lib.ptr, (xnew, xold, S, Kn, kn, Sn, Kp, kp, Sp, Sip, kld, mean))))
     return (kld, mean) if batched else (kld[:, 0], mean[0])
 
 
-def kl_div_wiki(xnew, xold, Σ_new, traj_new, traj_prev, *, handle=None):
+def kl_div_wiki(xnew, xold, Σ_new, traj_new, traj_prev, *, handle=None, wide=False):
     """``kl_div_wiki`` (klutils.jl:70-103): the clipped per-step divergences; ``Inf`` when a logdet throws (unbatched call)"""
-    kld, mean = _kl_div(xnew, xold, Σ_new, traj_new, traj_prev, handle)
+    kld, mean = _kl_div(xnew, xold, Σ_new, traj_new, traj_prev, handle, wide)
     if np.ndim(mean) == 0 and np.isinf(mean) and np.all(np.isfinite(kld)):
         return np.inf
     return kld
@@ -151,11 +189,11 @@ def geom(ηbracket):
     return np.sqrt(ηbracket[0] * ηbracket[2])                                             # klutils.jl:154-155
 
 
-def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, handle=None, _mean=None):
+def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, handle=None, _mean=None, wide=False):
     """scalar-``kl_step`` method (klutils.jl:112-133): returns ``(ηbracket, satisfied, divergence)``; mutates ``ηbracket``"""
     if not kl_step > 0:
         return ηbracket, True, 0
-    divergence = _kl_div(xnew, xold, sigmanew, traj_new, traj_prev, handle)[1] if _mean is None else _mean
+    divergence = _kl_div(xnew, xold, sigmanew, traj_new, traj_prev, handle, wide)[1] if _mean is None else _mean
     viol = divergence - kl_step
     satisfied = abs(viol) < 0.1 * kl_step
     if not satisfied:
@@ -169,7 +207,7 @@ def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, ha
 
 
 def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50, cost=None, ηbracket=(1e-8, 1.0, 1e16),
-           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None):
+           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False):
     """``iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step, lims, max_iter, cost, ηbracket, del0)`` with a registered
     ``problem`` or a ``DeviceProblem`` (the user's closures as device source; ``params`` as in ``iLQG``) standing in for the three
     closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the pre-rolled trajectory (the reference errors otherwise,
@@ -177,7 +215,8 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     linearisation (the fx of STEP 1).
     Returns ``(x, u, traj_new, Vx, Vxx, cost, trace)``; ``trace`` is a dict of per-trajectory arrays
     (status 1 SUCCESS :169 / 2 η > ηmax :174 / 3 max_iter :234, iter, η bracket, divergence, n_backpass).
-    The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead."""
+    The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead.
+    ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``."""
     if constrain_per_step:
         raise NotImplementedError("constrain_per_step (iLQGkl.jl:180-232) is not offloaded")
     if isinstance(problem, DeviceProblem) and problem.second_order:
@@ -194,6 +233,7 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     m = u.shape[0]
     if x.shape[1] != u.shape[1]:
         raise ValueError("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")            # :72
+    _kl_box("iLQGkl", n, m, wide)
     prev0 = GaussianPolicy(N, n, m, _b(traj_prev.K, 3), np.zeros_like(u), _b(traj_prev.Σ, 3), _b(traj_prev.Σi, 3))   # k *= 0 (:51)
     user = isinstance(problem, DeviceProblem)
     prm = _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched) if user else None
@@ -202,7 +242,16 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     del0 = np.full(B, float(del0))
     import os as _os
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
-        return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm)
+        with _wide(h, wide):
+            return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm)
+    with _wide(h, wide):
+        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide)
+
+
+def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide):
+    """DDP_KL_HOSTLOOP=1 (the body of iLQGkl on host arrays)"""
+    n, N, B = x.shape
+    m = u.shape[0]
     # ---- DDP_KL_HOSTLOOP=1: the loop of the reference on host arrays, one library call per array operation (cross-check in the tests)
     # STEP 1 (:86): the KL demos hand 3-D arrays to back_pass_gps (demo_linear.jl:91-101)
     if user:
@@ -216,7 +265,7 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
         dynb = bool(getattr(problem, "dyn_batched", False))
         fx, fu = _tv(fx, N, dynb), _tv(fu, N, dynb)
         cxx, cxu, cuu = _tv(cxx, N), _tv(cxu, N), _tv(cuu, N)
-    kl = grad_kl(prev0, handle=h)                                                                               # :90
+    kl = grad_kl(prev0, handle=h, wide=wide)                                                                    # :90
     status = np.zeros(B, dtype=int); iters = np.zeros(B, dtype=int); nback = np.zeros(B, dtype=int)
     divergence = np.zeros(B); satisfied = np.zeros(B, dtype=bool)
     live = np.ones(B, dtype=bool)
@@ -238,7 +287,7 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
             div, pol, Vx, Vxx, dV = back_pass_gps(sub(cx), sub(cu), cxx if cxx.ndim == 3 else sub(cxx), cxu if cxu.ndim == 3 else sub(cxu),
                                                   cuu if cuu.ndim == 3 else sub(cuu), fx if fx.ndim == 3 else sub(fx),
                                                   fu if fu.ndim == 3 else sub(fu), lims, sub(x), sub(u),
-                                                  (tuple(sub(a) for a in kl), etab[:, pend]), handle=h)
+                                                  (tuple(sub(a) for a in kl), etab[:, pend]), handle=h, wide=wide)
             nback[pend] += 1
             good = div == 0
             got = (pol.K, pol.k, pol.Σ, pol.Σi, Vx, Vxx, dV)
@@ -264,9 +313,9 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
         xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h)                  # :132
         del pb                                                 # (a DeviceProblem slice frees its compiled-problem pointer here)
         mdl = Model(model.fx if (np.ndim(model.fx) == 3 or allB) else model.fx[..., idx], model.fu, model.R1)
-        sig = forward_covariance(mdl, xs, sel(u), new, handle=h)                                                # :133
+        sig = forward_covariance(mdl, xs, sel(u), new, handle=h, wide=wide)                                     # :133
         pv = prev0 if allB else GaussianPolicy(N, n, m, sel(prev0.K), sel(prev0.k), sel(prev0.Σ), sel(prev0.Σi))
-        _, mean = _kl_div(xnew, xs, sig, new, pv, h)
+        _, mean = _kl_div(xnew, xs, sig, new, pv, h, wide)
         if out is None:
             out = dict(x=np.zeros((n, N, B)), u=np.zeros((m, N, B)), K=np.zeros((m, n, N, B)), S=np.zeros((m, m, N, B)),
                        Si=np.zeros((m, m, N, B)), Vx=np.zeros((n, N, B)), Vxx=np.zeros((n, n, N, B)), cost=np.zeros((cnew.shape[0], B)),
@@ -393,13 +442,14 @@ class _SubProblem:
         return p
 
 
-def demo_linear_kl(*, kl_step=1.0, rng=None, T=1000, n=10, m=2, h=0.01, outer=5, R1=None, handle=None, **kwargs):
+def demo_linear_kl(*, kl_step=1.0, rng=None, T=1000, n=10, m=2, h=0.01, outer=5, R1=None, handle=None, wide=False, **kwargs):
     """``demo_linear_kl(;kwargs...)`` (src/demo_linear.jl:63-136): the random LTI problem of ``demo_linear``, a rollout of the random
     initial controls, the exact model ``SimpleLTVModel(repeat(A), repeat(B))`` and five outer calls of ``iLQGkl`` starting from the
     identity policy ``GaussianPolicy(Float64,T,n,m)`` (k = 0, quirk Q20).  ``R1`` is what ``covariance(model,x,u)`` of the un-vendored
     LinearTimeVaryingModelsBase would return for that model — unknown here, default 1e-3·I (it only enters Σ of the state)."""
     import scipy.linalg as _sla
     from . import LQProblem, forward_pass
+    _kl_box("demo_linear_kl", n, m, wide)
     rng = rng if rng is not None else np.random.default_rng()
     A0 = rng.standard_normal((n, n))
     A = _sla.expm(h * (A0 - A0.T))
@@ -416,7 +466,7 @@ def demo_linear_kl(*, kl_step=1.0, rng=None, T=1000, n=10, m=2, h=0.01, outer=5,
     outercosts = np.zeros(outer)
     for it in range(outer):
         cost0 = 0.5 * np.sum(x * (Q @ x)) + 0.5 * np.sum(u * (R @ u))                              # :122
-        out = iLQGkl(prob, x, traj, model, kl_step=kl_step, cost=cost0, handle=handle, **kwargs)
+        out = iLQGkl(prob, x, traj, model, kl_step=kl_step, cost=cost0, handle=handle, wide=wide, **kwargs)
         x, u, traj = out[0], out[1], out[2]
         outercosts[it] = float(np.sum(out[5]))
     out[6]["outercosts"] = outercosts

@@ -106,8 +106,9 @@ typedef struct {
  *          8 < m <= 32 with any n <= 64: back_pass_wide_kernel, one work-group of four waves per trajectory, run-time sizes, every
  *          operand layout, limits by a box-QP across the lanes of a wave; operands are read from the caller's arrays (no padded
  *          copies, no scratch on the handle).  n > 64 or m > 32: return code < 0.
- *          back_pass_gps: n <= 32, m <= DDP_MAX_M.  User problems (ddp_user_*), the KL functions and the lane-per-problem boxQP
- *          stop at m = DDP_MAX_M.                                                                                          */
+ *          back_pass_gps and the KL functions: n <= 32, m <= DDP_MAX_M; after ddp_kl_set_wide(h, 1) any n <= 64 with
+ *          m <= DDP_MAX_M_WIDE (the KL section below).  User problems (ddp_user_*) without DDP_USER_WAVE and the lane-per-problem
+ *          boxQP stop at m = DDP_MAX_M.                                                                                    */
 int ddp_back_pass_f64_dev(ddp_handle h, const ddp_bp_desc *d,
                           const double *cx, const double *cu, const double *cxx, const double *cxu,
                           const double *cuu, const double *fx, const double *fu,
@@ -350,7 +351,17 @@ int ddp_costfun_f64_dev(ddp_handle h, const ddp_problem *p, const double *x, con
  * reference: back_pass_gps src/backward_pass.jl:259-350 (called from src/iLQGkl.jl:100,191), ∇kl and kl_div_wiki
  * src/klutils.jl:8-23,70-103, forward_covariance src/forward_pass.jl:37-56, calc_η src/klutils.jl:112-133 (ddp_kl_dual_*).
  * `df(model,·)` / `covariance(model,·)` belong to the un-vendored dependency LinearTimeVaryingModelsBase: the model is
- * passed as the arrays it would return (fx, R1).                                                                 */
+ * passed as the arrays it would return (fx, R1).
+ * shapes : 1 <= n <= 32, 1 <= m <= DDP_MAX_M (8) for every call of this section.  ddp_kl_set_wide(h, 1) opens 1 <= n <= 64,
+ *          1 <= m <= DDP_MAX_M_WIDE (32) for ddp_kl_terms_*, ddp_back_pass_gps_*, ddp_forward_covariance_*, ddp_kl_div_*,
+ *          ddp_ilqgkl_* (DDP_PROBLEM_LQ) and ddp_user_ilqgkl_* (problems made with DDP_USER_WAVE; DDP_USER_SECOND_ORDER stays
+ *          refused).  Shapes beyond n <= 32, m <= 8 then run on kernels of their own: back_pass_gps on the GPS instantiation of
+ *          back_pass_wide_kernel (ddp_last_kernel(h, 0) reports "back_pass_gps_wide"; Quui by Gauss-Jordan elimination across the
+ *          lanes of a wave), ∇kl, forward_covariance (v_mfma_f64_16x16x4 tiles, up to 136 KB of LDS) and kl_div_wiki (both
+ *          log-determinants by LU across lanes, klmean by a fixed-order sum: two runs agree bit for bit) on those of kl_wide.hip.
+ *          Shapes with n <= 32 and m <= 8 keep the kernels they had.  n > 64 or m > 32: return code < 0 before any launch, and so
+ *          for n > 32 or m > 8 while the switch is off.  DDP_GPS_WIDE=1 in the environment (read at ddp_create / ddp_reload_env)
+ *          sends every shape to the wide kernels (A/B timing, tests).                                                  */
 typedef struct {
     const double *cx, *cu;       /* cxkl[n,N,B], cukl[m,N,B]                                                     */
     const double *cxx, *cxu;     /* cxxkl[n,n,N,B], cxukl[m,n,N,B]  (m x n, the layout ∇kl returns, klutils.jl:20) */
@@ -358,6 +369,10 @@ typedef struct {
     const double *eta;           /* eta_tv == 0: η[B] (ηbracket[2] per trajectory); 1: η[N,B] (ηbracket[2,i])     */
     int eta_tv;
 } ddp_kl_cost_terms;
+
+/* The switch of the handle for the large shapes (default 0: every call of this section does what it always did).  Returns the
+ * previous value (0 or 1), < 0 for a null handle.                                                                   */
+int ddp_kl_set_wide(ddp_handle h, int on);
 
 /* ∇kl(traj_prev): K[m,n,N,B], k[m,N,B], Sigmai[m,m,N,B] -> the five arrays of ddp_kl_cost_terms (outputs)      */
 int ddp_kl_terms_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *K, const double *k, const double *Sigmai,
@@ -367,7 +382,8 @@ int ddp_kl_terms_f64(ddp_handle h, int n, int m, int N, int B, const double *K, 
 
 /* back_pass_gps: d->fx_tv and d->cost_tv must be 1 (3-D arrays, as the reference's method signature), regType unused.
  * Outputs as ddp_back_pass plus Quui[m,m,N,B] = inv(Quu_i) (the Σ field of the returned GaussianPolicy); Quu is the
- * KL-augmented, symmetrised matrix (the Σi field).  n <= 32, m <= 8.                                              */
+ * KL-augmented, symmetrised matrix (the Σi field).  n <= 32, m <= 8; with ddp_kl_set_wide n <= 64, m <= 32, where the
+ * layout flags of d are all honoured (fx_tv, cost_tv may be 0).                                                   */
 int ddp_back_pass_gps_f64_dev(ddp_handle h, const ddp_bp_desc *d,
                               const double *cx, const double *cu, const double *cxx, const double *cxu, const double *cuu,
                               const double *fx, const double *fu, const ddp_kl_cost_terms *kl,
@@ -541,8 +557,8 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  *   ddp_user_hessians       cost_hessians writes straight into cxx, cxu, cuu in memory.
  * The flag is legal at every shape (n <= 32, m <= 8 included: the same arithmetic on the other kernels) and with DDP_USER_TERMINAL,
  * DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF and DDP_USER_PLANT.  DDP_USER_SECOND_ORDER | DDP_USER_WAVE is refused (ddp_user_back_pass2
- * is sized for n <= 32, m <= 8), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch (back_pass_gps has no
- * kernel there).  diff_wrap names coordinates below 32 only.  The backward pass of a solve is the one ddp_back_pass_f64 chooses for
+ * is sized for n <= 32, m <= 8), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch unless the handle's
+ * ddp_kl_set_wide switch is on (back_pass_gps has no kernel there otherwise).  diff_wrap names coordinates below 32 only.  The backward pass of a solve is the one ddp_back_pass_f64 chooses for
  * the shape (32 < n <= 64, m <= 8: the MFMA kernels; m > 8: back_pass_wide).  user_examples/chain_ad.hip is a model with 7 parameters
  * at every size.  A problem without the flag compiles the text it always did and refuses n > 32, m > 8. */
 #define DDP_MAX_N_USER 32
