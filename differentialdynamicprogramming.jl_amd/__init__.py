@@ -162,7 +162,8 @@ def example_source(name):
     model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``; ``"car_plant"``: the car with a plant for the
     closed loop (``plant=True``); ``"bicycle_ad"``: a kinematic bicycle whose dynamics have mixed and control curvature, for
     ``second_order=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
-    for ``wave=True``."""
+    for ``wave=True``; ``"chain_ddp_ad"``: the same chain with the torque entering as ``g tanh(u_j) cos(q_j)`` (curvature in x, u
+    and mixed; ``n = 2 m``, 8 parameters), for ``second_order_wave=True``."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -181,16 +182,21 @@ class DeviceProblem:
     ``wave=True`` (DDP_USER_WAVE): large problems, ``n <= 64`` and ``m <= 32`` (without it ``n <= 32``, ``m <= 8``): the rollout runs on a
     group of lanes per rollout (``ddp_user_rollout_wave``) and, with ``autodiff=True``, df on one wave per time step and trajectory
     (``ddp_user_df_wave``).  Legal at every shape; not with ``second_order=True``; ``iLQGkl`` takes such a problem up to ``n = 32``,
-    ``m = 8``."""
+    ``m = 8``.  ``second_order_wave=True`` (DDP_USER_SECOND_ORDER_WAVE, implies ``wave=True``, needs ``autodiff=True``): full DDP at the
+    shapes of ``wave=True`` — the backward pass is ``ddp_user_back_pass2_wave``, the step of the wide-control kernel (four waves per
+    trajectory) with the curvature phase in front of it; accepted wherever a ``second_order=True`` problem is (``vhess``,
+    ``back_pass_ddp``, ``iLQG``, ``iLQG_queue``, ``iLQG_mpc``), refused by ``iLQGkl``; not together with ``second_order=True``."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False):
-        self.second_order, self.wave = bool(second_order), bool(wave)
+                 second_order=False, wave=False, second_order_wave=False):
+        self.second_order_wave = bool(second_order_wave)
+        self.second_order, self.wave = bool(second_order), bool(wave) or self.second_order_wave
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
-                      (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0))
+                      (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
+                      (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -569,7 +575,7 @@ def _user_df(problem, x, u, *, handle=None, params=None):
 
 def vhess(problem, x, u, v, *, handle=None, params=None):
     """``H[n+m, n+m, N(, B)] = Σ_k v[k, i] ∂²f_k/∂z∂z`` at ``(x[:, i], u[:, i], i)``, ``z = [x; u]``, of a ``DeviceProblem`` made with
-    ``second_order=True``: the ``vectens(v, fxx)`` / ``fxu`` / ``fuu`` blocks of backward_pass.jl:106-123 without the tensors,
+    ``second_order=True`` or ``second_order_wave=True``: the ``vectens(v, fxx)`` / ``fxu`` / ``fuu`` blocks of backward_pass.jl:106-123 without the tensors,
     exactly symmetric."""
     if not isinstance(problem, DeviceProblem):
         raise TypeError("vhess: a DeviceProblem is needed")
@@ -585,8 +591,8 @@ def vhess(problem, x, u, v, *, handle=None, params=None):
 
 
 def back_pass_ddp(problem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, u, *, handle=None, params=None):
-    """The second-order backward pass (backward_pass.jl:81-160) of a ``DeviceProblem`` made with ``second_order=True``: arguments as
-    ``back_pass`` with the arrays ``df(problem, x, u)`` returns (time-varying, a trailing batch axis with a batched ``u``; with
+    """The second-order backward pass (backward_pass.jl:81-160) of a ``DeviceProblem`` made with ``second_order=True`` or
+    ``second_order_wave=True`` (n <= 64, m <= 32, ``ddp_user_back_pass2_wave``): arguments as ``back_pass`` with the arrays ``df(problem, x, u)`` returns (time-varying, a trailing batch axis with a batched ``u``; with
     ``const_hessian`` the Hessians carry no time axis), the curvature terms derived on the device at ``(x, u)``.  Returns what
     ``back_pass`` returns: ``(diverge, GaussianPolicy, Vx, Vxx, dV)``."""
     if not isinstance(problem, DeviceProblem):

@@ -76,6 +76,7 @@ class ILQGKLOpts(C.Structure):
 
 ILQGKL_NSTATS = 12
 USER_WAVE = 32                 # DDP_USER_WAVE: the flag of DeviceProblem(..., wave=True)
+USER_SECOND_ORDER_WAVE = 128   # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(..., second_order_wave=True); 64 is not assigned
 MAX_N_USER_WAVE = 64           # DDP_MAX_N_USER_WAVE: n of a user problem with the flag (m <= 32)
 
 _lib = None

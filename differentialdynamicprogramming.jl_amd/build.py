@@ -33,12 +33,12 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_mf2_lims.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "kl_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "user_problem.hip": ["-I", OBJ]}                  # build/boxqp_dev_text.h (_boxqp_text)
+               "user_problem.hip": ["-I", OBJ]}                  # build/boxqp_dev_text.h (_boxqp_text), build/wide_kernel_text.h (_wide_text)
 
 
-EXTRA_DEPS = {"user_problem.hip": ["user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
+EXTRA_DEPS = {"user_problem.hip": ["user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "wide_tile.h", "back_pass_wide_kernel.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
-              "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h"], "kl_wide.hip": ["wide_tile.h"]}
+              "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"]}
 
 
 def _boxqp_text():
@@ -51,6 +51,20 @@ def _boxqp_text():
     assert ')DDPQ"' not in body
     text = "// written by build.py from csrc/boxqp_dev.h\nstatic const char *kBoxqpDevText = R\"DDPQ(\n" + body + ")DDPQ\";\n"
     out = os.path.join(OBJ, "boxqp_dev_text.h")
+    if not os.path.exists(out) or open(out).read() != text:
+        open(out, "w").write(text)
+
+
+def _wide_text():
+    """csrc/wide_tile.h and csrc/back_pass_wide_kernel.h as program text -> build/wide_kernel_text.h (kWideTileText, kWideKernelText), the
+    same way: ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE) is the step of back_pass_wide.hip compiled by hiprtc, not a copy."""
+    text = "// written by build.py from csrc/wide_tile.h and csrc/back_pass_wide_kernel.h\n"
+    for name, header in (("kWideTileText", "wide_tile.h"), ("kWideKernelText", "back_pass_wide_kernel.h")):
+        src = open(os.path.join(CSRC, header)).read()
+        body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
+        assert ')DDPQ"' not in body
+        text += "static const char *%s = R\"DDPQ(\n" % name + body + ")DDPQ\";\n"
+    out = os.path.join(OBJ, "wide_kernel_text.h")
     if not os.path.exists(out) or open(out).read() != text:
         open(out, "w").write(text)
 
@@ -116,6 +130,7 @@ def build(force=False, verbose=True):
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
     _boxqp_text()
+    _wide_text()
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         results = list(ex.map(_compile, srcs))

@@ -17,9 +17,12 @@
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
+#include "back_pass_wide_kernel.h"   // BPWArgs, WLds, bpw_fill: the wide kernel's step, shared with ddp_user_back_pass2_wave
+#include "wide_kernel_text.h"    // kWideTileText, kWideKernelText: the texts of wide_tile.h and back_pass_wide_kernel.h (written by build.py)
 
 DDP_USER_ABI
 DDP_USER_ABI2
+DDP_USER_ABI3
 
 namespace {
 
@@ -134,8 +137,15 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE)) == 0,
               "user problem: unknown flags 0x%x", flags);
+    if (flags & DDP_USER_SECOND_ORDER_WAVE) {
+        DDP_CHECK(wave, "user problem: DDP_USER_SECOND_ORDER_WAVE needs DDP_USER_WAVE (ddp_user_back_pass2_wave is the wide kernel's step)");
+        DDP_CHECK(flags & DDP_USER_AUTODIFF, "user problem: DDP_USER_SECOND_ORDER_WAVE needs DDP_USER_AUTODIFF (the curvature of the dynamics is "
+                                             "derived from the templated model)");
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER), "user problem: DDP_USER_SECOND_ORDER_WAVE excludes DDP_USER_SECOND_ORDER (one backward pass "
+                                                    "per problem: ddp_user_back_pass2_wave or ddp_user_back_pass2)");
+    }
     DDP_CHECK(!(wave && (flags & DDP_USER_SECOND_ORDER)),
               "user problem: DDP_USER_SECOND_ORDER | DDP_USER_WAVE is refused (ddp_user_back_pass2 is sized for n <= %d, m <= %d)",
               DDP_MAX_N_USER, DDP_MAX_M);
@@ -210,7 +220,30 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += "\n#line 1 \"ddp_user_kernels2\"\n";
         s += DDP_USER_ABI2_TEXT;
         s += "\n";
-        s += kUserKernels2;
+        s += kUserKernels2Head;
+        s += kUserKernels2Bp2;
+        s += kUserKernels2Vhess;
+    }
+    if (flags & DDP_USER_SECOND_ORDER_WAVE) {                    // the wave program above, then the wide kernel's step and its curvature phase
+        s += "\n#define DDP_SECOND_ORDER 1\n#line 1 \"ddp_user_autodiff_vhess\"\n";
+        s += kUserAutodiffVhess;
+        s += "\n#line 1 \"ddp_boxqp_dev\"\n";
+        s += kUserRsqrt;
+        s += kBoxqpDevText;
+        s += "\n#line 1 \"ddp_wide_tile\"\n";
+        s += kUserWidePrelude;
+        s += kWideTileText;
+        s += "\n#line 1 \"ddp_back_pass_wide_kernel\"\n";
+        s += kWideKernelText;
+        s += "\n#line 1 \"ddp_user_kernels2\"\n";
+        s += DDP_USER_ABI2_TEXT;
+        s += "\n";
+        s += DDP_USER_ABI3_TEXT;
+        s += "\n";
+        s += kUserKernels2Head;
+        s += kUserKernels2Vhess;
+        s += "\n#line 1 \"ddp_user_kernels2_wave\"\n";
+        s += kUserKernels2Wave;
     }
     return s;
 }
@@ -276,6 +309,7 @@ int compile(const char *source, int n, int m, int nparam, int flags, unsigned wr
 struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
+    hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
     const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
     Layout L{};
@@ -292,6 +326,10 @@ struct UserProblem final : ddp_family {
     // per call (ddp_user_ilqg_*): the parameters
     const double *params = nullptr;
     int params_batched = 0;
+    // DDP_USER_SECOND_ORDER_WAVE: H_i of the step in flight, [n+m, n+m] per trajectory (ddp_user_back_pass2_wave); grown on demand
+    mutable double *curv = nullptr;
+    mutable size_t curv_bytes = 0;
+    ~UserProblem() override { if (curv) hipFree(curv); }
 
     int df(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx, double *fu,
            double *cx, double *cu, double *cxx, double *cxu, double *cuu) const override
@@ -361,7 +399,7 @@ struct UserProblem final : ddp_family {
     // DDP_USER_SECOND_ORDER: the backward pass with the curvature of the dynamics (ddp_user_back_pass2); c.x and c.map are read
     int back_pass(ddp_handle hh, const BPCall &c) const override
     {
-        DDP_CHECK(mod->bp2, "user problem: compiled without DDP_USER_SECOND_ORDER");
+        DDP_CHECK(mod->bp2 || mod->bp2w, "user problem: compiled without DDP_USER_SECOND_ORDER");
         const ddp_bp_desc &d = c.d;
         DDP_CHECK(d.n == n && d.m == m && d.N == N && d.B >= 1, "back_pass: sizes n=%d m=%d N=%d B=%d do not match the problem", d.n, d.m, d.N, d.B);
         DDP_CHECK(d.regType == 1 || d.regType == 2, "back_pass: regType must be 1 or 2 (got %d)", d.regType);
@@ -369,6 +407,21 @@ struct UserProblem final : ddp_family {
                   "back_pass: a second-order pass takes the derivative arrays as ddp_user_df writes them");
         DDP_CHECK(c.x && c.u, "back_pass: a second-order pass needs x and u");
         DDP_CHECK(!d.has_lims || c.lims, "back_pass: has_lims needs lims");
+        if (mod->bp2w) {                                         // DDP_USER_SECOND_ORDER_WAVE: the wide kernel's step, one work-group per trajectory
+            const size_t need = (size_t)(n + m) * (n + m) * sizeof(double) * (size_t)d.B;
+            if (need > curv_bytes) {
+                if (curv) { DDP_HIP(hipStreamSynchronize(hh->stream)); DDP_HIP(hipFree(curv)); curv = nullptr; curv_bytes = 0; }
+                DDP_HIP(hipMalloc((void **)&curv, need));
+                curv_bytes = need;
+            }
+            UserBp2WaveArgs w;
+            bpw_fill(w.w, c);
+            w.params = params; w.x = c.x; w.H = curv; w.map = c.map; w.params_batched = params_batched; w.pad_ = 0;
+            void *wargs[] = {&w};
+            DDP_HIP(hipModuleLaunchKernel(mod->bp2w, (unsigned)d.B, 1, 1, WT, 1, 1, 0, hh->stream, wargs, nullptr));
+            hh->last_kernel[0] = "ddp_user_back_pass2_wave";
+            return 0;
+        }
         UserBp2Args a;
         a.N = N; a.B = d.B; a.regType = d.regType; a.has_lims = d.has_lims; a.params_batched = params_batched; a.pad_ = 0;
         a.params = params; a.x = c.x; a.u = c.u; a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu;
@@ -493,7 +546,10 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
                         (!(flags & DDP_USER_CONST_HESSIAN) || hipModuleGetFunction(&M.hess, M.mod, "ddp_user_hessians") == hipSuccess) &&
                         (!(flags & DDP_USER_PLANT) || hipModuleGetFunction(&M.plant, M.mod, "ddp_user_plant") == hipSuccess) &&
                         (!(flags & DDP_USER_SECOND_ORDER) || (hipModuleGetFunction(&M.bp2, M.mod, "ddp_user_back_pass2") == hipSuccess &&
-                                                              hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess));
+                                                              hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess)) &&
+                        (!(flags & DDP_USER_SECOND_ORDER_WAVE) ||
+                         (hipModuleGetFunction(&M.bp2w, M.mod, "ddp_user_back_pass2_wave") == hipSuccess &&
+                          hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess));
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -504,7 +560,7 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
     UserProblem *P = new UserProblem();
     P->h = h; P->n = n; P->m = m; P->N = 0; P->B = 0; P->CL = 0; P->const_hessian = (flags & DDP_USER_CONST_HESSIAN) != 0;
     P->has_plant = false;                                        // set by the closed-loop entry points only
-    P->second_order = (flags & DDP_USER_SECOND_ORDER) != 0;
+    P->second_order = (flags & (DDP_USER_SECOND_ORDER | DDP_USER_SECOND_ORDER_WAVE)) != 0;
     P->nparam = nparam; P->flags = flags; P->wrap = wrap; P->mod = &it->second;
     *out = P;
     return 0;

@@ -19,6 +19,8 @@
 //                      ended (xcl[:, t+1], and the next solve's initial state).
 // DDP_USER_WAVE (n <= 64, m <= 32): ddp_user_rollout_wave, ddp_user_df_wave and the direct-store ddp_user_df / ddp_user_hessians of
 // user_problem_wave_kernels.h take the place of the rollout, derivative and Hessian kernels here; ddp_user_cost and ddp_user_plant stay.
+// DDP_USER_SECOND_ORDER / DDP_USER_SECOND_ORDER_WAVE append a backward pass with the curvature of the dynamics (ddp_user_back_pass2, one
+// wave per trajectory, n <= 32, m <= 8; ddp_user_back_pass2_wave, the wide kernel's step, n <= 64, m <= 32) and ddp_user_vhess: below.
 #pragma once
 
 // argument structs of the kernels: compiled into the host library and, as text (DDP_USER_ABI_TEXT), into every user program.
@@ -383,7 +385,9 @@ __device__ __forceinline__ double ddp_rsqrt(double x)
 }
 )DDPK";
 
-static const char *kUserKernels2 = R"DDPK(
+// kUserKernels2 in three pieces: a DDP_USER_SECOND_ORDER problem compiles Head + Bp2 + Vhess (the same bytes as ever), one with
+// DDP_USER_SECOND_ORDER_WAVE Head + Vhess (the static_assert of ddp_user_back_pass2 on 64 KB fails at its shapes) + kUserKernels2Wave
+static const char *kUserKernels2Head = R"DDPK(
 #if DDP_SECOND_ORDER
 #define DDP_NZ (DDP_N + DDP_M)
 #define DDP_NPAIR (DDP_NZ * (DDP_NZ + 1) / 2)
@@ -411,7 +415,9 @@ __device__ __forceinline__ void ddp_tri(int e, int &i, int &j)
     i = e - c * (c + 1) / 2;
 }
 
-extern "C" __global__ __launch_bounds__(64) void ddp_user_back_pass2(UserBp2Args a)
+)DDPK";
+
+static const char *kUserKernels2Bp2 = R"DDPK(extern "C" __global__ __launch_bounds__(64) void ddp_user_back_pass2(UserBp2Args a)
 {
     constexpr int n = DDP_N, m = DDP_M, p = DDP_NZ, TC = DDP_TC, HS = DDP_CONST_HESSIAN ? 0 : 1;
     constexpr int nn = n * n, nm = n * m, mm = m * m, ntri = n * (n + 1) / 2;
@@ -760,7 +766,9 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_back_pass2(UserBp2Args
     if (lane == 0) a.diverge[b] = diverge;
 }
 
-extern "C" __global__ __launch_bounds__(64) void ddp_user_vhess(UserVhessArgs a)
+)DDPK";
+
+static const char *kUserKernels2Vhess = R"DDPK(extern "C" __global__ __launch_bounds__(64) void ddp_user_vhess(UserVhessArgs a)
 {
     constexpr int n = DDP_N, m = DDP_M, nz = DDP_NZ;
     const long total = (long)DDP_NPAIR * a.N * a.B, g = (long)blockIdx.x * 64 + threadIdx.x;
@@ -782,4 +790,79 @@ extern "C" __global__ __launch_bounds__(64) void ddp_user_vhess(UserVhessArgs a)
     H[pb + nz * pa] = hv;
 }
 #endif
+)DDPK";
+
+// ---- DDP_USER_SECOND_ORDER_WAVE: full DDP at the shapes of DDP_USER_WAVE.  The program is that of a wave problem, then DDP_SECOND_ORDER 1,
+// kUserAutodiffVhess, ddp_rsqrt + the text of boxqp_dev.h, kUserWidePrelude, the texts of wide_tile.h and back_pass_wide_kernel.h
+// (written by build.py: one definition of the wide kernel's step, its Cholesky and its box-QP for both compilers), DDP_USER_ABI2 and
+// DDP_USER_ABI3, kUserKernels2Head + Vhess, kUserKernels2Wave.
+//
+//   ddp_user_back_pass2_wave  back_pass_wide_body of back_pass_wide_kernel.h with n, m as constants: one work-group of four waves per
+//                             trajectory, P1-P4 on v_mfma_f64_16x16x4, the step in a static LDS array (at most 160 KB, a static_assert).
+//                             P0 in front of P1: the (n+m)(n+m+1)/2 pairs a <= b are dealt over the 256 threads, each thread calls
+//                             ddp_ad_vhess for its pairs (every thread runs the model the same number of times, with a clamped pair
+//                             where it has none: no thread leaves the phase early) and stores the value at (a, b) and (b, a) of the
+//                             trajectory's [n+m, n+m] scratch in global memory (the step's LDS is full at (64, 32)); the barrier that
+//                             ends P1 orders the stores before the reads of P2, which adds the entries to the cost Hessians where the
+//                             accumulators start.  x_i, u_i are read from the caller's arrays, Vx_{i+1} from the LDS.
+#define DDP_USER_ABI3                                                                                                                 \
+    struct UserBp2WaveArgs {                                                                                                         \
+        BPWArgs w;                                                                                                                   \
+        const double *params, *x;                                                                                                    \
+        double *H;                                                                                                                   \
+        const int *map;                                                                                                              \
+        int params_batched, pad_;                                                                                                    \
+    };
+#define DDP_USER_ABI3_TEXT DDP_USER_STR(DDP_USER_ABI3)
+
+// what back_pass_wide_kernel.h and wide_tile.h take from ddp_internal.h and ddp_amd.h (which hiprtc cannot include)
+#define DDP_USER_WIDE_PRELUDE_TEXT                                                                                                    \
+    "\ntypedef int int32_t;\n#define DDP_MAX_M_WIDE " DDP_USER_STR(DDP_MAX_M_WIDE) "\n"                                               \
+    "__device__ __forceinline__ void wave_sync()\n{\n"                                                                               \
+    "    __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\");\n    __builtin_amdgcn_wave_barrier();\n"                           \
+    "    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");\n}\n"
+static const char *kUserWidePrelude = DDP_USER_WIDE_PRELUDE_TEXT;
+
+static const char *kUserKernels2Wave = R"DDPK(
+struct ddp_bp2_wave_curv {
+#ifdef DDP_BP2_NO_CURVATURE                                   // (a source that defines it: the pass without P0, for bench/user_second_order_wave.py)
+    static constexpr bool on = false;
+#else
+    static constexpr bool on = true;
+#endif
+    double *H;                                                   // [n+m, n+m] of this trajectory
+    const double *x, *u, *pp;                                    // x[n, N], u[m, N] of this trajectory, its parameters
+    __device__ __forceinline__ void p0(int i, const double *vs, int t) const
+    {
+        constexpr int n = DDP_N, m = DDP_M, p = DDP_NZ;
+#pragma unroll 1
+        for (int e0 = 0; e0 < DDP_NPAIR; e0 += 256) {            // one call site: (a, b) and (b, a) are one number
+            const int e = e0 + t;
+            const bool mine = e < DDP_NPAIR;
+            int pa, pb;
+            ddp_tri(mine ? e : 0, pa, pb);
+            const double hv = ddp_ad_vhess(x + (size_t)n * i, u + (size_t)m * i, i, pp, vs, pa, pb);
+            if (mine) {
+                H[pa + p * pb] = hv;
+                H[pb + p * pa] = hv;
+            }
+        }
+    }
+    __device__ __forceinline__ double h(int a, int b) const { return H[a + DDP_NZ * b]; }
+};
+
+extern "C" __global__ __launch_bounds__(256) void ddp_user_back_pass2_wave(UserBp2WaveArgs a)
+{
+    constexpr int n = DDP_N, m = DDP_M;
+    constexpr WLds L(n, m);
+    static_assert(L.total * 8 <= 160 * 1024, "ddp_user_back_pass2_wave: the step does not fit 160 KB of LDS");
+    __shared__ double lds[L.total];
+    const int b = blockIdx.x;
+    ddp_bp2_wave_curv c;
+    c.H = a.H + (size_t)DDP_NZ * DDP_NZ * b;
+    c.x = a.x + (size_t)n * a.w.N * b;
+    c.u = a.w.u + (size_t)m * a.w.N * b;
+    c.pp = ddp_params(a.params, a.params_batched, a.map, b);
+    back_pass_wide_body<false, n, m>(a.w, lds, c);
+}
 )DDPK";

@@ -546,6 +546,7 @@ const _installed = Method[]            # the methods `install!` added (what `uni
 const MAX_N = 64                       # include/ddp_amd.h: the backward kernels take n <= 64, m <= 32
 const MAX_M = 8                        # DDP_MAX_M: user problems, the KL functions, the lane-per-problem boxQP
 const MAX_N_USER_WAVE = 64             # DDP_MAX_N_USER_WAVE: user problems made with wave=true (n <= 64, m <= MAX_M_WIDE)
+const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
 # What the GPU methods accept: dense Float64 arrays (and the `Diagonal` / vector cost terms of the reference's demos).  Everything else —
@@ -956,7 +957,7 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
 end
 
 # ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
-# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant, second_order, wave) holds the source; it is compiled with hiprtc
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant, second_order, wave, second_order_wave) holds the source; it is compiled with hiprtc
 # for the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
 # autodiff=true (DDP_USER_AUTODIFF): dynamics / stage_cost / terminal_cost are templates over the scalar type of x and u, the source
 # needs no `derivatives`, and df is derived on the device by forward-mode AD.
@@ -965,6 +966,9 @@ end
 # pass (backward_pass.jl:81-160), the curvature of the dynamics derived on the device; vhess and back_pass_ddp are its array-level pieces.
 # wave=true (DDP_USER_WAVE): large problems, n <= MAX_N_USER_WAVE and m <= MAX_M_WIDE (without it n <= 32, m <= MAX_M); the rollout runs on a
 # group of lanes per rollout, df (with autodiff=true) on one wave per step and trajectory.  Not with second_order=true.
+# second_order_wave=true (DDP_USER_SECOND_ORDER_WAVE, implies wave=true, needs autodiff=true): full DDP at the shapes of wave=true; the
+# backward pass is ddp_user_back_pass2_wave (the wide-control kernel's step with the curvature phase in front of it).  Accepted wherever a
+# second_order=true problem is, refused by iLQGkl; not together with second_order=true.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -976,9 +980,12 @@ mutable struct DeviceProblem
     made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
-                       const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false)
+                       const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
+                       second_order_wave::Bool=false)
     wrap = Int(_diff_mask(diff, n))
-    flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0)
+    wave = wave || second_order_wave
+    flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
+            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}())
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1055,7 +1062,7 @@ function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), param
     return fx, fu, Float64[], Float64[], Float64[], cx, cu, cxx, cxu, cuu
 end
 
-# vhess(problem, x, u, v) -> H[n+m, n+m, N(, B)] = Σ_k v[k, i] ∂²f_k/∂z∂z at (x[:, i], u[:, i]), z = [x; u] (second_order=true problems)
+# vhess(problem, x, u, v) -> H[n+m, n+m, N(, B)] = Σ_k v[k, i] ∂²f_k/∂z∂z at (x[:, i], u[:, i]), z = [x; u] (second_order=true or second_order_wave=true problems)
 function vhess(problem::DeviceProblem, x, u, v; handle::Handle=default_handle(), params=nothing)
     batched = ndims(u) == 3
     m, N = size(u, 1), size(u, 2)

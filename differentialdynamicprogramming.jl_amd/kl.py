@@ -219,6 +219,9 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``."""
     if constrain_per_step:
         raise NotImplementedError("constrain_per_step (iLQGkl.jl:180-232) is not offloaded")
+    if isinstance(problem, DeviceProblem) and problem.second_order_wave:
+        raise DDPError("iLQGkl: a DeviceProblem made with second_order_wave=True is refused (back_pass_gps has no second-order variant); "
+                       "make the problem without the flag for the KL loop")
     if isinstance(problem, DeviceProblem) and problem.second_order:
         raise DDPError("iLQGkl: a DeviceProblem made with second_order=True is refused (back_pass_gps has no second-order variant); "
                        "make the problem without the flag for the KL loop")

@@ -108,7 +108,7 @@ typedef struct {
  *          copies, no scratch on the handle).  n > 64 or m > 32: return code < 0.
  *          back_pass_gps and the KL functions: n <= 32, m <= DDP_MAX_M; after ddp_kl_set_wide(h, 1) any n <= 64 with
  *          m <= DDP_MAX_M_WIDE (the KL section below).  User problems (ddp_user_*) without DDP_USER_WAVE and the lane-per-problem
- *          boxQP stop at m = DDP_MAX_M.                                                                                    */
+ *          boxQP stop at m = DDP_MAX_M; full DDP of a user problem beyond n = 32, m = 8 is DDP_USER_SECOND_ORDER_WAVE.                                                                                    */
 int ddp_back_pass_f64_dev(ddp_handle h, const ddp_bp_desc *d,
                           const double *cx, const double *cu, const double *cxx, const double *cxu,
                           const double *cuu, const double *fx, const double *fu,
@@ -354,8 +354,8 @@ int ddp_costfun_f64_dev(ddp_handle h, const ddp_problem *p, const double *x, con
  * passed as the arrays it would return (fx, R1).
  * shapes : 1 <= n <= 32, 1 <= m <= DDP_MAX_M (8) for every call of this section.  ddp_kl_set_wide(h, 1) opens 1 <= n <= 64,
  *          1 <= m <= DDP_MAX_M_WIDE (32) for ddp_kl_terms_*, ddp_back_pass_gps_*, ddp_forward_covariance_*, ddp_kl_div_*,
- *          ddp_ilqgkl_* (DDP_PROBLEM_LQ) and ddp_user_ilqgkl_* (problems made with DDP_USER_WAVE; DDP_USER_SECOND_ORDER stays
- *          refused).  Shapes beyond n <= 32, m <= 8 then run on kernels of their own: back_pass_gps on the GPS instantiation of
+ *          ddp_ilqgkl_* (DDP_PROBLEM_LQ) and ddp_user_ilqgkl_* (problems made with DDP_USER_WAVE; DDP_USER_SECOND_ORDER and
+ *          DDP_USER_SECOND_ORDER_WAVE stay refused).  Shapes beyond n <= 32, m <= 8 then run on kernels of their own: back_pass_gps on the GPS instantiation of
  *          back_pass_wide_kernel (ddp_last_kernel(h, 0) reports "back_pass_gps_wide"; Quui by Gauss-Jordan elimination across the
  *          lanes of a wave), ∇kl, forward_covariance (v_mfma_f64_16x16x4 tiles, up to 136 KB of LDS) and kl_div_wiki (both
  *          log-determinants by LU across lanes, klmean by a fixed-order sum: two runs agree bit for bit) on those of kl_wide.hip.
@@ -537,7 +537,20 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * The λ schedule, line search and exits of the driver are untouched: an indefinite QuuF is a `diverge` like any other.  No tensor is
  * formed: H_i is the Hessian of the scalar Vx_{i+1}·f(z), one call of `dynamics` per pair a <= b on a dual over a dual, inside the
  * recursion (kernel ddp_user_back_pass2, one wave per trajectory; ddp_last_kernel(h, 0)).  ddp_user_ilqgkl_* refuses such a problem
- * (back_pass_gps has no second-order variant).  A problem without the flag compiles and runs exactly as before.
+ * (back_pass_gps has no second-order variant).  A problem without the flag compiles and runs exactly as before.  Shapes: n <= 32,
+ * m <= 8 (the kernel holds the step in 64 KB of LDS); larger problems take DDP_USER_SECOND_ORDER_WAVE.
+ *
+ * DDP_USER_SECOND_ORDER_WAVE: the same full DDP at the shapes of DDP_USER_WAVE, 1 <= n <= 64 and 1 <= m <= 32.  It needs DDP_USER_WAVE
+ * and DDP_USER_AUTODIFF (each refused by name when missing) and excludes DDP_USER_SECOND_ORDER; it combines with DDP_USER_TERMINAL,
+ * DDP_USER_CONST_HESSIAN, DDP_USER_PLANT and diff_wrap as DDP_USER_WAVE does.  Semantics are those of DDP_USER_SECOND_ORDER to the
+ * letter (Hxx, Hux, Huu, the regularised variants, the tail, `diverge`, `active`, per-trajectory λ, lims[0] > lims[m] = no limits read on
+ * the device).  Kernel ddp_user_back_pass2_wave (ddp_last_kernel(h, 0)): the step of back_pass_wide — one work-group of four waves per
+ * trajectory, products on the fp64 matrix cores, Cholesky and box-QP across the lanes of a wave — compiled with n, m as constants, with
+ * the curvature phase in front of it: the (n+m)(n+m+1)/2 pairs dealt over the 256 threads, H_i handed to the products through an
+ * [n+m, n+m] scratch per trajectory that the problem owns (allocated at the first pass, freed by ddp_user_destroy).  ddp_user_vhess_*
+ * and ddp_user_back_pass_* take such a problem as they take a DDP_USER_SECOND_ORDER one (ddp_user_vhess unchanged); ddp_user_ilqgkl_*
+ * refuses it the same way, with ddp_kl_set_wide on or off.  user_examples/chain_ddp_ad.hip is a model with curvature in x and u at
+ * every m (n = 2 m, 8 parameters).  Bit 64 of the flags is not assigned and stays refused as unknown.
  *
  * DDP_USER_WAVE: large problems, 1 <= n <= DDP_MAX_N_USER_WAVE (64) and 1 <= m <= DDP_MAX_M_WIDE (32), the shapes the backward-pass
  * kernels hold.  The user's functions and the argument lists do not change; the library compiles other kernels around them, in which no
@@ -557,7 +570,7 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  *   ddp_user_hessians       cost_hessians writes straight into cxx, cxu, cuu in memory.
  * The flag is legal at every shape (n <= 32, m <= 8 included: the same arithmetic on the other kernels) and with DDP_USER_TERMINAL,
  * DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF and DDP_USER_PLANT.  DDP_USER_SECOND_ORDER | DDP_USER_WAVE is refused (ddp_user_back_pass2
- * is sized for n <= 32, m <= 8), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch unless the handle's
+ * is sized for n <= 32, m <= 8; full DDP at these shapes is DDP_USER_SECOND_ORDER_WAVE, above), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch unless the handle's
  * ddp_kl_set_wide switch is on (back_pass_gps has no kernel there otherwise).  diff_wrap names coordinates below 32 only.  The backward pass of a solve is the one ddp_back_pass_f64 chooses for
  * the shape (32 < n <= 64, m <= 8: the MFMA kernels; m > 8: back_pass_wide).  user_examples/chain_ad.hip is a model with 7 parameters
  * at every size.  A problem without the flag compiles the text it always did and refuses n > 32, m > 8. */
@@ -565,7 +578,7 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
-       DDP_USER_WAVE = 32 };
+       DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128 };      /* 64: not assigned, refused as unknown */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
@@ -580,7 +593,7 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
                         const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
 int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                     double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu);
-/* DDP_USER_SECOND_ORDER problems only.  vhess: x[n,N,B] u[m,N,B] v[n,N,B] -> H[n+m,n+m,N,B] = Σ_k v[k,i,b] ∂²f_k/∂z∂z at (x_i, u_i, i),
+/* DDP_USER_SECOND_ORDER and DDP_USER_SECOND_ORDER_WAVE problems only.  vhess: x[n,N,B] u[m,N,B] v[n,N,B] -> H[n+m,n+m,N,B] = Σ_k v[k,i,b] ∂²f_k/∂z∂z at (x_i, u_i, i),
  * exactly symmetric (kernel ddp_user_vhess, one lane per pair, step and trajectory): the `vectens` terms for a caller of the array API. */
 int ddp_user_vhess_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                            const double *v, const int32_t *active, double *H);
