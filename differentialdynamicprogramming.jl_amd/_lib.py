@@ -19,7 +19,7 @@ u8p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
 EXPORTS = [
-    "ddp_last_error", "ddp_version", "ddp_device_count", "ddp_create", "ddp_create_with_stream", "ddp_destroy", "ddp_sync", "ddp_reload_env", "ddp_last_kernel", "ddp_sh_timeouts", "ddp_sh_timeout_info", "ddp_stream",
+    "ddp_last_error", "ddp_version", "ddp_device_count", "ddp_create", "ddp_create_with_stream", "ddp_destroy", "ddp_sync", "ddp_reload_env", "ddp_last_kernel", "ddp_sh_timeouts", "ddp_sh_timeout_info", "ddp_sh_reuse_stats", "ddp_stream",
     "ddp_malloc", "ddp_free", "ddp_memcpy_h2d", "ddp_memcpy_d2h", "ddp_memset", "ddp_host_alloc", "ddp_host_free", "ddp_host_trim",
     "ddp_event_create", "ddp_event_destroy", "ddp_event_record", "ddp_event_elapsed_ms",
     "ddp_back_pass_f64_dev", "ddp_back_pass_f64", "ddp_boxqp_f64_dev", "ddp_boxqp_f64",
@@ -251,6 +251,13 @@ class Handle:
         for d in recs:
             d["published_seen"] = d["progress_seen"] & ((1 << 24) - 1); d["finished_seen"] = bool(d["progress_seen"] & (1 << 30))
         return {"records": recs, "progress_now": [int(buf[64 + g]) for g in range(16)]}
+
+    def sh_reuse_stats(self):
+        """(hits, misses) of the shared-operand backward pass since its scratch was allocated: λ groups served from a record stream an
+        earlier call left behind / groups whose matrix recursion was computed (ddp_sh_reuse_stats)"""
+        buf = (C.c_int * 2)()
+        check(lib().ddp_sh_reuse_stats(self._h, buf))
+        return int(buf[0]), int(buf[1])
 
     def sync(self):
         check(lib().ddp_sync(self._h))

@@ -32,6 +32,14 @@
 // to the per-trajectory kernels through `fb_active` (the dispatcher launches them behind this kernel; with nothing to do they exit at once).
 // diverge / zero-fill (:37-38, :226-229) follow the group: QuuF not positive definite at step i stops the chain, the failing chunk is
 // published with zero records below the failing step, later chunks are written as zeros by the consumers.
+//
+// Reuse across calls: a group's record stream is a function of (fx, fu, cxx, cxu, cuu, N, regType, λ) and of nothing per trajectory, and
+// it outlives the launch in the handle's scratch.  The control block keeps a bit-exact copy of those operands and, per stream slot, the
+// λ it holds and whether it is complete.  sh_group_kernel compares the operands of EVERY call with the copy word by word (content, not
+// pointers: callers upload fresh buffers or change them in place); any difference empties every slot.  A group whose λ is in a complete
+// slot takes that slot with every chunk already published: its producer work-group returns at once and the tiles stream the records.
+// The other groups take the empty, then the least recently used slots (sh_slot_plan).  A slot becomes complete only when its publisher
+// has drained the last chunk of a chain that did not diverge.  DDP_SH_REUSE=0 (and DDP_TEST_SH_ABORT, -DSH_PROF) switch the reuse off.
 #include <stdlib.h>
 #include "ddp_internal.h"
 
@@ -94,13 +102,21 @@ enum { PF_CREADY = 0, PF_BDONE = 1, PF_BREADY = 2, PF_PDONE = 3, PF_CDIV = 4 };
 enum { CF_SREADY = 0, CF_KIND = 1 /* NSB */, CF_UDONE = 4 /* NAFF + NWR */ };
 static_assert(CF_UDONE + NAFF + NWR <= 32 && SH_THREADS <= 1024, "flag words, work-group size");
 
+constexpr int SH_NOPS = 244;                        // shared operand doubles: fx 100 | fu 20 | cxx 100 | cxu 20 | cuu 4
+enum { SH_REUSE_OFF = 0, SH_REUSE_FLUSH = 1, SH_REUSE_ON = 2 };       // ShArgs::reuse
+
 struct ShCtl {                                      // device-resident control block of a launch
     int ticket, G, W, nfb;
-    int error, errors_total, pad1, pad2;              // error: timed-out tiles of this launch; errors_total: since the block was allocated
-    int progress[SH_GMAX * 16];                     // chunks published by group g (| SH_FIN) at [16 g]: one 64-byte line each
-    int gdiverge[SH_GMAX];
-    int gcount[SH_GMAX], gstart[SH_GMAX];
-    double glam[SH_GMAX];
+    int error, errors_total, hitmask, pad2;         // error: timed-out tiles of this launch; errors_total: since the block was allocated; hitmask: groups (ordinals) of this launch whose stream was reused
+    int progress[SH_GMAX * 16];                     // chunks published to stream slot s (| SH_FIN) at [16 s]: one 64-byte line each
+    int gdiverge[SH_GMAX];                          // by slot
+    int gcount[SH_GMAX], gstart[SH_GMAX];           // by group ordinal
+    double glam[SH_GMAX];                           // by slot: the λ of the stream in it (the slot's key)
+    // the record streams kept across launches: whose operands they belong to (word SH_NOPS: N << 32 | regType), which slots hold a
+    // complete stream, the launch that last used each, the slot of each group of this launch, groups served from / computed into a slot
+    unsigned long long ops[SH_NOPS + 1];
+    int sstate[SH_GMAX], sused[SH_GMAX], gslot[SH_GMAX];
+    int hits, misses, pad5, pad6;
     unsigned long long prof[64];                    // -DSH_PROF: phase sums of group 0's chain wave + wall-clock marks (ddp_sh_prof)
     // the first SH_NDIAG tiles that gave up since the block was allocated (ddp_sh_timeout_info): which tile of which group waited for
     // which chunk, the progress word it last saw, for how long, on which XCD, with which ticket, in which launch
@@ -111,12 +127,13 @@ constexpr int SH_NDIAG = 8;
 
 struct ShArgs {
     int N, B, ncu, regType, wmax, test_abort;                   // wmax: the items[] capacity = the work-groups behind the SH_GMAX producers of the grid
+    int reuse;                                                  // SH_REUSE_OFF: no stream is kept or reused; _FLUSH: every slot counts as empty in this launch (the stream order of the handle was broken); _ON
     const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda;
     const int32_t *active;
     double *K, *k, *Quu, *Vx, *Vxx, *dV;
     int32_t *diverge;
     ShCtl *ctl;
-    int4 *items;                                    // (group, first position in perm, trajectories, 0)
+    int4 *items;                                    // (group, first position in perm, trajectories, stream slot of the group)
     int *perm;
     int32_t *fb_active;
     double *sink;                                   // 4 KB that lanes without a result may write (the handle's)
@@ -154,6 +171,48 @@ __device__ __forceinline__ void store16_res(void *p, d2 v)
     else asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// ============================================================ stream slots ====================================================
+// Which stream slot each of the G groups of a launch takes.  skey / sstate / sused: per slot the λ bits of its stream, 1 = complete
+// (0 = empty) and the launch number of its last use; gkey: the λ bits of the groups (distinct).  A group whose key is in a complete slot
+// keeps that slot (a hit); every other group takes a slot of its own that no group of this launch hit: empty slots first, then the least
+// recently used, lowest index among equals (so with every slot empty group g takes slot g).  gslot[g] receives the slots, the return
+// value is the bit mask of the groups that hit.  (A launch counter that wraps only makes the choice among used slots less than optimal.)
+// (The searches have no early exit: the kernel runs this on one thread in front of the whole launch, and the 16 reads of a search then
+// travel together instead of one after the other.)
+__host__ __device__ inline unsigned sh_slot_plan(const unsigned long long *__restrict__ skey, const int *__restrict__ sstate,
+                                                 const int *__restrict__ sused, int G, const unsigned long long *__restrict__ gkey,
+                                                 int *__restrict__ gslot)
+{
+    unsigned full = 0, taken = 0, hits = 0;
+#pragma unroll
+    for (int s = 0; s < SH_GMAX; ++s) full |= sstate[s] == 1 ? 1u << s : 0u;
+    for (int g = 0; g < G; ++g) {
+        const unsigned long long key = gkey[g];
+        unsigned match = 0;
+#pragma unroll
+        for (int s = 0; s < SH_GMAX; ++s) match |= skey[s] == key ? 1u << s : 0u;
+        match &= full & ~taken;
+        int slot = -1;
+        if (match) { slot = 0; while (!((match >> slot) & 1u)) ++slot; taken |= 1u << slot; hits |= 1u << g; }
+        gslot[g] = slot;
+    }
+    for (int g = 0; g < G; ++g) {
+        if ((hits >> g) & 1u) continue;
+        int best = -1, bestused = 0;
+        bool bestfull = true;
+#pragma unroll
+        for (int s = 0; s < SH_GMAX; ++s) {
+            const bool free_ = !((taken >> s) & 1u), sfull = (full >> s) & 1u;
+            const int u = sused[s];
+            // better than the best so far: the first free slot; an empty one when the best is used; an older one among used ones
+            const bool better = free_ && (best < 0 || (bestfull && (!sfull || u < bestused)));
+            if (better) { best = s; bestused = u; bestfull = sfull; }
+        }
+        gslot[g] = best; taken |= 1u << best;
+    }
+    return hits;
+}
+
 // =============================================================== grouping ====================================================
 // REGS: every thread keeps the table slots of its (at most 8) trajectories in registers between the two passes; otherwise they are parked
 // in global memory (perm[], then fb_active[]).  The kernel is a chain of dependent steps on ONE work-group in front of the whole backward
@@ -163,14 +222,32 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
 {
     __shared__ unsigned long long keys[SH_TAB];
     __shared__ int cnt[SH_TAB], gof[SH_TAB], cursor[SH_GMAX], gst[SH_GMAX], gcn[SH_GMAX], gtile[SH_GMAX + 1], Gs, Ts, nfb;
+    __shared__ unsigned long long skey[SH_GMAX], gkey[SH_GMAX];
+    __shared__ int sstate[SH_GMAX], sused[SH_GMAX], gsl[SH_GMAX], changed, hitslots;
     const unsigned long long EMPTY = ~0ull;
     const int tid = threadIdx.x, B = a.B, lane = tid & 63;
     constexpr int NPT = 8;
     int slotr[NPT];
     if (tid < SH_TAB) { keys[tid] = EMPTY; cnt[tid] = 0; gof[tid] = -1; }
     if (tid < SH_GMAX) cursor[tid] = 0;
-    if (tid == 0) nfb = 0;
+    if (tid == 0) { nfb = 0; changed = a.reuse != SH_REUSE_ON; }
     __syncthreads();
+    // the operands the kept streams were made from against those of this call, one 64-bit word per thread (the loads are issued behind the
+    // barrier above, which would wait for them, and travel while pass 1 fetches its λ; the verdict is collected behind it)
+    unsigned long long opcur = 0, opold = 0;
+    if (a.reuse != SH_REUSE_OFF && tid <= SH_NOPS) {
+        const unsigned long long *src = tid < 100 ? (const unsigned long long *)a.fx + tid
+                                      : tid < 120 ? (const unsigned long long *)a.fu + (tid - 100)
+                                      : tid < 220 ? (const unsigned long long *)a.cxx + (tid - 120)
+                                      : tid < 240 ? (const unsigned long long *)a.cxu + (tid - 220)
+                                                  : (const unsigned long long *)a.cuu + (tid - 240);
+        opcur = tid < SH_NOPS ? *src : ((unsigned long long)(unsigned)a.N << 32) | (unsigned)a.regType;
+        opold = a.ctl->ops[tid];
+    }
+    // (the slot table and the counters too: they stay in registers until pass 1 is over — nothing in front of it waits for memory)
+    unsigned long long skey_r = 0; int sstate_r = 0, sused_r = 0, launches_r = 0, hits_r = 0, misses_r = 0;
+    if (tid < SH_GMAX) { skey_r = (unsigned long long)__double_as_longlong(a.ctl->glam[tid]); sstate_r = a.ctl->sstate[tid]; sused_r = a.ctl->sused[tid]; }
+    if (tid == 0) { launches_r = a.ctl->launches; hits_r = a.ctl->hits; misses_r = a.ctl->misses; }
     // pass 1: distinct values and their populations.  A wave whose active lanes all carry the same λ (the usual case: one λ for the
     // batch, or a few values in runs) inserts ONCE and adds its population once — per-lane atomics on one LDS word serialise (18 us at
     // B = 1 024, 158 us at B = 32 768 before this).
@@ -208,6 +285,8 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
     } else {
         for (int b0 = 0; b0 < B; b0 += blockDim.x) { const int sl = pass1(b0 + tid); if (b0 + tid < B) a.perm[b0 + tid] = sl; }
     }
+    if (opcur != opold) { changed = 1; a.ctl->ops[tid] = opcur; }           // other operands, horizon or regType: no kept stream is theirs
+    if (tid < SH_GMAX) { skey[tid] = skey_r; sstate[tid] = sstate_r; sused[tid] = sused_r; }
     __syncthreads();
     if (tid < 64) {   // the SH_GMAX most populated values with at least two trajectories become groups (wave 0: an arg-max per group)
         int mine = cnt[tid] > 1 ? (cnt[tid] << 8) | (SH_TAB - 1 - tid) : 0;      // ties: the lowest slot
@@ -220,8 +299,7 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
             const int sb = SH_TAB - 1 - (best & 0xff), bc = best >> 8;
             if (tid == sb) { mine = 0; gof[sb] = G; }
             if (tid == 0) {
-                gst[G] = start; gcn[G] = bc;
-                a.ctl->glam[G] = __longlong_as_double((long long)keys[sb]);
+                gst[G] = start; gcn[G] = bc; gkey[G] = keys[sb];
                 a.ctl->gcount[G] = bc; a.ctl->gstart[G] = start;
             }
             start += bc;
@@ -231,8 +309,13 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
         // full machine for a lone last tile.  (The host sizes items[] and the grid for the most tiles ANY grouping of the batch can
         // produce — ddp_sh_max_tiles — and the count is clamped to that capacity here.)
         if (tid == 0) {
+            // the stream slots of the groups (sh_slot_plan); a slot taken by a group that did not hit is empty until its publisher is done
+            if (changed) for (int s = 0; s < SH_GMAX; ++s) sstate[s] = 0;
+            const unsigned hits = sh_slot_plan(skey, sstate, sused, G, gkey, gsl);
             int T = 4, W = 0;
             if (G > 0) {
+                // (a producer whose stream is reused holds no CU, but counting only the others — 256 tiles of 4 for the benchmark's
+                // warm call instead of 205 of 5 — measured 0.436 ms against 0.298: profiles/sh_reuse_ab.txt)
                 const int slots = a.ncu - G > 8 ? a.ncu - G : 8;
                 const int R = (start + slots * TMAX - 1) / (slots * TMAX);
                 T = (start + R * slots - 1) / (R * slots);
@@ -244,22 +327,35 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
             for (int g = 0; g < G; ++g) { gtile[g] = W; W += (gcn[g] + T - 1) / T; }
             gtile[G] = W;
             Gs = G; Ts = T;
-            a.ctl->G = G; a.ctl->W = W; a.ctl->ticket = 0; a.ctl->error = 0; a.ctl->launches += 1;
+            const int launch = launches_r + 1;
+            int hs = 0;
+            for (int g = 0; g < G; ++g) {
+                const int s = gsl[g];
+                if ((hits >> g) & 1u) hs |= 1 << s; else { sstate[s] = 0; skey[s] = gkey[g]; }
+                sused[s] = launch;
+            }
+            hitslots = hs;
+            a.ctl->hitmask = (int)hits; a.ctl->hits = hits_r + __popc(hits); a.ctl->misses = misses_r + G - __popc(hits);
+            a.ctl->G = G; a.ctl->W = W; a.ctl->ticket = 0; a.ctl->error = 0; a.ctl->launches = launch;
 #ifdef SH_PROF
             for (int e = 0; e < 64; ++e) a.ctl->prof[e] = 0;
             a.ctl->prof[19] = ~0ull;
 #endif
         }
     }
-    if (tid < SH_GMAX) { a.ctl->progress[16 * tid] = 0; a.ctl->gdiverge[tid] = 0; }
     __syncthreads();
+    if (tid < SH_GMAX) {                                // per slot: a reused stream has every chunk published, the others start empty
+        a.ctl->progress[16 * tid] = (hitslots >> tid) & 1 ? (((a.N - 1) / CH + 1) | SH_FIN) : 0; a.ctl->gdiverge[tid] = 0;
+        a.ctl->glam[tid] = __longlong_as_double((long long)skey[tid]); a.ctl->sstate[tid] = sstate[tid]; a.ctl->sused[tid] = sused[tid];
+        a.ctl->gslot[tid] = tid < Gs ? gsl[tid] : 0;
+    }
     {   // the tiles, one per thread
         const int G = Gs, T = Ts, W = gtile[G];
         for (int w = tid; w < W; w += blockDim.x) {
             int g = 0;
             while (g + 1 < G && gtile[g + 1] <= w) ++g;
             const int t0 = (w - gtile[g]) * T;
-            a.items[w] = make_int4(g, gst[g] + t0, gcn[g] - t0 < T ? gcn[g] - t0 : T, 0);
+            a.items[w] = make_int4(g, gst[g] + t0, gcn[g] - t0 < T ? gcn[g] - t0 : T, gsl[g]);
         }
     }
     // pass 2: counting sort into perm
@@ -615,6 +711,7 @@ __device__ __forceinline__ void sh_builder(const ShArgs &a, double *sm, const do
     lds_store_flag(&flags[PF_BREADY], (lds_load_flag(&flags[PF_BREADY]) & SH_CNT) | SH_FIN);
 }
 
+// gidx: the stream slot of the group
 __device__ __forceinline__ void sh_publisher(const ShArgs &a, double *sm, const int gidx)
 {
     const int lane = threadIdx.x % DDP_WAVE;
@@ -640,6 +737,8 @@ __device__ __forceinline__ void sh_publisher(const ShArgs &a, double *sm, const 
         const int have = r & SH_CNT;
         if (have <= q) {                                       // finished without another chunk
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // (the builder may announce the last chunk before it has seen the chain's end: then the stream is complete HERE)
+            if (lane == 0 && a.reuse != SH_REUSE_OFF && have == NCHK && lds_load_flag(&flags[PF_CDIV]) == 0) store4_sc1(&a.ctl->sstate[gidx], 1);
             if (lane == 0) store4_sc1(prog, have | SH_FIN);
             return;
         }
@@ -660,8 +759,11 @@ __device__ __forceinline__ void sh_publisher(const ShArgs &a, double *sm, const 
             pending = false;
         }
         if (last) {
-            if (lane == 0) store4_sc1(&a.ctl->gdiverge[gidx], lds_load_flag(&flags[PF_CDIV]));
+            const int cdiv = lds_load_flag(&flags[PF_CDIV]);
+            if (lane == 0) store4_sc1(&a.ctl->gdiverge[gidx], cdiv);
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the chunk has left (write-through) before the progress word says so
+            // the whole stream of a chain that did not diverge is in memory: later launches may take it from this slot
+            if (lane == 0 && a.reuse != SH_REUSE_OFF && cdiv == 0 && q + 1 == NCHK) store4_sc1(&a.ctl->sstate[gidx], 1);
             if (lane == 0) store4_sc1(prog, (q + 1) | SH_FIN);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             SH_MARK_MAX(21);
@@ -680,11 +782,12 @@ enum { KIND_NORMAL = 0, KIND_ZERO = 1 << 20 /* no data: everything is zero */ };
 // mask those kernels run under — they rewrite every output of a flagged trajectory), and ctl->error counts the event.
 __device__ __forceinline__ void sh_dma(const ShArgs &a, double *sm, const int gidx, const int nusers, const int4 item)
 {
+    const int gslot = item.w;                                   // the stream slot of group gidx
     const int lane = threadIdx.x % DDP_WAVE;
     int *flags = (int *)(sm + C_FLAGS);
     const int NCHK = (a.N - 1) / CH + 1;
-    const double *grec = a.rec + (size_t)gidx * NCHK * GCHUNK;
-    const int *prog = &a.ctl->progress[16 * gidx];
+    const double *grec = a.rec + (size_t)gslot * NCHK * GCHUNK;
+    const int *prog = &a.ctl->progress[16 * gslot];
     int pubd = 0;                                               // progress word as last seen
     const unsigned long long t0 = wall_clock64();
     // The gradients [cx; cu] of the tile's trajectories come through THIS wave too (round 5).  The affine waves used to fetch their own
@@ -976,11 +1079,12 @@ __global__ __launch_bounds__(SH_THREADS) void sh_back_kernel(ShArgs a)
     struct Mark { ShCtl *c; bool on; __device__ ~Mark() { if (on) atomicMax(&c->prof[18], wall_clock64()); } } mark_{a.ctl, threadIdx.x % DDP_WAVE == 0};
 #endif
     if (role < G) {
-        if (wave > 2) return;
-        const double lam = a.ctl->glam[role];
+        if (wave > 2 || ((a.ctl->hitmask >> role) & 1)) return;      // (a reused stream: nothing to produce)
+        const int slot = a.ctl->gslot[role];
+        const double lam = a.ctl->glam[slot];
         if (wave == 0) sh_chain<REG2>(a, sm, role, lam);
         else if (wave == 1) sh_builder<REG2>(a, sm, lam);
-        else sh_publisher(a, sm, role);
+        else sh_publisher(a, sm, slot);
         return;
     }
     const int it = role - G;
@@ -1036,10 +1140,13 @@ int ddp_launch_back_pass_sh(ddp_handle h, const BPCall &c, const int32_t **fb_ac
     if (!h->ncu) { hipDeviceProp_t pr; DDP_HIP(hipGetDeviceProperties(&pr, h->device)); h->ncu = pr.multiProcessorCount; }
     const int Wmax = ddp_sh_max_tiles(B, h->ncu);
     const int NCHK = (N - 1) / CH + 1;
-    // scratch of the handle: control block | items | perm | fb_active | record streams
+    // scratch of the handle: control block | record streams | items | perm | fb_active.  The streams are kept across calls, so where a
+    // stream lies must depend on nothing but what it is keyed by: they come first (slot s at s * NCHK chunks; N is part of the key),
+    // in front of the lists whose sizes follow the batch
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_items = al(sizeof(ShCtl)), o_perm = o_items + al(sizeof(int4) * (size_t)Wmax), o_fb = o_perm + al(sizeof(int) * (size_t)B),
-                 o_rec = o_fb + al(sizeof(int32_t) * (size_t)B), total = o_rec + al(sizeof(double) * (size_t)SH_GMAX * NCHK * GCHUNK);
+    const size_t o_rec = al(sizeof(ShCtl)), o_items = o_rec + al(sizeof(double) * (size_t)SH_GMAX * NCHK * GCHUNK),
+                 o_perm = o_items + al(sizeof(int4) * (size_t)Wmax), o_fb = o_perm + al(sizeof(int) * (size_t)B),
+                 total = o_fb + al(sizeof(int32_t) * (size_t)B);
     if (h->sh_bytes < total) {
         if (h->sh) {
             DDP_HIP(hipStreamSynchronize(h->stream));
@@ -1054,6 +1161,15 @@ int ddp_launch_back_pass_sh(ddp_handle h, const BPCall &c, const int32_t **fb_ac
     ShArgs a;
     a.N = N; a.B = B; a.ncu = h->ncu; a.regType = d->regType; a.wmax = Wmax;
     a.test_abort = ddp_env(h, ENV_TEST_SH_ABORT) ? 1 : 0;
+    // reuse of the kept record streams: it rests on the stream order between consecutive launches of the handle, so a launch on another
+    // stream than the last one starts from empty slots (a by-value flag: nothing is written or waited for here)
+    a.reuse = SH_REUSE_ON;
+    if (h->sh_launched && h->sh_last_stream != h->stream) a.reuse = SH_REUSE_FLUSH;
+    { const char *e = ddp_env(h, ENV_SH_REUSE); if ((e && atoi(e) == 0) || a.test_abort) a.reuse = SH_REUSE_OFF; }
+#ifdef SH_PROF
+    a.reuse = SH_REUSE_OFF;                                      // the phase profile measures the chain
+#endif
+    h->sh_launched = true; h->sh_last_stream = h->stream;
     a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
     a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
     a.ctl = (ShCtl *)base; a.items = (int4 *)(base + o_items); a.perm = (int *)(base + o_perm); a.fb_active = (int32_t *)(base + o_fb);
@@ -1117,6 +1233,37 @@ extern "C" int ddp_sh_timeout_info(ddp_handle h, int *out, int cap)
     for (int r = 0; r < nd; ++r) for (int e = 0; e < 8; ++e) out[8 * r + e] = c.diag[r][e];
     for (int g = 0; g < SH_GMAX; ++g) out[SH_NDIAG * 8 + g] = c.progress[16 * g];
     return nd;
+}
+
+// groups served from a kept record stream / groups whose stream was computed, since the scratch was allocated (out: 2 ints)
+extern "C" int ddp_sh_reuse_stats(ddp_handle h, int *out)
+{
+    DDP_DEVICE(h);
+    if (!out) { ddp_set_error("ddp_sh_reuse_stats: out is NULL"); return -1; }
+    out[0] = out[1] = 0;
+    if (!h->sh) return 0;
+    DDP_HIP(hipStreamSynchronize(h->stream));
+    ShCtl c;
+    DDP_HIP(hipMemcpy(&c, h->sh, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = c.hits; out[1] = c.misses;
+    return 0;
+}
+
+// debug hooks (unlisted, like ddp_bp_choice).  ddp_sh_slot_plan: the slot policy of the grouping kernel on the host — 16 slot keys, states
+// and last-use numbers, G group keys; writes G slots, returns the bit mask of the groups that hit (< 0: bad G).  ddp_sh_test_swap_stream:
+// puts the handle on another HIP stream, as the slot scheduler does for its side stream, and returns the one it was on through *prev.
+extern "C" int ddp_sh_slot_plan(const unsigned long long *skey, const int *sstate, const int *sused, int G, const unsigned long long *gkey, int *gslot)
+{
+    if (G < 0 || G > SH_GMAX) return -1;
+    return (int)sh_slot_plan(skey, sstate, sused, G, gkey, gslot);
+}
+extern "C" int ddp_sh_test_swap_stream(ddp_handle h, void *stream, void **prev)
+{
+    DDP_DEVICE(h);
+    DDP_HIP(hipStreamSynchronize(h->stream));
+    if (prev) *prev = (void *)h->stream;
+    h->stream = (hipStream_t)stream;
+    return 0;
 }
 
 extern "C" int ddp_sh_timeouts(ddp_handle h)

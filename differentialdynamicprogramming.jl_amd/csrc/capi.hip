@@ -24,7 +24,7 @@ extern "C" {
 const char *ddp_last_error(void) { return g_err; }
 const char *ddp_version(void) { return "ddp_amd 0.3.0 (gfx950, fp64)"; }
 
-static const char *const ddp_env_names[ENV_COUNT] = {"DDP_BACKPASS", "DDP_SH_MIN_B", "DDP_MX2", "DDP_DPPW", "DDP_MX_LDS", "DDP_Q4_SINGLE", "DDP_Q4_LDS", "DDP_GPS_Q4", "DDP_GPS_Q4L", "DDP_DF_DENSE", "DDP_FORWARD", "DDP_FORWARD64", "DDP_FORWARD_FAST", "DDP_FORWARD_FUSE", "DDP_FORWARD_LANE", "DDP_FORWARD_PEND", "DDP_FORWARD_PIPE", "DDP_ILQG_COMPACT", "DDP_ILQG_LSGROUPS", "DDP_TEST_COMPACT_ALLOC_FAIL", "DDP_GPS_LANE", "DDP_FCOV_Q4", "DDP_FCOV_Q4L", "DDP_KL_LDS", "DDP_TEST_SH_ABORT", "DDP_MXG_COAL", "DDP_FORWARD_MID", "DDP_PEND_CHUNK", "DDP_GPS_MID", "DDP_GPS_WIDE"};
+static const char *const ddp_env_names[ENV_COUNT] = {"DDP_BACKPASS", "DDP_SH_MIN_B", "DDP_MX2", "DDP_DPPW", "DDP_MX_LDS", "DDP_Q4_SINGLE", "DDP_Q4_LDS", "DDP_GPS_Q4", "DDP_GPS_Q4L", "DDP_DF_DENSE", "DDP_FORWARD", "DDP_FORWARD64", "DDP_FORWARD_FAST", "DDP_FORWARD_FUSE", "DDP_FORWARD_LANE", "DDP_FORWARD_PEND", "DDP_FORWARD_PIPE", "DDP_ILQG_COMPACT", "DDP_ILQG_LSGROUPS", "DDP_TEST_COMPACT_ALLOC_FAIL", "DDP_GPS_LANE", "DDP_FCOV_Q4", "DDP_FCOV_Q4L", "DDP_KL_LDS", "DDP_TEST_SH_ABORT", "DDP_MXG_COAL", "DDP_FORWARD_MID", "DDP_PEND_CHUNK", "DDP_GPS_MID", "DDP_GPS_WIDE", "DDP_SH_REUSE"};
 
 int ddp_reload_env(ddp_handle h)
 {
@@ -67,7 +67,7 @@ static int create_impl(int device, void *ext_stream, bool adopt, ddp_handle *out
     h->device = device;
     h->scratch = nullptr;
     h->scratch_bytes = 0;
-    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } h->last_kernel[0] = h->last_kernel[1] = nullptr; ddp_reload_env(h);
+    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->sh_last_stream = nullptr; h->sh_launched = false; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } h->last_kernel[0] = h->last_kernel[1] = nullptr; ddp_reload_env(h);
     h->h_pinned = nullptr;
     h->timing = nullptr; h->timing_cap = 0; h->tev_ok = false; h->kl_wide = 0;
     h->owns_stream = !adopt;

@@ -58,6 +58,11 @@ int  ddp_sh_timeouts(ddp_handle h);
  * stand now.  out: cap >= 80 ints.  Returns the number of records (0 in a healthy run), < 0 on error; synchronises the stream.  (Own
  * protocol of the shared-operand kernel: no counterpart in the reference.)                                                              */
 int  ddp_sh_timeout_info(ddp_handle h, int *out, int cap);
+/* The shared-operand backward pass keeps the matrix recursion of each λ it has computed (a record stream in the handle's scratch) and
+ * reuses it in later calls with bit-identical fx, fu, cxx, cxu, cuu, N, regType and λ (compared on the device in every call;
+ * DDP_SH_REUSE=0 switches the reuse off).  out[0]: λ groups served from a kept stream, out[1]: groups whose recursion was computed,
+ * since the scratch was (re)allocated.  out: 2 ints.  Synchronises the stream; 0, < 0 on error.  A debug query like ddp_sh_timeouts.  */
+int  ddp_sh_reuse_stats(ddp_handle h, int *out);
 void *ddp_stream(ddp_handle h);                 /* the hipStream_t of the handle */
 /* device memory helpers for hosts without their own allocator (the Julia wrapper, tests) */
 int  ddp_malloc(ddp_handle h, size_t bytes, void **dptr);
