@@ -911,7 +911,7 @@ int ddp_launch_back_pass(ddp_handle h, const BPCall &c)
 }
 
 // Unlisted debug hook (not in ddp_amd.h): the name ddp_last_kernel(h, 0) reports after a backward pass with these facts — the same
-// choice the dispatcher makes, callable without a GPU (tests/test_bp_choice_cpu.py).  al16: bit 0 cx, cu; bit 1 cxx, cuu; bit 2 K, k,
+// choice the dispatcher makes, callable without a GPU (tests/test_bp_choice.py).  al16: bit 0 cx, cu; bit 1 cxx, cuu; bit 2 K, k,
 // Quu, Vx, Vxx 16-byte aligned; lims_active: for 32 < n <= 64 with has_lims, whether lims[1,1] <= lims[1,2]; the switches as strings
 // (NULL: unset)
 extern "C" const char *ddp_bp_choice(const ddp_bp_desc *d, unsigned al16, int sink, int lims_active, const char *backpass,

@@ -210,27 +210,47 @@ int ddp_launch_back_pass_mf2(ddp_handle h, const BPCall &c, bool lims_active);
 int ddp_launch_back_pass_mfma(ddp_handle h, const BPCall &c, bool lims_active);
 // wide controls, any n <= 64 with m <= DDP_MAX_M_WIDE at run time: one work-group of four waves per trajectory (back_pass_wide.hip)
 int ddp_launch_back_pass_wide(ddp_handle h, const BPCall &c);
-// forward_pass_row.hip: the 16-lane-row rollout compiled for padded sizes (LQ problems, n <= 14, m <= 4); 1 = not applicable
-int ddp_launch_forward_row(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                           const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                           const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
-// 16-lane DPP-row forward pass + separate cost kernel; returns 1 when the shape has no such kernel
-int ddp_launch_forward_dpp(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
-
+// One forward-pass call as the C ABI passes it (ddp_forward_pass_f64_dev).  Every rollout launcher takes one; forward_pass.hip chooses
+// which one runs (fp_choose) and hands the launchers of several kernels the FPChoice it made.
+struct FPCall {
+    const ddp_problem *p;
+    const double *K, *k, *x0, *u, *x, *alpha, *lims;
+    int nalpha;
+    const int32_t *active;
+    double *xnew, *unew, *cnew, *csum;
+};
+// one enumerator per rollout kernel that differs (forward_pass.hip: the family overview and the names ddp_last_kernel(h, 1) reports)
+enum FPKernel { FP_NONE, FP_WIDE, FP_BIG64, FP_MID, FP_BIG, FP_PIPE4, FP_PIPE, FP_PIPE_TV, FP_PEND_LANE, FP_PEND_ROW, FP_DPP, FP_ROW, FP_GROUP };
+// fuse: pipe, pendulum and dpp kernels, the cost inside the rollout kernel (cost_diag without DDP_FORWARD_FUSE=0); chunked: FP_PEND_ROW, whole
+// 16-step chunks through LDS; fast: FP_DPP, the instantiation without the run-time dyn_tv test and with unmasked stores; wrap: pendulum
+// kernels, the instantiation that wraps x̂ - x (diff_wrap with a policy); cost_mid: FP_BIG, cost_mid_kernel behind forward_big_kernel
+// (cost_rt_kernel otherwise); na: FP_BIG64, step sizes of a trajectory per wave (1, 2 or 4)
+struct FPChoice { FPKernel k; bool fuse, chunked, fast, wrap, cost_mid; int na; };
+// what the argument struct of every rollout kernel takes from the call
+template <class Args>
+static inline void fp_fill(Args &a, const FPCall &c)
+{
+    a.N = c.p->N; a.B = c.p->B; a.nalpha = c.nalpha;
+    a.A = c.p->A; a.Bm = c.p->Bm; a.Q = c.p->Q; a.R = c.p->R; a.K = c.K; a.k = c.k; a.x0 = c.x0; a.u = c.u; a.x = c.x; a.active = c.active;
+    for (int i = 0; i < 16; ++i) a.alpha[i] = i < c.nalpha ? c.alpha[i] : 0.0;
+    a.xnew = c.xnew; a.unew = c.unew; a.cnew = c.cnew; a.csum = c.csum;
+}
+// Rollout launchers.  Each launches the kernel fp_choose has chosen it for (the shape, switch, batch-size and alignment tests live there);
+// 0 launched, < 0 error.
+// the 16-lane-row rollout compiled for padded sizes (forward_pass_row.hip): LQ, n <= 14, m <= 4 minus n > 12 with m > 2
+int ddp_launch_forward_row(ddp_handle h, const FPCall &c);
+// FP_DPP, FP_PEND_ROW, FP_PEND_LANE: 16-lane rows for LQ (10, 2) and pendcart, the pendulum's own row and lane kernels (forward_pass_dpp.hip)
+int ddp_launch_forward_dpp(ddp_handle h, const FPCall &c, const FPChoice &ch);
 // one wave per rollout for wide controls (LQ family, n <= 64, 8 < m <= DDP_MAX_M_WIDE; forward_pass_wide.hip)
-int ddp_launch_forward_wide(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
+int ddp_launch_forward_wide(ddp_handle h, const FPCall &c);
+// FP_PIPE4, FP_PIPE, FP_PIPE_TV: the LQ (10, 2) rollout as a producer/consumer pipeline, one work-group per 4 rollouts (forward_pass_pipe.hip)
+int ddp_launch_forward_pipe(ddp_handle h, const FPCall &c, const FPChoice &ch);
+// FP_BIG64, FP_MID, FP_BIG: one wave per rollout for large states (LQ family, n <= 64, m <= DDP_MAX_M; forward_pass_big.hip)
+int ddp_launch_forward_big(ddp_handle h, const FPCall &c, const FPChoice &ch);
 
 struct QPOptsDev;
 int ddp_launch_boxqp_big(ddp_handle h, int m, int count, const double *H, const double *g, const double *lower, const double *upper,
                          const double *x0, const QPOptsDev &o, double *x, int32_t *result, double *Hfree, uint8_t *free_out);   // boxqp_big.hip
-// LQ n=10/m=2 rollout as a producer/consumer pipeline of one work-group per 4 rollouts (forward_pass_pipe.hip); 1 = not applicable
-int ddp_launch_forward_pipe(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
 
 // 1/sqrt(x): hardware estimate (v_rsq_f64) + two Newton steps -> ~1 ulp.  The caller checks x > 0.
 __device__ __forceinline__ double ddp_rsqrt(double x)
@@ -242,11 +262,6 @@ __device__ __forceinline__ double ddp_rsqrt(double x)
     y = fma(0.5 * y, e, y);
     return y;
 }
-
-// one wave per rollout for large states (LQ family, n <= 64); returns 1 when not applicable
-int ddp_launch_forward_big(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                           const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                           const int32_t *active, double *xnew, double *unew, double *cnew, double *csum);
 
 // Upper Cholesky of H (column-major M x M, upper triangle read) with RECIPROCAL pivots: fills the strictly upper
 // entries of R and ri[j] = 1/R[j][j].  Division-free (v_rsq_f64 + Newton), which matters where every lane repeats

@@ -551,63 +551,48 @@ __global__ __launch_bounds__(DDP_WAVE) void cost_mid_kernel(FBArgs a)
 
 }   // namespace
 
-// returns 1 when not applicable (caller falls back), 0 launched, <0 error
-int ddp_launch_forward_big(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                           const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                           const int32_t *active, double *xnew, double *unew, double *cnew, double *csum)
+// FP_BIG64, FP_MID or FP_BIG with the cost kernel fp_choose (forward_pass.hip) names
+int ddp_launch_forward_big(ddp_handle h, const FPCall &c, const FPChoice &ch)
 {
-    if (p->kind != DDP_PROBLEM_LQ || p->n > 64 || p->m > DDP_MAX_M) return 1;
-    h->last_kernel[1] = "forward_big_kernel";                         // (the mid-size branch below renames it)
+    const ddp_problem *p = c.p;
+    DDP_CHECK(p->kind == DDP_PROBLEM_LQ && p->n <= 64 && p->m <= DDP_MAX_M && (ch.k != FP_BIG64 || (p->n == 64 && p->m == 8)) &&
+              (ch.k != FP_MID || p->n <= 32) && (!ch.cost_mid || p->n > 32),
+              "forward_pass: n=%d m=%d handed to the one-wave-per-rollout kernels (LQ family, n <= 64, m <= %d)", p->n, p->m, DDP_MAX_M);
+    const int nalpha = c.nalpha;
     FBArgs a;
-    a.n = p->n; a.m = p->m; a.N = p->N; a.B = p->B; a.nalpha = nalpha;
-    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = K != nullptr; a.has_lims = lims != nullptr;
-    a.A = p->A; a.Bm = p->Bm; a.Q = p->Q; a.R = p->R; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims;
-    a.active = active;
-    for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
-    a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum;
+    fp_fill(a, c);
+    a.n = p->n; a.m = p->m;
+    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = c.K != nullptr; a.has_lims = c.lims != nullptr;
+    a.lims = c.lims;
     const dim3 grid((unsigned)((long)p->B * nalpha)), block(DDP_WAVE);
-    const char *env = ddp_env(h, ENV_FORWARD64);                       // DDP_FORWARD64=0: run-time-sized kernels also at n = 64, m = 8
-    if (p->n == 64 && p->m == 8 && !(env && env[0] == '0')) {
-        // up to 4 step sizes of a trajectory per wave (operands fetched once); a single α keeps the one-rollout instantiation
-        const int na = nalpha >= 3 ? 4 : (nalpha == 2 ? 2 : 1);
+    if (ch.k == FP_BIG64) {
+        const int na = ch.na;                                          // step sizes of a trajectory per wave (operands fetched once)
         const dim3 g64((unsigned)p->B, (unsigned)((nalpha + na - 1) / na));
-        if (a.has_policy) {
-            if (na == 4) hipLaunchKernelGGL((forward_big64_kernel<true, 4>), g64, block, 0, h->stream, a);
-            else if (na == 2) hipLaunchKernelGGL((forward_big64_kernel<true, 2>), g64, block, 0, h->stream, a);
-            else hipLaunchKernelGGL((forward_big64_kernel<true, 1>), g64, block, 0, h->stream, a);
-        } else {
-            hipLaunchKernelGGL((forward_big64_kernel<false, 1>), dim3((unsigned)p->B, (unsigned)nalpha), block, 0, h->stream, a);
-        }
+        DDP_CHECK(a.has_policy || na == 1, "forward_pass: %d step sizes per wave without a policy", na);
+        if (na == 4) hipLaunchKernelGGL((forward_big64_kernel<true, 4>), g64, block, 0, h->stream, a);
+        else if (na == 2) hipLaunchKernelGGL((forward_big64_kernel<true, 2>), g64, block, 0, h->stream, a);
+        else if (a.has_policy) hipLaunchKernelGGL((forward_big64_kernel<true, 1>), g64, block, 0, h->stream, a);
+        else hipLaunchKernelGGL((forward_big64_kernel<false, 1>), g64, block, 0, h->stream, a);
         hipLaunchKernelGGL(cost_big64_kernel, dim3(grid.x, (unsigned)((p->N + 15) / 16)), block, 0, h->stream, a);
-        hipLaunchKernelGGL(cost_sum_kernel, grid, block, 0, h->stream, a);
-        DDP_HIP(hipGetLastError());
-        return 0;
-    }
-    const char *mid = ddp_env(h, ENV_FORWARD_MID);                     // DDP_FORWARD_MID=0: the run-time-sized kernels below n = 64 too (A/B, tests)
-    if (p->n <= 32 && p->m <= 8 && !(mid && mid[0] == '0')) {
-        if (p->n <= 16) hipLaunchKernelGGL((forward_mid_kernel<8>), grid, block, 0, h->stream, a);
+    } else {
+        if (ch.k != FP_MID) hipLaunchKernelGGL(forward_big_kernel, grid, block, 0, h->stream, a);
+        else if (p->n <= 16) hipLaunchKernelGGL((forward_mid_kernel<8>), grid, block, 0, h->stream, a);
         else if (p->n <= 24) hipLaunchKernelGGL((forward_mid_kernel<12>), grid, block, 0, h->stream, a);
         else hipLaunchKernelGGL((forward_mid_kernel<16>), grid, block, 0, h->stream, a);
-        const dim3 cgrid(grid.x, (unsigned)((p->N + DDP_WAVE - 1) / DDP_WAVE));
+        if (ch.k != FP_MID && !ch.cost_mid) {                          // the run-time-sized cost kernel (it sums over time itself)
+            const size_t shmem = ((size_t)p->n * p->n + (size_t)p->m * p->m) * sizeof(double);
+            hipLaunchKernelGGL(cost_rt_kernel, grid, block, shmem, h->stream, a);
+            DDP_HIP(hipGetLastError());
+            return 0;
+        }
+        const dim3 cgrid(grid.x, (unsigned)((p->N + DDP_WAVE - 1) / DDP_WAVE));      // cost_mid_kernel at the padding that holds n
         if (p->n <= 16) hipLaunchKernelGGL((cost_mid_kernel<16>), cgrid, block, 0, h->stream, a);
         else if (p->n <= 24) hipLaunchKernelGGL((cost_mid_kernel<24>), cgrid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((cost_mid_kernel<32>), cgrid, block, 0, h->stream, a);
-        hipLaunchKernelGGL(cost_sum_kernel, grid, block, 0, h->stream, a);
-        DDP_HIP(hipGetLastError());
-        h->last_kernel[1] = "forward_mid_kernel";
-        return 0;
-    }
-    hipLaunchKernelGGL(forward_big_kernel, grid, block, 0, h->stream, a);
-    if (p->n > 32 && !(mid && mid[0] == '0')) {                        // the cost kernel of the mid-size rollouts at the larger paddings
-        const dim3 cgrid(grid.x, (unsigned)((p->N + DDP_WAVE - 1) / DDP_WAVE));
-        if (p->n <= 48) hipLaunchKernelGGL((cost_mid_kernel<48>), cgrid, block, 0, h->stream, a);
+        else if (p->n <= 32) hipLaunchKernelGGL((cost_mid_kernel<32>), cgrid, block, 0, h->stream, a);
+        else if (p->n <= 48) hipLaunchKernelGGL((cost_mid_kernel<48>), cgrid, block, 0, h->stream, a);
         else hipLaunchKernelGGL((cost_mid_kernel<64>), cgrid, block, 0, h->stream, a);
-        hipLaunchKernelGGL(cost_sum_kernel, grid, block, 0, h->stream, a);
-        DDP_HIP(hipGetLastError());
-        return 0;
     }
-    const size_t shmem = ((size_t)p->n * p->n + (size_t)p->m * p->m) * sizeof(double);
-    hipLaunchKernelGGL(cost_rt_kernel, grid, block, shmem, h->stream, a);
+    hipLaunchKernelGGL(cost_sum_kernel, grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }

@@ -792,125 +792,90 @@ __global__ __launch_bounds__(DDP_WAVE) void cost_kernel(CostArgs a)
     if (lane == 0) a.csum[rho] = acc;
 }
 
+typedef void (*FDKernel)(FDArgs);
+
+// the tables below: [0] with limits, [1] without for the instantiations that need a policy; [has_policy][has_lims] for the others
 template <int KIND, int NS, int MS, bool FUSE>
-int launch_dpp(ddp_handle h, const FDArgs &a)
+int launch_dpp(ddp_handle h, const FDArgs &a, bool fast)
 {
-    const int key = (a.has_policy ? 2 : 0) | (a.has_lims ? 1 : 0);
+    // FAST: a policy, time-invariant dynamics, the sink, 16-byte loads of ū_i, k_i, K_i[:, j]
+    static const FDKernel fastk[2] = {forward_dpp_kernel<KIND, NS, MS, true, true, FUSE, true>, forward_dpp_kernel<KIND, NS, MS, true, false, FUSE, true>};
+    static const FDKernel kern[2][2] = {{forward_dpp_kernel<KIND, NS, MS, false, false, FUSE>, forward_dpp_kernel<KIND, NS, MS, false, true, FUSE>},
+                                        {forward_dpp_kernel<KIND, NS, MS, true, false, FUSE>, forward_dpp_kernel<KIND, NS, MS, true, true, FUSE>}};
     const long total = (long)a.B * a.nalpha;
     const int gpw = DDP_WAVE / 16;
     const dim3 grid((unsigned)((total + gpw - 1) / gpw)), block(DDP_WAVE);
-    const char *fv = ddp_env(h, ENV_FORWARD_FAST);                // 0: the variant with the run-time dyn_tv test and masked stores (A/B, tests)
-    const bool al16 = MS != 2 || ((((uintptr_t)a.u | (uintptr_t)a.k | (uintptr_t)a.K) & 15) == 0);     // 16-byte loads of ū_i, k_i, K_i[:, j]
-    if (a.has_policy && !a.dyn_tv && a.sink && al16 && !(fv && fv[0] == '0')) {
-        if (a.has_lims) hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, true, true, FUSE, true>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, true, false, FUSE, true>), grid, block, 0, h->stream, a);
-        DDP_HIP(hipGetLastError());
-        return 0;
-    }
-    switch (key) {
-    case 0: hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, false, false, FUSE>), grid, block, 0, h->stream, a); break;
-    case 1: hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, false, true, FUSE>), grid, block, 0, h->stream, a); break;
-    case 2: hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, true, false, FUSE>), grid, block, 0, h->stream, a); break;
-    case 3: hipLaunchKernelGGL((forward_dpp_kernel<KIND, NS, MS, true, true, FUSE>), grid, block, 0, h->stream, a); break;
-    }
+    hipLaunchKernelGGL(fast ? fastk[!a.has_lims] : kern[a.has_policy][a.has_lims], grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }
 
 template <bool FUSE>
-int launch_pend_row(ddp_handle h, const FDArgs &a0)
+int launch_pend_row(ddp_handle h, const FDArgs &a, bool wrap)
 {
-    FDArgs a = a0;
+    static const FDKernel wrapk[2] = {forward_pend_row_kernel<true, true, FUSE, true>, forward_pend_row_kernel<true, false, FUSE, true>};   // diff_fun with wrapped coordinates
+    static const FDKernel kern[2][2] = {{forward_pend_row_kernel<false, false, FUSE>, forward_pend_row_kernel<false, true, FUSE>},
+                                        {forward_pend_row_kernel<true, false, FUSE>, forward_pend_row_kernel<true, true, FUSE>}};
     const long total = (long)a.B * a.nalpha;
-    // 16-step chunks through LDS from 3 584 rollouts on: below that the element-wise streams keep up with the 208 ns step (0.133 ms at
-    // 2 048 rollouts of N = 600 against 0.142 chunked: ~15 ticks of chunk bookkeeping per step), above it they are the bound (4 096:
-    // 0.189 -> 0.147 ms).  DDP_PEND_CHUNK=0 / 1: never / always (A/B, tests).
-    const char *pc = ddp_env(h, ENV_PEND_CHUNK);
-    a.chunked = pc ? (pc[0] != '0') : (total >= 3584);
     const dim3 grid((unsigned)((total + 3) / 4)), block(DDP_WAVE);
-    const int key = (a.has_policy ? 2 : 0) | (a.has_lims ? 1 : 0);
-    if (a.wrap != 0 && a.has_policy) {                          // diff_fun with wrapped coordinates (only a policy has a difference to wrap)
-        if (a.has_lims) hipLaunchKernelGGL((forward_pend_row_kernel<true, true, FUSE, true>), grid, block, 0, h->stream, a);
-        else hipLaunchKernelGGL((forward_pend_row_kernel<true, false, FUSE, true>), grid, block, 0, h->stream, a);
-        DDP_HIP(hipGetLastError());
-        return 0;
-    }
-    switch (key) {
-    case 0: hipLaunchKernelGGL((forward_pend_row_kernel<false, false, FUSE>), grid, block, 0, h->stream, a); break;
-    case 1: hipLaunchKernelGGL((forward_pend_row_kernel<false, true, FUSE>), grid, block, 0, h->stream, a); break;
-    case 2: hipLaunchKernelGGL((forward_pend_row_kernel<true, false, FUSE>), grid, block, 0, h->stream, a); break;
-    case 3: hipLaunchKernelGGL((forward_pend_row_kernel<true, true, FUSE>), grid, block, 0, h->stream, a); break;
-    }
+    hipLaunchKernelGGL(wrap ? wrapk[!a.has_lims] : kern[a.has_policy][a.has_lims], grid, block, 0, h->stream, a);
+    DDP_HIP(hipGetLastError());
+    return 0;
+}
+
+// the lane-per-rollout kernel: the same tables, with and without the fused cost
+static int launch_pend_lane(ddp_handle h, const FDArgs &a, bool fuse, bool wrap)
+{
+#define DDP_LANE(...) forward_lane_pendcart_kernel<__VA_ARGS__>
+    static const FDKernel wrapk[2][2] = {{DDP_LANE(true, true, true, true), DDP_LANE(true, true, false, true)},
+                                         {DDP_LANE(true, false, true, true), DDP_LANE(true, false, false, true)}};     // [without limits][without fuse]
+    static const FDKernel kern[2][2][2] = {{{DDP_LANE(false, false, true), DDP_LANE(false, false, false)}, {DDP_LANE(false, true, true), DDP_LANE(false, true, false)}},
+                                           {{DDP_LANE(true, false, true), DDP_LANE(true, false, false)}, {DDP_LANE(true, true, true), DDP_LANE(true, true, false)}}};
+#undef DDP_LANE
+    const long total = (long)a.B * a.nalpha;
+    const dim3 grid((unsigned)((total + DDP_WAVE - 1) / DDP_WAVE)), block(DDP_WAVE);
+    hipLaunchKernelGGL(wrap ? wrapk[!a.has_lims][!fuse] : kern[a.has_policy][a.has_lims][!fuse], grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }
 
 }   // namespace
 
-// returns 1 when the shape has no DPP kernel (caller falls back to the group kernel), 0 launched, <0 error
-int ddp_launch_forward_dpp(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                           const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                           const int32_t *active, double *xnew, double *unew, double *cnew, double *csum)
+// FP_PEND_LANE, FP_PEND_ROW or FP_DPP with the variants fp_choose (forward_pass.hip) names; the separate cost kernel unless ch.fuse
+int ddp_launch_forward_dpp(ddp_handle h, const FPCall &c, const FPChoice &ch)
 {
+    const ddp_problem *p = c.p;
     const bool lq = p->kind == DDP_PROBLEM_LQ;
-    if (!((lq && p->n == 10 && p->m == 2) || (p->kind == DDP_PROBLEM_PENDCART))) return 1;
+    DDP_CHECK(lq ? (p->n == 10 && p->m == 2 && ch.k == FP_DPP) : (p->kind == DDP_PROBLEM_PENDCART && p->n == 4 && p->m == 1),
+              "forward_pass: n=%d m=%d (problem kind %d) handed to the 16-lane-row rollouts", p->n, p->m, p->kind);
+    DDP_CHECK(!ch.wrap || c.K, "forward_pass: wrapped differences without a policy");
+    DDP_CHECK(ch.k != FP_PEND_ROW || h->sink, "forward_pass: the pendulum's row kernel needs the handle's sink buffer");
     FDArgs a;
-    a.N = p->N; a.B = p->B; a.nalpha = nalpha;
-    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = K != nullptr; a.has_lims = lims != nullptr;
-    a.A = p->A; a.Bm = p->Bm; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active;
-    for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
+    fp_fill(a, c);
+    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = c.K != nullptr; a.has_lims = c.lims != nullptr;
+    a.lims = c.lims;
     a.g = p->g; a.l = p->l; a.h = p->h; a.d = p->d;
-    a.xnew = xnew; a.unew = unew; a.sink = (double *)h->sink; a.wrap = p->diff_wrap; a.chunked = 0;
-    // wrapped differences exist in the pendulum's own kernels only (row and lane); everything else goes to the run-time-sized kernel
-    if (p->diff_wrap != 0 && (lq || !a.sink || (ddp_env(h, ENV_FORWARD_PEND) && ddp_env(h, ENV_FORWARD_PEND)[0] == '0'))) return 1;
-    const char *fuse_env = ddp_env(h, ENV_FORWARD_FUSE);           // 0: keep the separate cost kernel (A/B timing, tests)
-    const bool fuse = p->cost_diag != 0 && !(fuse_env && fuse_env[0] == '0');     // Q, R declared diagonal: cost inside the rollout kernel
-    a.Q = p->Q; a.R = p->R; a.cnew = cnew; a.csum = csum;
+    a.sink = (double *)h->sink; a.wrap = p->diff_wrap; a.chunked = ch.chunked;
     for (int i = 0; i < 4; ++i) a.goal[i] = p->goal[i];
     int rc;
-    const char *lane_env = ddp_env(h, ENV_FORWARD_LANE);          // 1 / 0 forces the lane-per-rollout pendcart kernel on / off
-    const long total = (long)p->B * nalpha;
-    const bool lane = !lq && (lane_env ? lane_env[0] == '1' : total >= 3L * 4096);       // at least ~3 rollouts per lane of a row kernel wave
-    if (lane) {
-        const dim3 grid((unsigned)((total + DDP_WAVE - 1) / DDP_WAVE)), block(DDP_WAVE);
-        const int key = (a.has_policy ? 2 : 0) | (a.has_lims ? 1 : 0);
-#define DDP_LANE(P_, L_)                                                                                            \
-    do {                                                                                                              \
-        if (fuse) hipLaunchKernelGGL((forward_lane_pendcart_kernel<P_, L_, true>), grid, block, 0, h->stream, a);     \
-        else hipLaunchKernelGGL((forward_lane_pendcart_kernel<P_, L_, false>), grid, block, 0, h->stream, a);         \
-    } while (0)
-        if (a.wrap != 0 && a.has_policy) {                          // diff_fun with wrapped coordinates
-            if (a.has_lims && fuse) hipLaunchKernelGGL((forward_lane_pendcart_kernel<true, true, true, true>), grid, block, 0, h->stream, a);
-            else if (a.has_lims) hipLaunchKernelGGL((forward_lane_pendcart_kernel<true, true, false, true>), grid, block, 0, h->stream, a);
-            else if (fuse) hipLaunchKernelGGL((forward_lane_pendcart_kernel<true, false, true, true>), grid, block, 0, h->stream, a);
-            else hipLaunchKernelGGL((forward_lane_pendcart_kernel<true, false, false, true>), grid, block, 0, h->stream, a);
-        } else
-        switch (key) {
-        case 0: DDP_LANE(false, false); break;
-        case 1: DDP_LANE(false, true); break;
-        case 2: DDP_LANE(true, false); break;
-        case 3: DDP_LANE(true, true); break;
-        }
-#undef DDP_LANE
-        DDP_HIP(hipGetLastError());
-        rc = 0;
-    } else if (!lq && a.sink && !(ddp_env(h, ENV_FORWARD_PEND) && ddp_env(h, ENV_FORWARD_PEND)[0] == '0')) {
-        // the pendulum's own row kernel (DDP_FORWARD_PEND=0: the generic row kernel, for A/B timing and the tests of both)
-        rc = fuse ? launch_pend_row<true>(h, a) : launch_pend_row<false>(h, a);
+    if (ch.k == FP_PEND_LANE) {
+        rc = launch_pend_lane(h, a, ch.fuse, ch.wrap);
+    } else if (ch.k == FP_PEND_ROW) {
+        rc = ch.fuse ? launch_pend_row<true>(h, a, ch.wrap) : launch_pend_row<false>(h, a, ch.wrap);
     } else {
-        if (fuse) rc = lq ? launch_dpp<DDP_PROBLEM_LQ, 10, 2, true>(h, a) : launch_dpp<DDP_PROBLEM_PENDCART, 4, 1, true>(h, a);
-        else rc = lq ? launch_dpp<DDP_PROBLEM_LQ, 10, 2, false>(h, a) : launch_dpp<DDP_PROBLEM_PENDCART, 4, 1, false>(h, a);
+        if (ch.fuse) rc = lq ? launch_dpp<DDP_PROBLEM_LQ, 10, 2, true>(h, a, ch.fast) : launch_dpp<DDP_PROBLEM_PENDCART, 4, 1, true>(h, a, ch.fast);
+        else rc = lq ? launch_dpp<DDP_PROBLEM_LQ, 10, 2, false>(h, a, ch.fast) : launch_dpp<DDP_PROBLEM_PENDCART, 4, 1, false>(h, a, ch.fast);
     }
     if (rc) return rc;
-    if (fuse) return 0;                                         // cnew, csum already written
-    CostArgs c;
-    c.kind = p->kind; c.n = p->n; c.m = p->m; c.N = p->N; c.B = p->B; c.nalpha = nalpha; c.Q = p->Q; c.R = p->R;
-    c.active = active;
-    for (int i = 0; i < 4; ++i) c.goal[i] = p->goal[i];
-    c.xnew = xnew; c.unew = unew; c.cnew = cnew; c.csum = csum;
-    const dim3 cgrid((unsigned)((long)p->B * nalpha)), cblock(DDP_WAVE);
-    if (lq) hipLaunchKernelGGL((cost_kernel<DDP_PROBLEM_LQ, 10, 2>), cgrid, cblock, 0, h->stream, c);
-    else hipLaunchKernelGGL((cost_kernel<DDP_PROBLEM_PENDCART, 4, 1>), cgrid, cblock, 0, h->stream, c);
+    if (ch.fuse) return 0;                                         // cnew, csum already written
+    CostArgs ca;
+    ca.kind = p->kind; ca.n = p->n; ca.m = p->m; ca.N = p->N; ca.B = p->B; ca.nalpha = c.nalpha; ca.Q = p->Q; ca.R = p->R;
+    ca.active = c.active;
+    for (int i = 0; i < 4; ++i) ca.goal[i] = p->goal[i];
+    ca.xnew = c.xnew; ca.unew = c.unew; ca.cnew = c.cnew; ca.csum = c.csum;
+    const dim3 cgrid((unsigned)((long)p->B * c.nalpha)), cblock(DDP_WAVE);
+    if (lq) hipLaunchKernelGGL((cost_kernel<DDP_PROBLEM_LQ, 10, 2>), cgrid, cblock, 0, h->stream, ca);
+    else hipLaunchKernelGGL((cost_kernel<DDP_PROBLEM_PENDCART, 4, 1>), cgrid, cblock, 0, h->stream, ca);
     DDP_HIP(hipGetLastError());
     return 0;
 }

@@ -861,36 +861,21 @@ __global__ __launch_bounds__(DDP_WAVE * 4) void forward_pipe4_kernel(FPipeArgs a
 
 }   // namespace
 
-// returns 1 when this launch is not for the pipeline kernel (the caller goes on to the row kernel), 0 launched, <0 error
-int ddp_launch_forward_pipe(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                            const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                            const int32_t *active, double *xnew, double *unew, double *cnew, double *csum)
+// FP_PIPE4, FP_PIPE or FP_PIPE_TV, as fp_choose (forward_pass.hip) has it
+int ddp_launch_forward_pipe(ddp_handle h, const FPCall &c, const FPChoice &ch)
 {
-    if (p->kind != DDP_PROBLEM_LQ || p->n != 10 || p->m != 2 || !K || lims || !p->cost_diag || !h->sink) return 1;
-    const char *env = ddp_env(h, ENV_FORWARD_PIPE);               // 0: never, 1: whenever the shape allows (A/B timing, tests)
-    if (env && env[0] == '0') return 1;
-    const char *fuse_env = ddp_env(h, ENV_FORWARD_FUSE);
-    if (fuse_env && fuse_env[0] == '0') return 1;
-    const long total = (long)p->B * nalpha;
-    // one work-group (4 rollouts) per CU: with two the chain waves share their SIMDs and the pass is no faster than the row kernel
-    // (2 048 rollouts: 0.215 against 0.201 ms)
-    if (!(env && (env[0] == '1' || env[0] == '2')) && total > 1024) return 1;
-    if ((((uintptr_t)K | (uintptr_t)k | (uintptr_t)u | (uintptr_t)x) & 15) != 0) return 1;   // 16-byte pieces of K_i, x_i, k_i, ū_i for the DMA
-    if (p->dyn_tv && (((uintptr_t)p->A | (uintptr_t)p->Bm) & 15) != 0) return 1;
+    const ddp_problem *p = c.p;
+    DDP_CHECK(p->kind == DDP_PROBLEM_LQ && p->n == 10 && p->m == 2 && c.K && !c.lims && h->sink && (ch.k == FP_PIPE_TV) == (p->dyn_tv != 0),
+              "forward_pass: n=%d m=%d handed to the pipeline rollout (LQ (10, 2) with a policy, no limits)", p->n, p->m);
     FPipeArgs a;
-    a.N = p->N; a.B = p->B; a.nalpha = nalpha; a.dyn_batched = p->dyn_batched;
-    a.A = p->A; a.Bm = p->Bm; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.Q = p->Q; a.R = p->R; a.active = active;
-    for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
-    a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum; a.sink = (double *)h->sink;
-    const dim3 grid((unsigned)((total + 3) / 4));
+    fp_fill(a, c);
+    a.dyn_batched = p->dyn_batched; a.sink = (double *)h->sink;
+    const dim3 grid((unsigned)(((long)p->B * c.nalpha + 3) / 4));
     // time-varying dynamics: A_i, B_i (960 of the 1 232 bytes per step and rollout) come through the same image; chunks of 8 steps keep
     // three images (120 KB) in the LDS
-    h->last_kernel[1] = "forward_pipe_kernel";
-    if (p->dyn_tv) hipLaunchKernelGGL((forward_pipe_kernel<8, true, true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);
-    else if (!p->dyn_batched && !(env && env[0] == '2')) {       // shared time-invariant dynamics: one row per rollout (DDP_FORWARD_PIPE=2: the two-row kernel)
-        hipLaunchKernelGGL((forward_pipe4_kernel<true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);
-        h->last_kernel[1] = "forward_pipe4_kernel";
-    } else hipLaunchKernelGGL((forward_pipe_kernel<12, true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);
+    if (ch.k == FP_PIPE_TV) hipLaunchKernelGGL((forward_pipe_kernel<8, true, true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);
+    else if (ch.k == FP_PIPE4) hipLaunchKernelGGL((forward_pipe4_kernel<true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);   // shared time-invariant dynamics: one row per rollout
+    else hipLaunchKernelGGL((forward_pipe_kernel<12, true>), grid, dim3(DDP_WAVE * 4), 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }

@@ -233,47 +233,40 @@ __global__ __launch_bounds__(DDP_WAVE) void cost_row_kernel(FRArgs a)
 template <int NP, int MP>
 int launch_frow(ddp_handle h, const FRArgs &a)
 {
+    static void (*const kern[2][2])(FRArgs) = {{forward_row_kernel<NP, MP, false, false>, forward_row_kernel<NP, MP, false, true>},
+                                               {forward_row_kernel<NP, MP, true, false>, forward_row_kernel<NP, MP, true, true>}};      // [has_policy][has_lims]
     const long total = (long)a.B * a.nalpha;
     const dim3 grid((unsigned)((total + 3) / 4)), block(DDP_WAVE);
-    const int key = (a.has_policy ? 2 : 0) | (a.has_lims ? 1 : 0);
-    switch (key) {
-    case 0: hipLaunchKernelGGL((forward_row_kernel<NP, MP, false, false>), grid, block, 0, h->stream, a); break;
-    case 1: hipLaunchKernelGGL((forward_row_kernel<NP, MP, false, true>), grid, block, 0, h->stream, a); break;
-    case 2: hipLaunchKernelGGL((forward_row_kernel<NP, MP, true, false>), grid, block, 0, h->stream, a); break;
-    case 3: hipLaunchKernelGGL((forward_row_kernel<NP, MP, true, true>), grid, block, 0, h->stream, a); break;
-    }
+    hipLaunchKernelGGL(kern[a.has_policy][a.has_lims], grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
 }
 
 }   // namespace
 
-// LQ problems with n <= 14, m <= 4, n + m <= 16 minus the combinations the padded sizes do not hold; returns 1 when the shape (or the
-// problem kind, or a wrapped diff_fun) is not handled here, 0 launched, < 0 error
-int ddp_launch_forward_row(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0,
-                           const double *u, const double *x, const double *alpha, int nalpha, const double *lims,
-                           const int32_t *active, double *xnew, double *unew, double *cnew, double *csum)
+// LQ problems with n <= 14, m <= 4 minus the combinations the padded sizes do not hold (n > 12 with m > 2), no wrapped diff_fun
+int ddp_launch_forward_row(ddp_handle h, const FPCall &c)
 {
+    const ddp_problem *p = c.p;
     const int n = p->n, m = p->m;
-    if (p->kind != DDP_PROBLEM_LQ || p->diff_wrap != 0) return 1;
-    if (n < 1 || m < 1 || m > 4 || n > 14 || (n > 12 && m > 2) || (n > 10 && m > 4)) return 1;
+    DDP_CHECK(p->kind == DDP_PROBLEM_LQ && p->diff_wrap == 0 && n >= 1 && m >= 1 && m <= 4 && n <= 14 && !(n > 12 && m > 2),
+              "forward_pass: n=%d m=%d handed to the padded-row rollout (LQ, n <= 14, m <= 4, m <= 2 above n = 12)", n, m);
     const long N = p->N;
     FRArgs a;
-    a.n = n; a.m = m; a.N = p->N; a.B = p->B; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr;
+    fp_fill(a, c);
+    a.n = n; a.m = m; a.has_policy = c.K != nullptr; a.has_lims = c.lims != nullptr;
     const long nn = (long)n * n, nm = (long)n * m;
     a.A_t = p->dyn_tv ? nn : 0; a.A_b = p->dyn_batched ? nn * (p->dyn_tv ? N : 1) : 0;
     a.B_t = p->dyn_tv ? nm : 0; a.B_b = p->dyn_batched ? nm * (p->dyn_tv ? N : 1) : 0;
-    a.A = p->A; a.Bm = p->Bm; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.Q = p->Q; a.R = p->R; a.active = active;
-    for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
-    a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum;
+    a.lims = c.lims;
     const int np = n <= 4 ? 4 : (n + 1) & ~1, mp = m <= 2 ? 2 : 4;
-    int rc = 1;
+    int rc = -1;                                                 // (every shape that passed the check has its case)
 #define FROW_CASE(NP_, MP_) if (np == NP_ && mp == MP_) rc = launch_frow<NP_, MP_>(h, a);
     FROW_CASE(4, 2) FROW_CASE(4, 4) FROW_CASE(6, 2) FROW_CASE(6, 4) FROW_CASE(8, 2) FROW_CASE(8, 4)
     FROW_CASE(10, 2) FROW_CASE(10, 4) FROW_CASE(12, 2) FROW_CASE(12, 4) FROW_CASE(14, 2)
 #undef FROW_CASE
     if (rc) return rc;
-    const dim3 cgrid((unsigned)((long)p->B * nalpha)), cblock(DDP_WAVE);
+    const dim3 cgrid((unsigned)((long)p->B * c.nalpha)), cblock(DDP_WAVE);
     if (n <= 8 && m <= 2) hipLaunchKernelGGL((cost_row_kernel<8, 2>), cgrid, cblock, 0, h->stream, a);
     else hipLaunchKernelGGL((cost_row_kernel<14, 4>), cgrid, cblock, 0, h->stream, a);
     DDP_HIP(hipGetLastError());

@@ -137,23 +137,19 @@ __global__ __launch_bounds__(DDP_WAVE) void cost_wide_kernel(FWArgs a)
 
 }   // namespace
 
-// LQ family, n <= 64, m <= DDP_MAX_M_WIDE (the caller has checked the shape and diff_wrap)
-int ddp_launch_forward_wide(ddp_handle h, const ddp_problem *p, const double *K, const double *k, const double *x0, const double *u,
-                            const double *x, const double *alpha, int nalpha, const double *lims, const int32_t *active, double *xnew,
-                            double *unew, double *cnew, double *csum)
+// LQ family, n <= 64, m <= DDP_MAX_M_WIDE
+int ddp_launch_forward_wide(ddp_handle h, const FPCall &c)
 {
+    const ddp_problem *p = c.p;
     DDP_CHECK(p->kind == DDP_PROBLEM_LQ && p->n >= 1 && p->n <= 64 && p->m >= 1 && p->m <= DDP_MAX_M_WIDE,
               "forward_pass: n=%d m=%d outside the wide-control rollout (LQ family, n <= 64, m <= %d)", p->n, p->m, DDP_MAX_M_WIDE);
-    h->last_kernel[1] = "forward_wide_kernel";
     FWArgs a;
-    a.n = p->n; a.m = p->m; a.N = p->N; a.B = p->B; a.nalpha = nalpha;
-    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = K != nullptr; a.has_lims = lims != nullptr;
+    fp_fill(a, c);
+    a.n = p->n; a.m = p->m;
+    a.dyn_tv = p->dyn_tv; a.dyn_batched = p->dyn_batched; a.has_policy = c.K != nullptr; a.has_lims = c.lims != nullptr;
     a.wrap = p->diff_wrap;
-    a.A = p->A; a.Bm = p->Bm; a.Q = p->Q; a.R = p->R; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims;
-    a.active = active;
-    for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
-    a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum;
-    const dim3 grid((unsigned)((long)p->B * nalpha)), block(DDP_WAVE);
+    a.lims = c.lims;
+    const dim3 grid((unsigned)((long)p->B * c.nalpha)), block(DDP_WAVE);
     hipLaunchKernelGGL(forward_wide_kernel, grid, block, 0, h->stream, a);
     const size_t shmem = ((size_t)p->n * p->n + (size_t)p->m * p->m) * sizeof(double);      // <= 40 KB
     hipLaunchKernelGGL(cost_wide_kernel, grid, block, shmem, h->stream, a);

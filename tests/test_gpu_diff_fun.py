@@ -127,6 +127,37 @@ def test_diff_fun_refusals(ddp):
         ddp.forward_pass(polb, np.zeros(40), np.zeros((2, N)), np.zeros((40, N)), 1.0, big, None, ddp.WrappedDiff(3))
 
 
+def test_pendcart_of_another_shape_is_refused_before_any_kernel(ddp):
+    """the pendulum's kernels are compiled for n = 4, m = 1: a pendcart problem with n = 6 is refused by the device entry whichever kernel
+    the call would have got (default switches: the pendulum's own row kernel), and the four outputs keep their bits"""
+    import ctypes as C
+    from ddp_amd import _lib
+    from oracle import np_restatement as npr
+    h, L = ddp.default_handle(), _lib.lib()
+    n, m, N, B = 6, 1, 3, 2
+    sent = [np.uint64(0x7FF8DEAD5EED1230 + i) for i in range(4)]
+    shapes = ((n, N, B), (m, N, B), (N + 1, B), (B,))
+    bufs = []
+    try:
+        def put(a):
+            bufs.append(h.to_device(np.ascontiguousarray(a)))
+            return bufs[-1]
+        P = _lib.Problem()
+        P.kind, P.n, P.m, P.N, P.B = 1, n, m, N, B
+        P.Q, P.R = put(np.eye(n)).value, put(np.eye(m)).value
+        P.g, P.l, P.h, P.d = (npr.PENDCART[k] for k in "glhd")
+        x0, u, one = put(np.zeros((n, B))), put(np.zeros((m, N, B))), np.ones(1)
+        outs = [put(np.full(s, v, np.uint64)) for s, v in zip(shapes, sent)]
+        rc = L.ddp_forward_pass_f64_dev(h.raw, C.byref(P), None, None, x0, u, None, _lib.ptr(one), 1, None, None, *outs)
+        err = L.ddp_last_error().decode()
+        assert rc != 0 and "pendcart" in err and "n=6" in err and "m=1" in err, (rc, err)
+        for p, s, v in zip(outs, shapes, sent):
+            assert np.all(h.to_host(p, s, np.uint64) == v)
+    finally:
+        for p in bufs:
+            h.free(p)
+
+
 @pytest.mark.parametrize("hostloop", ["0", "1"])
 def test_ilqgkl_with_wrapped_diff_vs_oracle(ddp, monkeypatch, hostloop):
     """iLQGkl(...; diff_fun) (iLQGkl.jl:35,134): the mask travels with ddp_problem through the library's driver (`ddp_ilqgkl_f64`) and through
