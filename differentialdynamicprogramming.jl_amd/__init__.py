@@ -18,6 +18,7 @@ trajectories (``K[m,n,N,B]``), which the reference does not have.
 """
 from __future__ import annotations
 
+import contextlib as _contextlib
 import ctypes as _C
 import os as _os
 import time as _time
@@ -163,7 +164,8 @@ def example_source(name):
     closed loop (``plant=True``); ``"bicycle_ad"``: a kinematic bicycle whose dynamics have mixed and control curvature, for
     ``second_order=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
     for ``wave=True``; ``"chain_ddp_ad"``: the same chain with the torque entering as ``g tanh(u_j) cos(q_j)`` (curvature in x, u
-    and mixed; ``n = 2 m``, 8 parameters), for ``second_order_wave=True``."""
+    and mixed; ``n = 2 m``, 8 parameters), for ``second_order_wave=True``; ``"car_track"``, ``"car_track_ad"``, ``"car_track_plant"``: the
+    car following a sampled reference past a moving obstacle (``7 + 4 L`` parameters, the plant ``7 + 6 L``), for ``clock=True``."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -185,18 +187,24 @@ class DeviceProblem:
     ``m = 8``.  ``second_order_wave=True`` (DDP_USER_SECOND_ORDER_WAVE, implies ``wave=True``, needs ``autodiff=True``): full DDP at the
     shapes of ``wave=True`` — the backward pass is ``ddp_user_back_pass2_wave``, the step of the wide-control kernel (four waves per
     trajectory) with the curvature phase in front of it; accepted wherever a ``second_order=True`` problem is (``vhess``,
-    ``back_pass_ddp``, ``iLQG``, ``iLQG_queue``, ``iLQG_mpc``), refused by ``iLQGkl``; not together with ``second_order=True``."""
+    ``back_pass_ddp``, ``iLQG``, ``iLQG_queue``, ``iLQG_mpc``), refused by ``iLQGkl``; not together with ``second_order=True``.
+    ``clock=True`` (DDP_USER_CLOCK): a time-varying model.  ``dynamics``, ``stage_cost`` and ``derivatives`` take the absolute step
+    ``t = c + i`` as one more ``int`` behind ``i`` and ``terminal_cost`` takes ``t = c + N - 1`` behind ``x``; the clock ``c`` of every
+    trajectory comes from the ``t0=`` keyword of ``forward_pass``, ``df``, ``costfun``, ``iLQG``, ``iLQG_queue`` (one per problem),
+    ``iLQG_mpc`` (the solve at closed-loop step ``s`` runs with ``c = t0 + s``, ``plant`` gets ``t = t0 + s``) and ``kl.iLQGkl``: an int or
+    one int per trajectory, default 0.  Not together with ``second_order=True`` or ``second_order_wave=True``."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False):
+                 second_order=False, wave=False, second_order_wave=False, clock=False):
+        self.clock = bool(clock)
         self.second_order_wave = bool(second_order_wave)
         self.second_order, self.wave = bool(second_order), bool(wave) or self.second_order_wave
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
-                      (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0))
+                      (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -238,6 +246,26 @@ class DeviceProblem:
             return P, 1
         raise DDPError("DeviceProblem: params should be (%d,) or (%d, B=%d), got %s" % (self.nparam, self.nparam, B, P.shape))
 
+    @_contextlib.contextmanager
+    def _clock(self, h, t0):
+        """the clocks ``t0`` (``clock=True``; an int or one int per trajectory) for the calls inside the block (ddp_user_set_t0); every
+        clock is 0 again afterwards, also when the call raises"""
+        if t0 is None:
+            yield
+            return
+        if not self.clock:
+            raise DDPError("t0= needs a DeviceProblem made with clock=True (DDP_USER_CLOCK)")
+        t = np.atleast_1d(np.asarray(t0))
+        if t.ndim != 1 or not np.issubdtype(t.dtype, np.integer):
+            raise DDPError("t0 should be an int or a vector of ints (one per trajectory), got %s %s" % (t.dtype, t.shape))
+        t = np.ascontiguousarray(t, dtype=np.int32)
+        up = self._ptr(h)
+        _lib.check(_lib.lib().ddp_user_set_t0(up, t.ctypes.data_as(_lib.vp), len(t)))
+        try:
+            yield
+        finally:
+            _lib.lib().ddp_user_set_t0(up, None, 0)
+
     def __del__(self):
         try:
             for h, up in self._made.values():
@@ -245,6 +273,20 @@ class DeviceProblem:
             self._made = {}
         except Exception:
             pass
+
+
+def _no_clock(t0):
+    """the registered families have no clock: ``t0=`` with one of them is refused"""
+    if t0 is not None:
+        raise DDPError("t0= needs a DeviceProblem made with clock=True (DDP_USER_CLOCK)")
+
+
+def _clock(problem, h, t0):
+    """``with _clock(problem, h, t0):`` around a call — the clocks of a ``DeviceProblem(..., clock=True)``; any other problem has none"""
+    if isinstance(problem, DeviceProblem):
+        return problem._clock(h, t0)
+    _no_clock(t0)
+    return _contextlib.nullcontext()
 
 
 def _user_shapes(problem, n, m):
@@ -430,16 +472,17 @@ def _check_problem(problem, n, m, N, B):
 
 
 # ------------------------------------------------------------------------------- forward_pass
-def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None):
+def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None, t0=None):
     """Drop-in for ``forward_pass(traj_new,x0,u,x,α,f,costfun,lims,diff)`` (forward_pass.jl:9) with a
     registered ``problem`` standing in for the closures ``f``/``costfun``; ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
     ``traj_new`` may be an empty ``GaussianPolicy`` (then ``x`` is ignored, iLQG.jl:185).
     A vector ``α`` rolls all step sizes out concurrently (outputs get a trailing α axis).
-    A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in.
+    A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in; made with ``clock=True`` it takes ``t0``.
     Returns ``(xnew, unew, cnew)``."""
     if isinstance(problem, DeviceProblem):
-        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params)
+        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0)
     h = handle or default_handle()
+    _no_clock(t0)
     u, x0 = _lib.f64(u), _lib.f64(x0)
     batched = u.ndim == 3
     m, N = u.shape[:2]
@@ -474,13 +517,14 @@ def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=Non
 
 
 # ------------------------------------------------------------------------------------------ df
-def df(problem, x, u, *, handle=None, params=None):
+def df(problem, x, u, *, handle=None, params=None, t0=None):
     """The ``df`` closure of the registered families (STEP 1, iLQG.jl:225-229).  Returns
     ``(fx,fu,fxx,fxu,fuu,cx,cu,cxx,cxu,cuu)`` like the reference (second-order terms are ``[]``).
     A ``DeviceProblem`` returns its ``derivatives``: ``cxx[n,n,N(,B)]`` ... (``[n,n(,B)]`` with ``const_hessian``)."""
     if isinstance(problem, DeviceProblem):
-        return _user_df(problem, x, u, handle=handle, params=params)
+        return _user_df(problem, x, u, handle=handle, params=params, t0=t0)
     h = handle or default_handle()
+    _no_clock(t0)
     x, u = _lib.f64(x), _lib.f64(u)
     batched = u.ndim == 3
     m, N = u.shape[:2]
@@ -515,7 +559,7 @@ def _user_batch(x_or_x0, u, problem, x0_has_time=False):
     return u, batched, n, m, N, B
 
 
-def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None):
+def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None, t0=None):
     h = handle or default_handle()
     u, batched, n, m, N, B = _user_batch(x0, u, problem)
     x0 = _lib.f64(x0)
@@ -543,9 +587,10 @@ def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=No
     xnew = _lib.result_array((n, N, B, na)); unew = _lib.result_array((m, N, B, na))
     cnew = _lib.result_array((CL, B, na)); csum = np.zeros((B, na), order="F")
     up = problem._ptr(h)
-    _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
-                                                    _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
-                                                    _lib.ptr(cnew), _lib.ptr(csum)))
+    with problem._clock(h, t0):
+        _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
+                                                        _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
+                                                        _lib.ptr(cnew), _lib.ptr(csum)))
     if not batched:
         xnew, unew, cnew = xnew[:, :, 0], unew[:, :, 0], cnew[:, 0]
     if np.ndim(α) == 0:
@@ -553,7 +598,7 @@ def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=No
     return xnew, unew, cnew
 
 
-def _user_df(problem, x, u, *, handle=None, params=None):
+def _user_df(problem, x, u, *, handle=None, params=None, t0=None):
     h = handle or default_handle()
     u, batched, n, m, N, B = _user_batch(x, u, problem)
     x = _lib.f64(x)
@@ -565,8 +610,9 @@ def _user_df(problem, x, u, *, handle=None, params=None):
     cx = _lib.result_array((n, N, B)); cu = _lib.result_array((m, N, B))
     cxx = _lib.result_array((n, n) + ht + (B,)); cxu = _lib.result_array((n, m) + ht + (B,)); cuu = _lib.result_array((m, m) + ht + (B,))
     up = problem._ptr(h)
-    _lib.check(_lib.lib().ddp_user_df_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u),
-                                          *map(_lib.ptr, (fx, fu, cx, cu, cxx, cxu, cuu))))
+    with problem._clock(h, t0):
+        _lib.check(_lib.lib().ddp_user_df_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u),
+                                              *map(_lib.ptr, (fx, fu, cx, cu, cxx, cxu, cuu))))
     if not batched:
         fx, fu, cx, cu, cxx, cxu, cuu = (a[..., 0] for a in (fx, fu, cx, cu, cxx, cxu, cuu))
     e = np.zeros((0,))
@@ -623,7 +669,7 @@ def back_pass_ddp(problem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, 
     return div, GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, B)), Quu), Vx, Vxx, dV
 
 
-def costfun(problem, x, u, *, handle=None, params=None):
+def costfun(problem, x, u, *, handle=None, params=None, t0=None):
     """The ``costfun`` closure of a ``DeviceProblem`` on given trajectories: ``cost[CL(,B)]`` (CL = N, N+1 with ``terminal``)."""
     if not isinstance(problem, DeviceProblem):
         raise TypeError("costfun: a DeviceProblem is needed (the registered families evaluate their cost inside forward_pass)")
@@ -635,8 +681,9 @@ def costfun(problem, x, u, *, handle=None, params=None):
     P, pb = problem._params(B, params)
     cost = _lib.result_array((problem.cost_len(N), B))
     csum = np.zeros(B)
-    _lib.check(_lib.lib().ddp_user_costfun_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost),
-                                               _lib.ptr(csum)))
+    with problem._clock(h, t0):
+        _lib.check(_lib.lib().ddp_user_costfun_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost),
+                                                   _lib.ptr(csum)))
     return cost if batched else cost[:, 0]
 
 
@@ -661,7 +708,7 @@ STATUS = {1: "SUCCESS: gradient norm < tol_grad", 2: "SUCCESS: cost change < tol
 
 def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
          λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, verbosity=0, trace_cap=None, cost=None,
-         timing=True, diff_fun=None, handle=None, params=None):
+         timing=True, diff_fun=None, handle=None, params=None, t0=None):
     """Drop-in for ``iLQG(f,costfun,df,x0,u0; lims, α, tol_fun, ...)`` (iLQG.jl:143-163) with a registered
     ``problem`` standing in for the three closures (``diff_fun``: ``None`` = ``-``, or a ``WrappedDiff``).  ``u0[m,N,B]`` / ``x0[n,B]`` solve a batch of
     independent problems, each with its own λ schedule, line search and termination.
@@ -675,7 +722,8 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     ``trace["trace_cap"]`` is the cap used and ``trace["truncated"]`` says, per trajectory, whether it took more iterations than rows
     were kept (its later rows are missing, ``stats`` / ``iter`` are complete).
     Returns ``None`` when the initial control sequence diverges (iLQG.jl:205-210) in the unbatched case.
-    A ``DeviceProblem`` (the user's own closures as device source) takes ``params`` (default: its own); its ``diff`` is compiled in."""
+    A ``DeviceProblem`` (the user's own closures as device source) takes ``params`` (default: its own); its ``diff`` is compiled in;
+    made with ``clock=True`` it takes ``t0``, the clock of every trajectory (an int or B ints; default 0)."""
     h = handle or default_handle()
     user = isinstance(problem, DeviceProblem)
     if user:
@@ -738,10 +786,12 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     _lib.check(_lib.lib().ddp_ilqg_set_timing(h.raw, _lib.ptr(timing) if timing_on else None, tcap if timing_on else 0))
     try:
         if user:
-            _lib.check(_lib.lib().ddp_user_ilqg_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _C.byref(o), _lib.ptr(x0), int(prerolled),
-                                                    _lib.ptr(u0), _lib.ptr(c0), _lib.ptr(L), *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)),
-                                                    cap, _lib.ptr(tr7), _C.byref(git)))
+            with problem._clock(h, t0):
+                _lib.check(_lib.lib().ddp_user_ilqg_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _C.byref(o), _lib.ptr(x0), int(prerolled),
+                                                        _lib.ptr(u0), _lib.ptr(c0), _lib.ptr(L),
+                                                        *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), cap, _lib.ptr(tr7), _C.byref(git)))
         else:
+            _no_clock(t0)
             _lib.check(_lib.lib().ddp_ilqg_ex_f64(h.raw, _C.byref(dp.struct), _C.byref(o), _lib.ptr(x0), int(prerolled), _lib.ptr(u0),
                                                   _lib.ptr(c0), _lib.ptr(L), *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), cap,
                                                   _lib.ptr(tr7), _C.byref(git)))
@@ -807,11 +857,12 @@ def _user_sched_args(problem, x0, u0, L, params, diff_fun):
 
 
 def iLQG_queue(problem, x0, u0, *, slots=0, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
-               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None):
+               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None, t0=None):
     """``P = u0.shape[2]`` independent solves of ``iLQG`` through ``slots`` resident trajectories (``ddp_ilqg_queue_f64``): a slot whose
     solve has ended is flushed and armed with the next problem on the device, instead of idling until the slowest trajectory of a
     lock-step batch has ended.  Every solve is the solve ``iLQG`` performs at batch size ``slots``.
-    A ``DeviceProblem`` takes ``params`` (default: its own), ``(nparam,)`` shared or ``(nparam, P)`` one column per problem.
+    A ``DeviceProblem`` takes ``params`` (default: its own), ``(nparam,)`` shared or ``(nparam, P)`` one column per problem; made with
+    ``clock=True`` it takes ``t0``, an int or P ints: the slot that takes problem ``p`` runs with the clock ``t0[p]``.
     Returns ``(x, u, traj_new, Vx, Vxx, cost, trace)`` with P columns; ``trace`` holds ``stats[8,P]``, ``status``, ``iter``, ``global_iters``."""
     u0, x0 = _lib.f64(u0), _lib.f64(x0)
     if u0.ndim != 3 or x0.ndim != 2:
@@ -834,26 +885,30 @@ def iLQG_queue(problem, x0, u0, *, slots=0, lims=None, α=DEFAULT_ALPHA, tol_fun
     stats = np.zeros((8, P), order="F")
     git = _C.c_int(0)
     h = handle or default_handle()
-    t0 = _time.time()
+    t_start = _time.time()
     outs = tuple(map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)))
     if user:
-        _lib.check(_lib.lib().ddp_user_ilqg_queue_f64(h.raw, problem._ptr(h), N, P, _lib.ptr(prm), pb, _C.byref(o), int(slots), _lib.ptr(x0),
-                                                      _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
+        with problem._clock(h, t0):
+            _lib.check(_lib.lib().ddp_user_ilqg_queue_f64(h.raw, problem._ptr(h), N, P, _lib.ptr(prm), pb, _C.byref(o), int(slots), _lib.ptr(x0),
+                                                          _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
     else:
+        _no_clock(t0)
         _lib.check(_lib.lib().ddp_ilqg_queue_f64(h.raw, _C.byref(dp.struct), _C.byref(o), int(slots), _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L),
                                                  *outs, _C.byref(git)))
     trace = dict(stats=stats, status=stats[0].astype(int), iter=stats[1].astype(int), λ=stats[5], grad_norm=stats[6],
-                 global_iters=git.value, time_total=_time.time() - t0)
+                 global_iters=git.value, time_total=_time.time() - t_start)
     return x, u, GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, P)), Quu), Vx, Vxx, cost, trace
 
 
 def iLQG_mpc(problem, x0, u0, steps, *, zero_tail=False, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0,
-             dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None):
+             dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, diff_fun=None, handle=None, params=None, t0=None):
     """Closed loop on the device (``ddp_ilqg_mpc_f64``): every trajectory of the batch is solved ``steps`` times; after each solve the
     first control is applied (model = plant: the next initial state is ``x[:,1]`` of the solution), the control sequence is shifted by
     one step (``mpc_shift``) and the problem is solved again without returning to the host.
     A ``DeviceProblem`` takes ``params`` (default: its own), ``(nparam,)`` or ``(nparam, B)`` per trajectory; built with
-    ``plant=True`` its ``plant`` is the true system: ``xcl[:,t+1] = plant(xcl[:,t], ucl[:,t], t, p)`` starts the next solve.
+    ``plant=True`` its ``plant`` is the true system: ``xcl[:,t+1] = plant(xcl[:,t], ucl[:,t], t, p)`` starts the next solve.  Made with
+    ``clock=True`` it takes ``t0`` (an int or B ints, default 0): the solve at closed-loop step ``s`` runs with the clock ``t0 + s``, advanced
+    on the device, and ``plant`` gets the absolute ``t = t0 + s``.
     Returns ``(xcl[n,steps+1,B], ucl[m,steps,B], stats[8,steps,B], x_plan[n,N,B], u_plan[m,N,B], global_iters)``."""
     u0, x0 = _lib.f64(u0), _lib.f64(x0)
     if u0.ndim != 3 or x0.ndim != 2:
@@ -875,9 +930,11 @@ def iLQG_mpc(problem, x0, u0, steps, *, zero_tail=False, lims=None, α=DEFAULT_A
     h = handle or default_handle()
     outs = tuple(map(_lib.ptr, (xcl, ucl, scl, x, u)))
     if user:
-        _lib.check(_lib.lib().ddp_user_ilqg_mpc_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm), pb, _C.byref(o), steps, int(bool(zero_tail)),
-                                                    _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
+        with problem._clock(h, t0):
+            _lib.check(_lib.lib().ddp_user_ilqg_mpc_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm), pb, _C.byref(o), steps, int(bool(zero_tail)),
+                                                        _lib.ptr(x0), _lib.ptr(u0), _lib.ptr(L), *outs, _C.byref(git)))
     else:
+        _no_clock(t0)
         _lib.check(_lib.lib().ddp_ilqg_mpc_f64(h.raw, _C.byref(dp.struct), _C.byref(o), steps, int(bool(zero_tail)), _lib.ptr(x0), _lib.ptr(u0),
                                                _lib.ptr(L), *outs, _C.byref(git)))
     return xcl, ucl, scl, x, u, git.value

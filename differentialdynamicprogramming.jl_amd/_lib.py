@@ -34,7 +34,7 @@ EXPORTS = [
     "ddp_user_forward_pass_f64_dev", "ddp_user_forward_pass_f64", "ddp_user_costfun_f64_dev", "ddp_user_costfun_f64",
     "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64", "ddp_user_ilqg_queue_f64_dev", "ddp_user_ilqg_queue_f64", "ddp_user_ilqg_mpc_f64_dev",
     "ddp_user_ilqg_mpc_f64", "ddp_user_ilqgkl_f64_dev", "ddp_user_ilqgkl_f64",
-    "ddp_user_vhess_f64_dev", "ddp_user_vhess_f64", "ddp_user_back_pass_f64_dev", "ddp_user_back_pass_f64",
+    "ddp_user_vhess_f64_dev", "ddp_user_vhess_f64", "ddp_user_back_pass_f64_dev", "ddp_user_back_pass_f64", "ddp_user_set_t0",
 ]
 
 
@@ -77,6 +77,7 @@ class ILQGKLOpts(C.Structure):
 ILQGKL_NSTATS = 12
 USER_WAVE = 32                 # DDP_USER_WAVE: the flag of DeviceProblem(..., wave=True)
 USER_SECOND_ORDER_WAVE = 128   # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(..., second_order_wave=True); 64 is not assigned
+USER_CLOCK = 512               # DDP_USER_CLOCK: the flag of DeviceProblem(..., clock=True); 256 is not assigned
 MAX_N_USER_WAVE = 64           # DDP_MAX_N_USER_WAVE: n of a user problem with the flag (m <= 32)
 
 _lib = None
@@ -164,10 +165,14 @@ def lib():
         L.ddp_user_vhess_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci, cd, cd, cd, vp, cd]
         L.ddp_user_back_pass_f64.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 10 + [ci, cd] + [cd] * 6 + [vp]
         L.ddp_user_back_pass_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 10 + [ci, cd, vp] + [cd] * 6 + [vp]
+        if hasattr(L, "ddp_user_set_t0"):                     # DDP_USER_CLOCK; absent from A/B builds of the library from before the flag
+            L.ddp_user_set_t0.argtypes = [vp, vp, C.c_int]
         if hasattr(L, "ddp_user_program_text"):               # unlisted debug hook (tests); absent from older A/B builds of the library
             L.ddp_user_program_text.restype = C.c_char_p
             L.ddp_user_program_text.argtypes = [C.c_char_p, ci, ci, ci, ci, ci]
         for name in EXPORTS:
+            if name == "ddp_user_set_t0" and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):
                 fn.restype = C.c_int

@@ -102,10 +102,15 @@ void ddp_user_release(ddp_handle h);
 // has_plant: the closed loop of ddp_ilqg_sched_family_dev advances its trajectories with plant() instead of x_1 of the plan.
 // second_order (DDP_USER_SECOND_ORDER): STEP 2 of the iLQG drivers calls back_pass() — the family's own backward pass, with the
 // curvature of its dynamics — instead of the dispatcher of back_pass.hip; the call carries x and the slot map besides the operands.
+// t0 (DDP_USER_CLOCK, else NULL): the clock of every trajectory (problem) of the call, t0[B] on the device.  clk is the array the
+// family's kernels read, indexed by the slot they work on: t0 itself in a stand-alone call; a driver whose slots are not the caller's
+// trajectories (the slot scheduler, a compacted working set) points it at its own per-slot array for the time of the call (ClockScope).
 struct BPCall;
 struct ddp_family {
     int n, m, N, B, CL;
     bool const_hessian, has_plant, second_order = false;
+    const int32_t *t0 = nullptr;
+    mutable const int32_t *clk = nullptr;
     virtual ~ddp_family() {}
     virtual int back_pass(ddp_handle h, const BPCall &c) const { ddp_set_error("back_pass: the family has no backward pass of its own"); return -1; }
     virtual int df(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx,
@@ -121,6 +126,13 @@ struct ddp_family {
     // for that trajectory (map[b] == advp[b]).  xcl[n, steps+1, P], ucl[m, steps, P].
     virtual int plant(ddp_handle h, int S, int steps, const int32_t *adv, const int32_t *advp, const int32_t *map, const double *ucl,
                       double *xcl, double *x0s) const = 0;
+};
+// puts the family's clk back when the driver returns (every way out)
+struct ClockScope {
+    const ddp_family *f;
+    const int32_t *was;
+    explicit ClockScope(const ddp_family *f_) : f(f_), was(f_ ? f_->clk : nullptr) {}
+    ~ClockScope() { if (f) f->clk = was; }
 };
 // the device-resident iLQG of ilqg.hip for such a family (arguments as ddp_ilqg_ex_f64_dev)
 int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *o, const double *x0, int x0_prerolled, const double *u0,

@@ -289,7 +289,8 @@ struct WorkSet {            // where the state of the running trajectories lives
 
 // slot i of `dst` <- slot idx[i] of `src` (state only: x, u, cost, x0 and the scalar state machine; gains and value function are
 // recomputed by the next back pass, derivatives by the next df: dodf is set)
-__global__ __launch_bounds__(64) void gather_kernel(int n, int m, int N, int CL, const int32_t *idx, WorkSet src, WorkSet dst)
+__global__ __launch_bounds__(64) void gather_kernel(int n, int m, int N, int CL, const int32_t *idx, WorkSet src, WorkSet dst,
+                                                    const int32_t *src_clk, int32_t *dst_clk)
 {
     const int i = blockIdx.x, lane = threadIdx.x, j = idx[i];
     for (size_t e = lane; e < (size_t)n * N; e += 64) dst.x[(size_t)n * N * i + e] = src.x[(size_t)n * N * j + e];
@@ -302,6 +303,7 @@ __global__ __launch_bounds__(64) void gather_kernel(int n, int m, int N, int CL,
         dst.s.nfp[i] = src.s.nfp[j]; dst.s.flg[i] = src.s.flg[j]; dst.s.run[i] = src.s.run[j]; dst.s.dodf[i] = 1; dst.s.dofwd[i] = 0;
         dst.s.div0[i] = src.s.div0[j];
         dst.map[i] = src.map ? src.map[j] : j;
+        if (dst_clk) dst_clk[i] = src_clk[j];                       // a family with a clock: it moves with its trajectory
     }
 }
 
@@ -347,6 +349,10 @@ struct Sched {
     double *x, *u, *cost, *K, *k, *Quu, *Vx, *Vxx, *stats;
     double *xcl, *ucl, *stats_cl;       // MPC: closed-loop states [n,steps+1,P], controls [m,steps,P], summaries [8,steps,P]
     int32_t *adv, *advp;                // MPC with a plant (else NULL): step + 1 of the solve that ended in the last sched_take_kernel (0: none), its trajectory
+    // a family with a clock (else both NULL): clk[S] is the clock of the solve a slot runs, written where the slot is armed;
+    // t0[P] the clock of every problem (queue) / of every trajectory at closed-loop step 0 (MPC)
+    int32_t *clk;
+    const int32_t *t0;
 };
 
 // end of a global iteration (and once before the first): flush the slots whose solve has ended, re-arm them — one wave per slot
@@ -411,6 +417,7 @@ __global__ __launch_bounds__(TAKE_T) void sched_take_kernel(int n, int m, int N,
                     u0b[e] = (i + 1 < (size_t)N) ? ub[(i + 1) * m + c] : (q.zero_tail ? 0.0 : ub[(size_t)(N - 1) * m + c]);
                 }
                 for (int e = lane; e < n; e += TAKE_T) q.x0s[(size_t)n * b + e] = xb[(N > 1 ? n : 0) + e];
+                if (q.clk && lane == 0) q.clk[b] = q.t0[prob] + step + 1;      // the next solve of the trajectory: one step later
             } else if (valid) {                                       // the last plan
                 cp(q.x, ws.x, (size_t)n * N); cp(q.u, ws.u, (size_t)m * N);
             }
@@ -428,7 +435,7 @@ __global__ __launch_bounds__(TAKE_T) void sched_take_kernel(int n, int m, int N,
         double *u0b = q.u0s + (size_t)m * N * b;
         for (size_t e = lane; e < (size_t)m * N; e += TAKE_T) u0b[e] = u0p[e];
         for (int e = lane; e < n; e += TAKE_T) q.x0s[(size_t)n * b + e] = q.x0g[(size_t)n * head + e];
-        if (lane == 0) { q.map[b] = head; q.left[b] = q.mpc_steps; }
+        if (lane == 0) { q.map[b] = head; q.left[b] = q.mpc_steps; if (q.clk) q.clk[b] = q.t0[head]; }
     }
     // arm the slot: the scalar state of a fresh solve (init_state_kernel), the first candidate of the initial rollout (iLQG.jl:181-192)
     {
@@ -602,6 +609,7 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     ddp_problem pw = *p;                                   // the problem as the kernels see it (B = slots of the working set)
     size_t Bw = B;
     std::vector<void *> owned;                             // compacted working sets (freed on every way out)
+    ClockScope clock_scope(fam);                           // a compaction points the family's clock at the compacted copy
     struct Free { std::vector<void *> &v; ~Free() { for (void *q : v) hipFree(q); } } free_owned{owned};
     // Two schedulers for THROUGHPUT-bound batches; both leave every per-trajectory result unchanged (tests/test_gpu_edge_cases.py).
     // Up to about two waves per SIMD a pass takes the same time however many trajectories are live (each wave walks its N steps at
@@ -650,7 +658,7 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
             const size_t R = (size_t)running;
             const size_t w_d = al(n * N * R * 8) + al(m * N * R * 8) + al(CL * R * 8) + al(m * n * N * R * 8) + al(m * N * R * 8) +
                                al(m * m * N * R * 8) + al(n * N * R * 8) + al(n * n * N * R * 8) + al(n * R * 8) + 4 * al(R * 8) + 12 * al(R * 4) +
-                               al(Bw * 4) + 256;
+                               al(Bw * 4) + 256 + (fam && fam->clk ? al(R * 4) : 0);
             void *blk = nullptr;
             if (ddp_env(h, ENV_TEST_COMPACT_ALLOC_FAIL) || hipMalloc(&blk, w_d) != hipSuccess) {      // (the variable: tests of this path)
                 (void)hipGetLastError();                         // clear the sticky error: the solve goes on with the current working set
@@ -673,8 +681,11 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
             nw.s.dofwd = (int32_t *)tk(R * 4); nw.s.div0 = (int32_t *)tk(R * 4);
             nw.map = (int32_t *)tk(R * 4);
             int32_t *idx = (int32_t *)tk(Bw * 4);
+            const int32_t *clk_old = fam ? fam->clk : nullptr;
+            int32_t *clk_new = clk_old ? (int32_t *)tk(R * 4) : nullptr;
             hipLaunchKernelGGL(live_index_kernel, dim3(1), dim3(64), 0, st, (int)Bw, ws.s, idx, counter);
-            hipLaunchKernelGGL(gather_kernel, dim3((unsigned)R), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, idx, ws, nw);
+            hipLaunchKernelGGL(gather_kernel, dim3((unsigned)R), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, idx, ws, nw, clk_old, clk_new);
+            if (clk_new) fam->clk = clk_new;
             ws = nw;
             Bw = R;
             pw.B = (int)R; d.B = (int)R;
@@ -797,7 +808,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     const size_t n = p->n, m = p->m, N = p->N, P = p->B, na = oo->n_alpha, CL = fam ? fam->CL : ddp_cost_len(p);
     const bool pend = p->kind == DDP_PROBLEM_PENDCART, mpc = mpc_steps > 0;
     // a user family: own time-varying fx, fu and cost Hessians (per step, or one set per slot with const_hessian), as in ilqg_impl
-    const bool own_fx = pend || fam, chess = fam && fam->const_hessian, plant = mpc && fam && fam->has_plant;
+    const bool own_fx = pend || fam, chess = fam && fam->const_hessian, plant = mpc && fam && fam->has_plant, clocked = fam && fam->t0;
     DDP_CHECK(N >= 2, "ilqg_sched: N=%d (at least two time steps)", (int)N);
     if (mpc) slots = (int)P;                                            // every trajectory keeps its slot
     if (slots <= 0 || (size_t)slots > P) slots = (int)(P < 4096 ? P : 4096);
@@ -814,7 +825,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     const size_t bytes = 2 * f_x /* x, Vx */ + 2 * f_u /* u, k */ + f_c + f_K + f_Q + f_V + al(n * S * 8) /* x0s */ + 2 * f_u /* u0s, us */ +
                          f_x + f_u /* cx, cu */ + f_fx + f_fu + na * (f_x + f_u + f_c + f_d) /* candidates */ + (f_x + f_u + f_c + f_d) /* initial rollout */ +
                          al(2 * S * 8) + f_i /* dV, div */ + al(n * m * 8) + 4 * f_d + 10 * f_i /* Traj */ + 6 * f_i /* scheduler */ + 2 * f_i /* more */ + 512 +
-                         f_hxx + f_hxu + f_huu + (plant ? 2 * f_i : 0) /* adv, advp */;
+                         f_hxx + f_hxu + f_huu + (plant ? 2 * f_i : 0) /* adv, advp */ + (clocked ? f_i : 0) /* clk */;
     void *blk = nullptr;
     DDP_HIP(hipMalloc(&blk, bytes));
     struct Free { void *q; ~Free() { hipFree(q); } } free_blk{blk};
@@ -847,6 +858,9 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     q.qhead = (int *)take(256);
     q.x = x; q.u = u; q.cost = cost; q.K = K; q.k = k; q.Quu = Quu; q.Vx = Vx; q.Vxx = Vxx; q.stats = stats; q.xcl = xcl; q.ucl = ucl; q.stats_cl = stats_cl;
     q.adv = plant ? (int32_t *)take(f_i) : nullptr; q.advp = plant ? (int32_t *)take(f_i) : nullptr;
+    q.clk = clocked ? (int32_t *)take(f_i) : nullptr; q.t0 = clocked ? fam->t0 : nullptr;
+    ClockScope clock_scope(fam);
+    if (clocked) fam->clk = q.clk;                                     // the family's kernels read the clock of the slot they work on
     ws.map = q.map;
     DDP_CHECK(h->h_pinned, "ilqg_sched: pinned poll buffer missing");
 

@@ -121,6 +121,77 @@ bool has_identifier(const std::string &src, const char *name)
     return false;
 }
 
+// DDP_USER_CLOCK: the kernel text `text` with the absolute step handed to the user's functions (user_problem_kernels.h, at its end)
+std::string with_clock(const char *text)
+{
+    struct Rule { const char *name; int arg; char kind; };      // kind: 'i' insert behind argument `arg`, 'w' wrap it, 'n' insert N - 1
+    static const Rule rules[] = {{"dynamics", 3, 'i'}, {"stage_cost", 3, 'i'}, {"derivatives", 3, 'i'}, {"DDP_DERIVATIVES", 3, 'i'},
+                                 {"ddp_ad_derivatives", 3, 'i'}, {"ddp_ad_jacobian", 3, 'i'}, {"ddp_ad_hessian", 3, 'i'},
+                                 {"ddp_ad_hessian_block", 3, 'i'}, {"terminal_cost", 1, 'n'}, {"plant", 3, 'w'}};
+    auto ident = [](char c) { return c == '_' || (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); };
+    const std::string src(text);
+    std::string out;
+    size_t i = 0;
+    while (i < src.size()) {
+        if (src.compare(i, 2, "//") == 0) {                      // comments pass through
+            size_t e = src.find('\n', i);
+            if (e == std::string::npos) e = src.size();
+            out.append(src, i, e - i); i = e; continue;
+        }
+        if (src.compare(i, 2, "/*") == 0) {
+            size_t e = src.find("*/", i + 2);
+            e = e == std::string::npos ? src.size() : e + 2;
+            out.append(src, i, e - i); i = e; continue;
+        }
+        if (!ident(src[i]) || (i > 0 && ident(src[i - 1]))) { out.push_back(src[i++]); continue; }
+        size_t e = i;
+        while (e < src.size() && ident(src[e])) ++e;
+        const std::string word = src.substr(i, e - i);
+        const Rule *r = nullptr;
+        for (const Rule &c : rules)
+            if (word == c.name) r = &c;
+        size_t open = e;
+        if (r && open < src.size() && src[open] == '<') {         // explicit template arguments: name<...>(
+            const size_t gt = src.find('>', open);
+            open = gt == std::string::npos ? src.size() : gt + 1;
+        }
+        if (!r || open >= src.size() || src[open] != '(') { out.append(word); i = e; continue; }
+        // the arguments up to the one the rule names: [a0, a1) is argument r->arg (1-based), at parenthesis depth 0
+        size_t a0 = open + 1, a1 = a0;
+        int depth = 0, arg = 1;
+        for (size_t k = open + 1; k < src.size(); ++k) {
+            const char c = src[k];
+            if (c == '(' || c == '[') ++depth;
+            else if ((c == ')' || c == ']') && depth > 0) --depth;
+            else if (c == ',' || c == ')') {
+                if (arg == r->arg) { a1 = k; break; }
+                if (c == ')') break;
+                ++arg; a0 = k + 1;
+            }
+        }
+        if (a1 <= a0) { out.append(word); i = e; continue; }      // fewer arguments than the rule needs: not a call of the model
+        while (a0 < a1 && src[a0] == ' ') ++a0;
+        const std::string a = src.substr(a0, a1 - a0);
+        out.append(src, i, a0 - i);
+        if (r->kind == 'w') out += "DDP_PLANT_T(" + a + ")";
+        else if (r->kind == 'n') out += a + ", DDP_T(N - 1)";
+        else if (a.compare(0, 4, "int ") == 0) out += a + ", int ddp_t";
+        else out += a + ", DDP_T(" + a + ")";
+        i = a1;
+    }
+    // the clock of the kernel's slot, read once: behind every line that takes the slot's parameters
+    std::string res;
+    for (size_t b = 0; b < out.size();) {
+        size_t e = out.find('\n', b);
+        e = e == std::string::npos ? out.size() : e + 1;
+        res.append(out, b, e - b);
+        const size_t at = out.find("= ddp_params(", b);
+        if (at != std::string::npos && at < e) res += "    const int ddp_c = ddp_clock(a.clk, b);\n";
+        b = e;
+    }
+    return res;
+}
+
 int validate(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
 {
     DDP_CHECK(source, "user problem: null source");
@@ -137,8 +208,14 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK)) == 0,
               "user problem: unknown flags 0x%x", flags);
+    // deferred, not impossible: ddp_user_back_pass2 and ddp_user_back_pass2_wave evaluate the model inside the recursion (ddp_ad_vhess)
+    DDP_CHECK(!((flags & DDP_USER_CLOCK) && (flags & DDP_USER_SECOND_ORDER)),
+              "user problem: DDP_USER_CLOCK | DDP_USER_SECOND_ORDER is refused (ddp_user_back_pass2 runs the model on the horizon index)");
+    DDP_CHECK(!((flags & DDP_USER_CLOCK) && (flags & DDP_USER_SECOND_ORDER_WAVE)),
+              "user problem: DDP_USER_CLOCK | DDP_USER_SECOND_ORDER_WAVE is refused (ddp_user_back_pass2_wave runs the model on the horizon "
+              "index)");
     if (flags & DDP_USER_SECOND_ORDER_WAVE) {
         DDP_CHECK(wave, "user problem: DDP_USER_SECOND_ORDER_WAVE needs DDP_USER_WAVE (ddp_user_back_pass2_wave is the wide kernel's step)");
         DDP_CHECK(flags & DDP_USER_AUTODIFF, "user problem: DDP_USER_SECOND_ORDER_WAVE needs DDP_USER_AUTODIFF (the curvature of the dynamics is "
@@ -181,7 +258,10 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
              n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
              (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh, (flags & DDP_USER_PLANT) ? 1 : 0);
     std::string s(head);
-    const bool ad = (flags & DDP_USER_AUTODIFF) != 0, wave = (flags & DDP_USER_WAVE) != 0;
+    const bool ad = (flags & DDP_USER_AUTODIFF) != 0, wave = (flags & DDP_USER_WAVE) != 0, clock = (flags & DDP_USER_CLOCK) != 0;
+    // DDP_USER_CLOCK: the same texts with the absolute step in every call of the user's functions (a problem without the flag: the texts)
+    auto lib = [clock](const char *text) { return clock ? with_clock(text) : std::string(text); };
+    if (clock) s += "#define DDP_CLOCK 1\n";
     if (wave) {                                                  // a problem without the flag: not a byte of its text changes
         snprintf(head, sizeof head, "#define DDP_WAVE 1\n#define DDP_WG %d\n", L.wg);
         s += head;
@@ -193,24 +273,26 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
     s += "#line 1 \"user_source\"\n";
     s += source;
     if (ad) {
+        if (clock) s += kUserClockAd;
         s += "\n#line 1 \"ddp_user_autodiff_derivs\"\n";
-        s += kUserAutodiffDerivs;
+        s += lib(kUserAutodiffDerivs);
     }
     s += "\n#line 1 \"ddp_user_kernels\"\n";
-    s += DDP_USER_ABI_TEXT;
+    s += clock ? DDP_USER_ABI_CLOCK_TEXT : DDP_USER_ABI_TEXT;
     s += "\n";
+    if (clock) s += kUserClockKernels;
     s += kUserKernelsHead;
     if (wave) {
         s += "\n#line 1 \"ddp_user_wave_kernels\"\n";
-        s += kUserWaveKernels;
+        s += lib(kUserWaveKernels);
         s += "\n#line 1 \"ddp_user_kernels_shared\"\n";
-        s += kUserKernelsCost;
+        s += lib(kUserKernelsCost);
     } else {
-        s += kUserKernelsLane;
-        s += kUserKernelsCost;
+        s += lib(kUserKernelsLane);
+        s += lib(kUserKernelsCost);
         s += kUserKernelsHessians;
     }
-    s += kUserKernelsPlant;
+    s += lib(kUserKernelsPlant);
     if (flags & DDP_USER_SECOND_ORDER) {                         // a problem without the flag: the text above, nothing more
         s += "\n#define DDP_SECOND_ORDER 1\n#line 1 \"ddp_user_autodiff_vhess\"\n";
         s += kUserAutodiffVhess;
@@ -329,7 +411,16 @@ struct UserProblem final : ddp_family {
     // DDP_USER_SECOND_ORDER_WAVE: H_i of the step in flight, [n+m, n+m] per trajectory (ddp_user_back_pass2_wave); grown on demand
     mutable double *curv = nullptr;
     mutable size_t curv_bytes = 0;
-    ~UserProblem() override { if (curv) hipFree(curv); }
+    // DDP_USER_CLOCK: the clocks ddp_user_set_t0 gave (none: all 0, one: every trajectory's), and their device copy for the batch of
+    // the last call (t0 of ddp_family points at it)
+    std::vector<int32_t> t0_host;
+    int32_t *t0_dev = nullptr;
+    int t0_count = 0;                                            // entries of t0_dev that are valid (0: to be written)
+    ~UserProblem() override
+    {
+        if (curv) hipFree(curv);
+        if (t0_dev) hipFree(t0_dev);
+    }
 
     int df(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx, double *fu,
            double *cx, double *cu, double *cxx, double *cxu, double *cuu) const override
@@ -337,7 +428,7 @@ struct UserProblem final : ddp_family {
         UserDfArgs a;
         a.N = N; a.B = Bc; a.params_batched = params_batched; a.pad_ = 0;
         a.params = params; a.x = x; a.u = u; a.active = active; a.map = map;
-        a.fx = fx; a.fu = fu; a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu;
+        a.fx = fx; a.fu = fu; a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.clk = clk;
         void *args[] = {&a};
         const long R = (long)N * Bc;
         DDP_HIP(hipModuleLaunchKernel(mod->df, (unsigned)((R + mod->L.dflanes - 1) / mod->L.dflanes), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
@@ -364,7 +455,7 @@ struct UserProblem final : ddp_family {
         UserRollArgs a;
         a.N = N; a.B = Bc; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr; a.params_batched = params_batched;
         a.params = params; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active; a.map = map;
-        a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum;
+        a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum; a.clk = clk;
         for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
         void *args[] = {&a};
         const long total = (long)Bc * nalpha;
@@ -378,7 +469,7 @@ struct UserProblem final : ddp_family {
     {
         UserCostArgs a;
         a.N = N; a.B = Bc; a.params_batched = params_batched; a.pad_ = 0;
-        a.params = params; a.x = x; a.u = u; a.active = active; a.map = map; a.cost = cost; a.csum = csum;
+        a.params = params; a.x = x; a.u = u; a.active = active; a.map = map; a.cost = cost; a.csum = csum; a.clk = clk;
         void *args[] = {&a};
         DDP_HIP(hipModuleLaunchKernel(mod->cost, (unsigned)Bc, 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
         hh->last_kernel[3] = "ddp_user_cost";
@@ -391,6 +482,7 @@ struct UserProblem final : ddp_family {
         UserPlantArgs a;
         a.S = S; a.steps = steps; a.params_batched = params_batched; a.pad_ = 0;
         a.params = params; a.ucl = ucl; a.adv = adv; a.advp = advp; a.map = map; a.xcl = xcl; a.x0s = x0s;
+        a.clk = t0;                                              // (per trajectory: the slot's clock has moved on to the next solve)
         void *args[] = {&a};
         DDP_HIP(hipModuleLaunchKernel(mod->plant, (unsigned)((S + 63) / 64), 1, 1, 64, 1, 1, 0, hh->stream, args, nullptr));
         hh->last_kernel[4] = "ddp_user_plant";
@@ -463,6 +555,22 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
     P->N = N; P->B = B; P->CL = (P->flags & DDP_USER_TERMINAL) ? N + 1 : N;
     P->params = P->nparam ? params : nullptr; P->params_batched = params_batched;
     P->has_plant = false;
+    P->t0 = P->clk = nullptr;
+    if (!(P->flags & DDP_USER_CLOCK)) return 0;
+    // DDP_USER_CLOCK: one clock per trajectory (problem) of this call on the device, written when the batch or the clocks have changed
+    const int count = (int)P->t0_host.size();
+    DDP_CHECK(count <= 1 || count == B, "user problem: ddp_user_set_t0 gave %d clocks, the call has %d trajectories (1 or %d are taken)",
+              count, B, B);
+    if (P->t0_count != B) {
+        if (P->t0_dev) { DDP_HIP(hipStreamSynchronize(P->h->stream)); DDP_HIP(hipFree(P->t0_dev)); P->t0_dev = nullptr; }
+        P->t0_count = 0;
+        DDP_HIP(hipMalloc((void **)&P->t0_dev, (size_t)B * sizeof(int32_t)));
+        std::vector<int32_t> t(B, count == 1 ? P->t0_host[0] : 0);
+        if (count == B) t = P->t0_host;
+        DDP_HIP(hipMemcpy(P->t0_dev, t.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+        P->t0_count = B;
+    }
+    P->t0 = P->clk = P->t0_dev;
     return 0;
 }
 
@@ -569,6 +677,17 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
 int ddp_user_destroy(void *up)
 {
     delete (UserProblem *)up;
+    return 0;
+}
+
+int ddp_user_set_t0(void *up, const int32_t *t0, int count)
+{
+    UserProblem *P = (UserProblem *)up;
+    DDP_CHECK(P, "user problem: null problem");
+    DDP_CHECK(P->flags & DDP_USER_CLOCK, "set_t0: the problem was made without DDP_USER_CLOCK");
+    DDP_CHECK(count >= 0 && (count == 0 || t0), "set_t0: count = %d, t0 = %s", count, t0 ? "given" : "NULL");
+    P->t0_host.assign(t0, t0 + count);
+    P->t0_count = 0;                                             // the device copy is written by the next call, for its batch
     return 0;
 }
 

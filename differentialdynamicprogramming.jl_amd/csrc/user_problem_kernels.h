@@ -25,25 +25,32 @@
 
 // argument structs of the kernels: compiled into the host library and, as text (DDP_USER_ABI_TEXT), into every user program.
 // Only int / pointer / double members, so that both compilers lay them out alike.
-#define DDP_USER_ABI                                                                                                                  \
+// DDP_USER_CLOCK: the structs of the kernels that call the user's functions end in the clock pointer (clk[b] of the slot or trajectory b
+// the kernel works on; ddp_user_plant: t0[j] of trajectory j; NULL: every clock is 0).  The host always fills the long form; a program
+// without the flag is compiled with the text it always had (DDP_USER_ABI_TEXT, the structs without the member) and its kernels read
+// the leading bytes of the argument, which are laid out alike.
+#define DDP_USER_ABI_(CLK)                                                                                                               \
     struct UserRollArgs {                                                                                                            \
         int N, B, nalpha, has_policy, has_lims, params_batched;                                                                       \
         const double *params, *K, *k, *x0, *u, *x, *lims;                                                                            \
         const int *active, *map;                                                                                                     \
         double *xnew, *unew, *cnew, *csum;                                                                                           \
         double alpha[16];                                                                                                            \
+        CLK                                                                                                                          \
     };                                                                                                                               \
     struct UserDfArgs {                                                                                                              \
         int N, B, params_batched, pad_;                                                                                              \
         const double *params, *x, *u;                                                                                                \
         const int *active, *map;                                                                                                     \
         double *fx, *fu, *cx, *cu, *cxx, *cxu, *cuu;                                                                                 \
+        CLK                                                                                                                          \
     };                                                                                                                               \
     struct UserCostArgs {                                                                                                            \
         int N, B, params_batched, pad_;                                                                                              \
         const double *params, *x, *u;                                                                                                \
         const int *active, *map;                                                                                                     \
         double *cost, *csum;                                                                                                         \
+        CLK                                                                                                                          \
     };                                                                                                                               \
     struct UserHessArgs {                                                                                                            \
         int B, params_batched;                                                                                                       \
@@ -56,10 +63,13 @@
         const double *params, *ucl;                                                                                                  \
         const int *adv, *advp, *map;                                                                                                 \
         double *xcl, *x0s;                                                                                                           \
+        CLK                                                                                                                          \
     };
 #define DDP_USER_STR_(...) #__VA_ARGS__
 #define DDP_USER_STR(x) DDP_USER_STR_(x)
-#define DDP_USER_ABI_TEXT DDP_USER_STR(DDP_USER_ABI)
+#define DDP_USER_ABI DDP_USER_ABI_(const int *clk;)
+#define DDP_USER_ABI_TEXT DDP_USER_STR(DDP_USER_ABI_())
+#define DDP_USER_ABI_CLOCK_TEXT DDP_USER_STR(DDP_USER_ABI)
 
 // kUserKernels in five pieces: a problem without DDP_USER_WAVE compiles Head + Lane + Cost + Hessians + Plant (the same bytes as ever), one
 // with the flag Head + kUserWaveKernels (user_problem_wave_kernels.h) + Cost + Plant
@@ -865,4 +875,22 @@ extern "C" __global__ __launch_bounds__(256) void ddp_user_back_pass2_wave(UserB
     c.pp = ddp_params(a.params, a.params_batched, a.map, b);
     back_pass_wide_body<false, n, m>(a.w, lds, c);
 }
+)DDPK";
+
+// ---- DDP_USER_CLOCK: absolute time for the user's functions.  Every trajectory (every slot of the scheduler) has a clock c, an int, and
+// dynamics, stage_cost, derivatives and terminal_cost take the absolute step t = c + i behind i (include/ddp_amd.h).  The texts above and
+// those of user_autodiff.h are compiled byte for byte by every problem without the flag (the tests pin them), so their call sites carry
+// no macro: the program of a clocked problem is made from the SAME texts by with_clock() (user_problem.hip), which
+//   - puts DDP_T(i) behind the third argument of every call of dynamics, stage_cost, derivatives / DDP_DERIVATIVES and of the
+//     ddp_ad_* chain (`int ddp_t` where the third argument is the declaration `int i`), and DDP_T(N - 1) behind the first of terminal_cost;
+//   - wraps the third argument of plant in DDP_PLANT_T;
+//   - reads the clock once per kernel, behind the line that takes the slot's parameters: const int ddp_c = ddp_clock(a.clk, b).
+// A call that it misses does not compile (the user's functions take one argument more), so no kernel can run on the horizon index
+// alone by accident.  There is one definition of every kernel.
+static const char *kUserClockAd = "\n#define DDP_T(i) ddp_t\n";      // inside ddp_ad_*: the chain works on ONE step and carries its t
+static const char *kUserClockKernels = R"DDPK(
+#undef DDP_T
+#define DDP_T(i) (ddp_c + (i))                                // in a kernel: ddp_c is the clock of the slot or trajectory b it works on
+#define DDP_PLANT_T(t) (ddp_clock(a.clk, j) + (t))            // ddp_user_plant: t0 of trajectory j + the closed-loop step
+__device__ __forceinline__ int ddp_clock(const int *clk, int b) { return clk ? clk[b] : 0; }
 )DDPK";

@@ -546,6 +546,7 @@ const _installed = Method[]            # the methods `install!` added (what `uni
 const MAX_N = 64                       # include/ddp_amd.h: the backward kernels take n <= 64, m <= 32
 const MAX_M = 8                        # DDP_MAX_M: user problems, the KL functions, the lane-per-problem boxQP
 const MAX_N_USER_WAVE = 64             # DDP_MAX_N_USER_WAVE: user problems made with wave=true (n <= 64, m <= MAX_M_WIDE)
+const USER_CLOCK = 512                 # DDP_USER_CLOCK: the flag of DeviceProblem(...; clock=true); 256 is not assigned
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
@@ -957,7 +958,7 @@ function iLQGkl(problem::RegisteredProblem, x0, traj_prev, fx_model, R1; kl_step
 end
 
 # ---- user problems: f / costfun / df as HIP device source, compiled at run time (include/ddp_amd.h, ddp_user_*) ---------------------
-# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant, second_order, wave, second_order_wave) holds the source; it is compiled with hiprtc
+# DeviceProblem(source, n, m; nparam, params, terminal, const_hessian, autodiff, diff, plant, second_order, wave, second_order_wave, clock) holds the source; it is compiled with hiprtc
 # for the handle's device at first use (once per handle).  `params` is a vector [nparam] or a matrix [nparam, B] (one column per trajectory).
 # autodiff=true (DDP_USER_AUTODIFF): dynamics / stage_cost / terminal_cost are templates over the scalar type of x and u, the source
 # needs no `derivatives`, and df is derived on the device by forward-mode AD.
@@ -969,6 +970,10 @@ end
 # second_order_wave=true (DDP_USER_SECOND_ORDER_WAVE, implies wave=true, needs autodiff=true): full DDP at the shapes of wave=true; the
 # backward pass is ddp_user_back_pass2_wave (the wide-control kernel's step with the curvature phase in front of it).  Accepted wherever a
 # second_order=true problem is, refused by iLQGkl; not together with second_order=true.
+# clock=true (DDP_USER_CLOCK): a time-varying model — dynamics, stage_cost and derivatives take the absolute step t = c + i as one more
+# int behind i, terminal_cost takes t = c + N - 1 behind x.  The clock c of every trajectory is the keyword t0 (an integer or one per
+# trajectory / problem, default 0) of forward_pass, df, costfun, iLQG, iLQG_queue, iLQG_mpc (the solve at closed-loop step s runs with
+# t0 + s, the plant gets t = t0 + s) and iLQGkl.  Not together with second_order=true or second_order_wave=true.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -981,11 +986,11 @@ mutable struct DeviceProblem
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
-                       second_order_wave::Bool=false)
+                       second_order_wave::Bool=false, clock::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
-            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0)
+            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}())
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1006,6 +1011,20 @@ function _user_ptr(p::DeviceProblem, handle::Handle)
         r[]
     end
 end
+# f() with the clocks t0 of a clock=true problem (ddp_user_set_t0); every clock is 0 again afterwards, also when f throws
+function _with_clock(f, p::DeviceProblem, handle::Handle, t0)
+    t0 === nothing && return f()
+    (p.flags & USER_CLOCK) != 0 || throw(DDPError(-1, "t0= needs a DeviceProblem made with clock=true (DDP_USER_CLOCK)"))
+    t = t0 isa Integer ? Int32[t0] : Int32.(vec(collect(t0)))
+    up = _user_ptr(p, handle)
+    n = length(t)
+    GC.@preserve t check(@ccall libddp.ddp_user_set_t0(up::Ptr{Cvoid}, t::Ptr{Int32}, n::Cint)::Cint)
+    try
+        return f()
+    finally
+        @ccall libddp.ddp_user_set_t0(up::Ptr{Cvoid}, C_NULL::Ptr{Int32}, 0::Cint)::Cint
+    end
+end
 function _user_params(p::DeviceProblem, B, params)
     P = params === nothing ? p.params : _f64(params)
     p.nparam == 0 && return Float64[], 0
@@ -1014,7 +1033,7 @@ function _user_params(p::DeviceProblem, B, params)
     throw(DDPError(-1, "DeviceProblem: params must be [nparam] or [nparam, B]"))
 end
 
-function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff=-; handle::Handle=default_handle(), params=nothing)
+function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff=-; handle::Handle=default_handle(), params=nothing, t0=nothing)
     batched = ndims(u) == 3
     m, N = size(u, 1), size(u, 2)
     n = size(x0, 1)
@@ -1032,17 +1051,19 @@ function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff
     Kh = empty ? Float64[] : _f64(traj_new.K); kh = empty ? Float64[] : _f64(traj_new.k); xh = empty ? Float64[] : _f64(x)
     limsp = _lims(lims)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P Kh kh xh x0 u al limsp xnew unew cnew csum begin
-        check(@ccall libddp.ddp_user_forward_pass_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
-            pb::Cint, _ptr_or_null(Kh)::Ptr{Float64}, _ptr_or_null(kh)::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64},
-            _ptr_or_null(xh)::Ptr{Float64}, al::Ptr{Float64}, na::Cint, _ptr_or_null(limsp)::Ptr{Float64},
-            xnew::Ptr{Float64}, unew::Ptr{Float64}, cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P Kh kh xh x0 u al limsp xnew unew cnew csum begin
+            check(@ccall libddp.ddp_user_forward_pass_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, _ptr_or_null(Kh)::Ptr{Float64}, _ptr_or_null(kh)::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64},
+                _ptr_or_null(xh)::Ptr{Float64}, al::Ptr{Float64}, na::Cint, _ptr_or_null(limsp)::Ptr{Float64},
+                xnew::Ptr{Float64}, unew::Ptr{Float64}, cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+        end
     end
     return xnew_r, unew_r, cnew_r
 end
 
 # df(problem, x, u) -> (fx, fu, fxx, fxu, fuu, cx, cu, cxx, cxu, cuu) like the reference (second-order dynamics terms are [])
-function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)
+function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing, t0=nothing)
     batched = ndims(u) == 3
     m, N = size(u, 1), size(u, 2)
     n = size(x, 1)
@@ -1054,10 +1075,12 @@ function df(problem::DeviceProblem, x, u; handle::Handle=default_handle(), param
     cxx = result_array(n, n, ht..., bt...); cxu = result_array(n, m, ht..., bt...); cuu = result_array(m, m, ht..., bt...)
     x = _f64(x); u = _f64(u)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x u fx fu cx cu cxx cxu cuu begin
-        check(@ccall libddp.ddp_user_df_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
-            x::Ptr{Float64}, u::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64},
-            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P x u fx fu cx cu cxx cxu cuu begin
+            check(@ccall libddp.ddp_user_df_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
+                x::Ptr{Float64}, u::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64},
+                cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64})::Cint)
+        end
     end
     return fx, fu, Float64[], Float64[], Float64[], cx, cu, cxx, cxu, cuu
 end
@@ -1106,7 +1129,7 @@ function back_pass_ddp(problem::DeviceProblem, cx, cu, cxx, cxu, cuu, fx, fu, λ
     return (batched ? div : Int(div[1])), K, k, Quu, Vx, Vxx, dV
 end
 
-function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)
+function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing, t0=nothing)
     batched = ndims(u) == 3
     N = size(u, 2)
     B = batched ? size(u, 3) : 1
@@ -1114,16 +1137,18 @@ function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), 
     cost = result_array(cost_len(problem, N), (batched ? (B,) : ())...); csum = zeros(B)
     x = _f64(x); u = _f64(u)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x u cost csum begin
-        check(@ccall libddp.ddp_user_costfun_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
-            pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, cost::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P x u cost csum begin
+            check(@ccall libddp.ddp_user_costfun_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, cost::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+        end
     end
     return cost
 end
 
 function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0, cost=[], handle::Handle=default_handle(),
-              params=nothing, policy=GaussianPolicy{Float64})
+              params=nothing, t0=nothing, policy=GaussianPolicy{Float64})
     batched = ndims(u0) == 3
     m, N = size(u0, 1), size(u0, 2)
     n = size(x0, 1)
@@ -1141,11 +1166,13 @@ function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun
     c0 = (prerolled && !isempty(cost)) ? _f64(cost) : Float64[]
     limsp = _lims(lims)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x0h u0h c0 limsp x u K k Quu Vx Vxx costo stats tr7 begin
-        check(@ccall libddp.ddp_user_ilqg_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
-            Ref(o)::Ptr{ILQGOpts}, x0h::Ptr{Float64}, (prerolled ? 1 : 0)::Cint, u0h::Ptr{Float64}, _ptr_or_null(c0)::Ptr{Float64},
-            _ptr_or_null(limsp)::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64},
-            Vx::Ptr{Float64}, Vxx::Ptr{Float64}, costo::Ptr{Float64}, stats::Ptr{Float64}, cap::Cint, tr7::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P x0h u0h c0 limsp x u K k Quu Vx Vxx costo stats tr7 begin
+            check(@ccall libddp.ddp_user_ilqg_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64}, pb::Cint,
+                Ref(o)::Ptr{ILQGOpts}, x0h::Ptr{Float64}, (prerolled ? 1 : 0)::Cint, u0h::Ptr{Float64}, _ptr_or_null(c0)::Ptr{Float64},
+                _ptr_or_null(limsp)::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64},
+                Vx::Ptr{Float64}, Vxx::Ptr{Float64}, costo::Ptr{Float64}, stats::Ptr{Float64}, cap::Cint, tr7::Ptr{Float64}, git::Ptr{Cint})::Cint)
+        end
     end
     (!batched && stats[1, 1] == -1) && return nothing
     keys7 = (:λ, :dλ, :α, :improvement, :cost, :reduce_ratio, :grad_norm)
@@ -1167,7 +1194,7 @@ end
 
 function iLQG_queue(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{<:Real,3}; slots::Integer=0, lims=[], α=DEFAULT_ALPHA,
                     tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1,
-                    reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing, policy=GaussianPolicy{Float64})
+                    reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing, t0=nothing, policy=GaussianPolicy{Float64})
     n, m, N, P_ = _user_sched_check(problem, x0, u0)
     P, pb = _user_params(problem, P_, params)
     CL = cost_len(problem, N)
@@ -1177,11 +1204,13 @@ function iLQG_queue(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArra
     stats = zeros(8, P_); git = Ref{Cint}(0)
     x0h = _f64(x0); u0h = _f64(u0); limsp = _lims(lims)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x0h u0h limsp x u K k Quu Vx Vxx costo stats begin
-        check(@ccall libddp.ddp_user_ilqg_queue_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, P_::Cint, _ptr_or_null(P)::Ptr{Float64},
-            pb::Cint, Ref(o)::Ptr{ILQGOpts}, slots::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64},
-            x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
-            costo::Ptr{Float64}, stats::Ptr{Float64}, git::Ptr{Cint})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P x0h u0h limsp x u K k Quu Vx Vxx costo stats begin
+            check(@ccall libddp.ddp_user_ilqg_queue_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, P_::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, Ref(o)::Ptr{ILQGOpts}, slots::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64},
+                x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, k::Ptr{Float64}, Quu::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64},
+                costo::Ptr{Float64}, stats::Ptr{Float64}, git::Ptr{Cint})::Cint)
+        end
     end
     trace = Dict{Symbol,Any}(:stats => stats, :status => Int.(stats[1, :]), :iter => Int.(stats[2, :]), :global_iters => Int(git[]))
     return x, u, policy(N, n, m, K, k, zeros(m, m, N, P_), Quu), Vx, Vxx, costo, trace
@@ -1189,7 +1218,7 @@ end
 
 function iLQG_mpc(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{<:Real,3}, steps::Integer; zero_tail::Bool=false, lims=[],
                   α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1,
-                  reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing)
+                  reduce_ratio_min=0, handle::Handle=default_handle(), params=nothing, t0=nothing)
     n, m, N, B = _user_sched_check(problem, x0, u0)
     P, pb = _user_params(problem, B, params)
     o = _opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
@@ -1197,18 +1226,20 @@ function iLQG_mpc(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{
     x = result_array(n, N, B); u = result_array(m, N, B); git = Ref{Cint}(0)
     x0h = _f64(x0); u0h = _f64(u0); limsp = _lims(lims)
     up = _user_ptr(problem, handle)
-    GC.@preserve problem P x0h u0h limsp xcl ucl scl x u begin
-        check(@ccall libddp.ddp_user_ilqg_mpc_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
-            pb::Cint, Ref(o)::Ptr{ILQGOpts}, steps::Cint, (zero_tail ? 1 : 0)::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64},
-            _ptr_or_null(limsp)::Ptr{Float64}, xcl::Ptr{Float64}, ucl::Ptr{Float64}, scl::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64},
-            git::Ptr{Cint})::Cint)
+    _with_clock(problem, handle, t0) do
+        GC.@preserve problem P x0h u0h limsp xcl ucl scl x u begin
+            check(@ccall libddp.ddp_user_ilqg_mpc_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, Ref(o)::Ptr{ILQGOpts}, steps::Cint, (zero_tail ? 1 : 0)::Cint, x0h::Ptr{Float64}, u0h::Ptr{Float64},
+                _ptr_or_null(limsp)::Ptr{Float64}, xcl::Ptr{Float64}, ucl::Ptr{Float64}, scl::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64},
+                git::Ptr{Cint})::Cint)
+        end
     end
     return xcl, ucl, scl, x, u
 end
 
 # iLQGkl with the user's closures (`ddp_user_ilqgkl_f64`): as the method for registered problems; `fx_model = nothing` means the
 # problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B]
-function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
+function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, t0=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
                 ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
                 wide::Bool=false)
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
@@ -1240,14 +1271,16 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
     cnew, cnew_r = result_pair((CL, B), (CL, bt...)); dV = zeros(2, B); st = zeros(12, B)
     its = Ref{Cint}(0)
     up = _user_ptr(problem, handle)
-    _with_kl_wide(handle, wide) do
-        GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
-            check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
-                pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
-                Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
-                R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
-                S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
-                its::Ptr{Cint})::Cint)
+    _with_clock(problem, handle, t0) do
+        _with_kl_wide(handle, wide) do
+            GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
+                check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                    pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
+                    Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
+                    R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+                    S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
+                    its::Ptr{Cint})::Cint)
+            end
         end
     end
     trace = Dict{Symbol,Any}(:status => Int.(st[1, :]), :iter => Int.(st[2, :]), :n_backpass => Int.(st[3, :]), :satisfied => st[4, :] .!= 0,

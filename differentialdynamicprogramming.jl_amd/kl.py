@@ -32,7 +32,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from . import DDPError, DeviceProblem, GaussianPolicy, _DevProblem, _lims, _user_shapes, default_handle, df, forward_pass
+from . import DDPError, DeviceProblem, GaussianPolicy, _clock, _DevProblem, _lims, _user_shapes, default_handle, df, forward_pass
 
 __all__ = ["Model", "grad_kl", "∇kl", "back_pass_gps", "forward_covariance", "kl_div_wiki", "calc_η", "geom", "iLQGkl",
            "model_covariance", "demo_linear_kl"]
@@ -207,7 +207,7 @@ def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, ha
 
 
 def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50, cost=None, ηbracket=(1e-8, 1.0, 1e16),
-           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False):
+           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False, t0=None):
     """``iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step, lims, max_iter, cost, ηbracket, del0)`` with a registered
     ``problem`` or a ``DeviceProblem`` (the user's closures as device source; ``params`` as in ``iLQG``) standing in for the three
     closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the pre-rolled trajectory (the reference errors otherwise,
@@ -216,7 +216,9 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     Returns ``(x, u, traj_new, Vx, Vxx, cost, trace)``; ``trace`` is a dict of per-trajectory arrays
     (status 1 SUCCESS :169 / 2 η > ηmax :174 / 3 max_iter :234, iter, η bracket, divergence, n_backpass).
     The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead.
-    ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``."""
+    ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``.
+    ``t0``: the clock of every trajectory of a ``DeviceProblem`` made with ``clock=True`` (an int or B ints, default 0): STEP 1 and
+    every rollout evaluate the model at the absolute step ``t0 + i``."""
     if constrain_per_step:
         raise NotImplementedError("constrain_per_step (iLQGkl.jl:180-232) is not offloaded")
     if isinstance(problem, DeviceProblem) and problem.second_order_wave:
@@ -245,20 +247,20 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     del0 = np.full(B, float(del0))
     import os as _os
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
-        with _wide(h, wide):
+        with _wide(h, wide), _clock(problem, h, t0):
             return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm)
-    with _wide(h, wide):
-        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide)
+    with _wide(h, wide), _clock(problem, h, t0):           # (the clocks are checked here; the array calls below set their own)
+        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0)
 
 
-def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide):
+def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0=None):
     """DDP_KL_HOSTLOOP=1 (the body of iLQGkl on host arrays)"""
     n, N, B = x.shape
     m = u.shape[0]
     # ---- DDP_KL_HOSTLOOP=1: the loop of the reference on host arrays, one library call per array operation (cross-check in the tests)
     # STEP 1 (:86): the KL demos hand 3-D arrays to back_pass_gps (demo_linear.jl:91-101)
     if user:
-        fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h, params=prm[0])
+        fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h, params=prm[0], t0=t0)
         hb = problem.const_hessian                             # constant Hessians [.,.,B]: the time axis back_pass_gps wants
         cxx, cxu, cuu = _tv(cxx, N, hb), _tv(cxu, N, hb), _tv(cuu, N, hb)
         if model.fx is None:
@@ -313,7 +315,8 @@ def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, et
         sel = (lambda a: a) if allB else (lambda a: a[..., idx])                                                # noqa: E731
         pb = _SubProblem(problem, idx, B, prm[0]) if user else (problem if allB else _SubProblem(problem, idx, B))
         xs = sel(x)
-        xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h)                  # :132
+        ts = t0 if (t0 is None or np.size(t0) == 1) else np.asarray(t0)[idx]      # the clocks of the trajectories rolled out
+        xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h, t0=ts)           # :132
         del pb                                                 # (a DeviceProblem slice frees its compiled-problem pointer here)
         mdl = Model(model.fx if (np.ndim(model.fx) == 3 or allB) else model.fx[..., idx], model.fu, model.R1)
         sig = forward_covariance(mdl, xs, sel(u), new, handle=h, wide=wide)                                     # :133

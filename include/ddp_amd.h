@@ -578,12 +578,37 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * is sized for n <= 32, m <= 8; full DDP at these shapes is DDP_USER_SECOND_ORDER_WAVE, above), and ddp_user_ilqgkl_* refuses a problem with n > 32 or m > 8 before any launch unless the handle's
  * ddp_kl_set_wide switch is on (back_pass_gps has no kernel there otherwise).  diff_wrap names coordinates below 32 only.  The backward pass of a solve is the one ddp_back_pass_f64 chooses for
  * the shape (32 < n <= 64, m <= 8: the MFMA kernels; m > 8: back_pass_wide).  user_examples/chain_ad.hip is a model with 7 parameters
- * at every size.  A problem without the flag compiles the text it always did and refuses n > 32, m > 8. */
+ * at every size.  A problem without the flag compiles the text it always did and refuses n > 32, m > 8.
+ *
+ * DDP_USER_CLOCK: absolute time for a time-varying model (a reference that moves, a moving obstacle, a gain or disturbance schedule
+ * sampled in params), also where the solve is one of many in a closed loop or a queue.  Every trajectory has a clock c, an int32, and
+ * the user's functions take the absolute step t = c + i as one more int behind i:
+ *
+ *   __device__ void   dynamics(const double *x, const double *u, int i, int t, const double *p, double *xnext);
+ *   __device__ double stage_cost(const double *x, const double *u, int i, int t, const double *p);
+ *   __device__ double terminal_cost(const double *x, int t, const double *p);                              t = c + N - 1
+ *   __device__ void   derivatives(const double *x, const double *u, int i, int t, int N, const double *p, double *fx, ...);
+ *
+ * and the templates of DDP_USER_AUTODIFF the same way.  i and N keep their meaning (i == N-1 is still the terminal step);
+ * cost_hessians(p, ...) is unchanged (constant per solve by its contract); plant keeps its signature, and its t is absolute under the
+ * flag: t0 + s at closed-loop step s.  The clocks come from ddp_user_set_t0 (below): none (the state after ddp_user_create: every clock
+ * is 0), one value for every trajectory, or one per trajectory (per problem of the queue); a call whose batch or problem count is
+ * neither 1 nor that count is refused before any launch.  Clock of trajectory or problem b:
+ *   ddp_user_forward_pass_*, ddp_user_df_*, ddp_user_costfun_*, ddp_user_ilqg_*, ddp_user_ilqgkl_*     c = t0[b]
+ *   ddp_user_ilqg_queue_*    the slot that takes problem p runs with c = t0[p]
+ *   ddp_user_ilqg_mpc_*      the solve at closed-loop step s of trajectory b runs with c = t0[b] + s, the plant call after it gets
+ *                            t = t0[b] + s; the clock advances on the device, where the slot is armed again (no host work per step)
+ * Legal with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_WAVE and diff_wrap.  Together with
+ * DDP_USER_SECOND_ORDER or DDP_USER_SECOND_ORDER_WAVE it is refused by name: their backward kernels evaluate the model inside the
+ * recursion and would have to carry the clock as well — deferred, not impossible.  The kernels are the ones of a problem without the
+ * flag (same names, same text, with t handed on at every call of the user's functions); such a problem compiles and runs exactly as
+ * before.  user_examples/car_track.hip, car_track_ad.hip and car_track_plant.hip follow a sampled reference past a moving obstacle.
+ * Bits 64 and 256 of the flags are not assigned and stay refused as unknown. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
-       DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128 };      /* 64: not assigned, refused as unknown */
+       DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512 };      /* 64: not assigned, refused as unknown (256 too) */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
@@ -592,6 +617,10 @@ const char *ddp_user_compile_log(void);
 /* compile (or take from the handle's cache) and load on the handle's device: *out is the problem, used with this handle only */
 int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out);
 int ddp_user_destroy(void *up);
+/* DDP_USER_CLOCK problems only (others are refused by name): the clocks of the following calls.  t0 is a host pointer and is copied;
+ * count = 0: every clock is 0; 1: one value for every trajectory; B (P for the queue): one per trajectory or problem.  The problem
+ * owns the device copy (ddp_user_destroy frees it).                                                                             */
+int ddp_user_set_t0(void *up, const int32_t *t0, int count);
 /* df: x[n,N,B] u[m,N,B] -> fx[n,n,N,B] fu[n,m,N,B] cx[n,N,B] cu[m,N,B], cxx[n,n,N,B] cxu[n,m,N,B] cuu[m,m,N,B] (CONST_HESSIAN: [.,.,B]);
  * fx .. cu may not be NULL, the Hessians may (not computed then).  `active` as in ddp_back_pass_f64_dev.                        */
 int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
