@@ -226,7 +226,8 @@ class Handle:
         return self._h
 
     def last_kernel(self, which=0):
-        """kernel of the last back_pass (0) / forward_pass (1) dispatch, or user-problem derivative (2) / cost (3) kernel (ddp_last_kernel)"""
+        """kernel of the last back_pass (0) / forward_pass (1) dispatch, user-problem derivative (2) / cost (3) / plant (4) kernel, or
+        forward_covariance (5) / kl_div_wiki (6) kernel (ddp_last_kernel)"""
         return lib().ddp_last_kernel(self._h, int(which)).decode()
 
     def set_kl_wide(self, on):

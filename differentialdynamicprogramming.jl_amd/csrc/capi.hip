@@ -43,7 +43,8 @@ int ddp_reload_env(ddp_handle h)
 
 const char *ddp_last_kernel(ddp_handle h, int which)
 {
-    if (!h || which < 0 || which > 4 || !h->last_kernel[which]) return "";
+    // slots: 0 backward pass, 1 forward pass, 2 user derivatives, 3 user cost, 4 user plant, 5 forward_covariance, 6 kl_div_wiki
+    if (!h || which < 0 || which > 6 || !h->last_kernel[which]) return "";
     return h->last_kernel[which];
 }
 
@@ -67,7 +68,7 @@ static int create_impl(int device, void *ext_stream, bool adopt, ddp_handle *out
     h->device = device;
     h->scratch = nullptr;
     h->scratch_bytes = 0;
-    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->sh_last_stream = nullptr; h->sh_launched = false; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } h->last_kernel[0] = h->last_kernel[1] = nullptr; ddp_reload_env(h);
+    h->pad = nullptr; h->pad_bytes = 0; h->sink = nullptr; h->sh = nullptr; h->sh_bytes = 0; h->sh_timeouts = 0; h->sh_last_stream = nullptr; h->sh_launched = false; h->ncu = 0; h->sched_aux = nullptr; h->diag_next = 0; h->diag_skip = 0; for (auto &e : h->diag_cache) { e.Q = e.R = nullptr; e.n = e.m = e.ok = 0; } for (auto &lk : h->last_kernel) lk = nullptr; ddp_reload_env(h);
     h->h_pinned = nullptr;
     h->timing = nullptr; h->timing_cap = 0; h->tev_ok = false; h->kl_wide = 0;
     h->owns_stream = !adopt;

@@ -40,7 +40,7 @@ struct ddp_handle_s {
     hipEvent_t   sched_ev[2];
     char         envv[ENV_COUNT][24];
     bool         envset[ENV_COUNT];
-    const char  *last_kernel[5];  // what the last backward / forward / user-derivative / user-cost / user-plant dispatch launched (ddp_last_kernel)
+    const char  *last_kernel[7];  // what the last backward / forward / user-derivative / user-cost / user-plant / forward_covariance / kl_div_wiki dispatch launched (ddp_last_kernel)
     void        *sink;            // 4 KB of device memory that masked-out lanes may write (stores without an exec-mask branch) + a flag word (df.hip)
     std::vector<std::pair<const void *, int>> lds_raised;   // kernels whose dynamic-LDS limit has been raised on this device, to how many bytes
     double      *timing;          // ddp_ilqg_set_timing: host buffer [3, timing_cap] or NULL

@@ -400,7 +400,7 @@ __device__ __forceinline__ double kl_div_step(int n_, int m_, const double *xn, 
         }
     }
     v += 0.5 * (q2 + tr2) + q3;                                          // :93-94
-    return v > 0.0 ? v : 0.0;                                            // :101
+    return v <= 0.0 ? 0.0 : v;                                           // :101 max(0, v): a NaN stays a NaN, -0.0 becomes 0.0
 }
 
 __global__ __launch_bounds__(DDP_WAVE) void kl_div_kernel(int n, int m, int N, const double *__restrict__ xnew,
@@ -677,6 +677,52 @@ GpsKernel gps_choose2(const ddp_bp_desc &d, int eta_tv, int caller, const char *
     return sh ? GPS_WIDE : gps_choose(d, eta_tv, caller, gps_mid, gps_q4, gps_lane);
 }
 
+// ---- forward_covariance and kl_div_wiki kernel choice, host facts only (fcov_choose, kl_div_choose: what the two entry points launch;
+// the names are what ddp_last_kernel(h, 5) and (h, 6) report).
+// forward_covariance.  q4<M>: n = 4, m = M <= 2 on the matrix cores, four trajectories per wave (needs the handle's sink buffer;
+// DDP_FCOV_Q4=0: not); q4l: its m = 1 variant with chunks of eight steps through the LDS — N a multiple of 8 and >= 16, fx, K, Sigma and
+// sigmanew 16-byte aligned, B <= 6144 (DDP_FCOV_Q4L=0: not); generic: the run-time-sized kernel, every n <= 32, m <= 8; wide: kl_shape.
+enum FcovKernel { FCOV_GENERIC, FCOV_Q4_1, FCOV_Q4_2, FCOV_Q4L, FCOV_WIDE, FCOV_NONE };
+const char *const fcov_kernel_name[] = {"fcov_kernel", "fcov_q4_kernel<1>", "fcov_q4_kernel<2>", "fcov_q4l_kernel", "fcov_wide_kernel", "none"};
+
+FcovKernel fcov_choose(int n, int m, int N, int B, bool al16, bool sink, int wide_on, const char *gps_wide, const char *fcov_q4,
+                       const char *fcov_q4l)
+{
+    const int sh = kl_shape(n, m, wide_on, gps_wide);
+    if (sh < 0 || N < 1 || B < 1) return FCOV_NONE;
+    if (sh) return FCOV_WIDE;
+    if (n == 4 && (m == 1 || m == 2) && sink && !(fcov_q4 && fcov_q4[0] == '0')) {
+        if (m == 1 && N % FQL_CH == 0 && N >= 2 * FQL_CH && al16 && B <= 6144 && !(fcov_q4l && fcov_q4l[0] == '0')) return FCOV_Q4L;
+        return m == 1 ? FCOV_Q4_1 : FCOV_Q4_2;
+    }
+    return FCOV_GENERIC;
+}
+
+// kl_div_wiki.  lds: the operands of 64 steps through an LDS image when that fits 48 KB (DDP_KL_LDS=0: not) — <4,1> and <4,2> with
+// compile-time sizes, <0,0> the run-time-sized staging loop; direct: every n <= 32, m <= 8 from global memory; wide: kl_shape.
+enum KlDivKernel { KLDIV_DIRECT, KLDIV_LDS41, KLDIV_LDS42, KLDIV_LDS00, KLDIV_WIDE, KLDIV_NONE };
+const char *const kl_div_kernel_name[] = {"kl_div_kernel", "kl_div_lds_kernel<4,1>", "kl_div_lds_kernel<4,2>", "kl_div_lds_kernel<0,0>",
+                                          "kl_div_wide_kernel", "none"};
+
+// bytes of the LDS image of 64 steps: the ten operands of a step, each at an odd stride
+size_t kl_div_image(int n, int m)
+{
+    const int lens[10] = {n, n, (n + m) * (n + m), n * m, m, m * m, n * m, m, m * m, m * m};
+    size_t image = 0;
+    for (int l : lens) image += (size_t)(l | 1) * DDP_WAVE * sizeof(double);
+    return image;
+}
+
+KlDivKernel kl_div_choose(int n, int m, int N, int B, int wide_on, const char *gps_wide, const char *kl_lds)
+{
+    const int sh = kl_shape(n, m, wide_on, gps_wide);
+    if (sh < 0 || N < 1 || B < 1) return KLDIV_NONE;
+    if (sh) return KLDIV_WIDE;
+    if (kl_div_image(n, m) <= 48 * 1024 && !(kl_lds && kl_lds[0] == '0'))
+        return (n == 4 && m == 1) ? KLDIV_LDS41 : (n == 4 && m == 2) ? KLDIV_LDS42 : KLDIV_LDS00;
+    return KLDIV_DIRECT;
+}
+
 int gps_dispatch(ddp_handle h, const BPCall &c, int caller)
 {
     const ddp_kl_cost_terms *kl = c.kl;
@@ -754,6 +800,20 @@ const char *ddp_gps_choice2(const ddp_bp_desc *d, int eta_tv, int caller, const 
     return gps_kernel_name[gps_choose2(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane, wide_on, gps_wide)];
 }
 
+// Unlisted debug hooks (not in ddp_amd.h): the names ddp_last_kernel(h, 5) / (h, 6) report after a forward_covariance / kl_div_wiki with
+// these facts — fcov_choose and kl_div_choose, the functions the entry points call, callable without a GPU.  al16: fx, K, Sigma and sigmanew
+// are 16-byte aligned; sink: the handle has its sink buffer; wide_on: ddp_kl_set_wide; the switches DDP_GPS_WIDE, DDP_FCOV_Q4, DDP_FCOV_Q4L,
+// DDP_KL_LDS as strings (NULL: unset).  "none": the call is refused.
+const char *ddp_fcov_choice(int n, int m, int N, int B, int al16, int sink, int wide_on, const char *gps_wide, const char *fcov_q4,
+                            const char *fcov_q4l)
+{
+    return fcov_kernel_name[fcov_choose(n, m, N, B, al16 != 0, sink != 0, wide_on, gps_wide, fcov_q4, fcov_q4l)];
+}
+const char *ddp_kl_div_choice(int n, int m, int N, int B, int wide_on, const char *gps_wide, const char *kl_lds)
+{
+    return kl_div_kernel_name[kl_div_choose(n, m, N, B, wide_on, gps_wide, kl_lds)];
+}
+
 int ddp_kl_set_wide(ddp_handle h, int on)
 {
     if (!h) { ddp_set_error("null handle"); return -1; }
@@ -767,23 +827,28 @@ int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, con
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && fx && R1 && K && Sigma && sigmanew, "forward_covariance: null argument");
-    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1) return ddp_launch_fcov_wide(h, n, m, N, B, fx, fx_batched, R1, K, Sigma, sigmanew);
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "forward_covariance: bad sizes n=%d m=%d N=%d B=%d (n <= %d, "
-              "m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
-    const char *q4env = ddp_env(h, ENV_FCOV_Q4);                     // 0: the run-time-sized kernel for every shape (cross-check in the tests)
-    if (n == 4 && (m == 1 || m == 2) && h->sink && !(q4env && q4env[0] == '0')) {
-        const dim3 grid((unsigned)((B + 3) / 4)), block(DDP_WAVE);
-        const char *le = ddp_env(h, ENV_FCOV_Q4L);                     // 0: the step-by-step kernel (A/B timing, cross-check in the tests)
-        const bool al16 = ((((uintptr_t)fx | (uintptr_t)K | (uintptr_t)Sigma | (uintptr_t)sigmanew) & 15) == 0);
-        if (m == 1 && N % FQL_CH == 0 && N >= 2 * FQL_CH && al16 && B <= 6144 && !(le && le[0] == '0'))
-            hipLaunchKernelGGL(fcov_q4l_kernel, grid, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
-        else if (m == 1) hipLaunchKernelGGL(fcov_q4_kernel<1>, grid, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
-        else hipLaunchKernelGGL(fcov_q4_kernel<2>, grid, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
-        DDP_HIP(hipGetLastError());
-        return 0;
+    const bool al16 = ((((uintptr_t)fx | (uintptr_t)K | (uintptr_t)Sigma | (uintptr_t)sigmanew) & 15) == 0);
+    // DDP_FCOV_Q4=0: the run-time-sized kernel for every shape; DDP_FCOV_Q4L=0: the step-by-step q4 kernel (cross-checks in the tests)
+    const FcovKernel kern = fcov_choose(n, m, N, B, al16, h->sink != nullptr, h->kl_wide, ddp_env(h, ENV_GPS_WIDE), ddp_env(h, ENV_FCOV_Q4),
+                                        ddp_env(h, ENV_FCOV_Q4L));
+    if (kern == FCOV_WIDE) {
+        const int rc = ddp_launch_fcov_wide(h, n, m, N, B, fx, fx_batched, R1, K, Sigma, sigmanew);
+        if (!rc) h->last_kernel[5] = fcov_kernel_name[kern];
+        return rc;
     }
-    hipLaunchKernelGGL(fcov_kernel, dim3(B), dim3(DDP_WAVE), fcov_lds(n, m), h->stream, n, m, N, fx, fx_batched, R1, K, Sigma, sigmanew);
+    DDP_CHECK(kern != FCOV_NONE, "forward_covariance: bad sizes n=%d m=%d N=%d B=%d (n <= %d, "
+              "m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
+    const dim3 grid4((unsigned)((B + 3) / 4)), block(DDP_WAVE);
+    if (kern == FCOV_Q4L)
+        hipLaunchKernelGGL(fcov_q4l_kernel, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
+    else if (kern == FCOV_Q4_1)
+        hipLaunchKernelGGL(fcov_q4_kernel<1>, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
+    else if (kern == FCOV_Q4_2)
+        hipLaunchKernelGGL(fcov_q4_kernel<2>, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
+    else
+        hipLaunchKernelGGL(fcov_kernel, dim3(B), block, fcov_lds(n, m), h->stream, n, m, N, fx, fx_batched, R1, K, Sigma, sigmanew);
     DDP_HIP(hipGetLastError());
+    h->last_kernel[5] = fcov_kernel_name[kern];
     return 0;
 }
 
@@ -794,23 +859,25 @@ int ddp_kl_div_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *x
 {
     DDP_DEVICE(h);
     DDP_CHECK(h && xnew && xold && sigmanew && Kn && kn && Sn && Kp && kp && Sp && Sip && kldiv && klmean, "kl_div: null argument");
-    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1)
-        return ddp_launch_kl_div_wide(h, n, m, N, B, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip, kldiv, klmean);
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_div: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
+    const KlDivKernel kern = kl_div_choose(n, m, N, B, h->kl_wide, ddp_env(h, ENV_GPS_WIDE), ddp_env(h, ENV_KL_LDS));
+    if (kern == KLDIV_WIDE) {
+        const int rc = ddp_launch_kl_div_wide(h, n, m, N, B, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip, kldiv, klmean);
+        if (!rc) h->last_kernel[6] = kl_div_kernel_name[kern];
+        return rc;
+    }
+    DDP_CHECK(kern != KLDIV_NONE, "kl_div: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
               "after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     // operands through an LDS image of 64 steps when that fits (DDP_KL_LDS=0: the direct kernel, cross-check in the tests)
-    const int lens[10] = {n, n, (n + m) * (n + m), n * m, m, m * m, n * m, m, m * m, m * m};
-    size_t image = 0;
-    for (int l : lens) image += (size_t)(l | 1) * DDP_WAVE * sizeof(double);
-    const char *lenv = ddp_env(h, ENV_KL_LDS);
-    if (image <= 48 * 1024 && !(lenv && lenv[0] == '0')) {
+    if (kern != KLDIV_DIRECT) {
+        const int lens[10] = {n, n, (n + m) * (n + m), n * m, m, m * m, n * m, m, m * m, m * m};
+        const size_t image = kl_div_image(n, m);
         const double *ptr[10] = {xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip};
         KlSrc a[10];
         for (int i = 0; i < 10; ++i) a[i] = KlSrc{ptr[i], lens[i]};
 #define DDP_KLL(NC_, MC_) hipLaunchKernelGGL((kl_div_lds_kernel<NC_, MC_>), dim3(B), dim3(DDP_WAVE), image, h->stream, n, m, N, a[0], a[1], a[2], \
                                              a[3], a[4], a[5], a[6], a[7], a[8], a[9], kldiv, klmean)
-        if (n == 4 && m == 1) DDP_KLL(4, 1);
-        else if (n == 4 && m == 2) DDP_KLL(4, 2);
+        if (kern == KLDIV_LDS41) DDP_KLL(4, 1);
+        else if (kern == KLDIV_LDS42) DDP_KLL(4, 2);
         else DDP_KLL(0, 0);
 #undef DDP_KLL
     } else {
@@ -818,6 +885,7 @@ int ddp_kl_div_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *x
                            kldiv, klmean);
     }
     DDP_HIP(hipGetLastError());
+    h->last_kernel[6] = kl_div_kernel_name[kern];
     return 0;
 }
 

@@ -293,7 +293,7 @@ __global__ __launch_bounds__(DDP_WAVE) void kl_div_wide_kernel(int n, int m, int
     const double tr2 = kw_sum(tc, sb, lane, n);
     v += 0.5 * (q2 + tr2) + q3;                                         // :93-94
     if (lane == 0) {
-        kldiv[tb] = v > 0.0 ? v : 0.0;                                  // :101
+        kldiv[tb] = v <= 0.0 ? 0.0 : v;                                 // :101 max(0, v): a NaN stays a NaN
         if (sp < 0 || sn < 0) klmean[tb / (size_t)N] = INFINITY;
     }
 }

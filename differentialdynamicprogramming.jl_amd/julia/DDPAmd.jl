@@ -144,7 +144,7 @@ sync(h::Handle=default_handle()) = check(@ccall libddp.ddp_sync(h.ptr::Ptr{Cvoid
 device_count() = Int(@ccall libddp.ddp_device_count()::Cint)
 "re-read the DDP_* switches (kernel choice for A/B timing / tests) for this handle; they are read once, in ddp_create"
 reload_env(h::Handle=default_handle()) = check(@ccall libddp.ddp_reload_env(h.ptr::Ptr{Cvoid})::Cint)
-"kernel of the last back_pass (0) / forward_pass (1) dispatch of the handle (debug query)"
+"kernel of the last back_pass (0) / forward_pass (1) dispatch of the handle, of its last user-problem derivative (2) / cost (3) / plant (4) call, or of its last forward_covariance (5) / kl_div_wiki (6) (debug query)"
 last_kernel(which::Integer=0; handle::Handle=default_handle()) = unsafe_string(@ccall libddp.ddp_last_kernel(handle.ptr::Ptr{Cvoid}, which::Cint)::Cstring)
 # tiles of the shared-operand backward pass that gave their trajectories to the per-trajectory kernels after a timed-out wait (0 in a healthy run)
 sh_timeouts(; handle::Handle=default_handle()) = Int(@ccall libddp.ddp_sh_timeouts(handle.ptr::Ptr{Cvoid})::Cint)

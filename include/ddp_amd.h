@@ -45,7 +45,9 @@ int  ddp_reload_env(ddp_handle h);
 /* name of the kernel the last back_pass (which = 0) / forward_pass (which = 1) dispatch of this handle launched ("" before the first
  * one): a debug query — the tests assert through it that the timed path is the one they checked.  which = 2 / 3: the last derivative /
  * cost kernel of a user problem (ddp_user_df*, ddp_user_costfun*; the hessians of DDP_USER_CONST_HESSIAN count as derivatives);
- * which = 4: the plant kernel of a user problem's closed loop (ddp_user_plant).                                                    */
+ * which = 4: the plant kernel of a user problem's closed loop (ddp_user_plant).  which = 5 / 6: the kernel of the last
+ * ddp_forward_covariance_* / ddp_kl_div_* call, the iLQGkl drivers' included (fcov_kernel, fcov_q4_kernel<1|2>, fcov_q4l_kernel,
+ * fcov_wide_kernel / kl_div_kernel, kl_div_lds_kernel<4,1|4,2|0,0>, kl_div_wide_kernel).                                           */
 const char *ddp_last_kernel(ddp_handle h, int which);
 /* The shared-operand backward pass (one fx, fu, cxx, cxu, cuu for the batch) hands work between work-groups of one launch; every such
  * wait is time-bounded (4 s).  A tile whose wait ran out gives its trajectories to the per-trajectory kernels launched behind it — the

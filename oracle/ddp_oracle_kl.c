@@ -438,7 +438,7 @@ int ddp_oracle_kl_div_wiki(int n, int m, int T, const double *xnew, const double
             }
         v += 0.5 * (q2 + tr2);                                                 /* :93 */
         v += q3;
-        kldiv[t] = v > 0.0 ? v : 0.0;                                          /* :101 */
+        kldiv[t] = v <= 0.0 ? 0.0 : v;                                         /* :101 max(0, v): NaN stays NaN */
     }
     free(kd); free(Kd); free(SK); free(mu); free(Kmu);
     return threw;

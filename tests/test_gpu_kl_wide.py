@@ -184,6 +184,19 @@ def test_kl_div_identical_policies_and_negative_determinant(ddp, gps_wide, n, m)
     assert kl.kl_div_wiki(c["x"][..., 1], c["x"][..., 1], sig[..., 1], one(new, 1), one(prev, 1), wide=True) == np.inf
     assert oc.kl_div_wiki(c["x"][..., 1], c["x"][..., 1], sig[..., 1], dict(K=new.K[..., 1], k=new.k[..., 1], S=Sn[..., 1]),
                           dict(K=prev.K[..., 1], k=prev.k[..., 1], S=prev.Σ[..., 1], Si=prev.Σi[..., 1])) == np.inf
+    # a NaN in xnew at one step of trajectory 1: max(0, v) hands it on (klutils.jl:98) — that step and that mean are NaN, nothing else moves
+    xn = c["x"] + 0.1 * np.cos(np.arange(c["x"].size).reshape(c["x"].shape))
+    moved = ddp.GaussianPolicy(N, n, m, 1.5 * c["Kp"], c["kp"] + 0.1, c["Sp"], c["Sip"])
+    kld0, mean0 = kl._kl_div(xn, c["x"], sig, moved, prev, None, wide=True)
+    assert np.all(np.isfinite(kld0)) and np.all(kld0[3] > 0)
+    xn[0, 3, 1] = np.nan
+    kld, mean = kl._kl_div(xn, c["x"], sig, moved, prev, None, wide=True)
+    hit = np.zeros((N, B), bool); hit[3, 1] = True
+    assert np.array_equal(np.isnan(kld), hit) and np.array_equal(kld[~hit], kld0[~hit])
+    assert np.isnan(mean[1]) and np.array_equal(mean[[0, 2]], mean0[[0, 2]])
+    got = oc.kl_div_wiki(xn[..., 1], c["x"][..., 1], sig[..., 1], dict(K=moved.K[..., 1], k=moved.k[..., 1], S=moved.Σ[..., 1]),
+                         dict(K=prev.K[..., 1], k=prev.k[..., 1], S=prev.Σ[..., 1], Si=prev.Σi[..., 1]))
+    assert np.array_equal(np.isnan(got), hit[:, 1])
 
 
 # 4. --------------------------------------------------------------------------------------------- active mask (device entry)

@@ -105,6 +105,15 @@ def test_kl_div_wiki_known_answers():
     # a negative-determinant covariance makes logdet throw -> the reference returns Inf (:95-99)
     bad = dict(K=K, k=k, S=np.repeat(np.array([[1.0, 2.0], [2.0, 1.0]])[:, :, None], T, 2))
     assert np.isscalar(oc.kl_div_wiki(x, x, sig, bad, pol)) and oc.kl_div_wiki(x, x, sig, bad, pol) == np.inf
+    # a NaN step stays NaN through max.(0, kldiv) (:98), in both oracles; every other step keeps its value
+    from oracle import np_kl
+    xn = x + 0.1
+    xn[1, 2] = np.nan
+    for mod in (oc, np_kl):
+        clean = mod.kl_div_wiki(x + 0.1, x, sig, new, pol)
+        got = mod.kl_div_wiki(xn, x, sig, new, pol)
+        assert np.array_equal(np.isnan(got), np.arange(T) == 2), mod.__name__
+        assert np.array_equal(np.delete(got, 2), np.delete(clean, 2)) and np.isnan(got.mean())
 
 
 def test_forward_covariance_is_the_lyapunov_iteration():
