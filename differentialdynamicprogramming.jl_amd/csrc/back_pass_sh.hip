@@ -40,6 +40,16 @@
 // slot takes that slot with every chunk already published: its producer work-group returns at once and the tiles stream the records.
 // The other groups take the empty, then the least recently used slots (sh_slot_plan).  A slot becomes complete only when its publisher
 // has drained the last chunk of a chain that did not diverge.  DDP_SH_REUSE=0 (and DDP_TEST_SH_ABORT, -DSH_PROF) switch the reuse off.
+//
+// Groups that hit are split by what depends on time (sh_item_plan).  Of the 1 184 B a trajectory-step writes, Vxx | K | Quu (992 B) are
+// the same bytes for every trajectory of the group and, the stream being complete before the launch, wait for nothing; only Vx, k, dV
+// are a chain.  So a hit group gets AFFINE tiles (the DMA wave and the affine waves of a consumer tile, no writer on their ring) and
+// BROADCAST units (group, chunk, block of SH_WTB trajectories): a wave loads the chunk's Vxx | K | Quu image once from the stream in
+// global memory and stores it to every trajectory of the block — no LDS, no flag, no barrier, no wait on another work-group.  The units
+// are dealt statically (unit index modulo the number of writer waves) to all waves of writer-only work-groups on the compute units that
+// would otherwise stand idle and, when there is none, to the spare waves of the affine tiles' work-groups.  Groups that miss run the
+// chain and the classic tiles beside them in the same launch.  (-DSH_DIAG_NOAFF / -DSH_DIAG_NOWR: one half of the hit path does
+// nothing — timing of the other half only, the results are wrong: profiles/sh_warm_ab.txt.)
 #include <stdlib.h>
 #include "ddp_internal.h"
 
@@ -102,6 +112,37 @@ enum { PF_CREADY = 0, PF_BDONE = 1, PF_BREADY = 2, PF_PDONE = 3, PF_CDIV = 4 };
 enum { CF_SREADY = 0, CF_KIND = 1 /* NSB */, CF_UDONE = 4 /* NAFF + NWR */ };
 static_assert(CF_UDONE + NAFF + NWR <= 32 && SH_THREADS <= 1024, "flag words, work-group size");
 
+// ---- the split of the groups that hit (sh_item_plan) ------------------------------------------------------------------------
+#ifndef SH_WTB
+#define SH_WTB 16                                   // trajectories a broadcast unit stores one chunk image to
+#endif
+#ifndef SH_WARM_MAX
+// hit trajectories up to which a launch splits its hit groups; beyond, classic tiles (profiles/sh_warm_ab.txt: at 1 024 the split launch
+// takes 0.298 ms against 0.337, at 2 048 0.55-0.60 against 0.55-0.56, at 4 096 0.98-1.07 against 0.89; between 1 024 and 2 048 not measured)
+#define SH_WARM_MAX 1024
+#endif
+#ifndef SH_WARM_AFRAC
+#define SH_WARM_AFRAC 2                             // the affine tiles take at most 1 / SH_WARM_AFRAC of the free compute units
+#endif
+#ifndef SH_WARM_SC1
+#define SH_WARM_SC1 0                               // 1: the affine tiles of a hit group fetch the records by sc1 loads like a classic tile (A/B)
+#endif
+#ifndef SH_WARM_WA
+#define SH_WARM_WA 0                                // writer waves in an affine tile's work-group while writer-only work-groups exist
+#endif
+constexpr int NWAVES = 1 + NAFF + NWR;              // waves of a work-group
+struct ShPlan {
+    int T, Wc;                                      // classic tiles (groups that miss; every group when warm == 0): tile size, count — items [0, Wc)
+    int warm;                                       // 1: the hit groups are split
+    int TA, NA;                                     // affine tiles of the hit groups: size (a multiple of 4), count — items [Wc, Wc + NA)
+    int NWO;                                        // writer-only work-groups — items [Wc + NA, W)
+    int W;                                          // all items
+    int WA;                                         // writer waves of an affine tile's work-group (a writer-only one has NWAVES)
+    int NW;                                         // writer waves of the launch = NA WA + NWO NWAVES
+    int U;                                          // broadcast units
+    int ubase[SH_GMAX + 1];                         // units of the groups in front of group g (a group that missed has none)
+};
+
 constexpr int SH_NOPS = 244;                        // shared operand doubles: fx 100 | fu 20 | cxx 100 | cxu 20 | cuu 4
 enum { SH_REUSE_OFF = 0, SH_REUSE_FLUSH = 1, SH_REUSE_ON = 2 };       // ShArgs::reuse
 
@@ -117,6 +158,7 @@ struct ShCtl {                                      // device-resident control b
     unsigned long long ops[SH_NOPS + 1];
     int sstate[SH_GMAX], sused[SH_GMAX], gslot[SH_GMAX];
     int hits, misses, pad5, pad6;
+    ShPlan plan;                                    // the items and units of this launch (sh_group_kernel -> sh_back_kernel)
     unsigned long long prof[64];                    // -DSH_PROF: phase sums of group 0's chain wave + wall-clock marks (ddp_sh_prof)
     // the first SH_NDIAG tiles that gave up since the block was allocated (ddp_sh_timeout_info): which tile of which group waited for
     // which chunk, the progress word it last saw, for how long, on which XCD, with which ticket, in which launch
@@ -213,6 +255,113 @@ __host__ __device__ inline unsigned sh_slot_plan(const unsigned long long *__res
     return hits;
 }
 
+// ============================================================ items and units ==================================================
+// The tile-size rule of the classic tiles over the groups of `inc`: one work-group per CU is resident (LDS), the G producers hold a CU
+// each while the chain runs.  R rounds of (ncu - G) tiles of equal size, no tile more than TMAX trajectories: every CU is busy until the
+// end, nobody queues behind a full machine for a lone last tile.  (The host sizes items[] and the grid for the most tiles ANY grouping of
+// the batch can produce — ddp_sh_max_tiles — and the count is clamped to that capacity here.)
+__host__ __device__ inline void sh_classic_rule(int G, const int *__restrict__ gcn, unsigned inc, int ncu, int wmax, int &T, int &W)
+{
+    int start = 0;
+    for (int g = 0; g < G; ++g) if ((inc >> g) & 1u) start += gcn[g];
+    T = 4; W = 0;
+    if (start > 0) {
+        // (a producer whose stream is reused holds no CU, but counting only the others — 256 tiles of 4 for the benchmark's
+        // warm call instead of 205 of 5 — measured 0.436 ms against 0.298: profiles/sh_reuse_ab.txt)
+        const int slots = ncu - G > 8 ? ncu - G : 8;
+        const int R = (start + slots * TMAX - 1) / (slots * TMAX);
+        T = (start + R * slots - 1) / (R * slots);
+        T = T < 4 ? 4 : T;
+        // never more tiles than the host sized items[] and the grid for (at T = TMAX the count is <= B / TMAX + G <= wmax)
+        const int cap = R * slots < wmax ? R * slots : wmax;
+        for (; T < TMAX; ++T) { int w = 0; for (int g = 0; g < G; ++g) if ((inc >> g) & 1u) w += (gcn[g] + T - 1) / T; if (w <= cap) break; }
+    }
+    for (int g = 0; g < G; ++g) if ((inc >> g) & 1u) W += (gcn[g] + T - 1) / T;
+}
+
+// The work of a launch from its groups: gcn[g] trajectories in group g, bit g of `hit` set when its stream is complete.  With no hit (or
+// more than SH_WARM_MAX hit trajectories, or a list too short for the split) every group gets classic tiles by the rule above.  Otherwise
+// the groups that miss get classic tiles by that rule and the hit groups get
+//   affine tiles of TA trajectories: the smallest multiple of 4 with which they take at most 1 / SH_WARM_AFRAC of the compute units that
+//     the producers and the classic tiles leave free (a small tile reads the whole stream for few trajectories; a large one makes its CU
+//     write more than its share);
+//   NWO writer-only work-groups on the rest of the free CUs (never more items than wmax);
+//   U broadcast units of SH_WTB trajectories x one chunk, group by group, chunk-major (sh_plan_unit), unit u for writer wave u % NW.
+__host__ __device__ inline void sh_item_plan(int G, const int *__restrict__ gcn, unsigned hit, int ncu, int wmax, int N, ShPlan &p)
+{
+    // (the grouping kernel runs this on one thread in front of the whole launch, with p in the LDS: every field is written once and
+    // never read back here)
+    const unsigned all = G >= 32 ? ~0u : (1u << G) - 1u;
+    hit &= all;
+    int nh = 0, sh = 0;
+    for (int g = 0; g < G; ++g) if ((hit >> g) & 1u) { ++nh; sh += gcn[g]; }
+    int T = 4, Wc = 0, warm = 0, TA = 4, NA = 0, NWO = 0, WA = 0;
+    if (nh > 0 && sh <= SH_WARM_MAX) {
+        sh_classic_rule(G, gcn, all & ~hit, ncu, wmax, T, Wc);
+        int avail = ncu - (G - nh) - Wc;
+        avail = avail < 1 ? 1 : avail;
+        const int target = avail / SH_WARM_AFRAC > 1 ? avail / SH_WARM_AFRAC : 1;
+        for (;; TA += 4) {
+            NA = 0;
+            for (int g = 0; g < G; ++g) if ((hit >> g) & 1u) NA += (gcn[g] + TA - 1) / TA;
+            if (TA >= TMAX || (NA <= target && Wc + NA <= wmax)) break;
+        }
+        if (Wc + NA <= wmax) {
+            warm = 1;
+            const int nwo = avail - NA > 0 ? avail - NA : 0;
+            NWO = nwo < wmax - Wc - NA ? nwo : wmax - Wc - NA;
+            // writer waves beside the affine waves: every spare wave when there is no writer-only work-group, else SH_WARM_WA
+            WA = NWAVES - 1 - TA / 4;
+            if (NWO > 0 && WA > SH_WARM_WA) WA = SH_WARM_WA;
+        } else { TA = 4; NA = 0; }
+    }
+    if (!warm) sh_classic_rule(G, gcn, all, ncu, wmax, T, Wc);
+    const int nchk = (N - 1) / CH + 1;
+    int ub = 0;
+    p.ubase[0] = 0;
+#pragma unroll
+    for (int g = 0; g < SH_GMAX; ++g) {
+        if (warm && g < G && ((hit >> g) & 1u)) ub += nchk * ((gcn[g] + SH_WTB - 1) / SH_WTB);
+        p.ubase[g + 1] = ub;
+    }
+    p.T = T; p.Wc = Wc; p.warm = warm; p.TA = TA; p.NA = NA; p.NWO = NWO; p.W = Wc + NA + NWO; p.WA = WA;
+    p.NW = NA * WA + NWO * NWAVES; p.U = ub;
+}
+// item w < p.W: 0 a classic tile, 1 an affine tile (group g, trajectories t0 .. t0 + cnt - 1 of it), 2 a writer-only work-group
+__host__ __device__ inline int sh_plan_tile(const ShPlan &p, int G, const int *__restrict__ gcn, unsigned hit, int w, int &g, int &t0, int &cnt)
+{
+    g = -1; t0 = 0; cnt = 0;
+    if (w >= p.Wc + p.NA) return 2;
+    const bool aff = w >= p.Wc;
+    const int T = aff ? p.TA : p.T;
+    int left = aff ? w - p.Wc : w;
+    for (int gg = 0; gg < G; ++gg) {
+        if (p.warm && (((hit >> gg) & 1u) != 0) != aff) continue;
+        const int nt = (gcn[gg] + T - 1) / T;
+        if (left < nt) { g = gg; t0 = left * T; cnt = gcn[gg] - t0 < T ? gcn[gg] - t0 : T; break; }
+        left -= nt;
+    }
+    return aff ? 1 : 0;
+}
+// unit u < p.U: chunk q (in the order of the stream: 0 is the top chunk) of trajectories t0 .. t0 + cnt - 1 of group g
+__host__ __device__ inline void sh_plan_unit(const ShPlan &p, int G, const int *__restrict__ gcn, int u, int &g, int &q, int &t0, int &cnt)
+{
+    g = 0;
+    while (g + 1 < G && p.ubase[g + 1] <= u) ++g;
+    const int r = u - p.ubase[g], nb = (gcn[g] + SH_WTB - 1) / SH_WTB;
+    q = r / nb; t0 = (r % nb) * SH_WTB; cnt = gcn[g] - t0 < SH_WTB ? gcn[g] - t0 : SH_WTB;
+}
+// the writer wave of wave `wave` of the work-group of item `it` (-1: the wave is no writer): writer lw of every hit-path work-group h
+// is wave lw NH + h, so that consecutive units go to different compute units; the waves that only a writer-only work-group has follow
+__host__ __device__ inline int sh_plan_writer(const ShPlan &p, int it, int wave)
+{
+    const int h = it - p.Wc, NH = p.NA + p.NWO;
+    if (h < 0 || h >= NH) return -1;
+    const int lw = h < p.NA ? wave - (NWAVES - p.WA) : wave;
+    if (lw < 0 || wave >= NWAVES) return -1;
+    return lw < p.WA ? lw * NH + h : p.WA * NH + (lw - p.WA) * p.NWO + (h - p.NA);
+}
+
 // =============================================================== grouping ====================================================
 // REGS: every thread keeps the table slots of its (at most 8) trajectories in registers between the two passes; otherwise they are parked
 // in global memory (perm[], then fb_active[]).  The kernel is a chain of dependent steps on ONE work-group in front of the whole backward
@@ -221,9 +370,10 @@ template <bool REGS>
 __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
 {
     __shared__ unsigned long long keys[SH_TAB];
-    __shared__ int cnt[SH_TAB], gof[SH_TAB], cursor[SH_GMAX], gst[SH_GMAX], gcn[SH_GMAX], gtile[SH_GMAX + 1], Gs, Ts, nfb;
+    __shared__ int cnt[SH_TAB], gof[SH_TAB], cursor[SH_GMAX], gst[SH_GMAX], gcn[SH_GMAX], Gs, nfb;
     __shared__ unsigned long long skey[SH_GMAX], gkey[SH_GMAX];
-    __shared__ int sstate[SH_GMAX], sused[SH_GMAX], gsl[SH_GMAX], changed, hitslots;
+    __shared__ int sstate[SH_GMAX], sused[SH_GMAX], gsl[SH_GMAX], changed, hitslots, hitgroups;
+    __shared__ ShPlan pls;
     const unsigned long long EMPTY = ~0ull;
     const int tid = threadIdx.x, B = a.B, lane = tid & 63;
     constexpr int NPT = 8;
@@ -304,29 +454,16 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
             }
             start += bc;
         }
-        // Tile size: one work-group per CU is resident (LDS), the G producers hold a CU each while the chain runs.  R rounds of
-        // (ncu - G) tiles of equal size, no tile more than TMAX trajectories: every CU is busy until the end, nobody queues behind a
-        // full machine for a lone last tile.  (The host sizes items[] and the grid for the most tiles ANY grouping of the batch can
-        // produce — ddp_sh_max_tiles — and the count is clamped to that capacity here.)
+        // the tiles of the groups that miss, the affine tiles, writer-only work-groups and broadcast units of those that hit: sh_item_plan
         if (tid == 0) {
             // the stream slots of the groups (sh_slot_plan); a slot taken by a group that did not hit is empty until its publisher is done
             if (changed) for (int s = 0; s < SH_GMAX; ++s) sstate[s] = 0;
             const unsigned hits = sh_slot_plan(skey, sstate, sused, G, gkey, gsl);
-            int T = 4, W = 0;
-            if (G > 0) {
-                // (a producer whose stream is reused holds no CU, but counting only the others — 256 tiles of 4 for the benchmark's
-                // warm call instead of 205 of 5 — measured 0.436 ms against 0.298: profiles/sh_reuse_ab.txt)
-                const int slots = a.ncu - G > 8 ? a.ncu - G : 8;
-                const int R = (start + slots * TMAX - 1) / (slots * TMAX);
-                T = (start + R * slots - 1) / (R * slots);
-                T = T < 4 ? 4 : T;
-                // never more tiles than the host sized items[] and the grid for (at T = TMAX the count is <= B / TMAX + G <= wmax)
-                const int cap = R * slots < a.wmax ? R * slots : a.wmax;
-                for (; T < TMAX; ++T) { int w = 0; for (int g = 0; g < G; ++g) w += (gcn[g] + T - 1) / T; if (w <= cap) break; }
-            }
-            for (int g = 0; g < G; ++g) { gtile[g] = W; W += (gcn[g] + T - 1) / T; }
-            gtile[G] = W;
-            Gs = G; Ts = T;
+            ShPlan pl;                                   // (in registers: one copy to the LDS for the tiles below, one to the control block)
+            sh_item_plan(G, gcn, hits, a.ncu, a.wmax, a.N, pl);
+            const int W = pl.W;
+            Gs = G; hitgroups = (int)hits;
+            pls = pl; a.ctl->plan = pl;
             const int launch = launches_r + 1;
             int hs = 0;
             for (int g = 0; g < G; ++g) {
@@ -350,12 +487,11 @@ __global__ __launch_bounds__(1024) void sh_group_kernel(ShArgs a)
         a.ctl->gslot[tid] = tid < Gs ? gsl[tid] : 0;
     }
     {   // the tiles, one per thread
-        const int G = Gs, T = Ts, W = gtile[G];
+        const int G = Gs, W = pls.W;
         for (int w = tid; w < W; w += blockDim.x) {
-            int g = 0;
-            while (g + 1 < G && gtile[g + 1] <= w) ++g;
-            const int t0 = (w - gtile[g]) * T;
-            a.items[w] = make_int4(g, gst[g] + t0, gcn[g] - t0 < T ? gcn[g] - t0 : T, gsl[g]);
+            int g, t0, cnt;
+            const int kind = sh_plan_tile(pls, G, gcn, (unsigned)hitgroups, w, g, t0, cnt);
+            a.items[w] = kind == 2 ? make_int4(-1, 0, 0, 0) : make_int4(g, gst[g] + t0, cnt, gsl[g]);
         }
     }
     // pass 2: counting sort into perm
@@ -780,6 +916,9 @@ enum { KIND_NORMAL = 0, KIND_ZERO = 1 << 20 /* no data: everything is zero */ };
 // A wait that times out (a protocol error, or a producer that was starved of its CU for seconds) does not end in silently wrong
 // results: the tile hands ITS trajectories to the per-trajectory kernels that the dispatcher launches behind this one (fb_active, the
 // mask those kernels run under — they rewrite every output of a flagged trajectory), and ctl->error counts the event.
+// SC1: the records come by write-through-coherent (sc1) loads — a classic tile reads chunks that a producer of the same launch has just
+// published.  An affine tile of a group that hit reads a stream that an earlier launch completed: plain loads, served by the XCD's L2.
+template <bool SC1 = true>
 __device__ __forceinline__ void sh_dma(const ShArgs &a, double *sm, const int gidx, const int nusers, const int4 item)
 {
     const int gslot = item.w;                                   // the stream slot of group gidx
@@ -867,7 +1006,7 @@ __device__ __forceinline__ void sh_dma(const ShArgs &a, double *sm, const int gi
 #pragma unroll
             for (int it = 0; it < (GPIECES + 63) / 64; ++it) {
                 const int pc = 64 * it + lane;
-                if (pc < GPIECES) __builtin_amdgcn_global_load_lds((glb_void *)(src + 16 * pc), (lds_void *)(dst + 128 * it), 16, 0, 16 /* sc1 */);
+                if (pc < GPIECES) __builtin_amdgcn_global_load_lds((glb_void *)(src + 16 * pc), (lds_void *)(dst + 128 * it), 16, 0, SC1 ? 16 /* sc1 */ : 0);
             }
             const int top = q == 0 ? st : CH - 1;                   // (steps past N - 1 are not touched)
 #pragma unroll
@@ -1060,6 +1199,53 @@ __device__ __forceinline__ void sh_writer(const ShArgs &a, double *sm, const int
     }
 }
 
+// The broadcast units of writer wave gw (sh_item_plan): per unit the chunk's Vxx | K | Quu image in the 8 x 16-byte register image of
+// sh_writer, read from the group's complete stream in global memory by plain loads (an earlier launch on the same stream wrote it),
+// stored to every trajectory of the unit's block.  Nothing here waits for another wave.
+template <bool NTS>
+__device__ __forceinline__ void sh_bcast(const ShArgs &a, const ShPlan &pl, const int G, const int gw)
+{
+    const int lane = threadIdx.x % DDP_WAVE;
+    const int N = a.N, cTop = (N - 1) / CH, st = (N - 1) % CH, NCHK = cTop + 1;
+    constexpr size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
+    // instruction k < 6: Vxx pieces 64k + lane; 6: K pieces 0..63; 7: lanes 0-15 Vxx 384.., 16-31 K 64.., 32-47 Quu 0..15
+    int loff[8], goff[8], gslot[8];                             // offset (doubles) in a chunk of the stream, byte offset in the array's chunk, slot
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) { const int pc = 64 * kk + lane; gslot[kk] = pc / 50; loff[kk] = GREC * (pc / 50) + 2 * (pc % 50); goff[kk] = 16 * pc; }
+    { const int pc = lane; gslot[6] = pc / 10; loff[6] = GREC * (pc / 10) + G_K + 2 * (pc % 10); goff[6] = 16 * pc; }
+    const int part = lane >> 4, l16 = lane & 15;
+    {
+        if (part == 0) { const int pc = 384 + l16; gslot[7] = pc / 50; loff[7] = GREC * (pc / 50) + 2 * (pc % 50); goff[7] = 16 * pc; }
+        else if (part == 1) { const int pc = 64 + l16; gslot[7] = pc / 10; loff[7] = GREC * (pc / 10) + G_K + 2 * (pc % 10); goff[7] = 16 * pc; }
+        else { const int pc = l16; gslot[7] = pc / 2; loff[7] = GREC * (pc / 2) + G_QUU + 2 * (pc % 2); goff[7] = 16 * pc; }
+    }
+    const int U = pl.U, NW = pl.NW;
+    for (int u = gw; u < U; u += NW) {
+        int g, q, t0, cnt;
+        sh_plan_unit(pl, G, a.ctl->gcount, u, g, q, t0, cnt);
+        g = __builtin_amdgcn_readfirstlane(g); q = __builtin_amdgcn_readfirstlane(q);
+        t0 = __builtin_amdgcn_readfirstlane(t0); cnt = __builtin_amdgcn_readfirstlane(cnt);
+        const int top = q == 0 ? st : CH - 1;
+        const double *src = a.rec + ((size_t)a.ctl->gslot[g] * NCHK + (size_t)q) * GCHUNK;
+        const int *pm = a.perm + a.ctl->gstart[g] + t0;
+        d2 v[8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) v[kk] = (gslot[kk] <= top && (kk < 7 || part < 3)) ? *(const d2 *)(src + loff[kk]) : d2{0.0, 0.0};
+        const size_t c8 = (size_t)CH * (cTop - q);
+        for (int t = 0; t < cnt; ++t) {
+            const int b = __builtin_amdgcn_readfirstlane(pm[t]);
+            char *pV = (char *)(a.Vxx + ((size_t)b * N + c8) * nn), *pK = (char *)(a.K + ((size_t)b * N + c8) * nm),
+                 *pQ = (char *)(a.Quu + ((size_t)b * N + c8) * mm);
+#pragma unroll
+            for (int kk = 0; kk < 6; ++kk) if (gslot[kk] <= top) store16_res<NTS>(pV + goff[kk], v[kk]);
+            if (gslot[6] <= top) store16_res<NTS>(pK + goff[6], v[6]);
+            char *p7 = part == 0 ? pV : (part == 1 ? pK : pQ);
+            if (part < 3 && gslot[7] <= top) store16_res<NTS>(p7 + goff[7], v[7]);
+        }
+    }
+    SH_MARK_MAX(25);
+}
+
 template <bool REG2, bool NTS>
 __global__ __launch_bounds__(SH_THREADS) void sh_back_kernel(ShArgs a)
 {
@@ -1089,6 +1275,26 @@ __global__ __launch_bounds__(SH_THREADS) void sh_back_kernel(ShArgs a)
     }
     const int it = role - G;
     if (it >= W) return;
+    if (a.ctl->plan.warm && it >= a.ctl->plan.Wc) {
+        // a group that hit: its stream is complete, nothing below waits for another work-group
+        const ShPlan &pl = a.ctl->plan;
+        const int gw = sh_plan_writer(pl, it, wave);
+        if (it < pl.Wc + pl.NA) {
+            // an affine tile: the DMA wave and the affine waves of a classic tile (they alone use the ring), the other waves write units.
+            // (Their vector-memory instructions go in front of the writers': the time chain of the launch runs here.)
+            const int4 item = a.items[it];
+            const int naff = (item.z + 3) / 4;
+#ifdef SH_DIAG_NOAFF
+            if (wave <= naff) return;
+#endif
+            if (wave == 0) { __builtin_amdgcn_s_setprio(2); sh_dma<SH_WARM_SC1 != 0>(a, sm, item.x, naff, item); return; }
+            if (wave <= naff) { __builtin_amdgcn_s_setprio(2); sh_affine<NTS>(a, sm, item.x, wave - 1, item); return; }
+        }
+#ifndef SH_DIAG_NOWR
+        if (gw >= 0) sh_bcast<NTS>(a, pl, G, gw);
+#endif
+        return;
+    }
     const int4 item = a.items[it];
     const int naff = (item.z + 3) / 4;
 #ifdef SH_PROF
@@ -1167,7 +1373,9 @@ int ddp_launch_back_pass_sh(ddp_handle h, const BPCall &c, const int32_t **fb_ac
     if (h->sh_launched && h->sh_last_stream != h->stream) a.reuse = SH_REUSE_FLUSH;
     { const char *e = ddp_env(h, ENV_SH_REUSE); if ((e && atoi(e) == 0) || a.test_abort) a.reuse = SH_REUSE_OFF; }
 #ifdef SH_PROF
-    a.reuse = SH_REUSE_OFF;                                      // the phase profile measures the chain
+    // the phase profile measures the chain; DDP_SH_PROF_REUSE=1 (read in this build only) keeps the reuse on: marks 23 / 24 / 25 of
+    // ddp_sh_prof are then the ends of the last DMA, affine and broadcast-writer wave of a warm launch
+    { const char *e = getenv("DDP_SH_PROF_REUSE"); if (!(e && atoi(e) != 0)) a.reuse = SH_REUSE_OFF; }
 #endif
     h->sh_launched = true; h->sh_last_stream = h->stream;
     a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
@@ -1256,6 +1464,29 @@ extern "C" int ddp_sh_slot_plan(const unsigned long long *skey, const int *sstat
 {
     if (G < 0 || G > SH_GMAX) return -1;
     return (int)sh_slot_plan(skey, sstate, sused, G, gkey, gslot);
+}
+// ddp_sh_item_plan: the item and unit plan of the grouping kernel on the host, from the trajectory counts of the G groups and the mask
+// of those that hit.  plan: the 10 scalars of ShPlan in its order (T, Wc, warm, TA, NA, NWO, W, WA, NW, U); items: 4 ints per item
+// (kind 0 classic / 1 affine / 2 writer-only, group, first trajectory of the group, trajectories); units: 4 ints per unit (group, chunk,
+// first trajectory of the group, trajectories); writers: per item the NWAVES writer-wave numbers of its waves (-1: no writer).  Each
+// list is filled as far as its capacity (in entries) goes.  Returns the number of items, < 0 on bad arguments.
+extern "C" int ddp_sh_item_plan(int G, const int *gcount, unsigned hitmask, int ncu, int wmax, int N, int *plan, int *items, int cap_items,
+                                int *units, int cap_units, int *writers, int cap_writers)
+{
+    if (G < 0 || G > SH_GMAX || !plan || N < 1 || ncu < 1) return -1;
+    ShPlan p;
+    sh_item_plan(G, gcount, hitmask, ncu, wmax, N, p);
+    const int sc[10] = {p.T, p.Wc, p.warm, p.TA, p.NA, p.NWO, p.W, p.WA, p.NW, p.U};
+    for (int e = 0; e < 10; ++e) plan[e] = sc[e];
+    for (int w = 0; items && w < p.W && w < cap_items; ++w) {
+        int g, t0, cnt;
+        items[4 * w] = sh_plan_tile(p, G, gcount, p.warm ? hitmask : 0u, w, g, t0, cnt);
+        items[4 * w + 1] = g; items[4 * w + 2] = t0; items[4 * w + 3] = cnt;
+    }
+    for (int u = 0; units && u < p.U && u < cap_units; ++u) sh_plan_unit(p, G, gcount, u, units[4 * u], units[4 * u + 1], units[4 * u + 2], units[4 * u + 3]);
+    for (int w = 0; writers && w < p.W && w < cap_writers; ++w)
+        for (int wv = 0; wv < NWAVES; ++wv) writers[NWAVES * w + wv] = sh_plan_writer(p, w, wv);
+    return p.W;
 }
 extern "C" int ddp_sh_test_swap_stream(ddp_handle h, void *stream, void **prev)
 {
