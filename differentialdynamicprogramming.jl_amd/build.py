@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libddp_amd.so")
 SOURCES = ["capi.hip", "back_pass.hip", "back_pass_dpp.hip", "back_pass_dppw.hip", "back_pass_row.hip", "back_pass_row_hi.hip", "back_pass_mid.hip", "back_pass_big.hip", "back_pass_gps_lane.hip", "back_pass_mfma.hip", "back_pass_mfma_lims.hip", "back_pass_mf2.hip", "back_pass_mf2_lims.hip", "back_pass_mx.hip", "back_pass_mxg.hip", "back_pass_mx2.hip", "back_pass_sh.hip", "back_pass_q4.hip", "back_pass_wide.hip",
            "forward_pass.hip", "forward_pass_dpp.hip", "forward_pass_row.hip", "forward_pass_pipe.hip", "forward_pass_big.hip", "forward_pass_wide.hip", "df.hip", "ilqg.hip", "kl.hip", "kl_wide.hip", "comm.hip", "boxqp_big.hip", "user_problem.hip"]
-HEADERS = ["ddp_internal.h", "boxqp_dev.h", "boxqp_rows.h", "arena.h", os.path.join("..", "..", "include", "ddp_amd.h")]
+HEADERS = ["ddp_internal.h", "boxqp_dev.h", "boxqp_rows.h", "staging.h", os.path.join("..", "..", "include", "ddp_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-Wall", "-Wno-unused-function",
          "-Wno-unused-but-set-variable", "-Wno-unused-variable"]
 

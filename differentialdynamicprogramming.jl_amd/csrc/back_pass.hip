@@ -683,14 +683,8 @@ static int launch_back_pass_padded(ddp_handle h, const BPCall &c, int np_, int m
                  s_fu = al((size_t)np_ * mp * cf * 8), s_l = al((size_t)mp * 2 * 8), s_K = al((size_t)mp * np_ * NB * 8),
                  s_Quu = al((size_t)mp * mp * NB * 8), s_Vxx = al((size_t)np_ * np_ * NB * 8);
     const size_t bytes = s_cx + 2 * s_cu + s_cxx + s_cxu + s_cuu + s_fx + s_fu + s_l + s_K + s_cu + s_Quu + s_cx + s_Vxx;
-    if (bytes > h->pad_bytes) {
-        DDP_HIP(hipStreamSynchronize(h->stream));
-        if (h->pad) DDP_HIP(hipFree(h->pad));
-        h->pad = nullptr; h->pad_bytes = 0;
-        DDP_HIP(hipMalloc(&h->pad, bytes));
-        h->pad_bytes = bytes;
-    }
-    char *q = (char *)h->pad;
+    char *q;
+    { const int rp_ = ddp_pad(h, bytes, (void **)&q); if (rp_) return rp_; }
     auto tk = [&](size_t b_) { double *r_ = (double *)q; q += b_; return r_; };
     double *pcx = tk(s_cx), *pcu = tk(s_cu), *pu = tk(s_cu), *pcxx = tk(s_cxx), *pcxu = tk(s_cxu), *pcuu = tk(s_cuu), *pfx = tk(s_fx),
            *pfu = tk(s_fu), *pl = tk(s_l), *pK = tk(s_K), *pk = tk(s_cu), *pQuu = tk(s_Quu), *pVx = tk(s_cx), *pVxx = tk(s_Vxx);

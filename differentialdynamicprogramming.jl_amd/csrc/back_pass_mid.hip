@@ -827,14 +827,8 @@ int ddp_launch_back_pass_gps_mid(ddp_handle h, const BPCall &c)
     auto al = [](size_t b_) { return (b_ + 255) & ~(size_t)255; };
     const size_t sx = al((size_t)n * NB * 8), su = al((size_t)m * NB * 8), sxx = al((size_t)nn * NB * 8), sxu = al((size_t)nm * NB * 8),
                  suu = al((size_t)mm * NB * 8), bytes = sx + su + sxx + sxu + suu;
-    if (bytes > h->pad_bytes) {
-        DDP_HIP(hipStreamSynchronize(h->stream));
-        if (h->pad) DDP_HIP(hipFree(h->pad));
-        h->pad = nullptr; h->pad_bytes = 0;
-        DDP_HIP(hipMalloc(&h->pad, bytes));
-        h->pad_bytes = bytes;
-    }
-    char *q = (char *)h->pad;
+    char *q;
+    { const int rp_ = ddp_pad(h, bytes, (void **)&q); if (rp_) return rp_; }
     auto tk = [&](size_t b_) { double *r_ = (double *)q; q += b_; return r_; };
     GpsMidCombine g;
     g.n = n; g.m = m; g.N = d->N; g.B = d->B; g.eta_tv = kl->eta_tv;

@@ -1004,14 +1004,8 @@ int ddp_launch_back_pass_gps_q4(ddp_handle h, const BPCall &call)
     }
     auto al = [](size_t b_) { return (b_ + 255) & ~(size_t)255; };
     const size_t s4 = al((size_t)4 * NB * 8), s1 = al((size_t)NB * 8), s16 = al((size_t)16 * NB * 8), bytes = 2 * s4 + 2 * s1 + s16;
-    if (bytes > h->pad_bytes) {
-        DDP_HIP(hipStreamSynchronize(h->stream));
-        if (h->pad) DDP_HIP(hipFree(h->pad));
-        h->pad = nullptr; h->pad_bytes = 0;
-        DDP_HIP(hipMalloc(&h->pad, bytes));
-        h->pad_bytes = bytes;
-    }
-    char *q = (char *)h->pad;
+    char *q;
+    { const int rp_ = ddp_pad(h, bytes, (void **)&q); if (rp_) return rp_; }
     auto tk = [&](size_t b_) { double *r_ = (double *)q; q += b_; return r_; };
     GpsCombine c;
     c.N = d->N; c.B = d->B;

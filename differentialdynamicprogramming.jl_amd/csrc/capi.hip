@@ -304,26 +304,36 @@ int ddp_raise_lds(ddp_handle h, const void *kernel, int bytes)
     return 0;
 }
 
-int ddp_scratch(ddp_handle h, size_t bytes, void **out)
+// grows a buffer the handle keeps to at least `bytes` (contents not preserved): what the stream still does with the old one ends first
+static int grow(ddp_handle h, void **buf, size_t *have, size_t bytes)
 {
-    DDP_DEVICE(h);
-    if (bytes > h->scratch_bytes) {
+    if (bytes > *have) {
         DDP_HIP(hipStreamSynchronize(h->stream));
-        if (h->scratch) DDP_HIP(hipFree(h->scratch));
-        h->scratch = nullptr;
-        h->scratch_bytes = 0;
-        DDP_HIP(hipMalloc(&h->scratch, bytes));
-        h->scratch_bytes = bytes;
+        if (*buf) DDP_HIP(hipFree(*buf));
+        *buf = nullptr;
+        *have = 0;
+        DDP_HIP(hipMalloc(buf, bytes));
+        *have = bytes;
     }
-    *out = h->scratch;
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// bump allocator over the handle's scratch for the host-pointer flavours
-namespace {
-#include "arena.h"
-}   // namespace
+int ddp_scratch(ddp_handle h, size_t bytes, void **out)
+{
+    DDP_DEVICE(h);
+    const int rc = grow(h, &h->scratch, &h->scratch_bytes, bytes);
+    *out = h->scratch;
+    return rc;
+}
+
+int ddp_pad(ddp_handle h, size_t bytes, void **out)
+{
+    const int rc = grow(h, &h->pad, &h->pad_bytes, bytes);
+    *out = h->pad;
+    return rc;
+}
+
+#include "staging.h"
 
 extern "C" {
 
@@ -348,25 +358,18 @@ int ddp_back_pass_f64(ddp_handle h, const ddp_bp_desc *d, const double *cx, cons
     DDP_CHECK(h && d, "back_pass: null handle/descriptor");
     const size_t n = d->n, m = d->m, N = d->N, B = d->B;
     const size_t fxc = (d->fx_tv ? N : 1) * (d->fx_batched ? B : 1), cc = (d->cost_tv ? N : 1) * (d->cost_batched ? B : 1);
-    const size_t sizes_in[] = {n * N * B, m * N * B, n * n * cc, n * m * cc, m * m * cc, n * n * fxc, n * m * fxc, B, 2 * m, m * N * B};
-    const size_t sizes_out[] = {m * n * N * B, m * N * B, m * m * N * B, n * N * B, n * n * N * B, 2 * B};
-    Arena A; A.h = h;
-    for (size_t s : sizes_in) A.want(s * 8);
-    for (size_t s : sizes_out) A.want(s * 8);
-    A.want(B * 4);
-    int rc = A.commit();
+    const double *dcx, *dcu, *dcxx, *dcxu, *dcuu, *dfx, *dfu, *dlam, *dlims = nullptr, *du = nullptr;
+    double *dK, *dk, *dQuu, *dVx, *dVxx, *ddV;
+    int32_t *ddiv;
+    Staging S(h, Staging::SCRATCH, "back_pass");
+    S.in(&dcx, cx, n * N * B); S.in(&dcu, cu, m * N * B); S.in(&dcxx, cxx, n * n * cc); S.in(&dcxu, cxu, n * m * cc); S.in(&dcuu, cuu, m * m * cc);
+    S.in(&dfx, fx, n * n * fxc); S.in(&dfu, fu, n * m * fxc); S.in(&dlam, lambda, B);
+    if (d->has_lims) { S.in(&dlims, lims, 2 * m); S.in(&du, u, m * N * B); }
+    S.out(&dK, K, m * n * N * B); S.out(&dk, k, m * N * B); S.out(&dQuu, Quu, m * m * N * B); S.out(&dVx, Vx, n * N * B);
+    S.out(&dVxx, Vxx, n * n * N * B); S.out(&ddV, dV, 2 * B); S.out(&ddiv, diverge, B);
+    const int rc = S.commit();
     if (rc) return rc;
-    const double *dcx = A.in(cx, sizes_in[0]), *dcu = A.in(cu, sizes_in[1]), *dcxx = A.in(cxx, sizes_in[2]),
-                 *dcxu = A.in(cxu, sizes_in[3]), *dcuu = A.in(cuu, sizes_in[4]), *dfx = A.in(fx, sizes_in[5]),
-                 *dfu = A.in(fu, sizes_in[6]), *dlam = A.in(lambda, sizes_in[7]),
-                 *dlims = d->has_lims ? A.in(lims, sizes_in[8]) : nullptr, *du = d->has_lims ? A.in(u, sizes_in[9]) : nullptr;
-    double *dK = A.outp(K, sizes_out[0]), *dk = A.outp(k, sizes_out[1]), *dQuu = A.outp(Quu, sizes_out[2]),
-           *dVx = A.outp(Vx, sizes_out[3]), *dVxx = A.outp(Vxx, sizes_out[4]), *ddV = A.outp(dV, sizes_out[5]);
-    int32_t *ddiv = A.outp(diverge, B);
-    if ((rc = A.upload())) return rc;
-    rc = ddp_back_pass_f64_dev(h, d, dcx, dcu, dcxx, dcxu, dcuu, dfx, dfu, dlam, dlims, du, nullptr, dK, dk, dQuu, dVx, dVxx, ddV, ddiv);
-    if (rc) return rc;
-    return A.download();
+    return S.finish(ddp_back_pass_f64_dev(h, d, dcx, dcu, dcxx, dcxu, dcuu, dfx, dfu, dlam, dlims, du, nullptr, dK, dk, dQuu, dVx, dVxx, ddV, ddiv));
 }
 
 int ddp_forward_pass_f64(ddp_handle h, const ddp_problem *p, const double *K, const double *k,
@@ -377,31 +380,19 @@ int ddp_forward_pass_f64(ddp_handle h, const ddp_problem *p, const double *K, co
     DDP_CHECK(h && p, "forward_pass: null handle/problem");
     DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
     const size_t n = p->n, m = p->m, N = p->N, B = p->B, CL = ddp_cost_len(p), na = nalpha;
-    const size_t dc = (p->dyn_tv ? N : 1) * (p->dyn_batched ? B : 1);
-    Arena A; A.h = h;
-    const size_t tot = m * n * N * B + m * N * B + n * B + m * N * B + n * N * B + 2 * m + n * n * dc + n * m * dc + n * n + m * m +
-                       (n * N + m * N + CL + 1) * B * na;
-    A.want(tot * 8 + 32 * 256);
-    int rc = A.commit();
+    ddp_problem pd;
+    const double *dK, *dk, *dx0, *du, *dx, *dl;
+    double *dxn, *dun, *dcn, *dcs;
+    Staging S(h, Staging::SCRATCH, "forward_pass");
+    int rc = stage_problem(S, p, &pd);
     if (rc) return rc;
-    ddp_problem pd = *p;
-    if (p->kind == DDP_PROBLEM_LQ) { pd.A = A.in(p->A, n * n * dc); pd.Bm = A.in(p->Bm, n * m * dc); }
-    { const int rd_ = ddp_check_cost_diag_host(p); if (rd_) return rd_; }
-    DiagVerified diag_verified_(h);                          // Q, R were tested on the host; the staged copies need no second test
-    pd.Q = A.in(p->Q, n * n); pd.R = A.in(p->R, m * m);
-    const double *dK = A.in(K, m * n * N * B), *dk = A.in(k, m * N * B), *dx0 = A.in(x0, n * B), *du = A.in(u, m * N * B),
-                 *dx = A.in(x, n * N * B), *dl = A.in(lims, 2 * m);
-    double *dxn = A.outp(xnew, n * N * B * na), *dun = A.outp(unew, m * N * B * na), *dcn = A.outp(cnew, CL * B * na),
-           *dcs = A.outp(csum, B * na);
+    DiagVerified diag_verified_(h);
+    S.in(&dK, K, m * n * N * B); S.in(&dk, k, m * N * B); S.in(&dx0, x0, n * B); S.in(&du, u, m * N * B); S.in(&dx, x, n * N * B); S.in(&dl, lims, 2 * m);
     // outputs the caller does not want still need device storage
-    if (!dxn) dxn = (double *)A.take(n * N * B * na * 8);
-    if (!dun) dun = (double *)A.take(m * N * B * na * 8);
-    if (!dcn) dcn = (double *)A.take(CL * B * na * 8);
-    if (!dcs) dcs = (double *)A.take(B * na * 8);
-    if ((rc = A.upload())) return rc;
-    rc = ddp_forward_pass_f64_dev(h, &pd, dK, dk, dx0, du, dx, alpha, nalpha, dl, nullptr, dxn, dun, dcn, dcs);
-    if (rc) return rc;
-    return A.download();
+    S.out_or_temp(&dxn, xnew, n * N * B * na); S.out_or_temp(&dun, unew, m * N * B * na); S.out_or_temp(&dcn, cnew, CL * B * na);
+    S.out_or_temp(&dcs, csum, B * na);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_forward_pass_f64_dev(h, &pd, dK, dk, dx0, du, dx, alpha, nalpha, dl, nullptr, dxn, dun, dcn, dcs));
 }
 
 }   // extern "C"
@@ -490,19 +481,16 @@ int ddp_boxqp_f64(ddp_handle h, int m, int count, const double *H, const double 
     DDP_CHECK(h, "boxqp: null handle");
     DDP_CHECK(m >= 1 && count >= 1, "boxqp: bad sizes");
     const size_t M = m, C = count;
-    Arena A; A.h = h;
-    A.want((2 * M * M * C + 5 * M * C) * 8 + C * 4 + M * C + 16 * 256);
-    int rc = A.commit();
+    const double *dH, *dg, *dlo, *dup, *dx0;
+    double *dx, *dHf;
+    int32_t *dr;
+    uint8_t *df;
+    Staging S(h, Staging::SCRATCH, "boxqp");
+    S.in(&dH, H, M * M * C); S.in(&dg, g, M * C); S.in(&dlo, lower, M * C); S.in(&dup, upper, M * C); S.in(&dx0, x0, M * C);
+    S.out(&dx, x, M * C); S.out(&dHf, Hfree, M * M * C); S.out(&dr, result, C); S.out(&df, free_out, M * C);
+    const int rc = S.commit();
     if (rc) return rc;
-    const double *dH = A.in(H, M * M * C), *dg = A.in(g, M * C), *dlo = A.in(lower, M * C), *dup = A.in(upper, M * C),
-                 *dx0 = A.in(x0, M * C);
-    double *dx = A.outp(x, M * C), *dHf = A.outp(Hfree, M * M * C);
-    int32_t *dr = A.outp(result, C);
-    uint8_t *df = A.outp(free_out, M * C);
-    if ((rc = A.upload())) return rc;
-    rc = ddp_boxqp_f64_dev(h, m, count, dH, dg, dlo, dup, dx0, opts, dx, dr, dHf, df);
-    if (rc) return rc;
-    return A.download();
+    return S.finish(ddp_boxqp_f64_dev(h, m, count, dH, dg, dlo, dup, dx0, opts, dx, dr, dHf, df));
 }
 
 }   // extern "C"

@@ -82,6 +82,8 @@ static inline const char *ddp_env(ddp_handle h, int id) { return h->envset[id] ?
 
 // grows the handle's scratch to at least `bytes` (contents not preserved)
 int ddp_scratch(ddp_handle h, size_t bytes, void **out);
+// the same for the handle's pad buffer (the padded or combined operands of a backward pass); the caller has made the device current
+int ddp_pad(ddp_handle h, size_t bytes, void **out);
 
 // ddp_problem::cost_diag = 1 declares Q and R diagonal (the fused rollout cost reads only the diagonals): verified on the first call
 // with a (Q, R) pointer pair — one small device-to-host copy — and cached per handle; 0 ok, < 0 refused

@@ -7,6 +7,7 @@
 // (pendcart adds ~1.5 kflop of 5x5 Padé arithmetic per element, still far below the fp64 ridge).
 #include <stdlib.h>
 #include "ddp_internal.h"
+#include "staging.h"
 
 namespace {
 
@@ -484,28 +485,18 @@ int ddp_df_f64(ddp_handle h, const ddp_problem *p, const double *x, const double
     DDP_CHECK(h && p && x && u && cx && cu, "df: null argument");
     const size_t n = p->n, m = p->m, N = p->N, B = p->B;
     const bool pend = p->kind == DDP_PROBLEM_PENDCART;
-    const size_t bytes = ((n + m) * N * B * 2 + n * n + m * m + (pend ? (n * n + n * m) * N * B : 0)) * 8 + 16 * 256;
-    void *base;
-    int rc = ddp_scratch(h, bytes, &base);
-    if (rc) return rc;
-    char *pp = (char *)base;
-    auto take = [&](size_t cnt) { double *r = (double *)pp; pp += ((cnt * 8 + 255) & ~(size_t)255); return r; };
-    double *dx = take(n * N * B), *du = take(m * N * B), *dcx = take(n * N * B), *dcu = take(m * N * B), *dQ = take(n * n),
-           *dR = take(m * m), *dfx = pend ? take(n * n * N * B) : nullptr, *dfu = pend ? take(n * m * N * B) : nullptr;
-    DDP_HIP(hipMemcpyAsync(dx, x, n * N * B * 8, hipMemcpyHostToDevice, h->stream));
-    DDP_HIP(hipMemcpyAsync(du, u, m * N * B * 8, hipMemcpyHostToDevice, h->stream));
-    DDP_HIP(hipMemcpyAsync(dQ, p->Q, n * n * 8, hipMemcpyHostToDevice, h->stream));
-    DDP_HIP(hipMemcpyAsync(dR, p->R, m * m * 8, hipMemcpyHostToDevice, h->stream));
     ddp_problem pd = *p;
-    pd.Q = dQ; pd.R = dR;
-    rc = ddp_df_f64_dev(h, &pd, dx, du, nullptr, dcx, dcu, dfx, dfu);
+    const double *dx, *du;
+    double *dcx, *dcu, *dfx = nullptr, *dfu = nullptr;
+    Staging S(h, Staging::SCRATCH, "df");
+    S.in(&dx, x, n * N * B); S.in(&du, u, m * N * B);
+    S.out(&dcx, cx, n * N * B); S.out(&dcu, cu, m * N * B);
+    stage_cost(S, p, &pd);                                   // no diagonal test: df reads the whole of Q, R
+    // the pendulum's kernel writes fx, fu whether the caller wants them or not
+    if (pend) { S.out_or_temp(&dfx, fx, n * n * N * B); S.out_or_temp(&dfu, fu, n * m * N * B); }
+    const int rc = S.commit();
     if (rc) return rc;
-    DDP_HIP(hipMemcpyAsync(cx, dcx, n * N * B * 8, hipMemcpyDeviceToHost, h->stream));
-    DDP_HIP(hipMemcpyAsync(cu, dcu, m * N * B * 8, hipMemcpyDeviceToHost, h->stream));
-    if (pend && fx) DDP_HIP(hipMemcpyAsync(fx, dfx, n * n * N * B * 8, hipMemcpyDeviceToHost, h->stream));
-    if (pend && fu) DDP_HIP(hipMemcpyAsync(fu, dfu, n * m * N * B * 8, hipMemcpyDeviceToHost, h->stream));
-    DDP_HIP(hipStreamSynchronize(h->stream));
-    return 0;
+    return S.finish(ddp_df_f64_dev(h, &pd, dx, du, nullptr, dcx, dcu, dfx, dfu));
 }
 
 }   // extern "C"

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "ddp_internal.h"
+#include "staging.h"
 
 namespace {
 
@@ -1097,44 +1098,22 @@ static int ilqg_host(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o,
     DDP_DEVICE(h);
     DDP_CHECK(h && p && x0 && u0, "ilqg: null argument");
     const size_t n = p->n, m = p->m, N = p->N, B = p->B, CL = ddp_cost_len(p);
-    const size_t dc = (p->dyn_tv ? N : 1) * (p->dyn_batched ? B : 1);
-    // the driver uses the handle's scratch itself, so the host flavour owns separate allocations
-    // cost_diag = 1 is a declaration about Q, R: verified here, on the host copies, before anything is staged
-    { const int rd_ = ddp_check_cost_diag_host(p); if (rd_) return rd_; }
-    DiagVerified diag_verified_(h);                          // Q, R were tested on the host; the staged copies need no second test
-    struct Buf { void *d; void *hdst; size_t bytes; };
-    std::vector<Buf> bufs;
-    bool failed = false;
-    auto dev = [&](const void *src, void *dst, size_t bytes) -> void * {
-        void *d = nullptr;
-        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) { failed = true; return nullptr; }
-        if (src && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) failed = true;
-        bufs.push_back({d, dst, bytes});
-        return d;
-    };
-    ddp_problem pd = *p;
-    if (p->kind == DDP_PROBLEM_LQ) { pd.A = (double *)dev(p->A, nullptr, n * n * dc * 8); pd.Bm = (double *)dev(p->Bm, nullptr, n * m * dc * 8); }
-    pd.Q = (double *)dev(p->Q, nullptr, n * n * 8);
-    pd.R = (double *)dev(p->R, nullptr, m * m * 8);
-    double *dx0 = (double *)dev(x0, nullptr, n * (prerolled ? N : 1) * B * 8), *du0 = (double *)dev(u0, nullptr, m * N * B * 8),
-           *dl = lims ? (double *)dev(lims, nullptr, 2 * m * 8) : nullptr,
-           *dc0 = (prerolled && cost0) ? (double *)dev(cost0, nullptr, CL * B * 8) : nullptr;
-    double *dx = (double *)dev(nullptr, x, n * N * B * 8), *du = (double *)dev(nullptr, u, m * N * B * 8),
-           *dK = (double *)dev(nullptr, K, m * n * N * B * 8), *dk = (double *)dev(nullptr, k, m * N * B * 8),
-           *dQuu = (double *)dev(nullptr, Quu, m * m * N * B * 8), *dVx = (double *)dev(nullptr, Vx, n * N * B * 8),
-           *dVxx = (double *)dev(nullptr, Vxx, n * n * N * B * 8), *dcost = (double *)dev(nullptr, cost, CL * B * 8),
-           *dstats = (double *)dev(nullptr, stats, DDP_ILQG_NSTATS * B * 8),
-           *dtr = (trace_cost && trace_cap > 0) ? (double *)dev(nullptr, trace_cost, (size_t)trace_cap * B * 8) : nullptr,
-           *dt7 = (trace7 && trace_cap > 0) ? (double *)dev(nullptr, trace7, (size_t)7 * trace_cap * B * 8) : nullptr;
-    int rc = failed ? -2 : 0;
-    if (failed) ddp_set_error("ilqg: device allocation / upload failed");
-    if (!rc) rc = ilqg_impl(h, &pd, o, dx0, du0, dl, dx, du, dK, dk, dQuu, dVx, dVxx, dcost, dstats, trace_cap, dtr, global_iters, prerolled, dc0, dt7);
-    if (!rc)
-        for (auto &bf : bufs)
-            if (bf.hdst && hipMemcpyAsync(bf.hdst, bf.d, bf.bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = -2;
-    hipStreamSynchronize(h->stream);
-    for (auto &bf : bufs) hipFree(bf.d);
-    return rc;
+    ddp_problem pd;
+    const double *dx0, *du0, *dl, *dc0 = nullptr;
+    double *dx, *du, *dK, *dk, *dQuu, *dVx, *dVxx, *dcost, *dstats, *dtr = nullptr, *dt7 = nullptr;
+    Staging S(h, Staging::OWNED, "ilqg");                    // the driver carves the handle's scratch itself
+    int rc = stage_problem(S, p, &pd);
+    if (rc) return rc;
+    DiagVerified diag_verified_(h);
+    S.in(&dx0, x0, n * (prerolled ? N : 1) * B); S.in(&du0, u0, m * N * B); S.in(&dl, lims, 2 * m);
+    if (prerolled) S.in(&dc0, cost0, CL * B);
+    // the driver writes every result: device storage also for those the caller leaves out (it never sees a null K ... stats)
+    S.out_or_temp(&dx, x, n * N * B); S.out_or_temp(&du, u, m * N * B); S.out_or_temp(&dK, K, m * n * N * B); S.out_or_temp(&dk, k, m * N * B);
+    S.out_or_temp(&dQuu, Quu, m * m * N * B); S.out_or_temp(&dVx, Vx, n * N * B); S.out_or_temp(&dVxx, Vxx, n * n * N * B);
+    S.out_or_temp(&dcost, cost, CL * B); S.out_or_temp(&dstats, stats, DDP_ILQG_NSTATS * B);
+    if (trace_cap > 0) { S.out(&dtr, trace_cost, (size_t)trace_cap * B); S.out(&dt7, trace7, (size_t)7 * trace_cap * B); }
+    if ((rc = S.commit())) return rc;
+    return S.finish(ilqg_impl(h, &pd, o, dx0, du0, dl, dx, du, dK, dk, dQuu, dVx, dVxx, dcost, dstats, trace_cap, dtr, global_iters, prerolled, dc0, dt7));
 }
 
 int ddp_ilqg_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o, const double *x0, const double *u0,
@@ -1160,7 +1139,8 @@ int ddp_ilqg_ex_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o, 
                      trace_cap, nullptr, global_iters, trace7);
 }
 
-// host-pointer flavours of the slot scheduler: upload, run, download (the same staging as ilqg_host)
+// host-pointer flavours of the slot scheduler.  The driver reads a NULL K ... stats as "closed loop" (MPC keeps no policy) and a NULL
+// xcl, ucl, stats_cl as "queue": every result is staged with `out`, so a null host pointer reaches the driver as null.
 static int sched_host(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o, int slots, int steps, int zero_tail, const double *x0,
                       const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
                       double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters)
@@ -1168,44 +1148,20 @@ static int sched_host(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o
     DDP_DEVICE(h);
     DDP_CHECK(h && p && x0 && u0, "ilqg_sched: null argument");
     const size_t n = p->n, m = p->m, N = p->N, P = p->B, CL = ddp_cost_len(p);
-    const size_t dc = (p->dyn_tv ? N : 1) * (p->dyn_batched ? P : 1);
-    // cost_diag = 1 is a declaration about Q, R: verified here, on the host copies, before anything is staged
-    { const int rd_ = ddp_check_cost_diag_host(p); if (rd_) return rd_; }
-    DiagVerified diag_verified_(h);                          // Q, R were tested on the host; the staged copies need no second test
-    struct Buf { void *d; void *hdst; size_t bytes; };
-    std::vector<Buf> bufs;
-    bool failed = false;
-    auto dev = [&](const void *src, void *dst, size_t bytes) -> void * {
-        if (!src && !dst) return nullptr;
-        void *d = nullptr;
-        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) { failed = true; return nullptr; }
-        if (src && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) failed = true;
-        bufs.push_back({d, dst, bytes});
-        return d;
-    };
-    ddp_problem pd = *p;
-    if (p->kind == DDP_PROBLEM_LQ) { pd.A = (double *)dev(p->A, nullptr, n * n * dc * 8); pd.Bm = (double *)dev(p->Bm, nullptr, n * m * dc * 8); }
-    pd.Q = (double *)dev(p->Q, nullptr, n * n * 8);
-    pd.R = (double *)dev(p->R, nullptr, m * m * 8);
-    double *dx0 = (double *)dev(x0, nullptr, n * P * 8), *du0 = (double *)dev(u0, nullptr, m * N * P * 8),
-           *dl = lims ? (double *)dev(lims, nullptr, 2 * m * 8) : nullptr;
-    double *dx = (double *)dev(nullptr, x, n * N * P * 8), *du = (double *)dev(nullptr, u, m * N * P * 8),
-           *dK = (double *)dev(nullptr, K, m * n * N * P * 8), *dk = (double *)dev(nullptr, k, m * N * P * 8),
-           *dQuu = (double *)dev(nullptr, Quu, m * m * N * P * 8), *dVx = (double *)dev(nullptr, Vx, n * N * P * 8),
-           *dVxx = (double *)dev(nullptr, Vxx, n * n * N * P * 8), *dcost = (double *)dev(nullptr, cost, CL * P * 8),
-           *dstats = (double *)dev(nullptr, stats, DDP_ILQG_NSTATS * P * 8),
-           *dxcl = (double *)dev(nullptr, xcl, n * (size_t)(steps + 1) * P * 8), *ducl = (double *)dev(nullptr, ucl, m * (size_t)steps * P * 8),
-           *dscl = (double *)dev(nullptr, stats_cl, (size_t)DDP_ILQG_NSTATS * steps * P * 8);
-    int rc = failed ? -2 : 0;
-    if (failed) ddp_set_error("ilqg_sched: device allocation / upload failed");
-    if (!rc) rc = ilqg_sched_impl(h, &pd, o, slots, steps, zero_tail, dx0, du0, dl, dx, du, dK, dk, dQuu, dVx, dVxx, dcost, dstats, dxcl, ducl, dscl,
-                                  global_iters);
-    if (!rc)
-        for (auto &bf : bufs)
-            if (bf.hdst && hipMemcpyAsync(bf.hdst, bf.d, bf.bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = -2;
-    hipStreamSynchronize(h->stream);
-    for (auto &bf : bufs) hipFree(bf.d);
-    return rc;
+    ddp_problem pd;
+    const double *dx0, *du0, *dl;
+    double *dx, *du, *dK, *dk, *dQuu, *dVx, *dVxx, *dcost, *dstats, *dxcl, *ducl, *dscl;
+    Staging S(h, Staging::OWNED, "ilqg_sched");              // the driver carves the handle's scratch itself
+    int rc = stage_problem(S, p, &pd);
+    if (rc) return rc;
+    DiagVerified diag_verified_(h);
+    S.in(&dx0, x0, n * P); S.in(&du0, u0, m * N * P); S.in(&dl, lims, 2 * m);
+    S.out(&dx, x, n * N * P); S.out(&du, u, m * N * P); S.out(&dK, K, m * n * N * P); S.out(&dk, k, m * N * P); S.out(&dQuu, Quu, m * m * N * P);
+    S.out(&dVx, Vx, n * N * P); S.out(&dVxx, Vxx, n * n * N * P); S.out(&dcost, cost, CL * P); S.out(&dstats, stats, DDP_ILQG_NSTATS * P);
+    S.out(&dxcl, xcl, n * (size_t)(steps + 1) * P); S.out(&ducl, ucl, m * (size_t)steps * P); S.out(&dscl, stats_cl, (size_t)DDP_ILQG_NSTATS * steps * P);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ilqg_sched_impl(h, &pd, o, slots, steps, zero_tail, dx0, du0, dl, dx, du, dK, dk, dQuu, dVx, dVxx, dcost, dstats, dxcl, ducl, dscl,
+                                    global_iters));
 }
 
 int ddp_ilqg_queue_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *o, int slots, const double *x0, const double *u0,

@@ -6,11 +6,11 @@
 // the n = 4 ones of back_pass_q4.hip and back_pass_gps_lane.hip; gps_dispatch below chooses) and the iLQGkl driver for registered and
 // user problems.
 // None of this is on the benchmarked path; the kernels are written for clarity and coalescing, not tuned.
-#include "arena.h"
 #include <stdlib.h>
 #include <vector>
 #include <type_traits>
 #include "ddp_internal.h"
+#include "staging.h"
 
 namespace {
 
@@ -1113,7 +1113,7 @@ int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_op
 extern "C" {
 
 
-// host-pointer flavour of the driver: separate device allocations (the driver owns the handle's scratch), one upload, one download
+// host-pointer flavour of the driver: OWNED staging (the driver carves the handle's scratch itself), one upload, one download
 int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
                    const double *Kp, const double *kp, const double *Sp, const double *Sip,
                    const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
@@ -1123,45 +1123,23 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
     DDP_DEVICE(h);
     DDP_CHECK(p && x0 && Kp && kp && Sp && Sip && model_fx && R1, "ilqgkl: null argument");
     const size_t n = p->n, m = p->m, N = p->N, B = p->B, CL = ddp_cost_len(p), NB = N * B;
-    const size_t dc = (p->dyn_tv ? N : 1) * (p->dyn_batched ? B : 1);
-    // cost_diag = 1 is a declaration about Q, R: verified here, on the host copies, before anything is staged
-    { const int rd_ = ddp_check_cost_diag_host(p); if (rd_) return rd_; }
-    DiagVerified diag_verified_(h);                          // Q, R were tested on the host; the staged copies need no second test
-    struct Buf { void *d; void *hdst; size_t bytes; };
-    std::vector<Buf> bufs;
-    bool failed = false;
-    auto dev = [&](const void *src, void *dst, size_t bytes) -> void * {
-        void *d = nullptr;
-        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) { failed = true; return nullptr; }
-        if (src && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) failed = true;
-        bufs.push_back({d, dst, bytes});
-        return d;
-    };
-    ddp_problem pd = *p;
-    if (p->kind == DDP_PROBLEM_LQ) { pd.A = (double *)dev(p->A, nullptr, n * n * dc * 8); pd.Bm = (double *)dev(p->Bm, nullptr, n * m * dc * 8); }
-    pd.Q = (double *)dev(p->Q, nullptr, n * n * 8);
-    pd.R = (double *)dev(p->R, nullptr, m * m * 8);
-    const double *dx0 = (double *)dev(x0, nullptr, n * NB * 8), *dc0 = cost0 ? (double *)dev(cost0, nullptr, B * 8) : nullptr,
-                 *dKp = (double *)dev(Kp, nullptr, m * n * NB * 8), *dkp = (double *)dev(kp, nullptr, m * NB * 8),
-                 *dSp = (double *)dev(Sp, nullptr, m * m * NB * 8), *dSip = (double *)dev(Sip, nullptr, m * m * NB * 8),
-                 *dmf = (double *)dev(model_fx, nullptr, n * n * N * (model_fx_batched ? B : 1) * 8), *dR1 = (double *)dev(R1, nullptr, n * n * 8),
-                 *dl = lims ? (double *)dev(lims, nullptr, 2 * m * 8) : nullptr;
-    double *det = etab ? (double *)dev(etab, etab, 3 * B * 8) : nullptr;
-    double *dx = (double *)dev(nullptr, x, n * NB * 8), *du = (double *)dev(nullptr, u, m * NB * 8), *dK = (double *)dev(nullptr, K, m * n * NB * 8),
-           *dS = (double *)dev(nullptr, Sigma, m * m * NB * 8), *dSi = (double *)dev(nullptr, Sigmai, m * m * NB * 8),
-           *dVx = (double *)dev(nullptr, Vx, n * NB * 8), *dVxx = (double *)dev(nullptr, Vxx, n * n * NB * 8),
-           *dcost = (double *)dev(nullptr, cost, CL * B * 8), *ddV = (double *)dev(nullptr, dV, 2 * B * 8),
-           *dst = (double *)dev(nullptr, stats, DDP_ILQGKL_NSTATS * B * 8);
-    int rc = failed ? -2 : 0;
-    if (failed) ddp_set_error("ilqgkl: device allocation / upload failed");
-    if (!rc) rc = ddp_ilqgkl_f64_dev(h, &pd, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl, det, dx, du, dK, dS, dSi, dVx, dVxx,
-                                     dcost, ddV, dst, iters_out);
-    if (!rc)
-        for (auto &bf : bufs)
-            if (bf.hdst && hipMemcpyAsync(bf.hdst, bf.d, bf.bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = -2;
-    hipStreamSynchronize(h->stream);
-    for (auto &bf : bufs) hipFree(bf.d);
-    return rc;
+    ddp_problem pd;
+    const double *dx0, *dc0, *dKp, *dkp, *dSp, *dSip, *dmf, *dR1, *dl;
+    double *det, *dx, *du, *dK, *dS, *dSi, *dVx, *dVxx, *dcost, *ddV, *dst;
+    Staging S(h, Staging::OWNED, "ilqgkl");
+    int rc = stage_problem(S, p, &pd);
+    if (rc) return rc;
+    DiagVerified diag_verified_(h);
+    S.in(&dx0, x0, n * NB); S.in(&dc0, cost0, B); S.in(&dKp, Kp, m * n * NB); S.in(&dkp, kp, m * NB); S.in(&dSp, Sp, m * m * NB);
+    S.in(&dSip, Sip, m * m * NB); S.in(&dmf, model_fx, n * n * N * (model_fx_batched ? B : 1)); S.in(&dR1, R1, n * n); S.in(&dl, lims, 2 * m);
+    S.inout(&det, etab, 3 * B);
+    // the driver writes every result: device storage also for those the caller leaves out
+    S.out_or_temp(&dx, x, n * NB); S.out_or_temp(&du, u, m * NB); S.out_or_temp(&dK, K, m * n * NB); S.out_or_temp(&dS, Sigma, m * m * NB);
+    S.out_or_temp(&dSi, Sigmai, m * m * NB); S.out_or_temp(&dVx, Vx, n * NB); S.out_or_temp(&dVxx, Vxx, n * n * NB);
+    S.out_or_temp(&dcost, cost, CL * B); S.out_or_temp(&ddV, dV, 2 * B); S.out_or_temp(&dst, stats, DDP_ILQGKL_NSTATS * B);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_ilqgkl_f64_dev(h, &pd, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl, det, dx, du, dK, dS, dSi, dVx, dVxx,
+                                       dcost, ddV, dst, iters_out));
 }
 
 // ---- host-pointer flavours (stage through the handle's scratch; PCIe-inclusive, for drop-in use with host arrays)
@@ -1169,18 +1147,15 @@ int ddp_kl_terms_f64(ddp_handle h, int n, int m, int N, int B, const double *K, 
                      double *cx, double *cu, double *cxx, double *cxu, double *cuu)
 {
     DDP_CHECK(h, "kl_terms: null handle");
-    const size_t nb = (size_t)N * B, in[] = {(size_t)m * n * nb, (size_t)m * nb, (size_t)m * m * nb},
-                 out[] = {(size_t)n * nb, (size_t)m * nb, (size_t)n * n * nb, (size_t)m * n * nb, (size_t)m * m * nb};
-    Arena A; A.h = h;
-    for (size_t s : in) A.want(s * 8);
-    for (size_t s : out) A.want(s * 8);
-    int rc = A.commit();
+    const size_t nb = (size_t)N * B, sn = n, sm = m;
+    const double *dK, *dk, *dS;
+    double *o0, *o1, *o2, *o3, *o4;
+    Staging S(h, Staging::SCRATCH, "kl_terms");
+    S.in(&dK, K, sm * sn * nb); S.in(&dk, k, sm * nb); S.in(&dS, Sigmai, sm * sm * nb);
+    S.out(&o0, cx, sn * nb); S.out(&o1, cu, sm * nb); S.out(&o2, cxx, sn * sn * nb); S.out(&o3, cxu, sm * sn * nb); S.out(&o4, cuu, sm * sm * nb);
+    const int rc = S.commit();
     if (rc) return rc;
-    const double *dK = A.in(K, in[0]), *dk = A.in(k, in[1]), *dS = A.in(Sigmai, in[2]);
-    double *o0 = A.outp(cx, out[0]), *o1 = A.outp(cu, out[1]), *o2 = A.outp(cxx, out[2]), *o3 = A.outp(cxu, out[3]), *o4 = A.outp(cuu, out[4]);
-    if ((rc = A.upload())) return rc;
-    if ((rc = ddp_kl_terms_f64_dev(h, n, m, N, B, dK, dk, dS, o0, o1, o2, o3, o4))) return rc;
-    return A.download();
+    return S.finish(ddp_kl_terms_f64_dev(h, n, m, N, B, dK, dk, dS, o0, o1, o2, o3, o4));
 }
 
 int ddp_back_pass_gps_f64(ddp_handle h, const ddp_bp_desc *d,
@@ -1193,28 +1168,21 @@ int ddp_back_pass_gps_f64(ddp_handle h, const ddp_bp_desc *d,
     DDP_CHECK(h && d && kl, "back_pass_gps: null handle/descriptor/kl terms");
     const size_t n = d->n, m = d->m, N = d->N, B = d->B, nb = N * B;
     const size_t fxc = N * (d->fx_batched ? B : 1), cc = N * (d->cost_batched ? B : 1);
-    const size_t in[] = {n * nb, m * nb, n * n * cc, n * m * cc, m * m * cc, n * n * fxc, n * m * fxc, 2 * m, m * nb,
-                         n * nb, m * nb, n * n * nb, m * n * nb, m * m * nb, kl->eta_tv ? nb : B};
-    const size_t out[] = {m * n * nb, m * nb, m * m * nb, m * m * nb, n * nb, n * n * nb, 2 * B};
-    Arena A; A.h = h;
-    for (size_t s : in) A.want(s * 8);
-    for (size_t s : out) A.want(s * 8);
-    A.want(B * 4);
-    int rc = A.commit();
-    if (rc) return rc;
-    const double *dcx = A.in(cx, in[0]), *dcu = A.in(cu, in[1]), *dcxx = A.in(cxx, in[2]), *dcxu = A.in(cxu, in[3]), *dcuu = A.in(cuu, in[4]),
-                 *dfx = A.in(fx, in[5]), *dfu = A.in(fu, in[6]), *dl = d->has_lims ? A.in(lims, in[7]) : nullptr,
-                 *du = d->has_lims ? A.in(u, in[8]) : nullptr;
+    const double *dcx, *dcu, *dcxx, *dcxu, *dcuu, *dfx, *dfu, *dl = nullptr, *du = nullptr;
     ddp_kl_cost_terms kd;
-    kd.cx = A.in(kl->cx, in[9]); kd.cu = A.in(kl->cu, in[10]); kd.cxx = A.in(kl->cxx, in[11]); kd.cxu = A.in(kl->cxu, in[12]);
-    kd.cuu = A.in(kl->cuu, in[13]); kd.eta = A.in(kl->eta, in[14]); kd.eta_tv = kl->eta_tv;
-    double *dK = A.outp(K, out[0]), *dk = A.outp(k, out[1]), *dQuu = A.outp(Quu, out[2]), *dQuui = A.outp(Quui, out[3]),
-           *dVx = A.outp(Vx, out[4]), *dVxx = A.outp(Vxx, out[5]), *ddV = A.outp(dV, out[6]);
-    int32_t *ddiv = A.outp(diverge, B);
-    if ((rc = A.upload())) return rc;
-    if ((rc = ddp_back_pass_gps_f64_dev(h, d, dcx, dcu, dcxx, dcxu, dcuu, dfx, dfu, &kd, dl, du, nullptr, dK, dk, dQuu, dQuui, dVx, dVxx, ddV, ddiv)))
-        return rc;
-    return A.download();
+    double *dK, *dk, *dQuu, *dQuui, *dVx, *dVxx, *ddV;
+    int32_t *ddiv;
+    Staging S(h, Staging::SCRATCH, "back_pass_gps");
+    S.in(&dcx, cx, n * nb); S.in(&dcu, cu, m * nb); S.in(&dcxx, cxx, n * n * cc); S.in(&dcxu, cxu, n * m * cc); S.in(&dcuu, cuu, m * m * cc);
+    S.in(&dfx, fx, n * n * fxc); S.in(&dfu, fu, n * m * fxc);
+    if (d->has_lims) { S.in(&dl, lims, 2 * m); S.in(&du, u, m * nb); }
+    S.in(&kd.cx, kl->cx, n * nb); S.in(&kd.cu, kl->cu, m * nb); S.in(&kd.cxx, kl->cxx, n * n * nb); S.in(&kd.cxu, kl->cxu, m * n * nb);
+    S.in(&kd.cuu, kl->cuu, m * m * nb); S.in(&kd.eta, kl->eta, kl->eta_tv ? nb : B); kd.eta_tv = kl->eta_tv;
+    S.out(&dK, K, m * n * nb); S.out(&dk, k, m * nb); S.out(&dQuu, Quu, m * m * nb); S.out(&dQuui, Quui, m * m * nb); S.out(&dVx, Vx, n * nb);
+    S.out(&dVxx, Vxx, n * n * nb); S.out(&ddV, dV, 2 * B); S.out(&ddiv, diverge, B);
+    const int rc = S.commit();
+    if (rc) return rc;
+    return S.finish(ddp_back_pass_gps_f64_dev(h, d, dcx, dcu, dcxx, dcxu, dcuu, dfx, dfu, &kd, dl, du, nullptr, dK, dk, dQuu, dQuui, dVx, dVxx, ddV, ddiv));
 }
 
 int ddp_forward_covariance_f64(ddp_handle h, int n, int m, int N, int B, const double *fx, int fx_batched,
@@ -1222,17 +1190,14 @@ int ddp_forward_covariance_f64(ddp_handle h, int n, int m, int N, int B, const d
 {
     DDP_CHECK(h, "forward_covariance: null handle");
     const size_t nb = (size_t)N * B, p = (size_t)n + m;
-    const size_t in[] = {(size_t)n * n * N * (fx_batched ? B : 1), (size_t)n * n, (size_t)m * n * nb, (size_t)m * m * nb};
-    Arena A; A.h = h;
-    for (size_t s : in) A.want(s * 8);
-    A.want(p * p * nb * 8);
-    int rc = A.commit();
+    const double *dfx, *dR, *dK, *dS;
+    double *o;
+    Staging S(h, Staging::SCRATCH, "forward_covariance");
+    S.in(&dfx, fx, (size_t)n * n * N * (fx_batched ? B : 1)); S.in(&dR, R1, (size_t)n * n); S.in(&dK, K, (size_t)m * n * nb); S.in(&dS, Sigma, (size_t)m * m * nb);
+    S.out(&o, sigmanew, p * p * nb);
+    const int rc = S.commit();
     if (rc) return rc;
-    const double *dfx = A.in(fx, in[0]), *dR = A.in(R1, in[1]), *dK = A.in(K, in[2]), *dS = A.in(Sigma, in[3]);
-    double *o = A.outp(sigmanew, p * p * nb);
-    if ((rc = A.upload())) return rc;
-    if ((rc = ddp_forward_covariance_f64_dev(h, n, m, N, B, dfx, fx_batched, dR, dK, dS, o))) return rc;
-    return A.download();
+    return S.finish(ddp_forward_covariance_f64_dev(h, n, m, N, B, dfx, fx_batched, dR, dK, dS, o));
 }
 
 int ddp_kl_div_f64(ddp_handle h, int n, int m, int N, int B, const double *xnew, const double *xold,
@@ -1242,20 +1207,16 @@ int ddp_kl_div_f64(ddp_handle h, int n, int m, int N, int B, const double *xnew,
 {
     DDP_CHECK(h, "kl_div: null handle");
     const size_t nb = (size_t)N * B, p = (size_t)n + m;
-    const size_t in[] = {n * nb, n * nb, p * p * nb, (size_t)m * n * nb, m * nb, (size_t)m * m * nb, (size_t)m * n * nb, m * nb,
-                         (size_t)m * m * nb, (size_t)m * m * nb};
-    Arena A; A.h = h;
-    for (size_t s : in) A.want(s * 8);
-    A.want(nb * 8); A.want((size_t)B * 8);
-    int rc = A.commit();
+    const size_t sK = (size_t)m * n * nb, sk = (size_t)m * nb, sS = (size_t)m * m * nb;
+    const double *a0, *a1, *a2, *a3, *a4, *a5, *a6, *a7, *a8, *a9;
+    double *o0, *o1;
+    Staging S(h, Staging::SCRATCH, "kl_div");
+    S.in(&a0, xnew, n * nb); S.in(&a1, xold, n * nb); S.in(&a2, sigmanew, p * p * nb); S.in(&a3, Kn, sK); S.in(&a4, kn, sk); S.in(&a5, Sn, sS);
+    S.in(&a6, Kp, sK); S.in(&a7, kp, sk); S.in(&a8, Sp, sS); S.in(&a9, Sip, sS);
+    S.out_or_temp(&o0, kldiv, nb); S.out(&o1, klmean, (size_t)B);       // klmean is summed from kldiv: the kernel writes kldiv either way
+    const int rc = S.commit();
     if (rc) return rc;
-    const double *a0 = A.in(xnew, in[0]), *a1 = A.in(xold, in[1]), *a2 = A.in(sigmanew, in[2]), *a3 = A.in(Kn, in[3]), *a4 = A.in(kn, in[4]),
-                 *a5 = A.in(Sn, in[5]), *a6 = A.in(Kp, in[6]), *a7 = A.in(kp, in[7]), *a8 = A.in(Sp, in[8]), *a9 = A.in(Sip, in[9]);
-    double *o0 = A.outp(kldiv, nb), *o1 = A.outp(klmean, (size_t)B);
-    if (!o0) o0 = (double *)A.take(nb * 8);
-    if ((rc = A.upload())) return rc;
-    if ((rc = ddp_kl_div_f64_dev(h, n, m, N, B, a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, o0, o1))) return rc;
-    return A.download();
+    return S.finish(ddp_kl_div_f64_dev(h, n, m, N, B, a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, o0, o1));
 }
 
 }   // extern "C"

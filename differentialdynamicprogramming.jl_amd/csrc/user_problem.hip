@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "ddp_internal.h"
+#include "staging.h"
 #include "user_autodiff.h"
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
@@ -574,37 +575,16 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
     return 0;
 }
 
-// host-pointer flavours: device copies of the inputs, the _dev entry, copies of the outputs back
-struct Staging {
-    ddp_handle h;
-    struct Buf { void *d; void *hdst; size_t bytes; };
-    std::vector<Buf> bufs;
-    bool failed = false;
-    explicit Staging(ddp_handle h_) : h(h_) {}
-    ~Staging() { hipStreamSynchronize(h->stream); for (auto &b : bufs) hipFree(b.d); }
-    double *in(const double *src, size_t n) { return src ? (double *)put(src, nullptr, n * 8) : nullptr; }
-    double *out(double *dst, size_t n) { return dst ? (double *)put(nullptr, dst, n * 8) : nullptr; }
-    void *put(const void *src, void *dst, size_t bytes)
-    {
-        void *d = nullptr;
-        if (hipMalloc(&d, bytes ? bytes : 8) != hipSuccess) { failed = true; return nullptr; }
-        if (src && hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) failed = true;
-        bufs.push_back({d, dst, bytes});
-        return d;
-    }
-    int finish(int rc)
-    {
-        if (!rc)
-            for (auto &b : bufs)
-                if (b.hdst && hipMemcpyAsync(b.hdst, b.d, b.bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = -2;
-        if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { ddp_set_error("user problem: stream synchronisation failed"); rc = -2; }
-        return rc;
-    }
-};
-#define DDP_STAGED(S)                                                                                  \
-    do {                                                                                               \
-        if ((S).failed) { ddp_set_error("user problem: device allocation / upload failed"); return -2; } \
-    } while (0)
+// what every ddp_user_* entry does first: the handle's device made current, the problem checked against the handle, the sizes and
+// parameters of the call bound.  A host-pointer flavour binds twice, here (it needs CL to size its staging) and in its `_dev` twin, with
+// the device copy of the parameters; the second bind finds t0_count == B and leaves the clocks on the device alone.
+int enter(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, UserProblem **P)
+{
+    DDP_DEVICE(h);
+    *P = as_problem(h, up);
+    if (!*P) return -1;
+    return bind(*P, N, B, params, params_batched);
+}
 
 }   // namespace
 
@@ -694,10 +674,8 @@ int ddp_user_set_t0(void *up, const int32_t *t0, int count)
 int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                         const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
     rc = P->df(h, B, nullptr, x, u, active, fx, fu, cx, cu, P->const_hessian ? nullptr : cxx, P->const_hessian ? nullptr : cxu,
@@ -710,28 +688,26 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
 int ddp_user_df_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                     double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
+    DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
     const size_t n = P->n, m = P->m, T = (size_t)N * B, HT = P->const_hessian ? (size_t)B : T;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T);
-    double *dfx = S.out(fx, n * n * T), *dfu = S.out(fu, n * m * T), *dcx = S.out(cx, n * T), *dcu = S.out(cu, m * T),
-           *dxx = S.out(cxx, n * n * HT), *dxu = S.out(cxu, n * m * HT), *duu = S.out(cuu, m * m * HT);
-    DDP_STAGED(S);
+    const double *dp, *dx, *du;
+    double *dfx, *dfu, *dcx, *dcu, *dxx, *dxu, *duu;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx, x, n * T); S.in(&du, u, m * T);
+    S.out(&dfx, fx, n * n * T); S.out(&dfu, fu, n * m * T); S.out(&dcx, cx, n * T); S.out(&dcu, cu, m * T); S.out(&dxx, cxx, n * n * HT);
+    S.out(&dxu, cxu, n * m * HT); S.out(&duu, cuu, m * m * HT);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_df_f64_dev(h, up, N, B, dp, params_batched, dx, du, nullptr, dfx, dfu, dcx, dcu, dxx, dxu, duu));
 }
 
 int ddp_user_vhess_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                            const double *v, const int32_t *active, double *H)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(P->mod->vhess, "vhess: the problem was made without DDP_USER_SECOND_ORDER");
     DDP_CHECK(x && u && v && H, "vhess: null argument");
@@ -750,17 +726,17 @@ int ddp_user_vhess_f64_dev(ddp_handle h, void *up, int N, int B, const double *p
 int ddp_user_vhess_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x, const double *u,
                        const double *v, double *H)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    DDP_CHECK(x && u && v && H, "vhess: null argument");
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
+    DDP_CHECK(x && u && v && H, "vhess: null argument");
     const size_t n = P->n, m = P->m, T = (size_t)N * B;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T), *dv = S.in(v, n * T);
-    double *dH = S.out(H, (n + m) * (n + m) * T);
-    DDP_STAGED(S);
+    const double *dp, *dx, *du, *dv;
+    double *dH;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx, x, n * T); S.in(&du, u, m * T); S.in(&dv, v, n * T);
+    S.out(&dH, H, (n + m) * (n + m) * T);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_vhess_f64_dev(h, up, N, B, dp, params_batched, dx, du, dv, nullptr, dH));
 }
 
@@ -770,10 +746,8 @@ int ddp_user_back_pass_f64_dev(ddp_handle h, void *up, int N, int B, const doubl
                                const int32_t *active, double *K, double *k, double *Quu, double *Vx, double *Vxx, double *dV,
                                int32_t *diverge)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(P->second_order, "back_pass: the problem was made without DDP_USER_SECOND_ORDER; a first-order pass is ddp_back_pass_f64 "
                                "on the arrays of ddp_user_df");
@@ -792,22 +766,22 @@ int ddp_user_back_pass_f64(ddp_handle h, void *up, int N, int B, const double *p
                            const double *cuu, const double *lambda, int regType, const double *lims, double *K, double *k, double *Quu,
                            double *Vx, double *Vxx, double *dV, int32_t *diverge)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x && u && fx && fu && cx && cu && cxx && cxu && cuu && lambda && K && k && Quu && Vx && Vxx && dV && diverge,
               "back_pass: null argument");
     const size_t n = P->n, m = P->m, T = (size_t)N * B, HT = P->const_hessian ? (size_t)B : T;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T),
-           *dfx = S.in(fx, n * n * T), *dfu = S.in(fu, n * m * T), *dcx = S.in(cx, n * T), *dcu = S.in(cu, m * T), *dxx = S.in(cxx, n * n * HT),
-           *dxu = S.in(cxu, n * m * HT), *duu = S.in(cuu, m * m * HT), *dlam = S.in(lambda, (size_t)B), *dl = S.in(lims, 2 * m);
-    double *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T), *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T),
-           *ddV = S.out(dV, (size_t)2 * B);
-    int32_t *ddiv = (int32_t *)S.put(nullptr, diverge, (size_t)B * 4);
-    DDP_STAGED(S);
+    const double *dp, *dx, *du, *dfx, *dfu, *dcx, *dcu, *dxx, *dxu, *duu, *dlam, *dl;
+    double *dK, *dk, *dQ, *dVx, *dVxx, *ddV;
+    int32_t *ddiv;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx, x, n * T); S.in(&du, u, m * T); S.in(&dfx, fx, n * n * T);
+    S.in(&dfu, fu, n * m * T); S.in(&dcx, cx, n * T); S.in(&dcu, cu, m * T); S.in(&dxx, cxx, n * n * HT); S.in(&dxu, cxu, n * m * HT);
+    S.in(&duu, cuu, m * m * HT); S.in(&dlam, lambda, (size_t)B); S.in(&dl, lims, 2 * m);
+    S.out(&dK, K, m * n * T); S.out(&dk, k, m * T); S.out(&dQ, Quu, m * m * T); S.out(&dVx, Vx, n * T); S.out(&dVxx, Vxx, n * n * T);
+    S.out(&ddV, dV, (size_t)2 * B); S.out(&ddiv, diverge, (size_t)B);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_back_pass_f64_dev(h, up, N, B, dp, params_batched, dx, du, dfx, dfu, dcx, dcu, dxx, dxu, duu, dlam, regType, dl,
                                                nullptr, dK, dk, dQ, dVx, dVxx, ddV, ddiv));
 }
@@ -827,10 +801,8 @@ int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const do
                                   const double *alpha, int nalpha, const double *lims, const int32_t *active,
                                   double *xnew, double *unew, double *cnew, double *csum)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x0 && u && alpha && xnew && unew && cnew && csum, "forward_pass: null argument");
     return P->rollout(h, B, nullptr, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
@@ -841,20 +813,19 @@ int ddp_user_forward_pass_f64(ddp_handle h, void *up, int N, int B, const double
                               const double *alpha, int nalpha, const double *lims,
                               double *xnew, double *unew, double *cnew, double *csum)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x0 && u && alpha && xnew && unew && cnew && csum, "forward_pass: null argument");
     DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
     const size_t n = P->n, m = P->m, T = (size_t)N * B, na = nalpha;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dK = S.in(K, m * n * T), *dk = S.in(k, m * T),
-           *dx0 = S.in(x0, n * B), *du = S.in(u, m * T), *dx = S.in(x, n * T), *dl = S.in(lims, 2 * m);
-    double *dxn = S.out(xnew, n * T * na), *dun = S.out(unew, m * T * na), *dcn = S.out(cnew, (size_t)P->CL * B * na),
-           *dcs = S.out(csum, (size_t)B * na);
-    DDP_STAGED(S);
+    const double *dp, *dK, *dk, *dx0, *du, *dx, *dl;
+    double *dxn, *dun, *dcn, *dcs;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dK, K, m * n * T); S.in(&dk, k, m * T); S.in(&dx0, x0, n * B);
+    S.in(&du, u, m * T); S.in(&dx, x, n * T); S.in(&dl, lims, 2 * m);
+    S.out(&dxn, xnew, n * T * na); S.out(&dun, unew, m * T * na); S.out(&dcn, cnew, (size_t)P->CL * B * na); S.out(&dcs, csum, (size_t)B * na);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_forward_pass_f64_dev(h, up, N, B, dp, params_batched, dK, dk, dx0, du, dx, alpha, nalpha, dl, nullptr, dxn, dun,
                                                   dcn, dcs));
 }
@@ -862,10 +833,8 @@ int ddp_user_forward_pass_f64(ddp_handle h, void *up, int N, int B, const double
 int ddp_user_costfun_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
                              const double *u, const int32_t *active, double *cost, double *csum)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x && u && cost, "costfun: null argument");
     return P->costfun(h, B, nullptr, x, u, active, cost, csum);
@@ -874,17 +843,17 @@ int ddp_user_costfun_f64_dev(ddp_handle h, void *up, int N, int B, const double 
 int ddp_user_costfun_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
                          const double *u, double *cost, double *csum)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x && u && cost, "costfun: null argument");
     const size_t n = P->n, m = P->m, T = (size_t)N * B;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx = S.in(x, n * T), *du = S.in(u, m * T);
-    double *dc = S.out(cost, (size_t)P->CL * B), *ds = S.out(csum, (size_t)B);
-    DDP_STAGED(S);
+    const double *dp, *dx, *du;
+    double *dc, *ds;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx, x, n * T); S.in(&du, u, m * T);
+    S.out(&dc, cost, (size_t)P->CL * B); S.out(&ds, csum, (size_t)B);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_costfun_f64_dev(h, up, N, B, dp, params_batched, dx, du, nullptr, dc, ds));
 }
 
@@ -893,10 +862,8 @@ int ddp_user_ilqg_f64_dev(ddp_handle h, void *up, int N, int B, const double *pa
                           double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
                           double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     return ddp_ilqg_family_dev(h, P, o, x0, x0_prerolled, u0, cost0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, trace7,
                                global_iters);
@@ -907,20 +874,21 @@ int ddp_user_ilqg_f64(ddp_handle h, void *up, int N, int B, const double *params
                       double *x, double *u, double *K, double *k, double *Quu, double *Vx, double *Vxx,
                       double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *P = as_problem(h, up);
-    if (!P) return -1;
-    int rc = bind(P, N, B, params, params_batched);
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
     DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg: null argument");
     const size_t n = P->n, m = P->m, T = (size_t)N * B, CL = P->CL;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)P->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * (x0_prerolled ? T : (size_t)B)),
-           *du0 = S.in(u0, m * T), *dc0 = x0_prerolled ? S.in(cost0, CL * B) : nullptr, *dl = S.in(lims, 2 * m);
-    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T),
-           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * B), *ds = S.out(stats, (size_t)DDP_ILQG_NSTATS * B),
-           *dt7 = (trace7 && trace_cap > 0) ? S.out(trace7, (size_t)7 * trace_cap * B) : nullptr;
-    DDP_STAGED(S);
+    const double *dp, *dx0, *du0, *dc0 = nullptr, *dl;
+    double *dx, *du, *dK, *dk, *dQ, *dVx, *dVxx, *dc, *ds, *dt7 = nullptr;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * (x0_prerolled ? T : (size_t)B)); S.in(&du0, u0, m * T);
+    if (x0_prerolled) S.in(&dc0, cost0, CL * B);
+    S.in(&dl, lims, 2 * m);
+    S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dk, k, m * T); S.out(&dQ, Quu, m * m * T); S.out(&dVx, Vx, n * T);
+    S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * B); S.out(&ds, stats, (size_t)DDP_ILQG_NSTATS * B);
+    if (trace7 && trace_cap > 0) S.out(&dt7, trace7, (size_t)7 * trace_cap * B);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqg_f64_dev(h, up, N, B, dp, params_batched, o, dx0, x0_prerolled, du0, dc0, dl, dx, du, dK, dk, dQ, dVx, dVxx,
                                           dc, ds, trace_cap, dt7, global_iters));
 }
@@ -929,10 +897,8 @@ int ddp_user_ilqg_queue_f64_dev(ddp_handle h, void *up, int N, int P, const doub
                                 int slots, const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
                                 double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, P, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, P, params, params_batched, &U);
     if (rc) return rc;
     DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
     return ddp_ilqg_sched_family_dev(h, U, o, slots, 0, 0, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, nullptr, nullptr, nullptr,
@@ -943,19 +909,18 @@ int ddp_user_ilqg_queue_f64(ddp_handle h, void *up, int N, int P, const double *
                             int slots, const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
                             double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, P, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, P, params, params_batched, &U);
     if (rc) return rc;
     DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
     const size_t n = U->n, m = U->m, T = (size_t)N * P, CL = U->CL;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? P : 1)), *dx0 = S.in(x0, n * P), *du0 = S.in(u0, m * T),
-           *dl = S.in(lims, 2 * m);
-    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dk = S.out(k, m * T), *dQ = S.out(Quu, m * m * T),
-           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * P), *ds = S.out(stats, (size_t)DDP_ILQG_NSTATS * P);
-    DDP_STAGED(S);
+    const double *dp, *dx0, *du0, *dl;
+    double *dx, *du, *dK, *dk, *dQ, *dVx, *dVxx, *dc, *ds;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)U->nparam * (params_batched ? P : 1)); S.in(&dx0, x0, n * P); S.in(&du0, u0, m * T); S.in(&dl, lims, 2 * m);
+    S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dk, k, m * T); S.out(&dQ, Quu, m * m * T); S.out(&dVx, Vx, n * T);
+    S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * P); S.out(&ds, stats, (size_t)DDP_ILQG_NSTATS * P);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqg_queue_f64_dev(h, up, N, P, dp, params_batched, o, slots, dx0, du0, dl, dx, du, dK, dk, dQ, dVx, dVxx, dc, ds,
                                                 global_iters));
 }
@@ -964,10 +929,8 @@ int ddp_user_ilqg_mpc_f64_dev(ddp_handle h, void *up, int N, int B, const double
                               int steps, int zero_tail, const double *x0, const double *u0, const double *lims, double *xcl, double *ucl,
                               double *stats_cl, double *x, double *u, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, B, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U);
     if (rc) return rc;
     DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
     DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
@@ -982,20 +945,19 @@ int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *pa
                           int steps, int zero_tail, const double *x0, const double *u0, const double *lims, double *xcl, double *ucl,
                           double *stats_cl, double *x, double *u, int *global_iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, B, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U);
     if (rc) return rc;
     DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
     DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
     const size_t n = U->n, m = U->m, T = (size_t)N * B;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * B), *du0 = S.in(u0, m * T),
-           *dl = S.in(lims, 2 * m);
-    double *dxcl = S.out(xcl, n * (size_t)(steps + 1) * B), *ducl = S.out(ucl, m * (size_t)steps * B),
-           *dscl = S.out(stats_cl, (size_t)DDP_ILQG_NSTATS * steps * B), *dx = S.out(x, n * T), *du = S.out(u, m * T);
-    DDP_STAGED(S);
+    const double *dp, *dx0, *du0, *dl;
+    double *dxcl, *ducl, *dscl, *dx, *du;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)U->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * B); S.in(&du0, u0, m * T); S.in(&dl, lims, 2 * m);
+    S.out(&dxcl, xcl, n * (size_t)(steps + 1) * B); S.out(&ducl, ucl, m * (size_t)steps * B);
+    S.out(&dscl, stats_cl, (size_t)DDP_ILQG_NSTATS * steps * B); S.out(&dx, x, n * T); S.out(&du, u, m * T);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqg_mpc_f64_dev(h, up, N, B, dp, params_batched, o, steps, zero_tail, dx0, du0, dl, dxcl, ducl, dscl, dx, du,
                                               global_iters));
 }
@@ -1006,10 +968,8 @@ int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *
                             double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
                             double *cost, double *dV, double *stats, int *iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, B, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U);
     if (rc) return rc;
     return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
                                  Vxx, cost, dV, stats, iters);
@@ -1021,22 +981,21 @@ int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *para
                         double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
                         double *cost, double *dV, double *stats, int *iters)
 {
-    DDP_DEVICE(h);
-    UserProblem *U = as_problem(h, up);
-    if (!U) return -1;
-    int rc = bind(U, N, B, params, params_batched);
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U);
     if (rc) return rc;
     DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl: null argument");
     const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;
-    Staging S(h);
-    double *dp = S.in(params, (size_t)U->nparam * (params_batched ? B : 1)), *dx0 = S.in(x0, n * T), *dc0 = S.in(cost0, (size_t)B),
-           *dKp = S.in(Kp, m * n * T), *dkp = S.in(kp, m * T), *dSp = S.in(Sp, m * m * T), *dSip = S.in(Sip, m * m * T),
-           *dmf = S.in(model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)), *dR1 = S.in(R1, n * n), *dl = S.in(lims, 2 * m);
-    double *det = etab ? (double *)S.put(etab, etab, (size_t)3 * B * 8) : nullptr;
-    double *dx = S.out(x, n * T), *du = S.out(u, m * T), *dK = S.out(K, m * n * T), *dS = S.out(Sigma, m * m * T), *dSi = S.out(Sigmai, m * m * T),
-           *dVx = S.out(Vx, n * T), *dVxx = S.out(Vxx, n * n * T), *dc = S.out(cost, CL * B), *ddV = S.out(dV, (size_t)2 * B),
-           *ds = S.out(stats, (size_t)DDP_ILQGKL_NSTATS * B);
-    DDP_STAGED(S);
+    const double *dp, *dx0, *dc0, *dKp, *dkp, *dSp, *dSip, *dmf, *dR1, *dl;
+    double *det, *dx, *du, *dK, *dS, *dSi, *dVx, *dVxx, *dc, *ddV, *ds;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)U->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * T); S.in(&dc0, cost0, (size_t)B); S.in(&dKp, Kp, m * n * T);
+    S.in(&dkp, kp, m * T); S.in(&dSp, Sp, m * m * T); S.in(&dSip, Sip, m * m * T);
+    S.in(&dmf, model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)); S.in(&dR1, R1, n * n); S.in(&dl, lims, 2 * m);
+    S.inout(&det, etab, (size_t)3 * B); S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dS, Sigma, m * m * T);
+    S.out(&dSi, Sigmai, m * m * T); S.out(&dVx, Vx, n * T); S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * B); S.out(&ddV, dV, (size_t)2 * B);
+    S.out(&ds, stats, (size_t)DDP_ILQGKL_NSTATS * B);
+    if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqgkl_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
                                             det, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters));
 }
