@@ -123,11 +123,13 @@ __global__ void count_ok_kernel(int B, Traj s, int *counter)
     if (b < B && !s.div0[b]) atomicAdd(counter, 1);
 }
 
-__global__ void init_finish_kernel(int B, Traj s, int *counter)
+__global__ void init_finish_kernel(int B, int max_iter, Traj s, int *counter)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     if (s.div0[b]) { s.status[b] = DDP_EXIT_INIT_DIVERGED; s.run[b] = 0; s.dodf[b] = 0; }   // iLQG.jl:205-210
+    // while accepted_iter <= max_iter (:222) with accepted_iter = 1: max_iter < 1 never enters the loop, the initial rollout is the result
+    else if (s.acc[b] > max_iter) { s.status[b] = DDP_EXIT_MAXITER; s.run[b] = 0; s.dodf[b] = 0; }
     else atomicAdd(counter, 1);
 }
 
@@ -339,7 +341,7 @@ __global__ void stats_kernel(int B, Traj s, const int32_t *map, int only_finishe
 // polls the number of busy slots.  The state machine of a solve is the one of ilqg_impl (same kernels, same launches per global
 // iteration), so a solve does the arithmetic of its stand-alone solve at the same batch size.
 struct Sched {
-    int P, mpc_steps, zero_tail, nalpha;
+    int P, mpc_steps, zero_tail, nalpha, max_iter;
     double alpha[16];
     double lam0, dlam0;
     const double *x0g, *u0g;            // problems: x0[n,P], u0[m,N,P]
@@ -366,6 +368,15 @@ __global__ __launch_bounds__(TAKE_T) void sched_take_kernel(int n, int m, int N,
     const int ready = q.ready[b], running = s.run[b], arming = q.initm[b], prob = q.map[b], left0 = q.left[b], nofl = q.noflush[b];
     __syncthreads();
     if (q.adv && lane == 0) q.adv[b] = 0;
+    if (ready && q.max_iter < 1) {
+        // while accepted_iter <= max_iter (:222) is false from the start: the initial rollout is the result (status 4), gains and value
+        // function are the zeros of a stand-alone solve (the slot still holds those of its last problem); flushed by the next call
+        auto zero = [&](double *d, size_t per) { for (size_t e = lane; e < per; e += TAKE_T) d[per * (size_t)b + e] = 0.0; };
+        zero(ws.K, (size_t)m * n * N); zero(ws.k, (size_t)m * N); zero(ws.Quu, (size_t)m * m * N); zero(ws.Vx, (size_t)n * N);
+        zero(ws.Vxx, (size_t)n * n * N);
+        if (lane == 0) { q.ready[b] = 0; q.initm[b] = 0; s.status[b] = DDP_EXIT_MAXITER; atomicAdd(counter, 1); }
+        return;
+    }
     if (ready) {                                                   // its initial rollout (on the side stream) passed: the solve starts with
         if (lane == 0) { q.ready[b] = 0; q.initm[b] = 0; s.run[b] = 1; s.dodf[b] = 1; atomicAdd(counter, 1); }     // the next global iteration
         return;
@@ -588,7 +599,7 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
         }
     }
     DDP_HIP(hipMemsetAsync(counter, 0, 4, st));
-    hipLaunchKernelGGL(init_finish_kernel, dim3(gB), dim3(256), 0, st, (int)B, s, counter);
+    hipLaunchKernelGGL(init_finish_kernel, dim3(gB), dim3(256), 0, st, (int)B, oo->max_iter, s, counter);
     DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
     DDP_HIP(hipStreamSynchronize(st));
     int running = h->h_pinned[0];
@@ -849,7 +860,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     s.nfp = (int32_t *)take(f_i); s.flg = (int32_t *)take(f_i); s.run = (int32_t *)take(f_i); s.dodf = (int32_t *)take(f_i);
     s.dofwd = (int32_t *)take(f_i); s.div0 = (int32_t *)take(f_i);
     Sched q;
-    q.P = (int)P; q.mpc_steps = mpc_steps; q.zero_tail = zero_tail; q.nalpha = (int)na;
+    q.P = (int)P; q.mpc_steps = mpc_steps; q.zero_tail = zero_tail; q.nalpha = (int)na; q.max_iter = oo->max_iter;
     for (int i = 0; i < 16; ++i) q.alpha[i] = oo->alpha[i];
     q.lam0 = oo->lambda; q.dlam0 = oo->dlambda; q.x0g = x0; q.u0g = u0; q.u0s = u0s; q.us = us; q.x0s = ws.x0;
     q.initm = (int32_t *)take(f_i); q.ai = (int32_t *)take(f_i); q.map = (int32_t *)take(f_i); q.left = (int32_t *)take(f_i);

@@ -307,7 +307,7 @@ def ilqg_prerolled(p, x0, u0, cost0=None, lims=None, **kw):
 
 
 def ilqg_trace7(p, x0, u0, lims=None, trace_cap=2048, **kw):
-    """ilqg() returning all seven per-iteration trace keys (iLQG.jl:257,325-330) as info["history"]"""
+    """ilqg() returning all seven per-iteration trace keys (iLQG.jl:257,325-330) as info["history"], next to the summary ilqg() returns"""
     n, m, N = p.n, p.m, p.N
     CL = lib().ddp_oracle_cost_len(C.byref(p))
     o = ILQGOpts()
@@ -329,5 +329,7 @@ def ilqg_trace7(p, x0, u0, lims=None, trace_cap=2048, **kw):
                                  _p(cost), C.byref(res), trace_cap, _p(tr7))
     tl = res.trace_len
     hist = {key: tr7[c, :tl] for c, key in enumerate(("λ", "dλ", "α", "improvement", "cost", "reduce_ratio", "grad_norm"))}
-    info = dict(status=res.status, iter=res.iter, history=hist, trace_len=tl)
+    info = dict(status=res.status, iter=res.iter, history=hist, trace_len=tl, accepted_iter=res.accepted_iter,
+                n_backpass=res.n_backpass, n_forward=res.n_forward, lam=res.lambda_, dlam=res.dlambda, g_norm=res.g_norm,
+                dV=np.array(res.dV[:]))
     return x, u, (K, k, Quu), Vx, Vxx, cost, info
