@@ -19,7 +19,7 @@ u8p = C.POINTER(C.c_uint8)
 vp = C.c_void_p
 
 EXPORTS = [
-    "ddp_last_error", "ddp_version", "ddp_device_count", "ddp_create", "ddp_create_with_stream", "ddp_destroy", "ddp_sync", "ddp_reload_env", "ddp_last_kernel", "ddp_sh_timeouts", "ddp_sh_timeout_info", "ddp_sh_reuse_stats", "ddp_stream",
+    "ddp_last_error", "ddp_version", "ddp_device_count", "ddp_create", "ddp_create_with_stream", "ddp_destroy", "ddp_sync", "ddp_reload_env", "ddp_last_kernel", "ddp_sh_timeouts", "ddp_sh_timeout_info", "ddp_sh_reuse_stats", "ddp_df_expm_plan", "ddp_stream",
     "ddp_malloc", "ddp_free", "ddp_memcpy_h2d", "ddp_memcpy_d2h", "ddp_memset", "ddp_host_alloc", "ddp_host_free", "ddp_host_trim",
     "ddp_event_create", "ddp_event_destroy", "ddp_event_record", "ddp_event_elapsed_ms",
     "ddp_back_pass_f64_dev", "ddp_back_pass_f64", "ddp_boxqp_f64_dev", "ddp_boxqp_f64",
@@ -170,8 +170,10 @@ def lib():
         if hasattr(L, "ddp_user_program_text"):               # unlisted debug hook (tests); absent from older A/B builds of the library
             L.ddp_user_program_text.restype = C.c_char_p
             L.ddp_user_program_text.argtypes = [C.c_char_p, ci, ci, ci, ci, ci]
+        if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
+            L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name == "ddp_user_set_t0" and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

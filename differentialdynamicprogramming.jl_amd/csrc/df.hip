@@ -11,6 +11,25 @@
 
 namespace {
 
+// ---- the plan of one exponential: Padé degree and number of squarings from the 1-norm — the only place that decides them (expm_dev,
+// expm5_zlast_small, the flag test of df_pendcart_kernel and the debug hook ddp_df_expm_plan).  Higham (2005): degrees 3 / 5 / 7 / 9 up to
+// 0.015 / 0.25 / 0.95 / 2.1, degree 13 beyond with max(0, ceil(log2(nA / 5.4))) squarings.  A norm that is not finite (+Inf: an infinite
+// control; NaN) has no plan: degree 0, no exponential is formed and the result is NaN.  (The cast of ceil(log2(+Inf)) to int is undefined;
+// where it saturates, the squaring loop ran 2^31 - 1 times.  The reference throws there: ceil(Int, Inf) is an InexactError.)
+__host__ __device__ __forceinline__ void expm_plan(double nA, int *degree, int *squarings)
+{
+    *squarings = 0;
+    if (nA <= 0.015) *degree = 3;                                         // (a norm is not negative)
+    else if (nA <= 0.25) *degree = 5;
+    else if (nA <= 0.95) *degree = 7;
+    else if (nA <= 2.1) *degree = 9;
+    else if (nA <= 1.7976931348623157e308) {
+        *degree = 13;
+        const double s = log2(nA / 5.4);
+        if (s > 0) *squarings = (int)ceil(s);                             // nA <= DBL_MAX: at most 1022
+    } else *degree = 0;                                                   // +Inf, NaN
+}
+
 // ---- dense matrix exponential of a D x D matrix held in registers --------------------------------
 // Higham (2005) scaling & squaring with Padé 3/5/7/9/13 — the algorithm behind Julia's
 // exp(::Matrix{Float64}) (without gebal balancing, which only changes rounding).
@@ -90,8 +109,15 @@ __device__ void expm_dev(const Mat<D> &Ain, Mat<D> &E)
         for (int i = 0; i < D; ++i) s += fabs(Ain(i, j));
         nA = fmax(nA, s);
     }
+    int deg, si;
+    expm_plan(nA, &deg, &si);
+    if (deg == 0) {
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) E.a[i] = nA - nA;               // Inf - Inf, NaN - NaN: NaN
+        return;
+    }
     Mat<D> A = Ain, A2, U, V, T;
-    if (nA <= 2.1) {
+    if (deg <= 9) {
         const double C9[10] = {17643225600., 8821612800., 2075673600., 302702400., 30270240., 2162160., 110880., 3960., 90., 1.};
         const double C7[8] = {17297280., 8648640., 1995840., 277200., 25200., 1512., 56., 1.};
         const double C5[6] = {30240., 15120., 3360., 420., 30., 1.};
@@ -100,13 +126,13 @@ __device__ void expm_dev(const Mat<D> &Ain, Mat<D> &E)
         int nc;
 #pragma unroll
         for (int i = 0; i < 10; ++i) C[i] = 0.0;
-        if (nA > 0.95) { nc = 10;
+        if (deg == 9) { nc = 10;
 #pragma unroll
             for (int i = 0; i < 10; ++i) C[i] = C9[i]; }
-        else if (nA > 0.25) { nc = 8;
+        else if (deg == 7) { nc = 8;
 #pragma unroll
             for (int i = 0; i < 8; ++i) C[i] = C7[i]; }
-        else if (nA > 0.015) { nc = 6;
+        else if (deg == 5) { nc = 6;
 #pragma unroll
             for (int i = 0; i < 6; ++i) C[i] = C5[i]; }
         else { nc = 4;
@@ -136,10 +162,7 @@ __device__ void expm_dev(const Mat<D> &Ain, Mat<D> &E)
         const double CC[14] = {64764752532480000., 32382376266240000., 7771770303897600., 1187353796428800.,
                                129060195264000., 10559470521600., 670442572800., 33522128640., 1323241920.,
                                40840800., 960960., 16380., 182., 1.};
-        const double s = log2(nA / 5.4);
-        int si = 0;
-        if (s > 0) {
-            si = (int)ceil(s);
+        if (si > 0) {
             const double sc = ldexp(1.0, si);
 #pragma unroll
             for (int i = 0; i < D * D; ++i) A.a[i] /= sc;
@@ -187,13 +210,15 @@ __device__ __forceinline__ void expm5_zlast_small(const M45 &A, double nA, M45 &
     int nc;
 #pragma unroll
     for (int i = 0; i < 10; ++i) C[i] = 0.0;
-    if (nA > 0.95) { nc = 10;
+    int deg, si;
+    expm_plan(nA, &deg, &si);                                             // (never 13 or 0: the caller deals with those)
+    if (deg == 9) { nc = 10;
 #pragma unroll
         for (int i = 0; i < 10; ++i) C[i] = C9[i]; }
-    else if (nA > 0.25) { nc = 8;
+    else if (deg == 7) { nc = 8;
 #pragma unroll
         for (int i = 0; i < 8; ++i) C[i] = C7[i]; }
-    else if (nA > 0.015) { nc = 6;
+    else if (deg == 5) { nc = 6;
 #pragma unroll
         for (int i = 0; i < 6; ++i) C[i] = C5[i]; }
     else { nc = 4;
@@ -361,7 +386,10 @@ __global__ __launch_bounds__(256) void df_lq_tiled_kernel(int n, int m, int N, l
 
 // MODE 0: everything by the dense routine (the handle has no flag word).  MODE 1: cx, cu, and the exponential by expm5_zlast_small;
 // an element whose norm asks for Padé 13 (> 2.1: controls in the hundreds — a diverging rollout) only raises *flag.  MODE 2: a fixed
-// small grid that leaves at once unless the flag is up, then walks all elements and does those by the dense routine.
+// small grid that leaves at once unless the flag is up, then walks all elements and does those by the dense routine.  All three ask
+// expm_plan; an element without a plan (an infinite control: degree 0) gets NaN in fx and fu — stored by MODE 1 itself, by expm_dev in
+// MODE 0 — and is not a reason for MODE 2.  A NaN angle does not reach the norm (fmax drops the NaN column sums): the element takes the
+// degree of the other columns and its fx, fu come out NaN by arithmetic.
 template <int MODE>
 __global__ __launch_bounds__(64) void df_pendcart_kernel(int N, int B, double g, double l, double h, double d,
                                                          double g0, double g1, double g2, double g3, const double *Q,
@@ -396,8 +424,17 @@ __global__ __launch_bounds__(64) void df_pendcart_kernel(int N, int B, double g,
         const double m01 = 1.0 * h, m10 = (-g / l * cs - uu / l * sn) * h, m11 = (-d) * h, m23 = 1.0 * h, m14 = (cs / l) * h, m34 = 1.0 * h;     // fxc*h, fuc*h (:130-148)
         // 1-norm of the block matrix: the largest column sum (columns 0, 1, 3, 4; column 2 is zero)
         const double nA = fmax(fmax(0.0 + fabs(m10), fabs(m01) + fabs(m11)), fmax(fabs(m23), fabs(m14) + fabs(m34)));
+        int deg, si;
+        expm_plan(nA, &deg, &si);
         if (MODE == 1) {
-            if (!(nA <= 2.1)) { *flag = 1; continue; }
+            if (deg == 13 || deg == 0) {
+                if (deg == 13) *flag = 1;
+                else {                                                    // no plan for a norm that is not finite: NaN
+                    for (int e = 0; e < 16; ++e) fx[16 * t + e] = nA - nA;
+                    for (int e = 0; e < 4; ++e) fu[4 * t + e] = nA - nA;
+                }
+                continue;
+            }
             M45 A, X;
 #pragma unroll
             for (int i = 0; i < 20; ++i) A.a[i] = 0.0;
@@ -419,7 +456,7 @@ __global__ __launch_bounds__(64) void df_pendcart_kernel(int N, int B, double g,
                 for (int r = 0; r < 4; ++r) fu[4 * t + r] = X(r, 4);
             }
         } else {
-            if (MODE == 2 && nA <= 2.1) continue;
+            if (MODE == 2 && deg != 13) continue;
             Mat<5> M, E;
 #pragma unroll
             for (int i = 0; i < 25; ++i) M.a[i] = 0.0;
@@ -497,6 +534,17 @@ int ddp_df_f64(ddp_handle h, const ddp_problem *p, const double *x, const double
     const int rc = S.commit();
     if (rc) return rc;
     return S.finish(ddp_df_f64_dev(h, &pd, dx, du, nullptr, dcx, dcu, dfx, dfu));
+}
+
+// Debug hook: the plan the kernels above follow for a 1-norm — expm_plan itself, callable without a GPU.  degree 3 / 5 / 7 / 9 / 13,
+// or 0 for a norm that is not finite (fx, fu of that element are NaN); squarings: of the degree-13 result.
+int ddp_df_expm_plan(double nA, int *degree, int *squarings)
+{
+    int deg, sq;
+    expm_plan(nA, &deg, &sq);
+    if (degree) *degree = deg;
+    if (squarings) *squarings = sq;
+    return 0;
 }
 
 }   // extern "C"

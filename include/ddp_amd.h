@@ -65,6 +65,12 @@ int  ddp_sh_timeout_info(ddp_handle h, int *out, int cap);
  * DDP_SH_REUSE=0 switches the reuse off).  out[0]: λ groups served from a kept stream, out[1]: groups whose recursion was computed,
  * since the scratch was (re)allocated.  out: 2 ints.  Synchronises the stream; 0, < 0 on error.  A debug query like ddp_sh_timeouts.  */
 int  ddp_sh_reuse_stats(ddp_handle h, int *out);
+/* The plan ddp_df_* follows for the matrix exponential of a pendcart element whose ZoH block matrix has 1-norm nA (Higham's scaling and
+ * squaring): *degree = 3 / 5 / 7 / 9 for nA <= 0.015 / 0.25 / 0.95 / 2.1 and 13 beyond, *squarings = max(0, ceil(log2(nA / 5.4))) of the
+ * degree-13 result.  A norm that is not finite (an infinite control; NaN) has no plan: *degree = 0, no exponential is formed and that
+ * element's fx and fu are NaN (cx and cu are written as usual).  Needs no handle and no GPU; returns 0.  A debug query like
+ * ddp_last_kernel: the function the kernels call.                                                                                    */
+int  ddp_df_expm_plan(double nA, int *degree, int *squarings);
 void *ddp_stream(ddp_handle h);                 /* the hipStream_t of the handle */
 /* device memory helpers for hosts without their own allocator (the Julia wrapper, tests) */
 int  ddp_malloc(ddp_handle h, size_t bytes, void **dptr);

@@ -9,6 +9,7 @@
  * product stands in for OpenBLAS, so results agree with Julia to rounding, not bitwise.
  */
 #include "ddp_oracle.h"
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -387,6 +388,13 @@ void ddp_oracle_expm(int n, const double *Ain, double *E)
     memcpy(A, Ain, nn * sizeof(double));
     double nA = 0.0;
     for (int j = 0; j < n; ++j) { double s = 0.0; for (int i = 0; i < n; ++i) s += fabs(A[IDX2(i, j, n)]); if (s > nA) nA = s; }
+    if (!(nA <= DBL_MAX)) {
+        /* a norm that is not finite (an infinite control) has no Padé degree and no number of squarings: the result is NaN.  The
+         * reference throws here (ceil(Int, Inf)); the cast below would be undefined.  Same rule as expm_plan of csrc/df.hip. */
+        for (size_t t = 0; t < nn; ++t) E[t] = NAN;
+        free(w);
+        return;
+    }
     if (nA <= 2.1) {
         static const double C9[] = {17643225600., 8821612800., 2075673600., 302702400., 30270240., 2162160., 110880., 3960., 90., 1.};
         static const double C7[] = {17297280., 8648640., 1995840., 277200., 25200., 1512., 56., 1.};
