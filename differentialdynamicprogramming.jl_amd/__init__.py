@@ -30,7 +30,8 @@ from . import _lib
 from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
-           "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp"]
+           "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
+           "constraints", "iLQG_al"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -192,19 +193,28 @@ class DeviceProblem:
     ``t = c + i`` as one more ``int`` behind ``i`` and ``terminal_cost`` takes ``t = c + N - 1`` behind ``x``; the clock ``c`` of every
     trajectory comes from the ``t0=`` keyword of ``forward_pass``, ``df``, ``costfun``, ``iLQG``, ``iLQG_queue`` (one per problem),
     ``iLQG_mpc`` (the solve at closed-loop step ``s`` runs with ``c = t0 + s``, ``plant`` gets ``t = t0 + s``) and ``kl.iLQGkl``: an int or
-    one int per trajectory, default 0.  Not together with ``second_order=True`` or ``second_order_wave=True``."""
+    one int per trajectory, default 0.  Not together with ``second_order=True`` or ``second_order_wave=True``.
+    ``constraints=nc`` (DDP_USER_CONSTRAINTS, needs ``autodiff=True``): the source also defines the template
+    ``constraints(x, u, i, p, g)`` writing ``g[nc]``, feasible where ``g <= 0``.  ``constraints(problem, x, u)`` evaluates it, ``iLQG_al``
+    solves the constrained problem by an augmented Lagrangian on the device, and ``forward_pass``, ``df``, ``costfun`` and ``iLQG`` take
+    ``multipliers=(λ[nc,N(,B)], μ)`` and then work on the augmented cost (default: the raw cost).  Not together with ``const_hessian``,
+    ``clock``, ``second_order`` or ``second_order_wave``; ``iLQG_queue``, ``iLQG_mpc`` and ``kl.iLQGkl`` refuse such a problem."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False, clock=False):
+                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0):
         self.clock = bool(clock)
+        self.nc = int(constraints)
+        if self.nc < 0:
+            raise DDPError("DeviceProblem: constraints = %d (the number of constraints, 0 for none)" % self.nc)
         self.second_order_wave = bool(second_order_wave)
         self.second_order, self.wave = bool(second_order), bool(wave) or self.second_order_wave
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
-                      (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0))
+                      (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
+                      (_lib.USER_CONSTRAINTS if self.nc else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -213,8 +223,12 @@ class DeviceProblem:
         """Compile for gfx950 without a device (ddp_user_check), with the problem's flags (``autodiff`` included); returns the
         compiler log, raises DDPError with it on failure."""
         L = _lib.lib()
-        rc = L.ddp_user_check(self.source.encode(), self.n, self.m, self.nparam, self.flags,
-                              extra_options.encode() if extra_options else None)
+        if self.nc:
+            rc = L.ddp_user_check_c(self.source.encode(), self.n, self.m, self.nparam, self.nc, self.flags,
+                                    extra_options.encode() if extra_options else None)
+        else:
+            rc = L.ddp_user_check(self.source.encode(), self.n, self.m, self.nparam, self.flags,
+                                  extra_options.encode() if extra_options else None)
         log = L.ddp_user_compile_log().decode()
         if rc != 0:
             raise DDPError("libddp_amd: %s (rc=%d)\n%s" % (L.ddp_last_error().decode(), rc, log))
@@ -228,8 +242,12 @@ class DeviceProblem:
         e = self._made.get(id(h))
         if e is None or e[0] is not h:
             up = _C.c_void_p()
-            _lib.check(_lib.lib().ddp_user_create(h.raw, self.source.encode(), self.n, self.m, self.nparam, self.flags,
-                                                  int(self.diff_mask), _C.byref(up)))
+            if self.nc:
+                _lib.check(_lib.lib().ddp_user_create_c(h.raw, self.source.encode(), self.n, self.m, self.nparam, self.nc, self.flags,
+                                                        int(self.diff_mask), _C.byref(up)))
+            else:
+                _lib.check(_lib.lib().ddp_user_create(h.raw, self.source.encode(), self.n, self.m, self.nparam, self.flags,
+                                                      int(self.diff_mask), _C.byref(up)))
             e = self._made[id(h)] = (h, up)
         return e[1]
 
@@ -266,6 +284,41 @@ class DeviceProblem:
         finally:
             _lib.lib().ddp_user_set_t0(up, None, 0)
 
+    def _multiplier_arrays(self, multipliers, N, B, batched):
+        """``(λ[nc,N,B], μ[B])`` of a ``multipliers=`` keyword as the library takes them; raises on a malformed shape"""
+        if not self.nc:
+            raise DDPError("multipliers= needs a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS)")
+        try:
+            lam, mu = multipliers
+        except (TypeError, ValueError):
+            raise DDPError("multipliers should be a pair (λ, μ)")
+        lam = _lib.f64(lam)
+        if not batched and lam.shape == (self.nc, N):
+            lam = _lib.f64(lam[..., None])
+        if lam.shape != (self.nc, N, B):
+            raise DDPError("multipliers: λ should be (nc = %d, N = %d%s), got %s" % (self.nc, N, ", B = %d" % B if batched else "", lam.shape))
+        mu = np.asarray(mu, dtype=np.float64)
+        if mu.ndim == 0:
+            mu = np.full(B, float(mu))
+        if mu.shape != (B,):
+            raise DDPError("multipliers: μ should be a number or (B = %d,), got %s" % (B, mu.shape))
+        return lam, np.ascontiguousarray(mu)
+
+    @_contextlib.contextmanager
+    def _multipliers(self, h, multipliers, N, B, batched):
+        """the multipliers ``(λ, μ)`` (``constraints=nc``) for the calls inside the block (ddp_user_set_multipliers); none are set
+        afterwards, also when the call raises"""
+        if multipliers is None:
+            yield
+            return
+        lam, mu = self._multiplier_arrays(multipliers, N, B, batched)
+        up = self._ptr(h)
+        _lib.check(_lib.lib().ddp_user_set_multipliers(up, _lib.ptr(lam), _lib.ptr(mu), N, B))
+        try:
+            yield
+        finally:
+            _lib.lib().ddp_user_set_multipliers(up, None, None, 0, 0)
+
     def __del__(self):
         try:
             for h, up in self._made.values():
@@ -279,6 +332,12 @@ def _no_clock(t0):
     """the registered families have no clock: ``t0=`` with one of them is refused"""
     if t0 is not None:
         raise DDPError("t0= needs a DeviceProblem made with clock=True (DDP_USER_CLOCK)")
+
+
+def _no_multipliers(multipliers):
+    """the registered families have no constraints: ``multipliers=`` with one of them is refused"""
+    if multipliers is not None:
+        raise DDPError("multipliers= needs a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS)")
 
 
 def _clock(problem, h, t0):
@@ -472,17 +531,19 @@ def _check_problem(problem, n, m, N, B):
 
 
 # ------------------------------------------------------------------------------- forward_pass
-def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None, t0=None):
+def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None, t0=None, multipliers=None):
     """Drop-in for ``forward_pass(traj_new,x0,u,x,α,f,costfun,lims,diff)`` (forward_pass.jl:9) with a
     registered ``problem`` standing in for the closures ``f``/``costfun``; ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
     ``traj_new`` may be an empty ``GaussianPolicy`` (then ``x`` is ignored, iLQG.jl:185).
     A vector ``α`` rolls all step sizes out concurrently (outputs get a trailing α axis).
-    A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in; made with ``clock=True`` it takes ``t0``.
+    A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in; made with ``clock=True`` it takes ``t0``, made
+    with ``constraints=nc`` it takes ``multipliers=(λ, μ)`` (the augmented cost).
     Returns ``(xnew, unew, cnew)``."""
     if isinstance(problem, DeviceProblem):
-        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0)
+        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0, multipliers=multipliers)
     h = handle or default_handle()
     _no_clock(t0)
+    _no_multipliers(multipliers)
     u, x0 = _lib.f64(u), _lib.f64(x0)
     batched = u.ndim == 3
     m, N = u.shape[:2]
@@ -517,14 +578,15 @@ def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=Non
 
 
 # ------------------------------------------------------------------------------------------ df
-def df(problem, x, u, *, handle=None, params=None, t0=None):
+def df(problem, x, u, *, handle=None, params=None, t0=None, multipliers=None):
     """The ``df`` closure of the registered families (STEP 1, iLQG.jl:225-229).  Returns
     ``(fx,fu,fxx,fxu,fuu,cx,cu,cxx,cxu,cuu)`` like the reference (second-order terms are ``[]``).
     A ``DeviceProblem`` returns its ``derivatives``: ``cxx[n,n,N(,B)]`` ... (``[n,n(,B)]`` with ``const_hessian``)."""
     if isinstance(problem, DeviceProblem):
-        return _user_df(problem, x, u, handle=handle, params=params, t0=t0)
+        return _user_df(problem, x, u, handle=handle, params=params, t0=t0, multipliers=multipliers)
     h = handle or default_handle()
     _no_clock(t0)
+    _no_multipliers(multipliers)
     x, u = _lib.f64(x), _lib.f64(u)
     batched = u.ndim == 3
     m, N = u.shape[:2]
@@ -559,7 +621,7 @@ def _user_batch(x_or_x0, u, problem, x0_has_time=False):
     return u, batched, n, m, N, B
 
 
-def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None, t0=None):
+def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None, t0=None, multipliers=None):
     h = handle or default_handle()
     u, batched, n, m, N, B = _user_batch(x0, u, problem)
     x0 = _lib.f64(x0)
@@ -587,7 +649,7 @@ def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=No
     xnew = _lib.result_array((n, N, B, na)); unew = _lib.result_array((m, N, B, na))
     cnew = _lib.result_array((CL, B, na)); csum = np.zeros((B, na), order="F")
     up = problem._ptr(h)
-    with problem._clock(h, t0):
+    with problem._clock(h, t0), problem._multipliers(h, multipliers, N, B, batched):
         _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
                                                         _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
                                                         _lib.ptr(cnew), _lib.ptr(csum)))
@@ -598,7 +660,7 @@ def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=No
     return xnew, unew, cnew
 
 
-def _user_df(problem, x, u, *, handle=None, params=None, t0=None):
+def _user_df(problem, x, u, *, handle=None, params=None, t0=None, multipliers=None):
     h = handle or default_handle()
     u, batched, n, m, N, B = _user_batch(x, u, problem)
     x = _lib.f64(x)
@@ -610,7 +672,7 @@ def _user_df(problem, x, u, *, handle=None, params=None, t0=None):
     cx = _lib.result_array((n, N, B)); cu = _lib.result_array((m, N, B))
     cxx = _lib.result_array((n, n) + ht + (B,)); cxu = _lib.result_array((n, m) + ht + (B,)); cuu = _lib.result_array((m, m) + ht + (B,))
     up = problem._ptr(h)
-    with problem._clock(h, t0):
+    with problem._clock(h, t0), problem._multipliers(h, multipliers, N, B, batched):
         _lib.check(_lib.lib().ddp_user_df_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u),
                                               *map(_lib.ptr, (fx, fu, cx, cu, cxx, cxu, cuu))))
     if not batched:
@@ -669,7 +731,7 @@ def back_pass_ddp(problem, cx, cu, cxx, cxu, cuu, fx, fu, λ, regType, lims, x, 
     return div, GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, B)), Quu), Vx, Vxx, dV
 
 
-def costfun(problem, x, u, *, handle=None, params=None, t0=None):
+def costfun(problem, x, u, *, handle=None, params=None, t0=None, multipliers=None):
     """The ``costfun`` closure of a ``DeviceProblem`` on given trajectories: ``cost[CL(,B)]`` (CL = N, N+1 with ``terminal``)."""
     if not isinstance(problem, DeviceProblem):
         raise TypeError("costfun: a DeviceProblem is needed (the registered families evaluate their cost inside forward_pass)")
@@ -681,10 +743,26 @@ def costfun(problem, x, u, *, handle=None, params=None, t0=None):
     P, pb = problem._params(B, params)
     cost = _lib.result_array((problem.cost_len(N), B))
     csum = np.zeros(B)
-    with problem._clock(h, t0):
+    with problem._clock(h, t0), problem._multipliers(h, multipliers, N, B, batched):
         _lib.check(_lib.lib().ddp_user_costfun_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost),
                                                    _lib.ptr(csum)))
     return cost if batched else cost[:, 0]
+
+
+def constraints(problem, x, u, *, handle=None, params=None):
+    """``g[nc, N(, B)]`` of a ``DeviceProblem`` made with ``constraints=nc``: the user's ``constraints`` at every ``(x[:, i], u[:, i], i)``;
+    feasible where ``g <= 0``."""
+    if not isinstance(problem, DeviceProblem) or not problem.nc:
+        raise DDPError("constraints: a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS) is needed")
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x, u, problem)
+    x = _lib.f64(x)
+    if x.shape != ((n, N, B) if batched else (n, N)):
+        raise DDPError("x should be (n, N) — (n, N, B) with a batched u")
+    P, pb = problem._params(B, params)
+    g = _lib.result_array((problem.nc, N, B))
+    _lib.check(_lib.lib().ddp_user_constraints_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(g)))
+    return g if batched else g[..., 0]
 
 
 # ---------------------------------------------------------------------------------------- iLQG
@@ -708,7 +786,7 @@ STATUS = {1: "SUCCESS: gradient norm < tol_grad", 2: "SUCCESS: cost change < tol
 
 def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
          λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0.0, verbosity=0, trace_cap=None, cost=None,
-         timing=True, diff_fun=None, handle=None, params=None, t0=None):
+         timing=True, diff_fun=None, handle=None, params=None, t0=None, multipliers=None):
     """Drop-in for ``iLQG(f,costfun,df,x0,u0; lims, α, tol_fun, ...)`` (iLQG.jl:143-163) with a registered
     ``problem`` standing in for the three closures (``diff_fun``: ``None`` = ``-``, or a ``WrappedDiff``).  ``u0[m,N,B]`` / ``x0[n,B]`` solve a batch of
     independent problems, each with its own λ schedule, line search and termination.
@@ -723,9 +801,12 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     were kept (its later rows are missing, ``stats`` / ``iter`` are complete).
     Returns ``None`` when the initial control sequence diverges (iLQG.jl:205-210) in the unbatched case.
     A ``DeviceProblem`` (the user's own closures as device source) takes ``params`` (default: its own); its ``diff`` is compiled in;
-    made with ``clock=True`` it takes ``t0``, the clock of every trajectory (an int or B ints; default 0)."""
+    made with ``clock=True`` it takes ``t0``, the clock of every trajectory (an int or B ints; default 0); made with
+    ``constraints=nc`` it takes ``multipliers=(λ, μ)`` and then minimises the augmented cost (``iLQG_al`` is the whole loop)."""
     h = handle or default_handle()
     user = isinstance(problem, DeviceProblem)
+    if not user:
+        _no_multipliers(multipliers)
     if user:
         if np.ndim(u0) not in (2, 3):
             raise DDPError("u0 should be (m, N) or (m, N, B)")
@@ -786,7 +867,7 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
     _lib.check(_lib.lib().ddp_ilqg_set_timing(h.raw, _lib.ptr(timing) if timing_on else None, tcap if timing_on else 0))
     try:
         if user:
-            with problem._clock(h, t0):
+            with problem._clock(h, t0), problem._multipliers(h, multipliers, N, B, batched):
                 _lib.check(_lib.lib().ddp_user_ilqg_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _C.byref(o), _lib.ptr(x0), int(prerolled),
                                                         _lib.ptr(u0), _lib.ptr(c0), _lib.ptr(L),
                                                         *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats)), cap, _lib.ptr(tr7), _C.byref(git)))
@@ -827,6 +908,66 @@ def iLQG(problem, x0, u0, *, lims=None, α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad
         return x[..., 0], u[..., 0], pol, Vx[..., 0], Vxx[..., 0], cost[:, 0], trace
     pol = GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, B)), Quu)
     return x, u, pol, Vx, Vxx, cost, trace
+
+
+AL_STATUS = {1: "SUCCESS: constraint violation <= ctol", 2: "EXIT: max_outer rounds", -1: "EXIT: Initial control sequence caused divergence"}
+
+
+def iLQG_al(problem, x0, u0, *, mu0=1.0, mu_factor=10.0, mu_max=1e8, ctol=1e-5, max_outer=20, multipliers=None, lims=None,
+            α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0, λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1,
+            reduce_ratio_min=0.0, handle=None, params=None):
+    """The constrained solve of a ``DeviceProblem`` made with ``constraints=nc``: an augmented-Lagrangian loop around ``iLQG``, on the
+    device (ddp_user_ilqg_al_f64).  Per trajectory and round: the ``iLQG`` solve under the multipliers ``(λ, μ)`` (round 0 from
+    ``x0``, ``u0`` — ``x0`` may be pre-rolled as in ``iLQG`` —, later rounds from the last solution), ``cviol = max(0, g).max()``, then
+    either the end (``cviol <= ctol``: status 1; ``max_outer`` rounds: 2; diverged at the start: -1) or ``λ ← max(0, λ + μ g)``,
+    ``μ ← min(mu_factor μ, mu_max)``.  ``multipliers=(λ0, μ0)``: the initial ones (default zeros and ``mu0``).  The other keywords are
+    ``iLQG``'s.  Returns ``iLQG``'s tuple ``(x, u, traj_new, Vx, Vxx, cost, info)``; ``cost`` is the augmented one and ``info`` holds
+    ``λ``, ``μ``, ``g`` at the returned trajectory, ``al_stats`` and its columns ``status``, ``rounds``, ``inner_iters``, ``mu_last``,
+    ``cviol``, ``raw_cost``, the inner ``stats`` of the last round each trajectory ran, and ``global_iters``."""
+    if not isinstance(problem, DeviceProblem) or not problem.nc:
+        raise DDPError("iLQG_al: a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS) is needed")
+    h = handle or default_handle()
+    if np.ndim(u0) not in (2, 3):
+        raise DDPError("u0 should be (m, N) or (m, N, B)")
+    _user_shapes(problem, np.shape(x0)[0], np.shape(u0)[0])
+    u0, x0 = _lib.f64(u0), _lib.f64(x0)
+    batched = u0.ndim == 3
+    m, N = u0.shape[:2]
+    n = x0.shape[0]
+    B = u0.shape[2] if batched else 1
+    prerolled = x0.ndim == (3 if batched else 2)
+    if x0.shape != (((n, N) if prerolled else (n,)) + ((B,) if batched else ())):
+        raise ValueError("x0 should be (n,) / pre-rolled (n, N) — with a batched u0: (n, B) / (n, N, B)")
+    P, pb = problem._params(B, params)
+    L = _lims(lims)
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    lam0 = mu_init = None
+    if multipliers is not None:
+        lam0, mu_init = problem._multiplier_arrays(multipliers, N, B, batched)
+    if not (mu0 > 0 and mu_factor >= 1 and mu_max >= mu0 and ctol >= 0 and int(max_outer) >= 1):
+        raise DDPError("iLQG_al: mu0 > 0, mu_factor >= 1, mu_max >= mu0, ctol >= 0 and max_outer >= 1 are needed")
+    o = _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min)
+    ao = _lib.ALOpts(float(mu0), float(mu_factor), float(mu_max), float(ctol), int(max_outer))
+    nc, CL = problem.nc, problem.cost_len(N)
+    x = _lib.result_array((n, N, B)); u = _lib.result_array((m, N, B))
+    K = _lib.result_array((m, n, N, B)); k = _lib.result_array((m, N, B)); Quu = _lib.result_array((m, m, N, B))
+    Vx = _lib.result_array((n, N, B)); Vxx = _lib.result_array((n, n, N, B)); cost = _lib.result_array((CL, B))
+    stats = np.zeros((8, B), order="F"); al_stats = np.zeros((6, B), order="F")
+    lam = _lib.result_array((nc, N, B)); mu = np.zeros(B); g = _lib.result_array((nc, N, B))
+    git = _C.c_int(0)
+    _lib.check(_lib.lib().ddp_user_ilqg_al_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _C.byref(o), _C.byref(ao), _lib.ptr(x0),
+                                               int(prerolled), _lib.ptr(u0), _lib.ptr(L), _lib.ptr(lam0), _lib.ptr(mu_init),
+                                               *map(_lib.ptr, (x, u, K, k, Quu, Vx, Vxx, cost, stats, lam, mu, g, al_stats)), _C.byref(git)))
+    info = dict(λ=lam, μ=mu, g=g, al_stats=al_stats, status=al_stats[0].astype(int), rounds=al_stats[1].astype(int),
+                inner_iters=al_stats[2].astype(int), mu_last=al_stats[3], cviol=al_stats[4], raw_cost=al_stats[5], stats=stats,
+                global_iters=git.value)
+    if not batched:
+        info.update(λ=lam[..., 0], μ=mu[0], g=g[..., 0])
+        pol = GaussianPolicy(N, n, m, K[..., 0], k[..., 0], np.zeros((m, m, N)), Quu[..., 0])
+        return x[..., 0], u[..., 0], pol, Vx[..., 0], Vxx[..., 0], cost[:, 0], info
+    pol = GaussianPolicy(N, n, m, K, k, np.zeros((m, m, N, B)), Quu)
+    return x, u, pol, Vx, Vxx, cost, info
 
 
 def _ilqg_opts(α, tol_fun, tol_grad, max_iter, λ, dλ, λfactor, λmax, λmin, regType, reduce_ratio_min):

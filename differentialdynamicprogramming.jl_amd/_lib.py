@@ -35,7 +35,10 @@ EXPORTS = [
     "ddp_user_ilqg_f64_dev", "ddp_user_ilqg_f64", "ddp_user_ilqg_queue_f64_dev", "ddp_user_ilqg_queue_f64", "ddp_user_ilqg_mpc_f64_dev",
     "ddp_user_ilqg_mpc_f64", "ddp_user_ilqgkl_f64_dev", "ddp_user_ilqgkl_f64",
     "ddp_user_vhess_f64_dev", "ddp_user_vhess_f64", "ddp_user_back_pass_f64_dev", "ddp_user_back_pass_f64", "ddp_user_set_t0",
+    "ddp_user_check_c", "ddp_user_create_c", "ddp_user_set_multipliers", "ddp_user_constraints_f64_dev", "ddp_user_constraints_f64",
+    "ddp_al_default_opts", "ddp_user_ilqg_al_f64_dev", "ddp_user_ilqg_al_f64",
 ]
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-8:])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -74,7 +77,13 @@ class ILQGKLOpts(C.Structure):
     _fields_ = [("kl_step", C.c_double), ("max_iter", C.c_int), ("etabracket", C.c_double * 3), ("del0", C.c_double)]
 
 
+class ALOpts(C.Structure):
+    _fields_ = [("mu0", C.c_double), ("mu_factor", C.c_double), ("mu_max", C.c_double), ("ctol", C.c_double), ("max_outer", C.c_int)]
+
+
 ILQGKL_NSTATS = 12
+USER_CONSTRAINTS = 1024        # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(..., constraints=nc)
+USER_MAX_NC = 16               # DDP_USER_MAX_NC
 USER_WAVE = 32                 # DDP_USER_WAVE: the flag of DeviceProblem(..., wave=True)
 USER_SECOND_ORDER_WAVE = 128   # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(..., second_order_wave=True); 64 is not assigned
 USER_CLOCK = 512               # DDP_USER_CLOCK: the flag of DeviceProblem(..., clock=True); 256 is not assigned
@@ -167,19 +176,33 @@ def lib():
         L.ddp_user_back_pass_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 10 + [ci, cd, vp] + [cd] * 6 + [vp]
         if hasattr(L, "ddp_user_set_t0"):                     # DDP_USER_CLOCK; absent from A/B builds of the library from before the flag
             L.ddp_user_set_t0.argtypes = [vp, vp, C.c_int]
+        if hasattr(L, "ddp_user_check_c"):                    # DDP_USER_CONSTRAINTS; absent from A/B builds of the library from before the flag
+            L.ddp_user_check_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, C.c_char_p]
+            L.ddp_user_create_c.argtypes = [vp, C.c_char_p, ci, ci, ci, ci, ci, ci, C.POINTER(vp)]
+            L.ddp_user_set_multipliers.argtypes = [vp, cd, cd, ci, ci]
+            L.ddp_user_constraints_f64.argtypes = [vp, vp, ci, ci, cd, ci, cd, cd, cd]
+            L.ddp_user_constraints_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci, cd, cd, cd]
+            al_args = [vp, vp, ci, ci, cd, ci, vp, vp, cd, ci] + [cd] * 4 + [cd] * 13 + [vp]
+            L.ddp_user_ilqg_al_f64.argtypes = al_args
+            L.ddp_user_ilqg_al_f64_dev.argtypes = al_args
+        if hasattr(L, "ddp_user_program_text_c"):             # unlisted debug hook (tests), with the flag
+            L.ddp_user_program_text_c.restype = C.c_char_p
+            L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
         if hasattr(L, "ddp_user_program_text"):               # unlisted debug hook (tests); absent from older A/B builds of the library
             L.ddp_user_program_text.restype = C.c_char_p
             L.ddp_user_program_text.argtypes = [C.c_char_p, ci, ci, ci, ci, ci]
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):
                 fn.restype = C.c_int
         L.ddp_ilqg_default_opts.restype = None
         L.ddp_ilqgkl_default_opts.restype = None
+        if hasattr(L, "ddp_al_default_opts"):
+            L.ddp_al_default_opts.restype = None
         _lib = L
     return _lib
 

@@ -15,6 +15,7 @@
 #include "ddp_internal.h"
 #include "staging.h"
 #include "user_autodiff.h"
+#include "user_constraints.h"
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
@@ -24,6 +25,7 @@
 DDP_USER_ABI
 DDP_USER_ABI2
 DDP_USER_ABI3
+DDP_USER_ABI_C
 
 namespace {
 
@@ -193,9 +195,12 @@ std::string with_clock(const char *text)
     return res;
 }
 
-int validate(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
+// nc < 0: an entry from before DDP_USER_CONSTRAINTS (ddp_user_check, ddp_user_create), which has no way to say how many there are
+int validate(const char *source, int n, int m, int nparam, int flags, unsigned wrap, int nc = -1)
 {
     DDP_CHECK(source, "user problem: null source");
+    DDP_CHECK(nc >= 0 || !(flags & DDP_USER_CONSTRAINTS),
+              "user problem: DDP_USER_CONSTRAINTS needs the number of constraints: ddp_user_check_c / ddp_user_create_c take it");
     const bool wave = (flags & DDP_USER_WAVE) != 0;
     if (wave) {
         DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER_WAVE, "user problem: n = %d out of [1, %d] (DDP_MAX_N_USER_WAVE)", n, DDP_MAX_N_USER_WAVE);
@@ -209,8 +214,24 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS)) == 0,
               "user problem: unknown flags 0x%x", flags);
+    if (flags & DDP_USER_CONSTRAINTS) {
+        // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
+        // second-order kernels would have to carry the multipliers as well
+        DDP_CHECK(flags & DDP_USER_AUTODIFF, "user problem: DDP_USER_CONSTRAINTS needs DDP_USER_AUTODIFF (the augmented cost is differentiated by "
+                                             "forward-mode AD of the templated model)");
+        DDP_CHECK(!(flags & DDP_USER_CONST_HESSIAN), "user problem: DDP_USER_CONSTRAINTS | DDP_USER_CONST_HESSIAN is refused (the Hessian of the "
+                                                     "penalty changes with the active set)");
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_CONSTRAINTS | DDP_USER_CLOCK is refused (deferred: constraints take no clock)");
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER), "user problem: DDP_USER_CONSTRAINTS | DDP_USER_SECOND_ORDER is refused (deferred)");
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER_WAVE), "user problem: DDP_USER_CONSTRAINTS | DDP_USER_SECOND_ORDER_WAVE is refused (deferred)");
+        DDP_CHECK(nc >= 1 && nc <= DDP_USER_MAX_NC, "user problem: nc = %d out of [1, %d] (DDP_USER_MAX_NC)", nc, DDP_USER_MAX_NC);
+        DDP_CHECK(nparam + 2 <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d leaves no room for the two multiplier slots (DDP_USER_MAX_NPARAM "
+                                                     "= %d)", nparam, DDP_USER_MAX_NPARAM);
+    } else {
+        DDP_CHECK(nc <= 0, "user problem: nc = %d but DDP_USER_CONSTRAINTS is not set (flag and nc must agree)", nc);
+    }
     // deferred, not impossible: ddp_user_back_pass2 and ddp_user_back_pass2_wave evaluate the model inside the recursion (ddp_ad_vhess)
     DDP_CHECK(!((flags & DDP_USER_CLOCK) && (flags & DDP_USER_SECOND_ORDER)),
               "user problem: DDP_USER_CLOCK | DDP_USER_SECOND_ORDER is refused (ddp_user_back_pass2 runs the model on the horizon index)");
@@ -241,6 +262,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
         DDP_CHECK(has_identifier(src, "cost_hessians"), "user problem: DDP_USER_CONST_HESSIAN is set but the source defines no `cost_hessians`");
     if (flags & DDP_USER_PLANT)
         DDP_CHECK(has_identifier(src, "plant"), "user problem: DDP_USER_PLANT is set but the source defines no `plant`");
+    if (flags & DDP_USER_CONSTRAINTS)
+        DDP_CHECK(has_identifier(src, "constraints"), "user problem: DDP_USER_CONSTRAINTS is set but the source defines no `constraints`");
     if (wave) return 0;                                          // (the wave kernels check their LDS with a static_assert: it fits at every shape)
     const Layout L = layout_of(n, m, flags);
     const int ps = 2 * m + m * n + n;
@@ -248,7 +271,7 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     return 0;
 }
 
-std::string program_text(const char *source, int n, int m, int nparam, int flags, unsigned wrap)
+std::string program_text(const char *source, int n, int m, int nparam, int flags, unsigned wrap, int nc = 0)
 {
     const Layout L = layout_of(n, m, flags);
     char head[512];
@@ -256,7 +279,8 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
              "#define DDP_N %d\n#define DDP_M %d\n#define DDP_NP %d\n#define DDP_TERMINAL %d\n#define DDP_CONST_HESSIAN %d\n"
              "#define DDP_WRAP 0x%xu\n#define DDP_CHUNK %d\n#define DDP_RLANES %d\n#define DDP_DFLANES %d\n"
              "#define DDP_AUTODIFF %d\n#define DDP_ADJ %d\n#define DDP_ADH %d\n#define DDP_PLANT %d\n",
-             n, m, nparam, (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
+             n, m, (flags & DDP_USER_CONSTRAINTS) ? nparam + 2 : nparam,     // (the two multiplier slots of user_constraints.h)
+             (flags & DDP_USER_TERMINAL) ? 1 : 0, (flags & DDP_USER_CONST_HESSIAN) ? 1 : 0, wrap, L.chunk, L.rlanes, L.dflanes,
              (flags & DDP_USER_AUTODIFF) ? 1 : 0, L.adj, L.adh, (flags & DDP_USER_PLANT) ? 1 : 0);
     std::string s(head);
     const bool ad = (flags & DDP_USER_AUTODIFF) != 0, wave = (flags & DDP_USER_WAVE) != 0, clock = (flags & DDP_USER_CLOCK) != 0;
@@ -271,8 +295,18 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += "#line 1 \"ddp_user_autodiff\"\n";
         s += kUserAutodiff;
     }
+    const bool con = (flags & DDP_USER_CONSTRAINTS) != 0;        // a problem without the flag: not a byte of its text changes
+    if (con) {
+        snprintf(head, sizeof head, "#define DDP_NC %d\n", nc);
+        s += head;
+        s += kUserConstraintsBefore;
+    }
     s += "#line 1 \"user_source\"\n";
     s += source;
+    if (con) {
+        s += "\n#line 1 \"ddp_user_constraints\"\n";
+        s += kUserConstraintsAfter;
+    }
     if (ad) {
         if (clock) s += kUserClockAd;
         s += "\n#line 1 \"ddp_user_autodiff_derivs\"\n";
@@ -294,6 +328,12 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += kUserKernelsHessians;
     }
     s += lib(kUserKernelsPlant);
+    if (con) {
+        s += "\n#line 1 \"ddp_user_constraints_kernels\"\n";
+        s += DDP_USER_ABI_C_TEXT;
+        s += "\n";
+        s += kUserConstraintsKernels;
+    }
     if (flags & DDP_USER_SECOND_ORDER) {                         // a problem without the flag: the text above, nothing more
         s += "\n#define DDP_SECOND_ORDER 1\n#line 1 \"ddp_user_autodiff_vhess\"\n";
         s += kUserAutodiffVhess;
@@ -332,13 +372,13 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
 }
 
 // hiprtc: program text -> gfx950 code object; the log goes to g_log
-int compile(const char *source, int n, int m, int nparam, int flags, unsigned wrap, const char *extra, std::vector<char> *code)
+int compile(const char *source, int n, int m, int nparam, int flags, unsigned wrap, const char *extra, std::vector<char> *code, int nc = -1)
 {
-    int rc = validate(source, n, m, nparam, flags, wrap);
+    int rc = validate(source, n, m, nparam, flags, wrap, nc);
     if (rc) return rc;
     Hiprtc *R = hiprtc();
     DDP_CHECK(R, "user problem: hiprtc (libhiprtc.so) could not be loaded");
-    const std::string text = program_text(source, n, m, nparam, flags, wrap);
+    const std::string text = program_text(source, n, m, nparam, flags, wrap, nc);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
     if (extra) {
         const std::string e(extra);
@@ -393,11 +433,50 @@ struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
     hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
+    hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
     const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
     Layout L{};
 };
 struct Cache { std::map<std::string, Module> mods; };
+
+// DDP_USER_CONSTRAINTS: the parameter block of trajectory b, [user params | μ_b | the bits of the pointer to λ[:, :, b]] (user_constraints.h).
+// mu == NULL: μ = 0 and a null pointer, which the model never dereferences.  lam_stride = nc · N doubles per trajectory.
+__global__ void al_block_kernel(int B, int np, int batched, const double *params, const double *mu, const double *lam, size_t lam_stride,
+                                double *blk)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double *o = blk + (size_t)(np + 2) * b;
+    for (int e = 0; e < np; ++e) o[e] = params[batched ? (size_t)np * b + e : (size_t)e];
+    const bool on = mu && lam;
+    o[np] = on ? mu[b] : 0.0;
+    const double *q = on ? lam + lam_stride * b : nullptr;
+    double bits;
+    memcpy(&bits, &q, sizeof bits);                              // a plain 8-byte move: the bits of the pointer are preserved
+    o[np + 1] = bits;
+}
+
+__global__ void al_fill_kernel(int B, double v, double *mu, int32_t *live)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (mu) mu[b] = v;
+    live[b] = 1;
+}
+
+// the rows of the trajectories that are still live, from the arrays a later round was solved into, to the caller's arrays: one
+// work-group per (trajectory, array); a frozen trajectory keeps the outputs of the round it froze in
+struct AlMerge { const double *src[9]; double *dst[9]; size_t per[9]; };
+__global__ void al_merge_kernel(AlMerge a, const int32_t *live)
+{
+    const int b = blockIdx.x, k = blockIdx.y;
+    if (live[b] == 0) return;
+    const size_t per = a.per[k];
+    const double *s = a.src[k] + per * b;
+    double *d = a.dst[k] + per * b;
+    for (size_t e = threadIdx.x; e < per; e += blockDim.x) d[e] = s[e];
+}
 
 }   // namespace
 
@@ -417,10 +496,26 @@ struct UserProblem final : ddp_family {
     std::vector<int32_t> t0_host;
     int32_t *t0_dev = nullptr;
     int t0_count = 0;                                            // entries of t0_dev that are valid (0: to be written)
+    // DDP_USER_CONSTRAINTS: nc, the multipliers ddp_user_set_multipliers gave (device copies the problem owns; none: μ = 0), the ones an
+    // augmented-Lagrangian loop works on for the time of its call (al_lam, al_mu: the caller's arrays), and the parameter block of the
+    // last call.  The block is written again by every bind(), from pointers that are valid then: none outlives its array.
+    int nc = 0;
+    double *lam_dev = nullptr, *mu_dev = nullptr;
+    int lam_N = 0, lam_B = 0;
+    const double *al_lam = nullptr, *al_mu = nullptr;
+    double *blk = nullptr;
+    size_t blk_bytes = 0;
+    // ddp_user_ilqg_al_*: the arrays later rounds are solved into, the live flags and the counter; grown on demand, kept between calls
+    char *al_ws = nullptr;
+    size_t al_ws_bytes = 0;
     ~UserProblem() override
     {
         if (curv) hipFree(curv);
         if (t0_dev) hipFree(t0_dev);
+        if (lam_dev) hipFree(lam_dev);
+        if (mu_dev) hipFree(mu_dev);
+        if (blk) hipFree(blk);
+        if (al_ws) hipFree(al_ws);
     }
 
     int df(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx, double *fu,
@@ -548,7 +643,7 @@ UserProblem *as_problem(ddp_handle h, void *up)
 }
 
 // sizes and parameters of one call
-int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
+int bind(UserProblem *P, int N, int B, const double *params, int params_batched, bool params_on_device = false)
 {
     DDP_CHECK(N >= 1 && B >= 1, "user problem: N = %d, B = %d (both >= 1)", N, B);
     DDP_CHECK(params_batched == 0 || params_batched == 1, "user problem: params_batched = %d (0 or 1)", params_batched);
@@ -557,6 +652,25 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
     P->params = P->nparam ? params : nullptr; P->params_batched = params_batched;
     P->has_plant = false;
     P->t0 = P->clk = nullptr;
+    if (P->flags & DDP_USER_CONSTRAINTS) {
+        // the multipliers of ddp_user_set_multipliers belong to one (N, B); an augmented-Lagrangian loop brings its own for its call
+        const bool loop = P->al_lam != nullptr;
+        DDP_CHECK(loop || !P->lam_dev || (P->lam_N == N && P->lam_B == B),
+                  "user problem: ddp_user_set_multipliers gave lambda[%d, N = %d, B = %d], the call has N = %d, B = %d", P->nc, P->lam_N,
+                  P->lam_B, N, B);
+        if (!params_on_device) return 0;                         // (a host-pointer flavour: its `_dev` twin binds the device copy)
+        const size_t need = (size_t)(P->nparam + 2) * B * sizeof(double);
+        if (need > P->blk_bytes) {
+            if (P->blk) { DDP_HIP(hipStreamSynchronize(P->h->stream)); DDP_HIP(hipFree(P->blk)); P->blk = nullptr; P->blk_bytes = 0; }
+            DDP_HIP(hipMalloc((void **)&P->blk, need));
+            P->blk_bytes = need;
+        }
+        const double *lam = loop ? P->al_lam : P->lam_dev, *mu = loop ? P->al_mu : P->mu_dev;
+        hipLaunchKernelGGL(al_block_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, P->h->stream, B, P->nparam, params_batched,
+                           P->params, mu, lam, (size_t)P->nc * N, P->blk);
+        DDP_HIP(hipGetLastError());
+        P->params = P->blk; P->params_batched = 1;
+    }
     if (!(P->flags & DDP_USER_CLOCK)) return 0;
     // DDP_USER_CLOCK: one clock per trajectory (problem) of this call on the device, written when the batch or the clocks have changed
     const int count = (int)P->t0_host.size();
@@ -578,12 +692,17 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched)
 // what every ddp_user_* entry does first: the handle's device made current, the problem checked against the handle, the sizes and
 // parameters of the call bound.  A host-pointer flavour binds twice, here (it needs CL to size its staging) and in its `_dev` twin, with
 // the device copy of the parameters; the second bind finds t0_count == B and leaves the clocks on the device alone.
-int enter(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, UserProblem **P)
+// DDP_USER_CONSTRAINTS: `dev` says that params is a device pointer (the `_dev` entries that take such a problem: the parameter block is
+// assembled from it); `deferred` names an entry that refuses such a problem.
+int enter(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, UserProblem **P, bool dev = false,
+          const char *deferred = nullptr)
 {
     DDP_DEVICE(h);
     *P = as_problem(h, up);
     if (!*P) return -1;
-    return bind(*P, N, B, params, params_batched);
+    DDP_CHECK(!deferred || !((*P)->flags & DDP_USER_CONSTRAINTS), "%s: a DDP_USER_CONSTRAINTS problem is refused (deferred: constraints run "
+                                                                  "through ddp_user_ilqg_* and ddp_user_ilqg_al_* only)", deferred);
+    return bind(*P, N, B, params, params_batched, dev);
 }
 
 }   // namespace
@@ -596,6 +715,13 @@ int ddp_user_check(const char *source, int n, int m, int nparam, int flags, cons
     return compile(source, n, m, nparam, flags, 0u, extra_options, &code);
 }
 
+int ddp_user_check_c(const char *source, int n, int m, int nparam, int nc, int flags, const char *extra_options)
+{
+    DDP_CHECK(nc >= 0, "user problem: nc = %d (>= 0)", nc);
+    std::vector<char> code;
+    return compile(source, n, m, nparam, flags, 0u, extra_options, &code, nc);
+}
+
 const char *ddp_user_compile_log(void)
 {
     static thread_local std::string copy;
@@ -604,23 +730,24 @@ const char *ddp_user_compile_log(void)
     return copy.c_str();
 }
 
-int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out)
+static int user_create(ddp_handle h, const char *source, int n, int m, int nparam, int nc, int flags, int diff_wrap, void **out)
 {
     DDP_DEVICE(h);
     DDP_CHECK(out, "user problem: null output");
     *out = nullptr;
     const unsigned wrap = (unsigned)diff_wrap;
-    int rc = validate(source, n, m, nparam, flags, wrap);
+    int rc = validate(source, n, m, nparam, flags, wrap, nc);
     if (rc) return rc;
     char key_head[96];
-    snprintf(key_head, sizeof key_head, "%d,%d,%d,%d,%x\n", n, m, nparam, flags, wrap);
+    if (nc > 0) snprintf(key_head, sizeof key_head, "%d,%d,%d,%d,%x,c%d\n", n, m, nparam, flags, wrap, nc);
+    else snprintf(key_head, sizeof key_head, "%d,%d,%d,%d,%x\n", n, m, nparam, flags, wrap);
     const std::string key = std::string(key_head) + source;
     if (!h->user_cache) h->user_cache = new Cache();
     Cache *c = (Cache *)h->user_cache;
     auto it = c->mods.find(key);
     if (it == c->mods.end()) {
         std::vector<char> code;
-        rc = compile(source, n, m, nparam, flags, wrap, nullptr, &code);
+        rc = compile(source, n, m, nparam, flags, wrap, nullptr, &code, nc);
         if (rc) return rc;
         Module M;
         M.L = layout_of(n, m, flags);
@@ -637,7 +764,9 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
                                                               hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess)) &&
                         (!(flags & DDP_USER_SECOND_ORDER_WAVE) ||
                          (hipModuleGetFunction(&M.bp2w, M.mod, "ddp_user_back_pass2_wave") == hipSuccess &&
-                          hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess));
+                          hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess)) &&
+                        (!(flags & DDP_USER_CONSTRAINTS) || (hipModuleGetFunction(&M.con, M.mod, "ddp_user_constraints") == hipSuccess &&
+                                                             hipModuleGetFunction(&M.alup, M.mod, "ddp_user_al_update") == hipSuccess));
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -650,8 +779,20 @@ int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, 
     P->has_plant = false;                                        // set by the closed-loop entry points only
     P->second_order = (flags & (DDP_USER_SECOND_ORDER | DDP_USER_SECOND_ORDER_WAVE)) != 0;
     P->nparam = nparam; P->flags = flags; P->wrap = wrap; P->mod = &it->second;
+    P->nc = nc > 0 ? nc : 0;
     *out = P;
     return 0;
+}
+
+int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out)
+{
+    return user_create(h, source, n, m, nparam, -1, flags, diff_wrap, out);
+}
+
+int ddp_user_create_c(ddp_handle h, const char *source, int n, int m, int nparam, int nc, int flags, int diff_wrap, void **out)
+{
+    DDP_CHECK(nc >= 0, "user problem: nc = %d (>= 0)", nc);
+    return user_create(h, source, n, m, nparam, nc, flags, diff_wrap, out);
 }
 
 int ddp_user_destroy(void *up)
@@ -675,7 +816,7 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
                         const int32_t *active, double *fx, double *fu, double *cx, double *cu, double *cxx, double *cxu, double *cuu)
 {
     UserProblem *P;
-    int rc = enter(h, up, N, B, params, params_batched, &P);
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
     if (rc) return rc;
     DDP_CHECK(x && u && fx && fu && cx && cu, "df: null argument");
     rc = P->df(h, B, nullptr, x, u, active, fx, fu, cx, cu, P->const_hessian ? nullptr : cxx, P->const_hessian ? nullptr : cxu,
@@ -796,13 +937,191 @@ const char *ddp_user_program_text(const char *source, int n, int m, int nparam, 
     return text.c_str();
 }
 
+// the same hook with the number of constraints (the program of a DDP_USER_CONSTRAINTS problem)
+const char *ddp_user_program_text_c(const char *source, int n, int m, int nparam, int nc, int flags, int diff_wrap)
+{
+    static thread_local std::string text;
+    if (nc < 0 || validate(source, n, m, nparam, flags, (unsigned)diff_wrap, nc)) return nullptr;
+    text = program_text(source, n, m, nparam, flags, (unsigned)diff_wrap, nc);
+    return text.c_str();
+}
+
+int ddp_user_set_multipliers(void *up, const double *lambda, const double *mu, int N, int B)
+{
+    UserProblem *P = (UserProblem *)up;
+    DDP_CHECK(P, "user problem: null problem");
+    DDP_CHECK(P->flags & DDP_USER_CONSTRAINTS, "set_multipliers: the problem was made without DDP_USER_CONSTRAINTS");
+    DDP_HIP(hipSetDevice(P->h->device));
+    if (P->lam_dev || P->mu_dev) {                               // (kernels in flight may still read them)
+        DDP_HIP(hipStreamSynchronize(P->h->stream));
+        if (P->lam_dev) DDP_HIP(hipFree(P->lam_dev));
+        if (P->mu_dev) DDP_HIP(hipFree(P->mu_dev));
+        P->lam_dev = P->mu_dev = nullptr; P->lam_N = P->lam_B = 0;
+    }
+    if (!lambda && !mu) return 0;
+    DDP_CHECK(lambda && mu, "set_multipliers: lambda and mu must both be given or both NULL");
+    DDP_CHECK(N >= 1 && B >= 1, "set_multipliers: N = %d, B = %d (both >= 1)", N, B);
+    const size_t ln = (size_t)P->nc * N * B;
+    DDP_HIP(hipMalloc((void **)&P->lam_dev, ln * sizeof(double)));
+    DDP_HIP(hipMalloc((void **)&P->mu_dev, (size_t)B * sizeof(double)));
+    DDP_HIP(hipMemcpy(P->lam_dev, lambda, ln * sizeof(double), hipMemcpyHostToDevice));
+    DDP_HIP(hipMemcpy(P->mu_dev, mu, (size_t)B * sizeof(double), hipMemcpyHostToDevice));
+    P->lam_N = N; P->lam_B = B;
+    return 0;
+}
+
+int ddp_user_constraints_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                                 const double *u, double *g)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->con, "constraints: the problem was made without DDP_USER_CONSTRAINTS");
+    DDP_CHECK(x && u && g, "constraints: null argument");
+    UserConArgs a;
+    a.N = N; a.B = B; a.params = P->params; a.x = x; a.u = u; a.g = g;
+    void *args[] = {&a};
+    const long R = (long)N * B;
+    DDP_HIP(hipModuleLaunchKernel(P->mod->con, (unsigned)((R + 63) / 64), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    return 0;
+}
+
+int ddp_user_constraints_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                             const double *u, double *g)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->con, "constraints: the problem was made without DDP_USER_CONSTRAINTS");
+    DDP_CHECK(x && u && g, "constraints: null argument");
+    const size_t n = P->n, m = P->m, T = (size_t)N * B;
+    const double *dp, *dx, *du;
+    double *dg;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx, x, n * T); S.in(&du, u, m * T);
+    S.out(&dg, g, (size_t)P->nc * T);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_user_constraints_f64_dev(h, up, N, B, dp, params_batched, dx, du, dg));
+}
+
+void ddp_al_default_opts(ddp_al_opts *o)
+{
+    if (!o) return;
+    o->mu0 = 1.0; o->mu_factor = 10.0; o->mu_max = 1e8; o->ctol = 1e-5; o->max_outer = 20;
+}
+
+int ddp_user_ilqg_al_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                             const ddp_al_opts *ao, const double *x0, int x0_prerolled, const double *u0, const double *lims,
+                             const double *lambda0, const double *mu_init, double *x, double *u, double *K, double *k, double *Quu,
+                             double *Vx, double *Vxx, double *cost, double *stats, double *lambda, double *mu, double *g, double *al_stats,
+                             int *global_iters)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);      // (sizes only: every round binds with its multipliers, below)
+    if (rc) return rc;
+    DDP_CHECK(P->mod->alup, "ilqg_al: the problem was made without DDP_USER_CONSTRAINTS");
+    DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats && lambda && mu && g && al_stats, "ilqg_al: null argument");
+    ddp_al_opts ad;
+    if (!ao) { ddp_al_default_opts(&ad); ao = &ad; }
+    DDP_CHECK(ao->mu0 > 0.0 && ao->mu_factor >= 1.0 && ao->mu_max >= ao->mu0 && ao->ctol >= 0.0 && ao->max_outer >= 1,
+              "ilqg_al: mu0 = %g (> 0), mu_factor = %g (>= 1), mu_max = %g (>= mu0), ctol = %g (>= 0), max_outer = %d (>= 1)", ao->mu0,
+              ao->mu_factor, ao->mu_max, ao->ctol, ao->max_outer);
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, CL = P->CL, nc = P->nc;
+    // later rounds are solved into arrays of the loop's own and the rows of the live trajectories merged into the caller's
+    const size_t per[9] = {n * N, m * N, m * n * N, m * N, m * m * N, n * N, n * n * N, CL, (size_t)DDP_ILQG_NSTATS};
+    size_t off[10] = {0};
+    for (int e = 0; e < 9; ++e) off[e + 1] = off[e] + Staging::al(per[e] * B * sizeof(double));
+    const size_t o_live = off[9], o_cnt = o_live + Staging::al((size_t)B * sizeof(int32_t)), bytes = o_cnt + 256;
+    DDP_CHECK(h->h_pinned, "ilqg_al: pinned poll buffer missing");
+    hipStream_t st = h->stream;
+    if (bytes > P->al_ws_bytes) {                                // (as curv and blk: no allocation per call once the batch has been seen)
+        if (P->al_ws) { DDP_HIP(hipStreamSynchronize(st)); DDP_HIP(hipFree(P->al_ws)); P->al_ws = nullptr; P->al_ws_bytes = 0; }
+        DDP_HIP(hipMalloc((void **)&P->al_ws, bytes));
+        P->al_ws_bytes = bytes;
+    }
+    char *ws = P->al_ws;
+    struct Scope {                                               // every way out: the loop's multipliers leave the problem
+        UserProblem *P;
+        ~Scope() { P->al_lam = P->al_mu = nullptr; }
+    } scope{P};
+    double *sc[9];
+    for (int e = 0; e < 9; ++e) sc[e] = (double *)(ws + off[e]);
+    int32_t *live = (int32_t *)(ws + o_live);
+    int *counter = (int *)(ws + o_cnt);
+    double *user[9] = {x, u, K, k, Quu, Vx, Vxx, cost, stats};
+
+    if (lambda0) DDP_HIP(hipMemcpyAsync(lambda, lambda0, nc * T * sizeof(double), hipMemcpyDeviceToDevice, st));
+    else DDP_HIP(hipMemsetAsync(lambda, 0, nc * T * sizeof(double), st));
+    if (mu_init) DDP_HIP(hipMemcpyAsync(mu, mu_init, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(al_fill_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, ao->mu0, mu_init ? (double *)nullptr : mu, live);
+    DDP_HIP(hipGetLastError());
+    DDP_HIP(hipMemsetAsync(al_stats, 0, (size_t)6 * B * sizeof(double), st));
+
+    int total = 0;
+    for (int r = 0; r < ao->max_outer; ++r) {
+        P->al_lam = lambda; P->al_mu = mu;
+        rc = bind(P, N, B, params, params_batched, true);        // the block of this round: μ and the pointers to λ as they stand now
+        if (rc) return rc;
+        double **out = r == 0 ? user : sc;
+        int git = 0;
+        // round 0: the caller's start; later rounds: pre-rolled from the last solution, its cost evaluated again under the new multipliers
+        rc = ddp_ilqg_family_dev(h, P, o, r == 0 ? x0 : x, r == 0 ? x0_prerolled : 1, r == 0 ? u0 : u, nullptr, lims, out[0], out[1], out[2],
+                                 out[3], out[4], out[5], out[6], out[7], out[8], 0, nullptr, &git);
+        if (rc) return rc;
+        total += git;
+        if (r > 0) {
+            AlMerge mg;
+            for (int e = 0; e < 9; ++e) { mg.src[e] = sc[e]; mg.dst[e] = user[e]; mg.per[e] = per[e]; }
+            hipLaunchKernelGGL(al_merge_kernel, dim3((unsigned)B, 9), dim3(256), 0, st, mg, (const int32_t *)live);
+            DDP_HIP(hipGetLastError());
+        }
+        DDP_HIP(hipMemsetAsync(counter, 0, sizeof(int), st));
+        UserAlArgs a;
+        a.N = N; a.B = B; a.round = r; a.max_outer = ao->max_outer; a.mu_factor = ao->mu_factor; a.mu_max = ao->mu_max; a.ctol = ao->ctol;
+        a.params = P->params; a.x = x; a.u = u; a.stats = stats; a.lambda = lambda; a.mu = mu; a.g = g; a.al_stats = al_stats;
+        a.live = live; a.counter = counter;
+        void *args[] = {&a};
+        DDP_HIP(hipModuleLaunchKernel(P->mod->alup, (unsigned)B, 1, 1, 64, 1, 1, 0, st, args, nullptr));
+        DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, sizeof(int), hipMemcpyDeviceToHost, st));
+        DDP_HIP(hipStreamSynchronize(st));
+        if (h->h_pinned[0] == 0) break;                          // the one number the host reads per round: trajectories still live
+    }
+    if (global_iters) *global_iters = total;
+    return 0;
+}
+
+int ddp_user_ilqg_al_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                         const ddp_al_opts *ao, const double *x0, int x0_prerolled, const double *u0, const double *lims,
+                         const double *lambda0, const double *mu_init, double *x, double *u, double *K, double *k, double *Quu,
+                         double *Vx, double *Vxx, double *cost, double *stats, double *lambda, double *mu, double *g, double *al_stats,
+                         int *global_iters)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->alup, "ilqg_al: the problem was made without DDP_USER_CONSTRAINTS");
+    DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats && lambda && mu && g && al_stats, "ilqg_al: null argument");
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, CL = P->CL, nc = P->nc;
+    const double *dp, *dx0, *du0, *dl, *dl0, *dm0;
+    double *dx, *du, *dK, *dk, *dQ, *dVx, *dVxx, *dc, *ds, *dlam, *dmu, *dg, *das;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * (x0_prerolled ? T : (size_t)B)); S.in(&du0, u0, m * T);
+    S.in(&dl, lims, 2 * m); S.in(&dl0, lambda0, nc * T); S.in(&dm0, mu_init, (size_t)B);
+    S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dk, k, m * T); S.out(&dQ, Quu, m * m * T); S.out(&dVx, Vx, n * T);
+    S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * B); S.out(&ds, stats, (size_t)DDP_ILQG_NSTATS * B);
+    S.out(&dlam, lambda, nc * T); S.out(&dmu, mu, (size_t)B); S.out(&dg, g, nc * T); S.out(&das, al_stats, (size_t)6 * B);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_user_ilqg_al_f64_dev(h, up, N, B, dp, params_batched, o, ao, dx0, x0_prerolled, du0, dl, dl0, dm0, dx, du, dK, dk, dQ,
+                                             dVx, dVxx, dc, ds, dlam, dmu, dg, das, global_iters));
+}
+
 int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
                                   const double *K, const double *k, const double *x0, const double *u, const double *x,
                                   const double *alpha, int nalpha, const double *lims, const int32_t *active,
                                   double *xnew, double *unew, double *cnew, double *csum)
 {
     UserProblem *P;
-    int rc = enter(h, up, N, B, params, params_batched, &P);
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
     if (rc) return rc;
     DDP_CHECK(x0 && u && alpha && xnew && unew && cnew && csum, "forward_pass: null argument");
     return P->rollout(h, B, nullptr, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
@@ -834,7 +1153,7 @@ int ddp_user_costfun_f64_dev(ddp_handle h, void *up, int N, int B, const double 
                              const double *u, const int32_t *active, double *cost, double *csum)
 {
     UserProblem *P;
-    int rc = enter(h, up, N, B, params, params_batched, &P);
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
     if (rc) return rc;
     DDP_CHECK(x && u && cost, "costfun: null argument");
     return P->costfun(h, B, nullptr, x, u, active, cost, csum);
@@ -863,7 +1182,7 @@ int ddp_user_ilqg_f64_dev(ddp_handle h, void *up, int N, int B, const double *pa
                           double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
 {
     UserProblem *P;
-    int rc = enter(h, up, N, B, params, params_batched, &P);
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
     if (rc) return rc;
     return ddp_ilqg_family_dev(h, P, o, x0, x0_prerolled, u0, cost0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, trace7,
                                global_iters);
@@ -898,7 +1217,7 @@ int ddp_user_ilqg_queue_f64_dev(ddp_handle h, void *up, int N, int P, const doub
                                 double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, P, params, params_batched, &U);
+    int rc = enter(h, up, N, P, params, params_batched, &U, false, "ilqg_queue");
     if (rc) return rc;
     DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
     return ddp_ilqg_sched_family_dev(h, U, o, slots, 0, 0, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, nullptr, nullptr, nullptr,
@@ -910,7 +1229,7 @@ int ddp_user_ilqg_queue_f64(ddp_handle h, void *up, int N, int P, const double *
                             double *Quu, double *Vx, double *Vxx, double *cost, double *stats, int *global_iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, P, params, params_batched, &U);
+    int rc = enter(h, up, N, P, params, params_batched, &U, false, "ilqg_queue");
     if (rc) return rc;
     DDP_CHECK(x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg_queue: null argument");
     const size_t n = U->n, m = U->m, T = (size_t)N * P, CL = U->CL;
@@ -930,7 +1249,7 @@ int ddp_user_ilqg_mpc_f64_dev(ddp_handle h, void *up, int N, int B, const double
                               double *stats_cl, double *x, double *u, int *global_iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, B, params, params_batched, &U);
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqg_mpc");
     if (rc) return rc;
     DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
     DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
@@ -946,7 +1265,7 @@ int ddp_user_ilqg_mpc_f64(ddp_handle h, void *up, int N, int B, const double *pa
                           double *stats_cl, double *x, double *u, int *global_iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, B, params, params_batched, &U);
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqg_mpc");
     if (rc) return rc;
     DDP_CHECK(steps >= 1, "ilqg_mpc: steps=%d", steps);
     DDP_CHECK(x0 && u0 && xcl && ucl && stats_cl && x && u, "ilqg_mpc: null argument");
@@ -969,7 +1288,7 @@ int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *
                             double *cost, double *dV, double *stats, int *iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, B, params, params_batched, &U);
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
     if (rc) return rc;
     return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
                                  Vxx, cost, dV, stats, iters);
@@ -982,7 +1301,7 @@ int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *para
                         double *cost, double *dV, double *stats, int *iters)
 {
     UserProblem *U;
-    int rc = enter(h, up, N, B, params, params_batched, &U);
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
     if (rc) return rc;
     DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl: null argument");
     const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;

@@ -547,6 +547,8 @@ const MAX_N = 64                       # include/ddp_amd.h: the backward kernels
 const MAX_M = 8                        # DDP_MAX_M: user problems, the KL functions, the lane-per-problem boxQP
 const MAX_N_USER_WAVE = 64             # DDP_MAX_N_USER_WAVE: user problems made with wave=true (n <= 64, m <= MAX_M_WIDE)
 const USER_CLOCK = 512                 # DDP_USER_CLOCK: the flag of DeviceProblem(...; clock=true); 256 is not assigned
+const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(...; constraints=nc)
+const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
@@ -974,6 +976,10 @@ end
 # int behind i, terminal_cost takes t = c + N - 1 behind x.  The clock c of every trajectory is the keyword t0 (an integer or one per
 # trajectory / problem, default 0) of forward_pass, df, costfun, iLQG, iLQG_queue, iLQG_mpc (the solve at closed-loop step s runs with
 # t0 + s, the plant gets t = t0 + s) and iLQGkl.  Not together with second_order=true or second_order_wave=true.
+# constraints=nc (DDP_USER_CONSTRAINTS, needs autodiff=true): the source also defines the template constraints(x, u, i, p, g) writing g[nc],
+# feasible where g <= 0.  constraints(problem, x, u) evaluates it; with_multipliers(f, problem, handle, λ, μ) runs f() — calls of
+# forward_pass, df, costfun, iLQG — on the augmented cost under λ[nc,N,B], μ[B].  Not together with const_hessian, clock, second_order or
+# second_order_wave; iLQG_queue, iLQG_mpc and iLQGkl refuse such a problem.  The loop itself (ddp_user_ilqg_al_f64) is not bound here yet.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -983,21 +989,24 @@ mutable struct DeviceProblem
     wrap::Int
     params::Array{Float64}
     made::Dict{Ptr{Cvoid},Ptr{Cvoid}}
+    nc::Int
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
-                       second_order_wave::Bool=false, clock::Bool=false)
+                       second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
-            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0)
-    p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}())
+            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0)
+    p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
 end
 # compile-only check for gfx950 (no device): the compiler log, or a DDPError carrying it
 function check_source(p::DeviceProblem; extra_options::AbstractString="")
-    rc = @ccall libddp.ddp_user_check(p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint, extra_options::Cstring)::Cint
+    rc = p.nc > 0 ?
+        (@ccall libddp.ddp_user_check_c(p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.nc::Cint, p.flags::Cint, extra_options::Cstring)::Cint) :
+        (@ccall libddp.ddp_user_check(p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint, extra_options::Cstring)::Cint)
     log = unsafe_string(@ccall libddp.ddp_user_compile_log()::Cstring)
     rc == 0 || throw(DDPError(Int(rc), last_error() * "\n" * log))
     return log
@@ -1006,10 +1015,54 @@ cost_len(p::DeviceProblem, N) = (p.flags & 1) != 0 ? N + 1 : N
 function _user_ptr(p::DeviceProblem, handle::Handle)
     get!(p.made, handle.ptr) do
         r = Ref{Ptr{Cvoid}}(C_NULL)
-        check(@ccall libddp.ddp_user_create(handle.ptr::Ptr{Cvoid}, p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint,
-                                            p.wrap::Cint, r::Ptr{Ptr{Cvoid}})::Cint)
+        if p.nc > 0
+            check(@ccall libddp.ddp_user_create_c(handle.ptr::Ptr{Cvoid}, p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.nc::Cint,
+                                                  p.flags::Cint, p.wrap::Cint, r::Ptr{Ptr{Cvoid}})::Cint)
+        else
+            check(@ccall libddp.ddp_user_create(handle.ptr::Ptr{Cvoid}, p.source::Cstring, p.n::Cint, p.m::Cint, p.nparam::Cint, p.flags::Cint,
+                                                p.wrap::Cint, r::Ptr{Ptr{Cvoid}})::Cint)
+        end
         r[]
     end
+end
+"""
+    with_multipliers(f, problem, handle, λ, μ)
+
+`f()` with the multipliers `λ[nc,N,B]` and penalties `μ[B]` of a `constraints=nc` problem (ddp_user_set_multipliers): the calls of
+`forward_pass`, `df`, `costfun` and `iLQG` inside work on the augmented cost.  None are set afterwards, also when `f` throws.
+"""
+function with_multipliers(f, p::DeviceProblem, handle::Handle, λ, μ)
+    p.nc > 0 || throw(DDPError(-1, "multipliers need a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS)"))
+    lam = _f64(λ); mu = _f64(μ)
+    N = size(lam, 2); B = length(mu)
+    size(lam) == (p.nc, N, B) || throw(DDPError(-1, "multipliers: λ must be [nc, N, B] and μ [B]"))
+    up = _user_ptr(p, handle)
+    GC.@preserve lam mu check(@ccall libddp.ddp_user_set_multipliers(up::Ptr{Cvoid}, lam::Ptr{Float64}, mu::Ptr{Float64}, N::Cint, B::Cint)::Cint)
+    try
+        return f()
+    finally
+        @ccall libddp.ddp_user_set_multipliers(up::Ptr{Cvoid}, C_NULL::Ptr{Float64}, C_NULL::Ptr{Float64}, 0::Cint, 0::Cint)::Cint
+    end
+end
+"""
+    constraints(problem, x, u; handle, params)
+
+`g[nc,N(,B)]` of a `constraints=nc` problem at `x[n,N(,B)]`, `u[m,N(,B)]` (ddp_user_constraints_f64); feasible where `g <= 0`.
+"""
+function constraints(problem::DeviceProblem, x, u; handle::Handle=default_handle(), params=nothing)
+    problem.nc > 0 || throw(DDPError(-1, "constraints: a DeviceProblem made with constraints=nc (DDP_USER_CONSTRAINTS) is needed"))
+    batched = ndims(u) == 3
+    N = size(u, 2)
+    B = batched ? size(u, 3) : 1
+    P, pb = _user_params(problem, B, params)
+    g = batched ? zeros(problem.nc, N, B) : zeros(problem.nc, N)
+    x = _f64(x); u = _f64(u)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P x u g begin
+        check(@ccall libddp.ddp_user_constraints_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, x::Ptr{Float64}, u::Ptr{Float64}, g::Ptr{Float64})::Cint)
+    end
+    return g
 end
 # f() with the clocks t0 of a clock=true problem (ddp_user_set_t0); every clock is 0 again afterwards, also when f throws
 function _with_clock(f, p::DeviceProblem, handle::Handle, t0)

@@ -611,12 +611,31 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * recursion and would have to carry the clock as well — deferred, not impossible.  The kernels are the ones of a problem without the
  * flag (same names, same text, with t handed on at every call of the user's functions); such a problem compiles and runs exactly as
  * before.  user_examples/car_track.hip, car_track_ad.hip and car_track_plant.hip follow a sampled reference past a moving obstacle.
- * Bits 64 and 256 of the flags are not assigned and stay refused as unknown. */
+ * Bits 64 and 256 of the flags are not assigned and stay refused as unknown.
+ *
+ * DDP_USER_CONSTRAINTS: inequality constraints on the state, or on state and control together (a keep-out disc, a speed cap, a
+ * corridor), handled by an augmented Lagrangian around the iLQG solve.  The source also defines
+ *
+ *   template <class T> __device__ void constraints(const T *x, const T *u, int i, const double *p, T *g);   g[nc], feasible: g[j] <= 0
+ *
+ * evaluated at every stage i = 0..N-1 on (x_i, u_i), which covers every state of the horizon; nc <= DDP_USER_MAX_NC reaches the
+ * library through ddp_user_check_c / ddp_user_create_c (the entries without `_c` refuse the flag by name).  Every kernel of such a
+ * problem evaluates, in place of stage_cost, the user's stage cost plus the Powell-Hestenes-Rockafellar term
+ *   psi = sum_j (max(0, lambda_ij + mu g_j)^2 - lambda_ij^2) / (2 mu)   for mu > 0,   0 for mu <= 0
+ * with multipliers lambda[nc,N,B] and a penalty mu[B] per trajectory: those of ddp_user_set_multipliers (none set: mu = 0, the raw
+ * cost) in ddp_user_df_*, ddp_user_forward_pass_*, ddp_user_costfun_* and ddp_user_ilqg_*, and the loop's own in ddp_user_ilqg_al_*.
+ * The user's indices into p are unchanged (the library appends two slots of its own behind the nparam parameters).  The flag needs
+ * DDP_USER_AUTODIFF (the augmented cost is differentiated by AD) and combines with DDP_USER_TERMINAL, DDP_USER_WAVE, DDP_USER_PLANT and
+ * diff_wrap; with DDP_USER_CONST_HESSIAN, DDP_USER_CLOCK, DDP_USER_SECOND_ORDER or DDP_USER_SECOND_ORDER_WAVE it is refused by name, and
+ * ddp_user_ilqg_queue_*, ddp_user_ilqg_mpc_* and ddp_user_ilqgkl_* refuse such a problem by name before any launch.  Equality
+ * constraints are not offered.  user_examples/car_keepout_ad.hip keeps the car out of a disc and caps its speed. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
-       DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512 };      /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
+       DDP_USER_CONSTRAINTS = 1024 };                                                      /* 64: not assigned, refused as unknown (256 too) */
+#define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
 int ddp_user_check(const char *source, int n, int m, int nparam, int flags, const char *extra_options);
@@ -625,6 +644,19 @@ const char *ddp_user_compile_log(void);
 /* compile (or take from the handle's cache) and load on the handle's device: *out is the problem, used with this handle only */
 int ddp_user_create(ddp_handle h, const char *source, int n, int m, int nparam, int flags, int diff_wrap, void **out);
 int ddp_user_destroy(void *up);
+/* The same two entries with the number of constraints nc (DDP_USER_CONSTRAINTS: 1 <= nc <= DDP_USER_MAX_NC; a problem without the
+ * flag: nc = 0, and they do what the entries above do).                                                                        */
+int ddp_user_check_c(const char *source, int n, int m, int nparam, int nc, int flags, const char *extra_options);
+int ddp_user_create_c(ddp_handle h, const char *source, int n, int m, int nparam, int nc, int flags, int diff_wrap, void **out);
+/* DDP_USER_CONSTRAINTS problems only: the multipliers lambda[nc,N,B] and penalties mu[B] of the following ddp_user_df_*,
+ * ddp_user_forward_pass_*, ddp_user_costfun_* and ddp_user_ilqg_* calls.  Host pointers, copied; the problem owns the device copies.
+ * Both NULL clears them (mu = 0: the raw cost).  A call whose N or B differs from the ones given here is refused before any launch. */
+int ddp_user_set_multipliers(void *up, const double *lambda, const double *mu, int N, int B);
+/* constraints: x[n,N,B] u[m,N,B] -> g[nc,N,B] (kernel ddp_user_constraints, one lane per step and trajectory)                      */
+int ddp_user_constraints_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                                 const double *u, double *g);
+int ddp_user_constraints_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const double *x,
+                             const double *u, double *g);
 /* DDP_USER_CLOCK problems only (others are refused by name): the clocks of the following calls.  t0 is a host pointer and is copied;
  * count = 0: every clock is 0; 1: one value for every trajectory; B (P for the queue): one per trajectory or problem.  The problem
  * owns the device copy (ddp_user_destroy frees it).                                                                             */
@@ -715,6 +747,36 @@ int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *para
                         const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
                         double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
                         double *cost, double *dV, double *stats, int *iters);
+
+/* The augmented-Lagrangian loop of a DDP_USER_CONSTRAINTS problem, per trajectory, round r = 0, 1, ...:
+ *   1. the solve of ddp_user_ilqg_f64 under (lambda, mu): round 0 from x0[n,B] (x0_prerolled: x0[n,N,B]) and u0, later rounds pre-rolled
+ *      from the last (x, u) with the cost evaluated again under the new multipliers;
+ *   2. g = constraints(x, u), cviol = max_ij max(0, g_ij) (kernel ddp_user_al_update, reductions in a fixed order);
+ *   3. inner status DDP_EXIT_INIT_DIVERGED in round 0: AL status -1; cviol <= ctol: 1; r + 1 == max_outer: 2; each of them freezes the
+ *      trajectory with the multipliers its solution was computed under.  Otherwise lambda <- max(0, lambda + mu g),
+ *      mu <- min(mu_factor mu, mu_max), evaluated without contraction.
+ * A frozen trajectory's outputs are, bit for bit, those of the round it froze in.  The host reads one counter per round; lambda, mu, x
+ * and u stay on the device between rounds.  lambda0[nc,N,B] (NULL: zeros) and mu_init[B] (NULL: mu0 everywhere) are the initial
+ * multipliers.  Outputs: those of ddp_user_ilqg_f64 (cost is the augmented one, stats[8,B] those of the last round each trajectory
+ * ran; no trace), lambda[nc,N,B], mu[B], g[nc,N,B] at the returned (x, u), and
+ *   al_stats[6,B] = [status, rounds, total inner iterations, mu of the last solve, cviol, sum of the raw cost]
+ * global_iters (may be NULL): batch-level iterations of all rounds.                                                              */
+typedef struct {
+    double mu0, mu_factor, mu_max, ctol;
+    int max_outer;
+} ddp_al_opts;
+#define DDP_AL_NSTATS 6
+void ddp_al_default_opts(ddp_al_opts *o);      /* mu0 1, mu_factor 10, mu_max 1e8, ctol 1e-5, max_outer 20 */
+int ddp_user_ilqg_al_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                             const ddp_al_opts *ao, const double *x0, int x0_prerolled, const double *u0, const double *lims,
+                             const double *lambda0, const double *mu_init, double *x, double *u, double *K, double *k, double *Quu,
+                             double *Vx, double *Vxx, double *cost, double *stats, double *lambda, double *mu, double *g, double *al_stats,
+                             int *global_iters);
+int ddp_user_ilqg_al_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqg_opts *o,
+                         const ddp_al_opts *ao, const double *x0, int x0_prerolled, const double *u0, const double *lims,
+                         const double *lambda0, const double *mu_init, double *x, double *u, double *K, double *k, double *Quu,
+                         double *Vx, double *Vxx, double *cost, double *stats, double *lambda, double *mu, double *g, double *al_stats,
+                         int *global_iters);
 
 #ifdef __cplusplus
 }
