@@ -1,4 +1,5 @@
-// ilqg.hip — device-resident iLQG iteration for registered problem families.
+// ilqg.hip — device-resident iLQG iteration for the registered problem kinds and for the families of ddp_family (user problems,
+// user_problem.hip); what differs between them is behind Model (ilqg_model.h).
 //
 // Replaces the outer loop of  iLQG(f,costfun,df,x0,u0; ...)  (src/iLQG.jl:143-341).  Every trajectory
 // of the batch is an independent solve with its own scalar state machine (λ, dλ, iter, accepted_iter,
@@ -10,11 +11,13 @@
 //   STEP 3  all-α line-search rollouts (forward_pass.hip), first α in list order that passes  :264-283
 //   STEP 4  accept / reject, λ schedule, termination  iLQG.jl:293-323
 // The host only launches kernels and polls one counter (number of running trajectories) per global
-// iteration.  The λ-schedule quirks of the reference are kept: the increase uses the OLD dλ
+// iteration.  Two host drivers run it: the batch in lock step (ilqg_impl) and the slot scheduler (ilqg_sched_impl: queue and closed
+// loop); STEPS 1-3 are one function for both (ilqg_steps).  The λ-schedule quirks of the reference are kept: the increase uses the OLD dλ
 // (tuple assignment, :246,:313), the decrease the NEW one (:299-300), λ never drops below λmin.
 #include <stdlib.h>
 #include <vector>
 #include "ddp_internal.h"
+#include "ilqg_model.h"
 #include "staging.h"
 
 namespace {
@@ -22,6 +25,11 @@ namespace {
 struct Traj {           // per-trajectory scalar state (structure of arrays in one allocation)
     double *lam, *dlam, *gnorm, *csum;
     int32_t *status, *iter, *acc, *nbp, *nfp, *flg, *run, *dodf, *dofwd, *div0;
+    void carve(Carver &c, size_t slots)
+    {
+        for (double **d : {&lam, &dlam, &gnorm, &csum}) *d = c.take<double>(slots);
+        for (int32_t **i : {&status, &iter, &acc, &nbp, &nfp, &flg, &run, &dodf, &dofwd, &div0}) *i = c.take<int32_t>(slots);
+    }
 };
 
 struct Opt {
@@ -338,7 +346,7 @@ __global__ void stats_kernel(int B, Traj s, const int32_t *map, int only_finishe
 // slot re-solves its own problem `steps` times in closed loop (MPC: apply u_0, the model is the plant — or a user family's plant() —,
 // shift, solve again).  A slot
 // whose solve has ended is flushed and re-armed ON THE DEVICE at the end of the global iteration in which it ended; the host only
-// polls the number of busy slots.  The state machine of a solve is the one of ilqg_impl (same kernels, same launches per global
+// polls the number of busy slots.  The state machine of a solve is the one of ilqg_impl (ilqg_steps: the same launches per global
 // iteration), so a solve does the arithmetic of its stand-alone solve at the same batch size.
 struct Sched {
     int P, mpc_steps, zero_tail, nalpha, max_iter;
@@ -489,6 +497,110 @@ __global__ __launch_bounds__(64) void sched_init_advance_kernel(int m, int N, Sc
     }
 }
 
+// ---- what the two host drivers (ilqg_impl: the batch in lock step; ilqg_sched_impl: the slot scheduler) share: the pieces of their
+// workspaces, the options as the kernels take them, and STEPS 1-3 of a global iteration — one body, so a slot of the scheduler does
+// the launches of a stand-alone solve at the same batch size (same launches -> same kernels -> same bits per solve)
+
+// a working set of the driver's own: the arrays of `slots` trajectories and their scalar state (map stays with the caller)
+void carve_workset(Carver &c, WorkSet &w, const Model &M, size_t slots)
+{
+    const size_t n = M.n, m = M.m, N = M.N;
+    w.x = c.take<double>(n * N * slots); w.u = c.take<double>(m * N * slots); w.cost = c.take<double>(M.CL * slots);
+    w.K = c.take<double>(m * n * N * slots); w.k = c.take<double>(m * N * slots); w.Quu = c.take<double>(m * m * N * slots);
+    w.Vx = c.take<double>(n * N * slots); w.Vxx = c.take<double>(n * n * N * slots); w.x0 = c.take<double>(n * slots);
+    w.s.carve(c, slots);
+}
+
+// the rollouts of `na` step sizes for `slots` trajectories (step size a of slot b at index b + slots * a) and, for a line search in
+// groups, the masks of the trajectories whose search is still open behind the first and the second group (ls_more_kernel)
+struct Cand {
+    double *xn, *un, *cn, *cs;
+    int32_t *more, *more2;
+    void carve(Carver &c, const Model &M, size_t slots, size_t na)
+    {
+        xn = c.take<double>((size_t)M.n * M.N * slots * na); un = c.take<double>((size_t)M.m * M.N * slots * na);
+        cn = c.take<double>((size_t)M.CL * slots * na); cs = c.take<double>(slots * na);
+        more = c.take_if<int32_t>(na > 1, slots); more2 = c.take_if<int32_t>(na > 1, slots);
+    }
+};
+
+Opt make_opt(const ddp_ilqg_opts *oo)
+{
+    Opt o;
+    o.lfac = oo->lambda_factor; o.lmax = oo->lambda_max; o.lmin = oo->lambda_min; o.tol_fun = oo->tol_fun;
+    o.tol_grad = oo->tol_grad; o.rrmin = oo->reduce_ratio_min; o.max_iter = oo->max_iter; o.nalpha = oo->n_alpha;
+    for (int i = 0; i < 16; ++i) o.alpha[i] = oo->alpha[i];
+    return o;
+}
+
+// Line search in groups: the reference stops at the first accepted step size (iLQG.jl:267-281); groups [0,1) [1,3) [3,n_alpha) roll
+// the later step sizes out only for the trajectories whose search is still open.  DDP_ILQG_LSGROUPS=0 / 1: never / always.
+// Measured: it pays where the rollouts of all step sizes together are throughput-bound (two waves per SIMD and more) AND the first
+// step size is usually accepted, as in the linear-quadratic family (1 024 n=10 solves with 11 step sizes: 15.7 -> 10.6 ms); the
+// pendulum's line search regularly needs the later ones (B = 32 768: 0.93 vs 0.88 s of rollouts) and its lane-per-rollout
+// launches are latency-bound below that (B = 4 096: 0.083 -> 0.19 s).  Results are the same either way.
+bool line_search_groups(ddp_handle h, const Model &M, size_t na, size_t slots)
+{
+    const char *genv = ddp_env(h, ENV_ILQG_LSGROUPS);
+    const double rpw = M.pw.kind == DDP_PROBLEM_PENDCART ? 64.0 : (M.n <= 16 ? 4.0 : 1.0);      // rollouts per wave of the forward kernels
+    return na > 1 && (genv ? genv[0] == '1' : (M.pw.kind == DDP_PROBLEM_LQ && (double)na * (double)slots / rpw >= 2048.0));
+}
+
+// STEPS 1-3 of one global iteration for the `slots` slots of `ws`, on h->stream: df, the backward pass, post_bp_kernel, and the line
+// search — all step sizes at once, or in groups with the later ones masked by ls_more_kernel.  STEP 4 (accept_kernel) is the
+// caller's: its trace and counter arguments differ.  tev: NULL, or four events recorded around df, backward pass and line search.
+int ilqg_steps(ddp_handle h, const Model &M, const WorkSet &ws, size_t slots, const Deriv &dv, const Cand &cd, const Opt &o, int regType,
+               const double *lims, bool groups, hipEvent_t *tev)
+{
+    hipStream_t st = h->stream;
+    const size_t n = M.n, m = M.m, N = M.N, CL = M.CL, na = o.nalpha;
+    const Traj &s = ws.s;
+    int rc;
+    if (tev) DDP_HIP(hipEventRecord(tev[0], st));
+    if ((rc = M.df(h, (int)slots, ws.map, ws.x, ws.u, s.dodf, dv.fxw, dv.fuw, dv.cx, dv.cu, dv.hxx, dv.hxu, dv.huu))) return rc;     // STEP 1
+    if (tev) DDP_HIP(hipEventRecord(tev[1], st));
+    BPCall bc = {};
+    M.operands(bc, dv, (int)slots);
+    bc.d.regType = regType; bc.d.has_lims = lims != nullptr;
+    bc.lambda = s.lam; bc.lims = lims; bc.u = ws.u; bc.active = s.run;
+    bc.K = ws.K; bc.k = ws.k; bc.Quu = ws.Quu; bc.Vx = ws.Vx; bc.Vxx = ws.Vxx; bc.dV = dv.dV; bc.diverge = dv.div;
+    if ((rc = M.back_pass(h, bc, ws.x, ws.map))) return rc;                                                                          // STEP 2
+    hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)slots), dim3(64), 0, st, (int)m, (int)N, o, dv.div, ws.k, ws.u, s);
+    if (tev) DDP_HIP(hipEventRecord(tev[2], st));
+    const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};                                                  // STEP 3
+    const int32_t *mask = s.dofwd;
+    for (int gi = 0; gi < 3; ++gi) {
+        const size_t a0 = gb[gi], a1 = gb[gi + 1];
+        if (a1 <= a0) continue;
+        if (a0 > 0) {
+            int32_t *mk = (gi == 1) ? cd.more : cd.more2;
+            hipLaunchKernelGGL(ls_more_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (int)slots, (int)a0, o, dv.dV, cd.cs, s,
+                               gi == 1 ? (const int32_t *)nullptr : (const int32_t *)cd.more, mk);
+            mask = mk;
+        }
+        rc = M.rollout(h, (int)slots, ws.map, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask,
+                       cd.xn + n * N * slots * a0, cd.un + m * N * slots * a0, cd.cn + CL * slots * a0, cd.cs + slots * a0);
+        if (rc) return rc;
+    }
+    if (tev) DDP_HIP(hipEventRecord(tev[3], st));
+    return 0;
+}
+
+// The host looks at the number of running trajectories every POLL iterations only: a synchronisation per iteration leaves the GPU idle
+// for a round trip, and iterations launched after the last trajectory has stopped find nothing to do (every wave leaves at once).
+// Each iteration of a group writes its own count (counter[git % POLL]), so `global_iters` stays exact: poll_running reads the `cnt`
+// counts of the group back; *running = the last one, and behind a zero *git goes back to the iteration that wrote it.
+constexpr int POLL = 4;
+int poll_running(ddp_handle h, const int *counter, int cnt, int *git, int *running)
+{
+    DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4 * cnt, hipMemcpyDeviceToHost, h->stream));
+    DDP_HIP(hipStreamSynchronize(h->stream));
+    *running = h->h_pinned[cnt - 1];
+    for (int e = 0; e < cnt; ++e)
+        if (h->h_pinned[e] == 0) { *git -= cnt - 1 - e; *running = 0; break; }     // the iterations after it did nothing
+    return 0;
+}
+
 }   // namespace
 
 extern "C" {
@@ -501,61 +613,41 @@ void ddp_ilqg_default_opts(ddp_ilqg_opts *o)
     for (int i = 0; i < 16; ++i) o->alpha[i] = i < 11 ? pow(10.0, -3.0 * i / 10.0) : 0.0;
 }
 
+// the lock-step batch driver: the registered kind of `p`, or (p == NULL) the family `fam`
 static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo, const double *x0, const double *u0,
                      const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                      double *Vxx, double *cost, double *stats, int trace_cap, double *trace_cost, int *global_iters,
                      bool prerolled, const double *cost0, double *trace7 = nullptr, const ddp_family *fam = nullptr)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && p && x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg: null argument");
+    DDP_CHECK(h && (p || fam) && x0 && u0 && x && u && K && k && Quu && Vx && Vxx && cost && stats, "ilqg: null argument");
     ddp_ilqg_opts od;
     if (!oo) { ddp_ilqg_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->n_alpha >= 1 && oo->n_alpha <= 16, "ilqg: n_alpha=%d out of [1,16]", oo->n_alpha);
     DDP_CHECK(x0 != x && u0 != u, "ilqg: x0/u0 must not alias the outputs x/u (the outputs are cleared before the initial rollout)");
-    const size_t n = p->n, m = p->m, N = p->N, B = p->B, na = oo->n_alpha, CL = fam ? fam->CL : ddp_cost_len(p);
-    const bool pend = p->kind == DDP_PROBLEM_PENDCART;
-    // a user family (fam): time-varying per-trajectory fx, fu like the pendulum, and cost Hessians of its own (per step, or once per
-    // trajectory with const_hessian)
-    const bool own_fx = pend || fam, chess = fam && fam->const_hessian;
+    const Model M(p, fam);
+    const size_t n = M.n, m = M.m, N = M.N, B = M.B, na = oo->n_alpha, CL = M.CL;
 
-    // ---- workspace (device): derivatives, candidates, scalar state
-    size_t bytes = 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t s_cx = al(n * N * B * 8), s_cu = al(m * N * B * 8), s_fx = own_fx ? al(n * n * N * B * 8) : 0,
-                 s_fu = own_fx ? al(n * m * N * B * 8) : 0, hT = chess ? 1 : N, s_hxx = fam ? al(n * n * hT * B * 8) : 0,
-                 s_hxu = fam ? al(n * m * hT * B * 8) : 0, s_huu = fam ? al(m * m * hT * B * 8) : 0, s_xn = al(n * N * B * na * 8), s_un = al(m * N * B * na * 8),
-                 s_cn = al(CL * B * na * 8), s_cs = al(B * na * 8), s_dV = al(2 * B * 8), s_div = al(B * 4),
-                 s_cxu = al(n * m * 8), s_us = al(m * N * B * 8), s_d = al(B * 8), s_i = al(B * 4), s_x0 = al(n * B * 8);
-    bytes = s_cx + s_cu + s_fx + s_fu + s_hxx + s_hxu + s_huu + s_xn + s_un + s_cn + s_cs + s_dV + s_div + s_cxu + s_us + 4 * s_d + 10 * s_i + 256 + s_x0 + 2 * s_i;
+    // ---- workspace (the handle's scratch): derivatives, candidates, scalar state
+    Deriv dv; Cand cd; Traj s;
+    double *us, *x0c;                                    // α·u0 of the initial rollout; first column of a pre-rolled x0
+    int *counter;
+    auto layout = [&](Carver c) {
+        dv.carve(c, M, B); cd.carve(c, M, B, na); us = c.take<double>(m * N * B); s.carve(c, B);
+        counter = c.take<int>(64); x0c = c.take<double>(n * B);
+        return (size_t)c.p;
+    };
     void *base;
-    int rc = ddp_scratch(h, bytes, &base);
+    int rc = ddp_scratch(h, layout(Carver()), &base);
     if (rc) return rc;
-    char *pp = (char *)base;
-    auto take = [&](size_t b) { void *r = pp; pp += b; return r; };
-    double *cx = (double *)take(s_cx), *cu = (double *)take(s_cu), *fxw = own_fx ? (double *)take(s_fx) : nullptr,
-           *fuw = own_fx ? (double *)take(s_fu) : nullptr, *hxx = fam ? (double *)take(s_hxx) : nullptr,
-           *hxu = fam ? (double *)take(s_hxu) : nullptr, *huu = fam ? (double *)take(s_huu) : nullptr, *xn = (double *)take(s_xn), *un = (double *)take(s_un),
-           *cn = (double *)take(s_cn), *cs = (double *)take(s_cs), *dV = (double *)take(s_dV);
-    int32_t *div = (int32_t *)take(s_div);
-    double *cxu = (double *)take(s_cxu), *us = (double *)take(s_us);
-    Traj s;
-    s.lam = (double *)take(s_d); s.dlam = (double *)take(s_d); s.gnorm = (double *)take(s_d); s.csum = (double *)take(s_d);
-    s.status = (int32_t *)take(s_i); s.iter = (int32_t *)take(s_i); s.acc = (int32_t *)take(s_i); s.nbp = (int32_t *)take(s_i);
-    s.nfp = (int32_t *)take(s_i); s.flg = (int32_t *)take(s_i); s.run = (int32_t *)take(s_i); s.dodf = (int32_t *)take(s_i);
-    s.dofwd = (int32_t *)take(s_i); s.div0 = (int32_t *)take(s_i);
-    int *counter = (int *)take(256);
-    double *x0c = (double *)take(s_x0);                  // first column of a pre-rolled x0
+    layout(Carver(base));
     DDP_CHECK(h->h_pinned, "ilqg: pinned poll buffer missing");
-
-    Opt o;
-    o.lfac = oo->lambda_factor; o.lmax = oo->lambda_max; o.lmin = oo->lambda_min; o.tol_fun = oo->tol_fun;
-    o.tol_grad = oo->tol_grad; o.rrmin = oo->reduce_ratio_min; o.max_iter = oo->max_iter; o.nalpha = (int)na;
-    for (int i = 0; i < 16; ++i) o.alpha[i] = oo->alpha[i];
+    const Opt o = make_opt(oo);
 
     hipStream_t st = h->stream;
     const unsigned gB = (unsigned)((B + 255) / 256);
     hipLaunchKernelGGL(init_state_kernel, dim3(gB), dim3(256), 0, st, (int)B, oo->lambda, oo->dlambda, s);
-    DDP_HIP(hipMemsetAsync(cxu, 0, n * m * 8, st));
+    DDP_HIP(hipMemsetAsync(dv.cxu, 0, n * m * 8, st));
     DDP_HIP(hipMemsetAsync(K, 0, m * n * N * B * 8, st));
     DDP_HIP(hipMemsetAsync(k, 0, m * N * B * 8, st));
     DDP_HIP(hipMemsetAsync(Quu, 0, m * m * N * B * 8, st));
@@ -572,23 +664,17 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     if (prerolled) {                                     // iLQG.jl:193-197: x = x0, cost given or costfun(x, u); no divergence test
         hipLaunchKernelGGL(preroll_init_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, x0, u0, cost0, s,
                            x, u, cost, x0c);
-        if (!cost0 && fam) {
-            rc = fam->costfun(h, (int)B, nullptr, x, u, nullptr, cost, s.csum);
-            if (rc) return rc;
-        } else if (!cost0)
-            hipLaunchKernelGGL(costfun_kernel, dim3((unsigned)B), dim3(64), 0, st, p->kind, (int)n, (int)m, (int)N, (int)CL, p->Q, p->R,
-                               p->goal[0], p->goal[1], p->goal[2], p->goal[3], x, u, (const int32_t *)nullptr, cost, s.csum);
+        if (!cost0 && (rc = M.costfun(h, (int)B, nullptr, x, u, nullptr, cost, s.csum))) return rc;
         x0 = x0c;
     }
     for (size_t ai = 0; !prerolled && ai < na; ++ai) {
         const size_t tot = m * N * B;
         hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m * N, (int)B, oo->alpha[ai], u0,
                            s.div0, us);
-        rc = fam ? fam->rollout(h, (int)B, nullptr, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, xn, un, cn, cs)
-                 : ddp_forward_pass_f64_dev(h, p, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, xn, un, cn, cs);
+        rc = M.rollout(h, (int)B, nullptr, nullptr, nullptr, x0, us, nullptr, &one, 1, lims, s.div0, cd.xn, cd.un, cd.cn, cd.cs);
         if (rc) return rc;
-        hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, xn, un, cn, cs, s,
-                           x, u, cost);
+        hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, cd.xn, cd.un, cd.cn,
+                           cd.cs, s, x, u, cost);
         // most batches are done after the first α; poll only if there are more candidates to try
         if (ai + 1 < na) {
             DDP_HIP(hipMemsetAsync(counter, 0, 4, st));
@@ -604,22 +690,13 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     DDP_HIP(hipStreamSynchronize(st));
     int running = h->h_pinned[0];
 
-    ddp_bp_desc d;
-    d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B;
-    d.fx_tv = own_fx ? 1 : p->dyn_tv; d.fx_batched = own_fx ? 1 : p->dyn_batched;
-    d.cost_tv = (fam && !chess) ? 1 : 0; d.cost_batched = fam ? 1 : 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
-    const double *fx = own_fx ? fxw : p->A, *fu = own_fx ? fuw : p->Bm;
-    const double *cxx = fam ? hxx : p->Q, *cxu_ = fam ? hxu : cxu, *cuu = fam ? huu : p->R;
-    if (chess) {                                           // the constant cost Hessians: once per trajectory (again after a compaction)
-        rc = fam->hessians(h, (int)B, nullptr, nullptr, hxx, hxu, huu);
-        if (rc) return rc;
-    }
+    // the constant cost Hessians: once per trajectory (again after a compaction)
+    if ((rc = M.hessians(h, (int)B, nullptr, nullptr, dv.hxx, dv.hxu, dv.huu))) return rc;
 
     // ---- the working set: the caller's arrays until the first compaction
     WorkSet user = {x, u, cost, K, k, Quu, Vx, Vxx, const_cast<double *>(x0), s, nullptr};
     WorkSet ws = user;
-    ddp_problem pw = *p;                                   // the problem as the kernels see it (B = slots of the working set)
-    size_t Bw = B;
+    size_t Bw = B;                                         // slots of the working set
     std::vector<void *> owned;                             // compacted working sets (freed on every way out)
     ClockScope clock_scope(fam);                           // a compaction points the family's clock at the compacted copy
     struct Free { std::vector<void *> &v; ~Free() { for (void *q : v) hipFree(q); } } free_owned{owned};
@@ -632,25 +709,15 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
     //    (C3: mean 59 iterations per solve, 264 for the slowest).  Once half of the slots have stopped the live ones move to a
     //    smaller working set.  Not for per-trajectory dynamics (their operands would have to move as well).
     //    DDP_ILQG_COMPACT=0: never;  =k (k > 1): whenever a working set of >= k slots is half empty.
-    //  * line search in groups: the reference stops at the first accepted step size (iLQG.jl:267-281); groups [0,1) [1,3) [3,n_alpha)
-    //    roll the later step sizes out only for the trajectories whose search is still open.  DDP_ILQG_LSGROUPS=0 / 1: never / always.
+    //  * line search in groups: line_search_groups, decided once for the caller's batch.
     const char *cenv = ddp_env(h, ENV_ILQG_COMPACT);
-    bool may_compact = !(cenv && cenv[0] == '0') && !(p->kind == DDP_PROBLEM_LQ && p->dyn_batched);
+    bool may_compact = !(cenv && cenv[0] == '0') && !(M.pw.kind == DDP_PROBLEM_LQ && M.pw.dyn_batched);
     // trajectories per wave of the backward kernel the dispatcher picks (back_pass.hip) -> slots that make two waves per SIMD
     const double tpw = (n == 4 && m == 1) ? 4.0 : (n == 10 && m == 2) ? (B < 5120 ? 1.0 : 4.0) : (n > DDP_MAX_N_GENERIC ? 0.25 : 1.0);
     const size_t min_slots = (cenv && atoi(cenv) > 1) ? (size_t)atoi(cenv) : (size_t)(2048.0 * tpw);
-    const char *genv = ddp_env(h, ENV_ILQG_LSGROUPS);
-    const double rpw = pend ? 64.0 : (n <= 16 ? 4.0 : 1.0);                       // rollouts per wave of the forward kernels
-    // Measured: it pays where the rollouts of all step sizes together are throughput-bound (two waves per SIMD and more) AND the first
-    // step size is usually accepted, as in the linear-quadratic family (1 024 n=10 solves with 11 step sizes: 15.7 -> 10.6 ms); the
-    // pendulum's line search regularly needs the later ones (B = 32 768: 0.93 vs 0.88 s of rollouts) and its lane-per-rollout
-    // launches are latency-bound below that (B = 4 096: 0.083 -> 0.19 s).  Results are the same either way.
-    const bool groups = na > 1 && (genv ? genv[0] == '1' : (p->kind == DDP_PROBLEM_LQ && (double)na * (double)B / rpw >= 2048.0));
-    int32_t *more = (int32_t *)take(0);                    // two masks of B int32 were reserved behind x0c (see `bytes`)
-    int32_t *more2 = more + B;
+    const bool groups = line_search_groups(h, M, na, B);
 
     int git = 0;
-    constexpr int POLL = 4;
     const long hard_cap = 4L * oo->max_iter + 1000;      // every global iteration advances iter or λ of each running trajectory
     // ddp_ilqg_set_timing: the time_derivs / time_backward / time_forward keys of the reference's trace (iLQG.jl:227,241,281)
     // per global iteration, from HIP events on the stream (the loop synchronises once per iteration anyway)
@@ -668,95 +735,43 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
             // ---- drop the finished slots.  Compaction is an optimisation: the block is allocated BEFORE anything is written to the
             // caller's arrays, and a failed allocation (a memory-tight batch) only switches compaction off for the rest of the solve.
             const size_t R = (size_t)running;
-            const size_t w_d = al(n * N * R * 8) + al(m * N * R * 8) + al(CL * R * 8) + al(m * n * N * R * 8) + al(m * N * R * 8) +
-                               al(m * m * N * R * 8) + al(n * N * R * 8) + al(n * n * N * R * 8) + al(n * R * 8) + 4 * al(R * 8) + 12 * al(R * 4) +
-                               al(Bw * 4) + 256 + (fam && fam->clk ? al(R * 4) : 0);
+            const int32_t *clk_old = fam ? fam->clk : nullptr;      // a family with a clock: it moves with its trajectory
+            WorkSet nw;
+            int32_t *idx, *clk_new;
+            auto compacted = [&](Carver c) {
+                carve_workset(c, nw, M, R); nw.map = c.take<int32_t>(R); idx = c.take<int32_t>(Bw);
+                clk_new = c.take_if<int32_t>(clk_old != nullptr, R);
+                return (size_t)c.p;
+            };
             void *blk = nullptr;
-            if (ddp_env(h, ENV_TEST_COMPACT_ALLOC_FAIL) || hipMalloc(&blk, w_d) != hipSuccess) {      // (the variable: tests of this path)
+            if (ddp_env(h, ENV_TEST_COMPACT_ALLOC_FAIL) || hipMalloc(&blk, compacted(Carver())) != hipSuccess) {      // (the variable: tests of this path)
                 (void)hipGetLastError();                         // clear the sticky error: the solve goes on with the current working set
                 may_compact = false;
                 continue;
             }
             owned.push_back(blk);
+            compacted(Carver(blk));
             // their summary and (from a compacted set) their results go to the caller's arrays first
             launch_stats(1);
             if (ws.map) hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, 0, ws, user);
-            char *q = (char *)blk;
-            auto tk = [&](size_t b_) { void *r_ = q; q += al(b_); return r_; };
-            WorkSet nw;
-            nw.x = (double *)tk(n * N * R * 8); nw.u = (double *)tk(m * N * R * 8); nw.cost = (double *)tk(CL * R * 8);
-            nw.K = (double *)tk(m * n * N * R * 8); nw.k = (double *)tk(m * N * R * 8); nw.Quu = (double *)tk(m * m * N * R * 8);
-            nw.Vx = (double *)tk(n * N * R * 8); nw.Vxx = (double *)tk(n * n * N * R * 8); nw.x0 = (double *)tk(n * R * 8);
-            nw.s.lam = (double *)tk(R * 8); nw.s.dlam = (double *)tk(R * 8); nw.s.gnorm = (double *)tk(R * 8); nw.s.csum = (double *)tk(R * 8);
-            nw.s.status = (int32_t *)tk(R * 4); nw.s.iter = (int32_t *)tk(R * 4); nw.s.acc = (int32_t *)tk(R * 4); nw.s.nbp = (int32_t *)tk(R * 4);
-            nw.s.nfp = (int32_t *)tk(R * 4); nw.s.flg = (int32_t *)tk(R * 4); nw.s.run = (int32_t *)tk(R * 4); nw.s.dodf = (int32_t *)tk(R * 4);
-            nw.s.dofwd = (int32_t *)tk(R * 4); nw.s.div0 = (int32_t *)tk(R * 4);
-            nw.map = (int32_t *)tk(R * 4);
-            int32_t *idx = (int32_t *)tk(Bw * 4);
-            const int32_t *clk_old = fam ? fam->clk : nullptr;
-            int32_t *clk_new = clk_old ? (int32_t *)tk(R * 4) : nullptr;
             hipLaunchKernelGGL(live_index_kernel, dim3(1), dim3(64), 0, st, (int)Bw, ws.s, idx, counter);
             hipLaunchKernelGGL(gather_kernel, dim3((unsigned)R), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)CL, idx, ws, nw, clk_old, clk_new);
             if (clk_new) fam->clk = clk_new;
             ws = nw;
             Bw = R;
-            pw.B = (int)R; d.B = (int)R;
-            if (chess) {
-                rc = fam->hessians(h, (int)R, ws.map, nullptr, hxx, hxu, huu);
-                if (rc) return rc;
-            }
+            if ((rc = M.hessians(h, (int)R, ws.map, nullptr, dv.hxx, dv.hxu, dv.huu))) return rc;
         }
         polled = false;
-        if (timed) DDP_HIP(hipEventRecord(h->tev[0], st));
-        rc = fam ? fam->df(h, (int)Bw, ws.map, ws.x, ws.u, ws.s.dodf, fxw, fuw, cx, cu, chess ? nullptr : hxx, chess ? nullptr : hxu,
-                           chess ? nullptr : huu)
-                 : ddp_df_f64_dev(h, &pw, ws.x, ws.u, ws.s.dodf, cx, cu, fxw, fuw);                              // STEP 1
+        rc = ilqg_steps(h, M, ws, Bw, dv, cd, o, oo->regType, lims, groups, timed ? h->tev : nullptr);       // STEPS 1-3
         if (rc) return rc;
-        if (timed) DDP_HIP(hipEventRecord(h->tev[1], st));
-        {
-            BPCall bc = {d, cx, cu, cxx, cxu_, cuu, fx, fu, ws.s.lam, lims, ws.u, ws.s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div};
-            if (fam && fam->second_order) { bc.x = ws.x; bc.map = ws.map; rc = fam->back_pass(h, bc); }
-            else rc = ddp_launch_back_pass(h, bc);                                                               // STEP 2
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, ws.s);
-        if (timed) DDP_HIP(hipEventRecord(h->tev[2], st));
-        // STEP 3: all step sizes at once, or in groups with the later ones masked by `more`
-        const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};
-        const int32_t *mask = ws.s.dofwd;
-        for (int gi = 0; gi < 3; ++gi) {
-            const size_t a0 = gb[gi], a1 = gb[gi + 1];
-            if (a1 <= a0) continue;
-            if (a0 > 0) {
-                int32_t *mk = (gi == 1) ? more : more2;
-                hipLaunchKernelGGL(ls_more_kernel, dim3((unsigned)((Bw + 255) / 256)), dim3(256), 0, st, (int)Bw, (int)a0, o, dV, cs, ws.s,
-                                   gi == 1 ? (const int32_t *)nullptr : (const int32_t *)more, mk);
-                mask = mk;
-            }
-            rc = fam ? fam->rollout(h, (int)Bw, ws.map, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask,
-                                    xn + n * N * Bw * a0, un + m * N * Bw * a0, cn + CL * Bw * a0, cs + Bw * a0)
-                     : ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask,
-                                                xn + n * N * Bw * a0, un + m * N * Bw * a0, cn + CL * Bw * a0, cs + Bw * a0);
-            if (rc) return rc;
-        }
-        if (timed) DDP_HIP(hipEventRecord(h->tev[3], st));
-        // The host looks at the number of running trajectories every POLL iterations only (every iteration while the per-iteration
-        // timing keys are recorded): a synchronisation per iteration leaves the GPU idle for a round trip, and iterations launched
-        // after the last trajectory has stopped find nothing to do (every wave leaves at once).  Each iteration of a group writes
-        // its own count, so `global_iters` stays exact.
         const int slot = git % POLL;
         DDP_HIP(hipMemsetAsync(counter + slot, 0, 4, st));
-        hipLaunchKernelGGL(accept_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)Bw, (int)CL, o, dV, xn,
-                           un, cn, cs, ws.s, ws.x, ws.u, ws.cost, ws.k, trace_cap, trace_cost, trace7, ws.map, counter + slot);    // STEP 4
+        hipLaunchKernelGGL(accept_kernel, dim3((unsigned)Bw), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)Bw, (int)CL, o, dv.dV, cd.xn,
+                           cd.un, cd.cn, cd.cs, ws.s, ws.x, ws.u, ws.cost, ws.k, trace_cap, trace_cost, trace7, ws.map, counter + slot);    // STEP 4
         ++git;
-        if (timed || slot == POLL - 1 || git >= hard_cap) {
-            const int cnt = slot + 1;
-            DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4 * cnt, hipMemcpyDeviceToHost, st));
-            DDP_HIP(hipStreamSynchronize(st));
-            running = h->h_pinned[cnt - 1];
+        if (timed || slot == POLL - 1 || git >= hard_cap) {      // every iteration while the per-iteration timing keys are recorded
+            if ((rc = poll_running(h, counter, slot + 1, &git, &running))) return rc;
             polled = true;
-            for (int e2 = 0; e2 < cnt; ++e2)
-                if (h->h_pinned[e2] == 0) { git -= cnt - 1 - e2; running = 0; break; }     // the iterations after it did nothing
             if (timed && git - 1 < h->timing_cap) {
                 for (int e = 0; e < 3; ++e) {
                     float ms = 0.0f;
@@ -776,15 +791,13 @@ static int ilqg_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo
 
 }   // extern "C"
 
-// the same loop for a family of ddp_family (user_problem.hip): a problem struct that carries the sizes only
+// the same loop for a family of ddp_family (user_problem.hip)
 int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *oo, const double *x0, int x0_prerolled, const double *u0,
                         const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                         double *Vxx, double *cost, double *stats, int trace_cap, double *trace7, int *global_iters)
 {
     DDP_CHECK(f, "ilqg: null family");
-    ddp_problem pf = {};
-    pf.kind = -1; pf.n = f->n; pf.m = f->m; pf.N = f->N; pf.B = f->B;
-    return ilqg_impl(h, &pf, oo, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, nullptr, global_iters, x0_prerolled != 0,
+    return ilqg_impl(h, nullptr, oo, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, trace_cap, nullptr, global_iters, x0_prerolled != 0,
                      x0_prerolled ? cost0 : nullptr, trace7, f);
 }
 
@@ -805,81 +818,60 @@ int ddp_ilqg_warm_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opt
 }
 
 // ---- the slot scheduler (kernels above).  S slots, P problems (queue: P >= S; MPC: S == P, `steps` solves per trajectory).
-// fam: a user family (ddp_ilqg_sched_family_dev) in place of the registered kind of `p`, as in ilqg_impl; every family call reads the
-// parameters of a slot's problem through the slot map.
+// p == NULL: the user family `fam` (ddp_ilqg_sched_family_dev) in place of a registered kind, as in ilqg_impl; every family call reads
+// the parameters of a slot's problem through the slot map.
 static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_opts *oo, int slots, int mpc_steps, int zero_tail,
                            const double *x0, const double *u0, const double *lims, double *x, double *u, double *K, double *k,
                            double *Quu, double *Vx, double *Vxx, double *cost, double *stats, double *xcl, double *ucl,
                            double *stats_cl, int *global_iters, const ddp_family *fam = nullptr)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && p && x0 && u0 && x && u, "ilqg_sched: null argument");
+    DDP_CHECK(h && (p || fam) && x0 && u0 && x && u, "ilqg_sched: null argument");
     ddp_ilqg_opts od;
     if (!oo) { ddp_ilqg_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->n_alpha >= 1 && oo->n_alpha <= 16, "ilqg_sched: n_alpha=%d out of [1,16]", oo->n_alpha);
-    const size_t n = p->n, m = p->m, N = p->N, P = p->B, na = oo->n_alpha, CL = fam ? fam->CL : ddp_cost_len(p);
-    const bool pend = p->kind == DDP_PROBLEM_PENDCART, mpc = mpc_steps > 0;
-    // a user family: own time-varying fx, fu and cost Hessians (per step, or one set per slot with const_hessian), as in ilqg_impl
-    const bool own_fx = pend || fam, chess = fam && fam->const_hessian, plant = mpc && fam && fam->has_plant, clocked = fam && fam->t0;
+    const Model M(p, fam);
+    const size_t n = M.n, m = M.m, N = M.N, P = M.B, na = oo->n_alpha, CL = M.CL;
+    const bool mpc = mpc_steps > 0, plant = mpc && M.has_plant;
     DDP_CHECK(N >= 2, "ilqg_sched: N=%d (at least two time steps)", (int)N);
     if (mpc) slots = (int)P;                                            // every trajectory keeps its slot
     if (slots <= 0 || (size_t)slots > P) slots = (int)(P < 4096 ? P : 4096);
     const size_t S = (size_t)slots;
-    DDP_CHECK(!(p->kind == DDP_PROBLEM_LQ && p->dyn_batched) || mpc, "ilqg_queue: per-trajectory dynamics (dyn_batched) are not supported by the queue");
+    DDP_CHECK(!(M.pw.kind == DDP_PROBLEM_LQ && M.pw.dyn_batched) || mpc, "ilqg_queue: per-trajectory dynamics (dyn_batched) are not supported by the queue");
     DDP_CHECK(mpc ? (xcl && ucl && stats_cl) : (K && k && Quu && Vx && Vxx && cost && stats), "ilqg_sched: null output");
 
-    // ---- one block: working set of S slots, derivative / candidate workspace, scheduler state
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t f_x = al(n * N * S * 8), f_u = al(m * N * S * 8), f_c = al(CL * S * 8), f_K = al(m * n * N * S * 8), f_Q = al(m * m * N * S * 8),
-                 f_V = al(n * n * N * S * 8), f_fx = own_fx ? al(n * n * N * S * 8) : 0, f_fu = own_fx ? al(n * m * N * S * 8) : 0,
-                 hT = chess ? 1 : N, f_hxx = fam ? al(n * n * hT * S * 8) : 0, f_hxu = fam ? al(n * m * hT * S * 8) : 0,
-                 f_huu = fam ? al(m * m * hT * S * 8) : 0, f_d = al(S * 8), f_i = al(S * 4);
-    const size_t bytes = 2 * f_x /* x, Vx */ + 2 * f_u /* u, k */ + f_c + f_K + f_Q + f_V + al(n * S * 8) /* x0s */ + 2 * f_u /* u0s, us */ +
-                         f_x + f_u /* cx, cu */ + f_fx + f_fu + na * (f_x + f_u + f_c + f_d) /* candidates */ + (f_x + f_u + f_c + f_d) /* initial rollout */ +
-                         al(2 * S * 8) + f_i /* dV, div */ + al(n * m * 8) + 4 * f_d + 10 * f_i /* Traj */ + 6 * f_i /* scheduler */ + 2 * f_i /* more */ + 512 +
-                         f_hxx + f_hxu + f_huu + (plant ? 2 * f_i : 0) /* adv, advp */ + (clocked ? f_i : 0) /* clk */;
+    // ---- one block of the scheduler's own: working set of S slots, derivative / candidate workspace, scheduler state
+    WorkSet ws;
+    Deriv dv;
+    Cand cd, ini;                                                       // the line search; the initial rollout of the armed slots (one step size)
+    Sched q;
+    int *counter;
+    auto layout = [&](Carver c) {
+        carve_workset(c, ws, M, S);
+        q.u0s = c.take<double>(m * N * S); q.us = c.take<double>(m * N * S);
+        dv.carve(c, M, S); cd.carve(c, M, S, na); ini.carve(c, M, S, 1);
+        for (int32_t **i : {&q.initm, &q.ai, &q.map, &q.left, &q.noflush, &q.ready}) *i = c.take<int32_t>(S);
+        counter = c.take<int>(64); q.qhead = c.take<int>(64);
+        q.adv = c.take_if<int32_t>(plant, S); q.advp = c.take_if<int32_t>(plant, S);
+        q.clk = c.take_if<int32_t>(M.clocked, S);
+        return (size_t)c.p;
+    };
+    const size_t bytes = layout(Carver());
     void *blk = nullptr;
     DDP_HIP(hipMalloc(&blk, bytes));
     struct Free { void *q; ~Free() { hipFree(q); } } free_blk{blk};
-    char *pp = (char *)blk;
-    auto take = [&](size_t b) { void *r = pp; pp += b; return r; };
-    WorkSet ws;
-    ws.x = (double *)take(f_x); ws.Vx = (double *)take(f_x); ws.u = (double *)take(f_u); ws.k = (double *)take(f_u); ws.cost = (double *)take(f_c);
-    ws.K = (double *)take(f_K); ws.Quu = (double *)take(f_Q); ws.Vxx = (double *)take(f_V); ws.x0 = (double *)take(al(n * S * 8));
-    double *u0s = (double *)take(f_u), *us = (double *)take(f_u);
-    double *cx = (double *)take(f_x), *cu = (double *)take(f_u), *fxw = own_fx ? (double *)take(f_fx) : nullptr, *fuw = own_fx ? (double *)take(f_fu) : nullptr;
-    double *hxx = fam ? (double *)take(f_hxx) : nullptr, *hxu = fam ? (double *)take(f_hxu) : nullptr, *huu = fam ? (double *)take(f_huu) : nullptr;
-    double *xn = (double *)take(na * f_x), *un = (double *)take(na * f_u), *cn = (double *)take(na * f_c), *cs = (double *)take(na * f_d);
-    double *xi = (double *)take(f_x), *ui = (double *)take(f_u), *ci = (double *)take(f_c), *csi = (double *)take(f_d);
-    double *dV = (double *)take(al(2 * S * 8));
-    int32_t *div = (int32_t *)take(f_i);
-    double *cxu = (double *)take(al(n * m * 8));
+    layout(Carver(blk));
     Traj &s = ws.s;
-    s.lam = (double *)take(f_d); s.dlam = (double *)take(f_d); s.gnorm = (double *)take(f_d); s.csum = (double *)take(f_d);
-    s.status = (int32_t *)take(f_i); s.iter = (int32_t *)take(f_i); s.acc = (int32_t *)take(f_i); s.nbp = (int32_t *)take(f_i);
-    s.nfp = (int32_t *)take(f_i); s.flg = (int32_t *)take(f_i); s.run = (int32_t *)take(f_i); s.dodf = (int32_t *)take(f_i);
-    s.dofwd = (int32_t *)take(f_i); s.div0 = (int32_t *)take(f_i);
-    Sched q;
     q.P = (int)P; q.mpc_steps = mpc_steps; q.zero_tail = zero_tail; q.nalpha = (int)na; q.max_iter = oo->max_iter;
     for (int i = 0; i < 16; ++i) q.alpha[i] = oo->alpha[i];
-    q.lam0 = oo->lambda; q.dlam0 = oo->dlambda; q.x0g = x0; q.u0g = u0; q.u0s = u0s; q.us = us; q.x0s = ws.x0;
-    q.initm = (int32_t *)take(f_i); q.ai = (int32_t *)take(f_i); q.map = (int32_t *)take(f_i); q.left = (int32_t *)take(f_i);
-    q.noflush = (int32_t *)take(f_i); q.ready = (int32_t *)take(f_i);
-    int32_t *more = (int32_t *)take(f_i), *more2 = (int32_t *)take(f_i);
-    int *counter = (int *)take(256);
-    q.qhead = (int *)take(256);
+    q.lam0 = oo->lambda; q.dlam0 = oo->dlambda; q.x0g = x0; q.u0g = u0; q.x0s = ws.x0;
     q.x = x; q.u = u; q.cost = cost; q.K = K; q.k = k; q.Quu = Quu; q.Vx = Vx; q.Vxx = Vxx; q.stats = stats; q.xcl = xcl; q.ucl = ucl; q.stats_cl = stats_cl;
-    q.adv = plant ? (int32_t *)take(f_i) : nullptr; q.advp = plant ? (int32_t *)take(f_i) : nullptr;
-    q.clk = clocked ? (int32_t *)take(f_i) : nullptr; q.t0 = clocked ? fam->t0 : nullptr;
+    q.t0 = M.clocked ? fam->t0 : nullptr;
     ClockScope clock_scope(fam);
-    if (clocked) fam->clk = q.clk;                                     // the family's kernels read the clock of the slot they work on
+    if (M.clocked) fam->clk = q.clk;                                   // the family's kernels read the clock of the slot they work on
     ws.map = q.map;
     DDP_CHECK(h->h_pinned, "ilqg_sched: pinned poll buffer missing");
-
-    Opt o;
-    o.lfac = oo->lambda_factor; o.lmax = oo->lambda_max; o.lmin = oo->lambda_min; o.tol_fun = oo->tol_fun;
-    o.tol_grad = oo->tol_grad; o.rrmin = oo->reduce_ratio_min; o.max_iter = oo->max_iter; o.nalpha = (int)na;
-    for (int i = 0; i < 16; ++i) o.alpha[i] = oo->alpha[i];
+    const Opt o = make_opt(oo);
 
     hipStream_t st = h->stream;
     if (!h->sched_aux) {
@@ -887,7 +879,7 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
         for (int e = 0; e < 2; ++e) DDP_HIP(hipEventCreateWithFlags(&h->sched_ev[e], hipEventDisableTiming));
     }
     // slots start empty: nothing runs, nothing to flush (map = -1); the working set is finite from the start (the line-search launches
-    // touch every slot's operands only under their masks, but a masked wave may still prefetch)
+    // touch every slot's operands only under their masks, but a masked wave may still prefetch); the zero cxu of the registered kinds
     DDP_HIP(hipMemsetAsync(blk, 0, bytes, st));
     DDP_HIP(hipMemsetAsync(q.map, 0xff, S * 4, st));
     // outputs of problems that never produce any (initial divergence) are zero, like the arrays ilqg_impl clears
@@ -902,23 +894,11 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
     DDP_HIP(hipMemsetAsync(x, 0, n * N * P * 8, st));
     DDP_HIP(hipMemsetAsync(u, 0, m * N * P * 8, st));
 
-    ddp_problem pw = *p;
-    pw.B = (int)S;
-    ddp_bp_desc d;
-    d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)S;
-    d.fx_tv = own_fx ? 1 : p->dyn_tv; d.fx_batched = own_fx ? 1 : p->dyn_batched;
-    d.cost_tv = (fam && !chess) ? 1 : 0; d.cost_batched = fam ? 1 : 0; d.regType = oo->regType; d.has_lims = lims != nullptr;
-    const double *fx = own_fx ? fxw : p->A, *fu = own_fx ? fuw : p->Bm;
-    const double *cxx = fam ? hxx : p->Q, *cxu_ = fam ? hxu : cxu, *cuu = fam ? huu : p->R;
-    // the line search in the groups ilqg_impl uses at this batch size (same launches -> same kernels -> same bits per solve)
-    const char *genv = ddp_env(h, ENV_ILQG_LSGROUPS);
-    const double rpw = pend ? 64.0 : (n <= 16 ? 4.0 : 1.0);
-    const bool groups = na > 1 && (genv ? genv[0] == '1' : (p->kind == DDP_PROBLEM_LQ && (double)na * (double)S / rpw >= 2048.0));
+    const bool groups = line_search_groups(h, M, na, S);              // the groups ilqg_impl uses at this batch size
     const double one = 1.0;
 
     hipLaunchKernelGGL(sched_take_kernel, dim3((unsigned)S), dim3(TAKE_T), 0, st, (int)n, (int)m, (int)N, (int)CL, q, ws, counter);      // initial fill
     int git = 0, running = (int)S;
-    constexpr int POLL = 4;
     const long hard_cap = ((long)(mpc ? mpc_steps : (P + S - 1) / S) + 1) * (4L * oo->max_iter + 1000 + na);
     int rc = 0;
     while (running > 0 && git < hard_cap) {
@@ -929,61 +909,28 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
         DDP_HIP(hipStreamWaitEvent(h->sched_aux, h->sched_ev[0], 0));
         h->stream = h->sched_aux;
         // const_hessian: the Hessians of the problem an armed slot has just taken, before it joins (the running slots keep theirs)
-        if (chess) rc = fam->hessians(h, (int)S, q.map, q.initm, hxx, hxu, huu);
-        if (!rc)
-            rc = fam ? fam->rollout(h, (int)S, q.map, nullptr, nullptr, ws.x0, us, nullptr, &one, 1, lims, q.initm, xi, ui, ci, csi)
-                     : ddp_forward_pass_f64_dev(h, &pw, nullptr, nullptr, ws.x0, us, nullptr, &one, 1, lims, q.initm, xi, ui, ci, csi);
+        rc = M.hessians(h, (int)S, q.map, q.initm, dv.hxx, dv.hxu, dv.huu);
+        if (!rc) rc = M.rollout(h, (int)S, q.map, nullptr, nullptr, ws.x0, q.us, nullptr, &one, 1, lims, q.initm, ini.xn, ini.un, ini.cn, ini.cs);
         h->stream = st;
         if (rc) return rc;
-        hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)S), dim3(64), 0, h->sched_aux, (int)n, (int)m, (int)N, (int)CL, xi, ui, ci, csi, s, ws.x, ws.u, ws.cost);
+        hipLaunchKernelGGL(init_check_kernel, dim3((unsigned)S), dim3(64), 0, h->sched_aux, (int)n, (int)m, (int)N, (int)CL, ini.xn, ini.un,
+                           ini.cn, ini.cs, s, ws.x, ws.u, ws.cost);
         hipLaunchKernelGGL(sched_init_advance_kernel, dim3((unsigned)S), dim3(64), 0, h->sched_aux, (int)m, (int)N, q, s);
         DDP_HIP(hipEventRecord(h->sched_ev[1], h->sched_aux));
-        rc = fam ? fam->df(h, (int)S, q.map, ws.x, ws.u, s.dodf, fxw, fuw, cx, cu, chess ? nullptr : hxx, chess ? nullptr : hxu,
-                           chess ? nullptr : huu)
-                 : ddp_df_f64_dev(h, &pw, ws.x, ws.u, s.dodf, cx, cu, fxw, fuw);                                 // STEP 1
-        if (rc) return rc;
-        {
-            BPCall bc = {d, cx, cu, cxx, cxu_, cuu, fx, fu, s.lam, lims, ws.u, s.run, ws.K, ws.k, ws.Quu, ws.Vx, ws.Vxx, dV, div};
-            if (fam && fam->second_order) { bc.x = ws.x; bc.map = q.map; rc = fam->back_pass(h, bc); }
-            else rc = ddp_launch_back_pass(h, bc);                                                               // STEP 2
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL(post_bp_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)m, (int)N, o, div, ws.k, ws.u, s);
-        const size_t gb[4] = {0, groups ? 1 : na, groups ? (na < 3 ? na : 3) : na, na};                         // STEP 3
-        const int32_t *mask = s.dofwd;
-        for (int gi = 0; gi < 3; ++gi) {
-            const size_t a0 = gb[gi], a1 = gb[gi + 1];
-            if (a1 <= a0) continue;
-            if (a0 > 0) {
-                int32_t *mk = (gi == 1) ? more : more2;
-                hipLaunchKernelGGL(ls_more_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, (int)S, (int)a0, o, dV, cs, s,
-                                   gi == 1 ? (const int32_t *)nullptr : (const int32_t *)more, mk);
-                mask = mk;
-            }
-            rc = fam ? fam->rollout(h, (int)S, q.map, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * S * a0,
-                                    un + m * N * S * a0, cn + CL * S * a0, cs + S * a0)
-                     : ddp_forward_pass_f64_dev(h, &pw, ws.K, ws.k, ws.x0, ws.u, ws.x, o.alpha + a0, (int)(a1 - a0), lims, mask, xn + n * N * S * a0,
-                                                un + m * N * S * a0, cn + CL * S * a0, cs + S * a0);
-            if (rc) return rc;
-        }
+        if ((rc = ilqg_steps(h, M, ws, S, dv, cd, o, oo->regType, lims, groups, nullptr))) return rc;             // STEPS 1-3 of the running slots
+        // STEP 4 without trace; what it counts is not read (sched_take_kernel counts the busy slots)
         const int slot = git % POLL;
         DDP_HIP(hipMemsetAsync(counter + slot, 0, 4, st));
-        hipLaunchKernelGGL(accept_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)S, (int)CL, o, dV, xn, un, cn, cs, s,
-                           ws.x, ws.u, ws.cost, ws.k, 0, (double *)nullptr, (double *)nullptr, (const int32_t *)nullptr, counter + 32);      // STEP 4
+        hipLaunchKernelGGL(accept_kernel, dim3((unsigned)S), dim3(64), 0, st, (int)n, (int)m, (int)N, (int)S, (int)CL, o, dv.dV, cd.xn, cd.un,
+                           cd.cn, cd.cs, s, ws.x, ws.u, ws.cost, ws.k, 0, (double *)nullptr, (double *)nullptr, (const int32_t *)nullptr, counter + 32);
         DDP_HIP(hipStreamWaitEvent(st, h->sched_ev[1], 0));
         hipLaunchKernelGGL(sched_take_kernel, dim3((unsigned)S), dim3(TAKE_T), 0, st, (int)n, (int)m, (int)N, (int)CL, q, ws, counter + slot);
         if (plant) {                 // the true system replaces x_1 of the plan, before the next initial rollout reads x0s
-            rc = fam->plant(h, (int)S, mpc_steps, q.adv, q.advp, q.map, ucl, xcl, ws.x0);
+            rc = M.plant(h, (int)S, mpc_steps, q.adv, q.advp, q.map, ucl, xcl, ws.x0);
             if (rc) return rc;
         }
         ++git;
-        if (slot == POLL - 1 || git >= hard_cap) {
-            DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4 * (slot + 1), hipMemcpyDeviceToHost, st));
-            DDP_HIP(hipStreamSynchronize(st));
-            running = h->h_pinned[slot];
-            for (int e2 = 0; e2 <= slot; ++e2)
-                if (h->h_pinned[e2] == 0) { git -= slot - e2; running = 0; break; }       // the iterations after it did nothing
-        }
+        if ((slot == POLL - 1 || git >= hard_cap) && (rc = poll_running(h, counter, slot + 1, &git, &running))) return rc;
     }
     DDP_HIP(hipGetLastError());
     DDP_HIP(hipStreamSynchronize(st));
@@ -994,16 +941,14 @@ static int ilqg_sched_impl(ddp_handle h, const ddp_problem *p, const ddp_ilqg_op
 
 }   // extern "C"
 
-// the scheduler for a family of ddp_family (user_problem.hip), with a problem struct that carries the sizes only (B = problems)
+// the scheduler for a family of ddp_family (user_problem.hip): f->B problems
 int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *oo, int slots, int steps, int zero_tail, const double *x0,
                               const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                               double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters)
 {
     DDP_CHECK(f, "ilqg_sched: null family");
     DDP_CHECK(steps >= 0, "ilqg_mpc: steps=%d", steps);
-    ddp_problem pf = {};
-    pf.kind = -1; pf.n = f->n; pf.m = f->m; pf.N = f->N; pf.B = f->B;
-    return ilqg_sched_impl(h, &pf, oo, slots, steps, zero_tail, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, xcl, ucl, stats_cl,
+    return ilqg_sched_impl(h, nullptr, oo, slots, steps, zero_tail, x0, u0, lims, x, u, K, k, Quu, Vx, Vxx, cost, stats, xcl, ucl, stats_cl,
                            global_iters, f);
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 #include <type_traits>
 #include "ddp_internal.h"
+#include "ilqg_model.h"
 #include "staging.h"
 
 namespace {
@@ -937,7 +938,8 @@ void ddp_ilqgkl_default_opts(ddp_ilqgkl_opts *o)
 }
 
 // The body of ddp_ilqgkl_f64_dev and ddp_user_ilqgkl_f64_dev: the registered problem `p`, or the family `f` (a user problem) with its
-// derivatives [.,.,N,B] (constant Hessians [.,.,B]), its costfun and its rollout.  model_fx == NULL (family only): the model is the
+// derivatives [.,.,N,B] (constant Hessians [.,.,B]), its costfun and its rollout — the three calls go through Model (ilqg_model.h); the
+// operand layouts below are back_pass_gps's own.  model_fx == NULL (family only): the model is the
 // problem itself, forward_covariance takes the fx of STEP 1.
 static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, const ddp_ilqgkl_opts *oo, const double *x0,
                        const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
@@ -951,8 +953,9 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     if (!oo) { ddp_ilqgkl_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->max_iter >= 1, "ilqgkl: max_iter=%d (the reference returns undefined arrays without an iteration)", oo->max_iter);
     DDP_CHECK(x0 != x && kp != u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
-    const size_t n = f ? f->n : p->n, m = f ? f->m : p->m, N = f ? f->N : p->N, B = f ? f->B : p->B, NB = N * B, P2 = (n + m) * (n + m);
-    const bool pend = !f && p->kind == DDP_PROBLEM_PENDCART;
+    const Model M(p, f);
+    const size_t n = M.n, m = M.m, N = M.N, B = M.B, NB = N * B, P2 = (n + m) * (n + m);
+    const bool pend = M.pw.kind == DDP_PROBLEM_PENDCART;
     const int wide = kl_shape(h, (int)n, (int)m);          // 1: back_pass_gps, ∇kl, forward_covariance and kl_div_wiki on the wide kernels
     DDP_CHECK(wide >= 0, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m,
               NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
@@ -1014,21 +1017,16 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     DDP_HIP(hipMemsetAsync(kzero, 0, m * NB * 8, st));
     hipLaunchKernelGGL(kl_first_col_kernel, grid(n * B), dim3(256), 0, st, (int)n, (int)N, (int)B, x0, x0c);
     // STEP 1 (:86): derivs(x, u) with u = copy(traj_prev.k) (:45); a family evaluates every trajectory (no slot map: the loop recomputes all)
-    if (f) {
-        if ((rc = f->df(h, (int)B, nullptr, x0, kp, nullptr, fxw, fuw, cx, cu, cst ? nullptr : cxx, cst ? nullptr : cxu, cst ? nullptr : cuu)))
-            return rc;
-        if (cst && (rc = f->hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;
-        if (hrep) {
-            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * NB), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * NB), 1, (const double *)hxx, cxx);
-            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * NB), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * NB), 1, (const double *)hxu, cxu);
-            hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * NB), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * NB), 1, (const double *)huu, cuu);
-        }
-    } else {
-        if ((rc = ddp_df_f64_dev(h, p, x0, kp, nullptr, cx, cu, pend ? fxw : nullptr, pend ? fuw : nullptr))) return rc;
-        if (fx_rep) {
-            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
-            hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
-        }
+    if ((rc = M.df(h, (int)B, nullptr, x0, kp, nullptr, fxw, fuw, cx, cu, cxx, cxu, cuu))) return rc;
+    if ((rc = M.hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;      // const_hessian only
+    if (hrep) {
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * NB), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * NB), 1, (const double *)hxx, cxx);
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * NB), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * NB), 1, (const double *)hxu, cxu);
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * NB), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * NB), 1, (const double *)huu, cuu);
+    }
+    if (fx_rep) {                                          // (a registered LTI problem)
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
     }
     const double *fx = fx_own ? fxw : p->A, *fu = fx_own ? fuw : p->Bm;
     if (!f) {
@@ -1038,8 +1036,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     }
     if ((rc = ddp_kl_terms_f64_dev(h, (int)n, (int)m, (int)N, (int)B, Kp, kzero, Sip, kcx, kcu, kcxx, kcxu, kcuu))) return rc;   // :90
     if (!cost0) {                                          // the reference insists on `cost` (:69); a C caller may leave it to costfun(x0, u)
-        if ((rc = f ? f->costfun(h, (int)B, nullptr, x0, kp, nullptr, cost, c0buf) : ddp_costfun_f64_dev(h, p, x0, kp, nullptr, cost, c0buf)))
-            return rc;
+        if ((rc = M.costfun(h, (int)B, nullptr, x0, kp, nullptr, cost, c0buf))) return rc;
         cost0 = c0buf;
     }
     if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56)
@@ -1068,8 +1065,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
             if (!pending) break;
             DDP_CHECK(guard < 200, "ilqgkl: back_pass_gps keeps diverging (the reference would loop forever)");
         }
-        rc = f ? f->rollout(h, (int)B, nullptr, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs)
-               : ddp_forward_pass_f64_dev(h, p, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs);                                // :132
+        rc = M.rollout(h, (int)B, nullptr, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs);                                      // :132
         if (rc) return rc;
         if ((rc = ddp_forward_covariance_f64_dev(h, (int)n, (int)m, (int)N, (int)B, model_fx, model_fx_batched, R1, K, Sigma, sig))) return rc;   // :133
         if ((rc = ddp_kl_div_f64_dev(h, (int)n, (int)m, (int)N, (int)B, x, x0, sig, K, k, Sigma, Kp, kzero, Sp, Sip, kld, klm))) return rc;

@@ -3,8 +3,8 @@
 // The reference's iLQG(f, costfun, df, x0, u0; ...) takes the user's own closures.  Here the user writes four device functions
 // (include/ddp_amd.h lists the contract); the library wraps them in its kernel templates (user_problem_kernels.h), compiles the
 // program with hiprtc once per (source, n, m, nparam, flags, diff_wrap) and handle, and loads it on the handle's device.  The
-// device-resident iLQG of ilqg.hip runs such a problem through its ddp_family interface, so the whole loop — statuses, trace keys,
-// timing, pre-rolled starts, compaction — is the one of the registered families.
+// device-resident iLQG of ilqg.hip runs such a problem through its ddp_family interface (behind Model, ilqg_model.h), so the whole
+// loop — statuses, trace keys, timing, pre-rolled starts, compaction, the slot scheduler — is the one the registered kinds run.
 // hiprtc is loaded at first use (dlopen), like RCCL in comm.hip: the library has no link-time dependency on it.
 #include <dlfcn.h>
 #include <string.h>
