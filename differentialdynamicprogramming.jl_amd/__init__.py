@@ -31,7 +31,7 @@ from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
            "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
-           "constraints", "iLQG_al"]
+           "constraints", "iLQG_al", "normal", "sample_policy"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -198,12 +198,17 @@ class DeviceProblem:
     ``constraints(x, u, i, p, g)`` writing ``g[nc]``, feasible where ``g <= 0``.  ``constraints(problem, x, u)`` evaluates it, ``iLQG_al``
     solves the constrained problem by an augmented Lagrangian on the device, and ``forward_pass``, ``df``, ``costfun`` and ``iLQG`` take
     ``multipliers=(λ[nc,N(,B)], μ)`` and then work on the augmented cost (default: the raw cost).  Not together with ``const_hessian``,
-    ``clock``, ``second_order`` or ``second_order_wave``; ``iLQG_queue``, ``iLQG_mpc`` and ``kl.iLQGkl`` refuse such a problem."""
+    ``clock``, ``second_order`` or ``second_order_wave``; ``iLQG_queue``, ``iLQG_mpc`` and ``kl.iLQGkl`` refuse such a problem.
+    ``sample=True`` (DDP_USER_SAMPLE): the program also holds ``ddp_user_sample``, and ``sample_policy`` runs ``S`` closed-loop rollouts
+    per trajectory of the linear-Gaussian policy a solve returns (``û = u + L ξ + K diff(x̂, x)``, ``L`` the lower Cholesky factor of
+    ``Σ``, ``ξ`` generated on the device) on the model or, with ``plant=True``, on the plant; every other entry point ignores the flag.
+    Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0):
+                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False):
         self.clock = bool(clock)
+        self.sample = bool(sample)
         self.nc = int(constraints)
         if self.nc < 0:
             raise DDPError("DeviceProblem: constraints = %d (the number of constraints, 0 for none)" % self.nc)
@@ -214,7 +219,7 @@ class DeviceProblem:
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
                       (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
-                      (_lib.USER_CONSTRAINTS if self.nc else 0))
+                      (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -763,6 +768,81 @@ def constraints(problem, x, u, *, handle=None, params=None):
     g = _lib.result_array((problem.nc, N, B))
     _lib.check(_lib.lib().ddp_user_constraints_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(P), pb, _lib.ptr(x), _lib.ptr(u), _lib.ptr(g)))
     return g if batched else g[..., 0]
+
+
+# ------------------------------------------------------------------------------ sample_policy
+def _seed_words(seed):
+    """the two 32-bit words of a seed in [0, 2^64), as the C ints that carry their bits"""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise DDPError("seed should be an int in [0, 2^64), got %d" % seed)
+    return _C.c_int32(seed & 0xffffffff).value, _C.c_int32(seed >> 32).value
+
+
+def normal(seed, m, N, S, B=None, *, sample0=0, traj0=0, handle=None):
+    """``ξ[m, N, S(, B)]``: the standard normals ``sample_policy(..., seed=seed)`` draws — Philox4x32-10 with counter
+    ``(i, sample0 + s, traj0 + b, q)`` and key ``seed``, one Box-Muller pair per call (include/ddp_amd.h, DDP_USER_SAMPLE).  A block
+    taken with ``sample0`` / ``traj0`` is the slice of the full array, bit for bit."""
+    lo, hi = _seed_words(seed)
+    h = handle or default_handle()
+    nb = 1 if B is None else int(B)
+    xi = _lib.result_array((int(m), int(N), int(S), nb))
+    _lib.check(_lib.lib().ddp_normal_f64(h.raw, lo, hi, int(m), int(N), int(S), nb, int(sample0), int(traj0), _lib.ptr(xi)))
+    return xi[..., 0] if B is None else xi
+
+
+def sample_policy(problem, traj, x0, x, u, S, *, seed=0, noise=None, lims=None, plant=False, params=None, moments=False, sample0=0,
+                  traj0=0, handle=None):
+    """``S`` closed-loop rollouts per trajectory of the policy ``traj`` (``K``, ``Σ``; a solve's ``traj_new``) around the nominal
+    ``(x, u)`` from ``x0``, on a ``DeviceProblem`` made with ``sample=True``: at step ``i``
+    ``û = u[:, i] + L_i ξ_i + K[:, :, i] diff(x̂, x[:, i])``, clamped to ``lims``, with ``L_i`` the lower Cholesky factor of ``Σ[:, :, i]``
+    (the reference's docstring uses the upper one, whose samples do not have covariance ``Σ`` for m > 1) — the sampling step of the
+    guided-policy-search loop.  ``ξ`` is generated on the device from ``seed`` (an int in [0, 2^64); see ``normal``), or taken from
+    ``noise[m, N, S(, B)]``.  ``traj.Σ`` all zero or empty: the noise-free closed loop.  ``plant=True`` runs the problem's ``plant``
+    instead of its ``dynamics``.  Returns ``(xs[n,N,S(,B)], us[m,N,S(,B)], cs[CL,S(,B)], info)``; ``info`` holds ``csum[S(,B)]``,
+    ``status`` (0, or ``i + 1`` of the first step whose ``Σ`` is not positive definite: that trajectory's outputs are NaN) and, with
+    ``moments=True``, ``mean[n,N(,B)]`` and the unbiased ``cov[n,n,N(,B)]`` over the samples.  ``sample0`` / ``traj0`` offset the
+    generator's sample and trajectory counters: a shard reproduces its slice of the full call bit for bit."""
+    if not isinstance(problem, DeviceProblem):
+        raise TypeError("sample_policy: a DeviceProblem is needed")
+    h = handle or default_handle()
+    u, batched, n, m, N, B = _user_batch(x0, u, problem)
+    x0, x, K = _lib.f64(x0), _lib.f64(x), _lib.f64(traj.K)
+    tb = (B,) if batched else ()
+    if x0.shape != (n,) + tb and not (not batched and x0.shape == (n, 1)):
+        raise DDPError("x0 should be (n,) — (n, B) with a batched u")
+    if K.shape != (m, n, N) + tb or x.shape != (n, N) + tb:
+        raise DDPError("traj.K, x should be (m,n,N), (n,N) [+ batch axis]")
+    S = int(S)
+    Sg = getattr(traj, "Σ", None)
+    Sg = None if Sg is None or np.size(Sg) == 0 or not np.any(Sg) else _lib.f64(Sg)
+    if Sg is not None and Sg.shape != (m, m, N) + tb:
+        raise DDPError("traj.Σ should be (m,m,N) [+ batch axis]")
+    if noise is not None:
+        noise = _lib.f64(noise)
+        if noise.shape != (m, N, S) + tb:
+            raise DDPError("noise should be (m, N, S) [+ batch axis], got %s" % (noise.shape,))
+    L = _lims(lims)
+    if L is not None and L.shape != (m, 2):
+        raise DDPError("lims should be (m, 2)")
+    P, pb = problem._params(B, params)
+    lo, hi = _seed_words(seed)
+    CL = problem.cost_len(N)
+    xs = _lib.result_array((n, N, S, B)); us = _lib.result_array((m, N, S, B)); cs = _lib.result_array((CL, S, B))
+    csum = np.zeros((S, B), order="F"); status = np.zeros(B, dtype=np.int32)
+    mean = _lib.result_array((n, N, B)) if moments else None
+    cov = _lib.result_array((n, n, N, B)) if moments else None
+    _lib.check(_lib.lib().ddp_user_sample_f64(h.raw, problem._ptr(h), N, B, S, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(Sg), _lib.ptr(x0),
+                                              _lib.ptr(u), _lib.ptr(x), _lib.ptr(L), _lib.ptr(noise), lo, hi, int(sample0), int(traj0),
+                                              int(bool(plant)), _lib.ptr(xs), _lib.ptr(us), _lib.ptr(cs), _lib.ptr(csum), _lib.ptr(mean),
+                                              _lib.ptr(cov), status.ctypes.data_as(_lib.vp)))
+    info = {"csum": csum, "status": status}
+    if moments:
+        info["mean"], info["cov"] = mean, cov
+    if not batched:
+        xs, us, cs = xs[..., 0], us[..., 0], cs[..., 0]
+        info = {k: (int(v[0]) if k == "status" else v[..., 0]) for k, v in info.items()}
+    return xs, us, cs, info
 
 
 # ---------------------------------------------------------------------------------------- iLQG

@@ -37,8 +37,10 @@ EXPORTS = [
     "ddp_user_vhess_f64_dev", "ddp_user_vhess_f64", "ddp_user_back_pass_f64_dev", "ddp_user_back_pass_f64", "ddp_user_set_t0",
     "ddp_user_check_c", "ddp_user_create_c", "ddp_user_set_multipliers", "ddp_user_constraints_f64_dev", "ddp_user_constraints_f64",
     "ddp_al_default_opts", "ddp_user_ilqg_al_f64_dev", "ddp_user_ilqg_al_f64",
+    "ddp_normal_f64_dev", "ddp_normal_f64", "ddp_user_sample_f64_dev", "ddp_user_sample_f64",
 ]
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-8:])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+SAMPLE_EXPORTS = tuple(EXPORTS[-4:])           # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-12:-4])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -82,6 +84,7 @@ class ALOpts(C.Structure):
 
 
 ILQGKL_NSTATS = 12
+USER_SAMPLE = 2048             # DDP_USER_SAMPLE: the flag of DeviceProblem(..., sample=True)
 USER_CONSTRAINTS = 1024        # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(..., constraints=nc)
 USER_MAX_NC = 16               # DDP_USER_MAX_NC
 USER_WAVE = 32                 # DDP_USER_WAVE: the flag of DeviceProblem(..., wave=True)
@@ -185,6 +188,12 @@ def lib():
             al_args = [vp, vp, ci, ci, cd, ci, vp, vp, cd, ci] + [cd] * 4 + [cd] * 13 + [vp]
             L.ddp_user_ilqg_al_f64.argtypes = al_args
             L.ddp_user_ilqg_al_f64_dev.argtypes = al_args
+        if hasattr(L, "ddp_user_sample_f64"):                 # DDP_USER_SAMPLE; absent from A/B builds of the library from before the flag
+            L.ddp_normal_f64.argtypes = [vp] + [ci] * 8 + [cd]
+            L.ddp_normal_f64_dev.argtypes = [vp] + [ci] * 8 + [cd]
+            sample_args = [vp, vp, ci, ci, ci, cd, ci] + [cd] * 7 + [ci] * 5 + [cd] * 6 + [vp]
+            L.ddp_user_sample_f64.argtypes = sample_args
+            L.ddp_user_sample_f64_dev.argtypes = sample_args
         if hasattr(L, "ddp_user_program_text_c"):             # unlisted debug hook (tests), with the flag
             L.ddp_user_program_text_c.restype = C.c_char_p
             L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
@@ -194,7 +203,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

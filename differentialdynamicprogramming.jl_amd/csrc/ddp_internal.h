@@ -152,6 +152,11 @@ int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_op
                           int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
                           double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters);
 
+// sample.hip: the lower Cholesky factors L[m,m,N,B] of Sigma[m,m,N,B] and status[B] (0, or i + 1 of the first step that is not positive
+// definite), and the moments xmean[n,N,B] / xcov[n,n,N,B] (either may be NULL) of xs[n,N,S,B] over its samples; the device is current
+int ddp_policy_factor_dev(ddp_handle h, int m, int N, int B, const double *Sigma, double *L, int32_t *status);
+int ddp_sample_moments_dev(ddp_handle h, int n, int N, int S, int B, const double *xs, double *xmean, double *xcov);
+
 // raises the dynamic-LDS limit of `kernel` to at least `bytes`, once per handle (capi.hip; the attribute belongs to the device the handle
 // runs on: a process-wide flag would leave a second handle on another device at the 64 KB default)
 int ddp_raise_lds(ddp_handle h, const void *kernel, int bytes);

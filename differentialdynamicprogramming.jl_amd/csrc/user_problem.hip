@@ -18,14 +18,17 @@
 #include "user_constraints.h"
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
+#include "user_sample_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 #include "back_pass_wide_kernel.h"   // BPWArgs, WLds, bpw_fill: the wide kernel's step, shared with ddp_user_back_pass2_wave
+#include "philox_text.h"         // kPhiloxText: the text of philox.h (written by build.py)
 #include "wide_kernel_text.h"    // kWideTileText, kWideKernelText: the texts of wide_tile.h and back_pass_wide_kernel.h (written by build.py)
 
 DDP_USER_ABI
 DDP_USER_ABI2
 DDP_USER_ABI3
 DDP_USER_ABI_C
+DDP_USER_ABI_SAMPLE
 
 namespace {
 
@@ -73,7 +76,7 @@ std::string g_log;                                          // log of the last c
 // dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
 constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024;
 
-struct Layout { int chunk, rlanes, dflanes, adj, adh, wg; };
+struct Layout { int chunk, rlanes, dflanes, adj, adh, wg, schunk, slanes; };
 
 // chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit.
 // DDP_USER_WAVE: rlanes and dflanes are the same two counts of the wave kernels (the launch geometry reads nothing else), wg the group.
@@ -98,6 +101,12 @@ Layout layout_of(int n, int m, int flags)
     const int dt = n * n + n * m + n + m + ((flags & DDP_USER_CONST_HESSIAN) ? 0 : n * n + n * m + m * m);
     L.dflanes = 64;
     while (L.dflanes > 1 && (size_t)L.dflanes * (dt | 1) * 8 > (size_t)DF_LDS) L.dflanes /= 2;
+    // ddp_user_sample (DDP_USER_SAMPLE): 64 samples of one trajectory per work-group; per step the shared operands u, x, K, L once and
+    // x̂, û, c per sample.  The chunk that fits the rollout's budget, one step at least (n = 32, m = 8: 24 KB a step)
+    L.slanes = 64;
+    L.schunk = (ROLL_LDS / 8 - L.slanes) / (L.slanes * (n + m + 1) + m + n + m * n + m * m);
+    if (L.schunk > 16) L.schunk = 16;
+    if (L.schunk < 1) L.schunk = 1;
     L.wg = 0;
     if (flags & DDP_USER_WAVE) {
         // ddp_user_rollout_wave: a group of wg lanes (the power of two >= m, 8 at least) per rollout, 64 / wg rollouts per work-group;
@@ -214,8 +223,19 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE)) == 0,
               "user problem: unknown flags 0x%x", flags);
+    if (flags & DDP_USER_SAMPLE) {
+        // deferred, not impossible: ddp_user_sample is a lane-per-sample kernel with the state in registers (n <= 32, m <= 8) and hands
+        // the user's functions neither a clock nor multipliers
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER_WAVE), "user problem: DDP_USER_SAMPLE | DDP_USER_SECOND_ORDER_WAVE is refused (deferred: "
+                                                         "ddp_user_sample is sized for n <= %d, m <= %d)", DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!wave, "user problem: DDP_USER_SAMPLE | DDP_USER_WAVE is refused (deferred: ddp_user_sample is sized for n <= %d, m <= %d)",
+                  DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_SAMPLE | DDP_USER_CLOCK is refused (deferred: ddp_user_sample takes no clock)");
+        DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_SAMPLE | DDP_USER_CONSTRAINTS is refused (deferred: ddp_user_sample "
+                                                   "takes no multipliers)");
+    }
     if (flags & DDP_USER_CONSTRAINTS) {
         // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
         // second-order kernels would have to carry the multipliers as well
@@ -368,6 +388,15 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += "\n#line 1 \"ddp_user_kernels2_wave\"\n";
         s += kUserKernels2Wave;
     }
+    if (flags & DDP_USER_SAMPLE) {                               // a problem without the flag: the text above, nothing more
+        snprintf(head, sizeof head, "\n#define DDP_SLANES %d\n#define DDP_SCHUNK %d\n#line 1 \"ddp_philox\"\n", L.slanes, L.schunk);
+        s += head;
+        s += kPhiloxText;
+        s += "\n#line 1 \"ddp_user_kernels_sample\"\n";
+        s += DDP_USER_ABI_SAMPLE_TEXT;
+        s += "\n";
+        s += kUserKernelsSample;
+    }
     return s;
 }
 
@@ -433,6 +462,7 @@ struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
     hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
+    hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE)
     hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
     const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
@@ -508,6 +538,9 @@ struct UserProblem final : ddp_family {
     // ddp_user_ilqg_al_*: the arrays later rounds are solved into, the live flags and the counter; grown on demand, kept between calls
     char *al_ws = nullptr;
     size_t al_ws_bytes = 0;
+    // ddp_user_sample_*: the noise factors L[m,m,N,B] of the last call; grown on demand, kept between calls
+    double *chol = nullptr;
+    size_t chol_bytes = 0;
     ~UserProblem() override
     {
         if (curv) hipFree(curv);
@@ -516,6 +549,7 @@ struct UserProblem final : ddp_family {
         if (mu_dev) hipFree(mu_dev);
         if (blk) hipFree(blk);
         if (al_ws) hipFree(al_ws);
+        if (chol) hipFree(chol);
     }
 
     int df(ddp_handle hh, int Bc, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx, double *fu,
@@ -766,7 +800,8 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
                          (hipModuleGetFunction(&M.bp2w, M.mod, "ddp_user_back_pass2_wave") == hipSuccess &&
                           hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess)) &&
                         (!(flags & DDP_USER_CONSTRAINTS) || (hipModuleGetFunction(&M.con, M.mod, "ddp_user_constraints") == hipSuccess &&
-                                                             hipModuleGetFunction(&M.alup, M.mod, "ddp_user_al_update") == hipSuccess));
+                                                             hipModuleGetFunction(&M.alup, M.mod, "ddp_user_al_update") == hipSuccess)) &&
+                        (!(flags & DDP_USER_SAMPLE) || hipModuleGetFunction(&M.sample, M.mod, "ddp_user_sample") == hipSuccess);
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -1317,6 +1352,80 @@ int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *para
     if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqgkl_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
                                             det, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters));
+}
+
+// what both flavours of ddp_user_sample refuse, before anything is staged or launched
+static int sample_check(const UserProblem *P, int S, const double *K, const double *x0, const double *u, const double *x, int sample0,
+                        int traj0, int use_plant, const double *xs, const double *cs, const double *csum, const double *xmean,
+                        const double *xcov, const int32_t *status)
+{
+    DDP_CHECK(P->mod->sample, "sample: the problem was made without DDP_USER_SAMPLE");
+    DDP_CHECK(use_plant == 0 || use_plant == 1, "sample: use_plant = %d (0 or 1)", use_plant);
+    DDP_CHECK(!use_plant || (P->flags & DDP_USER_PLANT), "sample: use_plant = 1 but the problem was made without DDP_USER_PLANT");
+    DDP_CHECK(S >= 1, "sample: S = %d (>= 1)", S);
+    DDP_CHECK(sample0 >= 0 && traj0 >= 0, "sample: sample0 = %d, traj0 = %d (both >= 0)", sample0, traj0);
+    DDP_CHECK(K && x0 && u && x && cs && csum && status, "sample: null argument");
+    DDP_CHECK(xs || (!xmean && !xcov), "sample: xmean / xcov need xs (the moments are computed from the stored samples)");
+    return 0;
+}
+
+int ddp_user_sample_f64_dev(ddp_handle h, void *up, int N, int B, int S, const double *params, int params_batched, const double *K,
+                            const double *Sigma, const double *x0, const double *u, const double *x, const double *lims, const double *noise,
+                            int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
+                            double *xmean, double *xcov, int32_t *status)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
+    if (rc) return rc;
+    if ((rc = sample_check(P, S, K, x0, u, x, sample0, traj0, use_plant, xs, cs, csum, xmean, xcov, status))) return rc;
+    const int m = P->m;
+    const long groups = ((long)S + P->mod->L.slanes - 1) / P->mod->L.slanes;
+    DDP_CHECK(groups * B <= 0x7fffffffL, "sample: S = %d, B = %d is too large for one launch", S, B);
+    if (Sigma) {
+        const size_t need = (size_t)m * m * N * B * sizeof(double);
+        if (need > P->chol_bytes) {
+            if (P->chol) { DDP_HIP(hipStreamSynchronize(h->stream)); DDP_HIP(hipFree(P->chol)); P->chol = nullptr; P->chol_bytes = 0; }
+            DDP_HIP(hipMalloc((void **)&P->chol, need));
+            P->chol_bytes = need;
+        }
+        if ((rc = ddp_policy_factor_dev(h, m, N, B, Sigma, P->chol, status))) return rc;
+    } else {
+        DDP_HIP(hipMemsetAsync(status, 0, (size_t)B * sizeof(int32_t), h->stream));
+    }
+    UserSampleArgs a;
+    a.N = N; a.B = B; a.S = S; a.has_lims = lims != nullptr; a.params_batched = params_batched; a.use_plant = use_plant;
+    a.sample0 = sample0; a.traj0 = traj0; a.seed_lo = seed_lo; a.seed_hi = seed_hi;
+    a.params = P->params; a.K = K; a.L = Sigma ? P->chol : nullptr; a.x0 = x0; a.u = u; a.x = x; a.lims = lims;
+    a.noise = Sigma ? noise : nullptr; a.status = status; a.xs = xs; a.us = us; a.cs = cs; a.csum = csum;
+    void *args[] = {&a};
+    DDP_HIP(hipModuleLaunchKernel(P->mod->sample, (unsigned)(groups * B), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    h->last_kernel[1] = "ddp_user_sample";
+    if (xmean || xcov) return ddp_sample_moments_dev(h, P->n, N, S, B, xs, xmean, xcov);
+    return 0;
+}
+
+int ddp_user_sample_f64(ddp_handle h, void *up, int N, int B, int S, const double *params, int params_batched, const double *K,
+                        const double *Sigma, const double *x0, const double *u, const double *x, const double *lims, const double *noise,
+                        int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
+                        double *xmean, double *xcov, int32_t *status)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
+    if (rc) return rc;
+    if ((rc = sample_check(P, S, K, x0, u, x, sample0, traj0, use_plant, xs, cs, csum, xmean, xcov, status))) return rc;
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, R = (size_t)S * B;
+    const double *dp, *dK, *dSg, *dx0, *du, *dx, *dl, *dno;
+    double *dxs, *dus, *dcs, *dcsum, *dmean, *dcov;
+    int32_t *dst;
+    Staging St(h, Staging::OWNED, "user problem");
+    St.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); St.in(&dK, K, m * n * T); St.in(&dSg, Sigma, m * m * T);
+    St.in(&dx0, x0, n * B); St.in(&du, u, m * T); St.in(&dx, x, n * T); St.in(&dl, lims, 2 * m);
+    St.in(&dno, Sigma ? noise : nullptr, m * N * R);
+    St.out(&dxs, xs, n * N * R); St.out(&dus, us, m * N * R); St.out(&dcs, cs, (size_t)P->CL * R); St.out(&dcsum, csum, R);
+    St.out(&dmean, xmean, n * T); St.out(&dcov, xcov, n * n * T); St.out(&dst, status, (size_t)B);
+    if ((rc = St.commit())) return rc;
+    return St.finish(ddp_user_sample_f64_dev(h, up, N, B, S, dp, params_batched, dK, dSg, dx0, du, dx, dl, dno, seed_lo, seed_hi, sample0,
+                                             traj0, use_plant, dxs, dus, dcs, dcsum, dmean, dcov, dst));
 }
 
 }   // extern "C"

@@ -549,6 +549,7 @@ const MAX_N_USER_WAVE = 64             # DDP_MAX_N_USER_WAVE: user problems made
 const USER_CLOCK = 512                 # DDP_USER_CLOCK: the flag of DeviceProblem(...; clock=true); 256 is not assigned
 const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(...; constraints=nc)
 const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
+const USER_SAMPLE = 2048               # DDP_USER_SAMPLE: the flag of DeviceProblem(...; sample=true)
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
@@ -980,6 +981,8 @@ end
 # feasible where g <= 0.  constraints(problem, x, u) evaluates it; with_multipliers(f, problem, handle, λ, μ) runs f() — calls of
 # forward_pass, df, costfun, iLQG — on the augmented cost under λ[nc,N,B], μ[B].  Not together with const_hessian, clock, second_order or
 # second_order_wave; iLQG_queue, iLQG_mpc and iLQGkl refuse such a problem.  The loop itself (ddp_user_ilqg_al_f64) is not bound here yet.
+# sample=true (DDP_USER_SAMPLE): the program also holds ddp_user_sample, and sample_policy runs S closed-loop rollouts per trajectory of a
+# linear-Gaussian policy on the model or, with plant=true, on the plant.  Not together with wave, second_order_wave, clock or constraints.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -993,11 +996,12 @@ mutable struct DeviceProblem
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
-                       second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0)
+                       second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
-            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0)
+            (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0) |
+            (sample ? USER_SAMPLE : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1197,6 +1201,76 @@ function costfun(problem::DeviceProblem, x, u; handle::Handle=default_handle(), 
         end
     end
     return cost
+end
+
+# the two 32-bit words of a seed in [0, 2^64), as the C ints that carry their bits
+function _seed_words(seed::Integer)
+    0 <= seed <= typemax(UInt64) || throw(DDPError(-1, "seed must be an integer in [0, 2^64)"))
+    s = UInt64(seed)
+    return reinterpret(Int32, UInt32(s & 0xffffffff)), reinterpret(Int32, UInt32(s >> 32))
+end
+
+"""
+    normal(seed, m, N, S[, B]; sample0=0, traj0=0, handle)
+
+`ξ[m,N,S(,B)]`: the standard normals `sample_policy(...; seed=seed)` draws (ddp_normal_f64) — Philox4x32-10 with counter
+`(i, sample0 + s, traj0 + b, q)` and key `seed`, one Box-Muller pair per call.  A block taken with `sample0` / `traj0` is the slice of
+the full array, bit for bit.
+"""
+function normal(seed::Integer, m::Integer, N::Integer, S::Integer, B::Union{Nothing,Integer}=nothing; sample0::Integer=0, traj0::Integer=0,
+                handle::Handle=default_handle())
+    lo, hi = _seed_words(seed)
+    nb = B === nothing ? 1 : Int(B)
+    xi = B === nothing ? zeros(m, N, S) : zeros(m, N, S, nb)
+    GC.@preserve xi begin
+        check(@ccall libddp.ddp_normal_f64(handle.ptr::Ptr{Cvoid}, lo::Cint, hi::Cint, m::Cint, N::Cint, S::Cint, nb::Cint, sample0::Cint,
+            traj0::Cint, xi::Ptr{Float64})::Cint)
+    end
+    return xi
+end
+
+"""
+    sample_policy(problem, traj, x0, x, u, S; seed=0, noise=nothing, lims=[], plant=false, params=nothing, moments=false,
+                  sample0=0, traj0=0, handle) -> xs, us, cs, info
+
+`S` closed-loop rollouts per trajectory of the policy `traj` (`K`, `Σ`) around the nominal `(x, u)` from `x0`, on a `DeviceProblem` made
+with `sample=true` (ddp_user_sample_f64): `û = u[:,i] + L_i ξ_i + K[:,:,i] diff(x̂, x[:,i])`, clamped to `lims`, `L_i` the LOWER
+Cholesky factor of `Σ[:,:,i]` (the docstring of the reference's iLQGkl uses the upper one, whose samples do not have covariance `Σ` for
+m > 1).  `ξ` is generated on the device from `seed`, or taken from `noise[m,N,S(,B)]`; `Σ` empty or all zero: the noise-free closed loop.
+`plant=true` runs the problem's `plant` instead of its `dynamics`.  Returns `xs[n,N,S(,B)]`, `us[m,N,S(,B)]`, `cs[CL,S(,B)]` and `info`
+with `csum`, `status` (0, or `i + 1` of the first step whose `Σ` is not positive definite: NaN outputs) and, with `moments=true`, `mean`
+and the unbiased `cov` over the samples.
+"""
+function sample_policy(problem::DeviceProblem, traj, x0, x, u, S::Integer; seed::Integer=0, noise=nothing, lims=[], plant::Bool=false,
+                       params=nothing, moments::Bool=false, sample0::Integer=0, traj0::Integer=0, handle::Handle=default_handle())
+    batched = ndims(u) == 3
+    m, N = size(u, 1), size(u, 2)
+    n = size(x0, 1)
+    B = batched ? size(u, 3) : 1
+    (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
+    P, pb = _user_params(problem, B, params)
+    CL = cost_len(problem, N)
+    bt = batched ? (B,) : ()
+    lo, hi = _seed_words(seed)
+    Kh = _f64(traj.K)
+    Sg = (isempty(traj.Σ) || all(iszero, traj.Σ)) ? Float64[] : _f64(traj.Σ)
+    nz = noise === nothing ? Float64[] : _f64(noise)
+    xs = result_array(n, N, S, bt...); us = result_array(m, N, S, bt...); cs = result_array(CL, S, bt...)
+    csum = zeros(S, bt...); status = zeros(Int32, B)
+    mean = moments ? zeros(n, N, bt...) : Float64[]; cov = moments ? zeros(n, n, N, bt...) : Float64[]
+    x0 = _f64(x0); x = _f64(x); u = _f64(u)
+    limsp = _lims(lims)
+    up = _user_ptr(problem, handle)
+    use_plant = plant ? 1 : 0
+    GC.@preserve problem P Kh Sg nz x0 x u limsp xs us cs csum mean cov status begin
+        check(@ccall libddp.ddp_user_sample_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, S::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, Kh::Ptr{Float64}, _ptr_or_null(Sg)::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64}, x::Ptr{Float64},
+            _ptr_or_null(limsp)::Ptr{Float64}, _ptr_or_null(nz)::Ptr{Float64}, lo::Cint, hi::Cint, sample0::Cint, traj0::Cint, use_plant::Cint,
+            xs::Ptr{Float64}, us::Ptr{Float64}, cs::Ptr{Float64}, csum::Ptr{Float64}, _ptr_or_null(mean)::Ptr{Float64},
+            _ptr_or_null(cov)::Ptr{Float64}, status::Ptr{Int32})::Cint)
+    end
+    info = (csum=csum, status=(batched ? status : Int(status[1])), mean=(moments ? mean : nothing), cov=(moments ? cov : nothing))
+    return xs, us, cs, info
 end
 
 function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,

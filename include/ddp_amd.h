@@ -45,7 +45,8 @@ int  ddp_reload_env(ddp_handle h);
 /* name of the kernel the last back_pass (which = 0) / forward_pass (which = 1) dispatch of this handle launched ("" before the first
  * one): a debug query — the tests assert through it that the timed path is the one they checked.  which = 2 / 3: the last derivative /
  * cost kernel of a user problem (ddp_user_df*, ddp_user_costfun*; the hessians of DDP_USER_CONST_HESSIAN count as derivatives);
- * which = 4: the plant kernel of a user problem's closed loop (ddp_user_plant).  which = 5 / 6: the kernel of the last
+ * which = 4: the plant kernel of a user problem's closed loop (ddp_user_plant).  ddp_user_sample_* counts as a forward_pass
+ * (which = 1: ddp_user_sample).  which = 5 / 6: the kernel of the last
  * ddp_forward_covariance_* / ddp_kl_div_* call, the iLQGkl drivers' included (fcov_kernel, fcov_q4_kernel<1|2>, fcov_q4l_kernel,
  * fcov_wide_kernel / kl_div_kernel, kl_div_lds_kernel<4,1|4,2|0,0>, kl_div_wide_kernel).                                           */
 const char *ddp_last_kernel(ddp_handle h, int which);
@@ -628,13 +629,32 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * DDP_USER_AUTODIFF (the augmented cost is differentiated by AD) and combines with DDP_USER_TERMINAL, DDP_USER_WAVE, DDP_USER_PLANT and
  * diff_wrap; with DDP_USER_CONST_HESSIAN, DDP_USER_CLOCK, DDP_USER_SECOND_ORDER or DDP_USER_SECOND_ORDER_WAVE it is refused by name, and
  * ddp_user_ilqg_queue_*, ddp_user_ilqg_mpc_* and ddp_user_ilqgkl_* refuse such a problem by name before any launch.  Equality
- * constraints are not offered.  user_examples/car_keepout_ad.hip keeps the car out of a disc and caps its speed. */
+ * constraints are not offered.  user_examples/car_keepout_ad.hip keeps the car out of a disc and caps its speed.
+ *
+ * DDP_USER_SAMPLE: sampled closed-loop rollouts of a time-varying linear-Gaussian policy (ddp_user_sample_*, below; every other entry
+ * point ignores the flag) — the sampling step of the guided-policy-search loop, and, without noise, "run this policy on the plant".
+ * S samples of every trajectory b run
+ *   u^ = u_i + L_i xi_i + K_i diff(x^, x_i), clamped to lims;  c_i = stage_cost(x^, u^, i, p);  x^ <- dynamics(x^, u^, i, p), i < N-1
+ * (src/forward_pass.jl:17-28 with the noise of iLQGkl's docstring; with use_plant = 1 the user's plant(x^, u^, i, p, .) of
+ * DDP_USER_PLANT takes the place of dynamics), L_i the LOWER Cholesky factor of Sigma_i and xi_i standard normal.  The reference's
+ * chol(Sigma)*randn(m) uses the upper factor U, whose samples have covariance U U', not Sigma, for m > 1: the lower factor is a
+ * deliberate deviation (L xi has covariance Sigma).  xi is generated inside the kernel and never stored: Philox4x32-10 (Salmon et al.,
+ * SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), one call per (step, sample, trajectory, pair) with
+ *   counter = (i, sample0 + s, traj0 + b, q),  key = (seed_lo, seed_hi)
+ * and from its words r0..r3: k1 = (r0 >> 5) 2^26 + (r1 >> 6), k2 = (r2 >> 5) 2^26 + (r3 >> 6), u1 = (k1 + 1) 2^-53 in (0, 1],
+ * u2 = k2 2^-53 in [0, 1), xi[2q] = sqrt(-2 log u1) cos(2 pi u2), xi[2q+1] = sqrt(-2 log u1) sin(2 pi u2) (dropped when 2q+1 == m).
+ * Nothing depends on the launch geometry, S, B or the device: a call that passes its own sample0 / traj0 reproduces its slice of the
+ * full call bit for bit.  Kernel ddp_user_sample (ddp_last_kernel(h, 1)): one lane per sample, all lanes of a work-group on one
+ * trajectory, u_i, x_i, K_i, L_i through LDS once per work-group (broadcast reads), the state in registers, results out through LDS in
+ * contiguous runs; n <= 32, m <= 8.  Legal with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT,
+ * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
+ * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
        DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
-       DDP_USER_CONSTRAINTS = 1024 };                                                      /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048 };                              /* 64: not assigned, refused as unknown (256 too) */
 #define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
@@ -777,6 +797,27 @@ int ddp_user_ilqg_al_f64(ddp_handle h, void *up, int N, int B, const double *par
                          const double *lambda0, const double *mu_init, double *x, double *u, double *K, double *k, double *Quu,
                          double *Vx, double *Vxx, double *cost, double *stats, double *lambda, double *mu, double *g, double *al_stats,
                          int *global_iters);
+
+/* xi[m,N,S,B]: the standard normals ddp_user_sample_* draws for (seed_lo, seed_hi, sample0, traj0) — see DDP_USER_SAMPLE above.  The
+ * two seed words are the low and high 32 bits of a 64-bit seed, passed as int (their bits are what counts).  Kernel ddp_normal_fill. */
+int ddp_normal_f64_dev(ddp_handle h, int seed_lo, int seed_hi, int m, int N, int S, int B, int sample0, int traj0, double *xi);
+int ddp_normal_f64(ddp_handle h, int seed_lo, int seed_hi, int m, int N, int S, int B, int sample0, int traj0, double *xi);
+/* DDP_USER_SAMPLE problems only (others are refused by name).  K[m,n,N,B], Sigma[m,m,N,B] (lower triangle read), x0[n,B], u[m,N,B],
+ * x[n,N,B], lims[m,2] or NULL -> xs[n,N,S,B], us[m,N,S,B], cs[CL,S,B], csum[S,B], status[B], and the moments over the samples
+ * xmean[n,N,B], xcov[n,n,N,B] (unbiased; S = 1: NaN).  Sigma == NULL: no noise, the deterministic policy rollout (S is usually 1).
+ * noise[m,N,S,B] != NULL overrides the seed (ignored without Sigma).  xs, us, xmean, xcov may be NULL; moments without xs are
+ * refused by name.  status[b] is 0, or i + 1 for the smallest step whose Sigma_i is not positive definite (a pivot of its Cholesky
+ * factorisation that is not a positive finite number): such a trajectory runs no rollout and its rows of every non-NULL output are
+ * NaN.  use_plant = 1 on a problem without DDP_USER_PLANT is refused by name.  The noise factors (kernel ddp_policy_factor) live in a
+ * buffer the problem owns; the moments are ddp_sample_moments, one wave per step and trajectory, a fixed summation order.        */
+int ddp_user_sample_f64_dev(ddp_handle h, void *up, int N, int B, int S, const double *params, int params_batched, const double *K,
+                            const double *Sigma, const double *x0, const double *u, const double *x, const double *lims, const double *noise,
+                            int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
+                            double *xmean, double *xcov, int32_t *status);
+int ddp_user_sample_f64(ddp_handle h, void *up, int N, int B, int S, const double *params, int params_batched, const double *K,
+                        const double *Sigma, const double *x0, const double *u, const double *x, const double *lims, const double *noise,
+                        int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
+                        double *xmean, double *xcov, int32_t *status);
 
 #ifdef __cplusplus
 }
