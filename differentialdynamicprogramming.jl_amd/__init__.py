@@ -31,7 +31,7 @@ from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
            "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
-           "constraints", "iLQG_al", "normal", "sample_policy"]
+           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -843,6 +843,59 @@ def sample_policy(problem, traj, x0, x, u, S, *, seed=0, noise=None, lims=None, 
         xs, us, cs = xs[..., 0], us[..., 0], cs[..., 0]
         info = {k: (int(v[0]) if k == "status" else v[..., 0]) for k, v in info.items()}
     return xs, us, cs, info
+
+
+# ------------------------------------------------------------------------------ fit_dynamics
+def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
+    """Time-varying linear-Gaussian dynamics ``x̂[i+1] ≈ fx[:,:,i] x̂[i] + fu[:,:,i] û[i] + fc[:,i]`` with residual covariance
+    ``cov[:,:,i]``, fitted on the device to the rollouts ``xs[n,N,S(,B)]``, ``us[m,N,S(,B)]`` that ``sample_policy`` returns — the
+    step between sampling and ``kl.iLQGkl`` in a guided-policy-search round, and the way to a model of a ``plant`` whose equations
+    the controller does not know.  Per step ``i < N-1`` and trajectory, with ``w = [x̂_i; û_i; x̂_{i+1}]`` (``z`` its first ``n+m``
+    entries, ``y`` the last ``n``): ``μ`` the sample mean, ``C`` the unbiased covariance of the centred samples — with
+    ``prior=(Φ, μ0, m0, n0)`` the normal-inverse-Wishart posterior ``(E + Φ + (S m0/(S+m0)) (μ-μ0)(μ-μ0)ᵀ)/(S+n0)``, ``E`` the centred
+    sum; ``Φ[p,p]``, ``μ0[p]`` (``p = 2n+m``) serve every step, ``Φ[p,p,N(,B)]``, ``μ0[p,N(,B)]`` one each — then
+    ``[fx fu] = (A⁻¹ C_zy)ᵀ`` with ``A = C_zz + ridge·I`` (Cholesky, ``ridge >= 0`` absolute), ``fc = μ_y - [fx fu] μ_z`` and
+    ``cov = C_yy - [fx fu] C_zy``, symmetrised.  Returns ``(fx[n,n,N(,B)], fu[n,m,N(,B)], fc[n,N(,B)], cov[n,n,N(,B)],
+    status[N(,B)])``; ``kl.Model(fx, fu, R1)`` takes the first two as they are.  ``status`` is per step: 0, or ``c + 1`` for the first
+    pivot ``c`` of the factorisation that is not a positive finite number (``n + m + 1``: every pivot is fine but the results are not
+    finite, a NaN in ``x̂_{i+1}``) — that step's outputs are NaN and no other step is touched.
+    Every rollout of the sampler starts at the same ``x0``, so without ``ridge`` and ``prior`` step 0 reports pivot 1.  Slot ``N-1`` has
+    no transition: zeros.  1 <= n <= 32, 1 <= m <= 8, S >= 2.  Two calls give the same bits, and a call on some of the trajectories
+    gives the bits of their slice of the full call."""
+    xs, us = _lib.f64(xs), _lib.f64(us)
+    if xs.ndim not in (3, 4) or us.ndim != xs.ndim:
+        raise DDPError("fit_dynamics: xs, us should be (n, N, S), (m, N, S) [+ batch axis], got %s, %s" % (xs.shape, us.shape))
+    batched = xs.ndim == 4
+    if not batched:
+        xs, us = xs[..., None], us[..., None]
+    n, N, S, B = xs.shape
+    m = us.shape[0]
+    if us.shape[1:] != (N, S, B):
+        raise DDPError("fit_dynamics: us (m, %s) does not match xs (n, %s) in N, S [, B]" % (us.shape[1:], xs.shape[1:]))
+    p = 2 * n + m
+    Phi = mu0 = None
+    m0 = n0 = 0.0
+    layout = 0
+    if prior is not None:
+        Phi, mu0, m0, n0 = prior
+        Phi, mu0, m0, n0 = _lib.f64(Phi), _lib.f64(mu0), float(m0), float(n0)
+        tb = (B,) if batched else ()
+        if Phi.shape == (p, p) and mu0.shape == (p,):
+            layout = 0
+        elif Phi.shape == (p, p, N) + tb and mu0.shape == (p, N) + tb:
+            layout = 1
+        else:
+            raise DDPError("fit_dynamics: prior Φ, μ0 should be (p, p), (p,) or (p, p, N), (p, N) [+ batch axis] with p = 2n + m = %d, got %s, %s"
+                           % (p, Phi.shape, mu0.shape))
+    h = handle or default_handle()
+    fx = _lib.result_array((n, n, N, B)); fu = _lib.result_array((n, m, N, B)); fc = _lib.result_array((n, N, B))
+    cov = _lib.result_array((n, n, N, B)); status = np.zeros((N, B), dtype=np.int32, order="F")
+    _lib.check(_lib.lib().ddp_fit_dynamics_f64(h.raw, n, m, N, S, B, _lib.ptr(xs), _lib.ptr(us), float(ridge), _lib.ptr(Phi), _lib.ptr(mu0), m0,
+                                               n0, layout, _lib.ptr(fx), _lib.ptr(fu), _lib.ptr(fc), _lib.ptr(cov),
+                                               status.ctypes.data_as(_lib.vp)))
+    if not batched:
+        return fx[..., 0], fu[..., 0], fc[..., 0], cov[..., 0], status[..., 0]
+    return fx, fu, fc, cov, status
 
 
 # ---------------------------------------------------------------------------------------- iLQG

@@ -38,9 +38,11 @@ EXPORTS = [
     "ddp_user_check_c", "ddp_user_create_c", "ddp_user_set_multipliers", "ddp_user_constraints_f64_dev", "ddp_user_constraints_f64",
     "ddp_al_default_opts", "ddp_user_ilqg_al_f64_dev", "ddp_user_ilqg_al_f64",
     "ddp_normal_f64_dev", "ddp_normal_f64", "ddp_user_sample_f64_dev", "ddp_user_sample_f64",
+    "ddp_fit_dynamics_f64_dev", "ddp_fit_dynamics_f64",
 ]
-SAMPLE_EXPORTS = tuple(EXPORTS[-4:])           # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-12:-4])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-2:])              # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-6:-2])         # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-14:-6])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -194,7 +196,11 @@ def lib():
             sample_args = [vp, vp, ci, ci, ci, cd, ci] + [cd] * 7 + [ci] * 5 + [cd] * 6 + [vp]
             L.ddp_user_sample_f64.argtypes = sample_args
             L.ddp_user_sample_f64_dev.argtypes = sample_args
-        if hasattr(L, "ddp_user_program_text_c"):             # unlisted debug hook (tests), with the flag
+        if hasattr(L, "ddp_fit_dynamics_f64"):                # absent from A/B builds of the library from before it
+            fit_args = [vp] + [ci] * 5 + [cd, cd, C.c_double, cd, cd, C.c_double, C.c_double, ci] + [cd] * 4 + [vp]
+            L.ddp_fit_dynamics_f64.argtypes = fit_args
+            L.ddp_fit_dynamics_f64_dev.argtypes = fit_args
+        if hasattr(L, "ddp_user_program_text_c"):            # unlisted debug hook (tests), with the flag
             L.ddp_user_program_text_c.restype = C.c_char_p
             L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
         if hasattr(L, "ddp_user_program_text"):               # unlisted debug hook (tests); absent from older A/B builds of the library
@@ -203,7 +209,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

@@ -1273,6 +1273,47 @@ function sample_policy(problem::DeviceProblem, traj, x0, x, u, S::Integer; seed:
     return xs, us, cs, info
 end
 
+"""
+    fit_dynamics(xs, us; ridge=0.0, prior=nothing, handle) -> fx, fu, fc, cov, status
+
+Time-varying linear-Gaussian dynamics `x̂[i+1] ≈ fx[:,:,i] x̂[i] + fu[:,:,i] û[i] + fc[:,i]` with residual covariance `cov[:,:,i]`, fitted
+on the device to the rollouts `xs[n,N,S(,B)]`, `us[m,N,S(,B)]` of `sample_policy` (ddp_fit_dynamics_f64; the formula is in
+include/ddp_amd.h).  `prior = (Φ, μ0, m0, n0)` is a normal-inverse-Wishart prior, `Φ[p,p]`, `μ0[p]` for every step or `Φ[p,p,N(,B)]`,
+`μ0[p,N(,B)]` one each (`p = 2n + m`); `ridge >= 0` is added to the diagonal of `C_zz`.  `status[N(,B)]` is per step: 0, or `c + 1` for
+the first pivot `c` of the Cholesky factorisation that is not a positive finite number, `n + m + 1` when only the results are not
+finite (that step's outputs are NaN, no other step is touched); slot `N` has no transition and is zeros.  `Model(fx, fu, R1)` of `iLQGkl` takes the first two as they are.
+"""
+function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, handle::Handle=default_handle())
+    batched = ndims(xs) == 4
+    n, N, S = size(xs, 1), size(xs, 2), size(xs, 3)
+    m = size(us, 1)
+    B = batched ? size(xs, 4) : 1
+    bt = batched ? (B,) : ()
+    size(us) == (m, N, S, bt...) || throw(DDPError(-1, "fit_dynamics: us does not match xs in N, S [, B]"))
+    p = 2n + m
+    Phi = Float64[]; mu0 = Float64[]; m0 = 0.0; n0 = 0.0; layout = 0
+    if prior !== nothing
+        Phi = _f64(prior[1]); mu0 = _f64(prior[2]); m0 = Float64(prior[3]); n0 = Float64(prior[4])
+        if size(Phi) == (p, p) && size(mu0) == (p,)
+            layout = 0
+        elseif size(Phi) == (p, p, N, bt...) && size(mu0) == (p, N, bt...)
+            layout = 1
+        else
+            throw(DDPError(-1, "fit_dynamics: prior Φ, μ0 should be (p,p), (p,) or (p,p,N), (p,N) [+ batch axis], p = 2n + m"))
+        end
+    end
+    xs = _f64(xs); us = _f64(us)
+    fx = result_array(n, n, N, bt...); fu = result_array(n, m, N, bt...); fc = result_array(n, N, bt...); cov = result_array(n, n, N, bt...)
+    status = zeros(Int32, N, bt...)
+    rdg = Float64(ridge)
+    GC.@preserve xs us Phi mu0 fx fu fc cov status begin
+        check(@ccall libddp.ddp_fit_dynamics_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, xs::Ptr{Float64},
+            us::Ptr{Float64}, rdg::Cdouble, _ptr_or_null(Phi)::Ptr{Float64}, _ptr_or_null(mu0)::Ptr{Float64}, m0::Cdouble, n0::Cdouble,
+            layout::Cint, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, cov::Ptr{Float64}, status::Ptr{Int32})::Cint)
+    end
+    return fx, fu, fc, cov, status
+end
+
 function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0, cost=[], handle::Handle=default_handle(),
               params=nothing, t0=nothing, policy=GaussianPolicy{Float64})

@@ -819,6 +819,30 @@ int ddp_user_sample_f64(ddp_handle h, void *up, int N, int B, int S, const doubl
                         int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
                         double *xmean, double *xcov, int32_t *status);
 
+/* The linear-Gaussian dynamics fit of the guided-policy-search round (sample -> fit -> iLQGkl): xs[n,N,S,B], us[m,N,S,B] (the arrays
+ * ddp_user_sample_* writes) -> fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B], cov[n,n,N,B], status[N,B], per step i < N - 1 and trajectory b
+ * independently.  With w_s = [xs_i; us_i; xs_{i+1}] of sample s (p = 2n + m entries; z the first d = n + m, y the last n):
+ *   mu = mean_s w_s,   E = sum_s (w_s - mu)(w_s - mu)'  (the samples are centred before the products),
+ *   C = E / (S - 1) without a prior (Phi == NULL: mu0, m0, n0, prior_layout are not read), else the normal-inverse-Wishart posterior
+ *   C = (E + Phi + (S m0 / (S + m0)) (mu - mu0)(mu - mu0)') / (S + n0),
+ *   A = C_zz + ridge I (ridge >= 0, absolute), A = L L' (the lower triangle is read),
+ *   [fx fu] = (A^-1 C_zy)',   fc = mu_y - [fx fu] mu_z,   cov = C_yy - [fx fu] C_zy, symmetrised as (M + M') / 2.
+ * prior_layout = 0: one Phi[p,p], mu0[p] for every step and trajectory; 1: Phi[p,p,N,B], mu0[p,N,B] (slot N - 1 is not read).
+ * status[i,b] is 0, or c + 1 for the first pivot c of the factorisation that is not a positive finite number: that step's fx, fu, fc,
+ * cov are NaN and no other step is touched (every rollout of the sampler starts at the same x0, so C_xx of step 0 is exactly zero:
+ * with ridge = 0 and no prior that step reports pivot 1; the mean is formed as w_0 + mean_s (w_s - w_0), which gives a column that
+ * is the same in every sample exactly).  A step whose pivots are all fine but whose results are not finite (a NaN in xs_{i+1} of one
+ * sample, which is no part of A) fails too, with status d + 1 = n + m + 1.  Slot N - 1 has no transition: zeros, status 0.  1 <= n <= 32, 1 <= m <= 8,
+ * S >= 2; anything else is refused by name before any launch.  The summation order is fixed: two calls give the same bits, and a call
+ * on a slice of the trajectories gives the bits of that slice of the full call.  kl's Model takes fx, fu as they are.  Kernel
+ * ddp_fit_dynamics (fit.hip): one work-group per run of steps of one trajectory, the Gram matrix on v_mfma_f64_16x16x4.          */
+int ddp_fit_dynamics_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, const double *xs, const double *us, double ridge,
+                             const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
+                             double *fc, double *cov, int32_t *status);
+int ddp_fit_dynamics_f64(ddp_handle h, int n, int m, int N, int S, int B, const double *xs, const double *us, double ridge,
+                         const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
+                         double *fc, double *cov, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif
