@@ -166,7 +166,9 @@ def example_source(name):
     ``second_order=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
     for ``wave=True``; ``"chain_ddp_ad"``: the same chain with the torque entering as ``g tanh(u_j) cos(q_j)`` (curvature in x, u
     and mixed; ``n = 2 m``, 8 parameters), for ``second_order_wave=True``; ``"car_track"``, ``"car_track_ad"``, ``"car_track_plant"``: the
-    car following a sampled reference past a moving obstacle (``7 + 4 L`` parameters, the plant ``7 + 6 L``), for ``clock=True``."""
+    car following a sampled reference past a moving obstacle (``7 + 4 L`` parameters, the plant ``7 + 6 L``), for ``clock=True``;
+    ``"car_table"``: the car's cost on a tabulated time-varying affine model in the parameter block (``9 + 28 N`` parameters), the
+    emulation of ``fitted=True`` on the kernels from before the flag."""
     with open(_os.path.join(_EXAMPLES, name + ".hip")) as f:
         return f.read()
 
@@ -202,13 +204,18 @@ class DeviceProblem:
     ``sample=True`` (DDP_USER_SAMPLE): the program also holds ``ddp_user_sample``, and ``sample_policy`` runs ``S`` closed-loop rollouts
     per trajectory of the linear-Gaussian policy a solve returns (``û = u + L ξ + K diff(x̂, x)``, ``L`` the lower Cholesky factor of
     ``Σ``, ``ξ`` generated on the device) on the model or, with ``plant=True``, on the plant; every other entry point ignores the flag.
-    Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
+    Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred).
+    ``fitted=True`` (DDP_USER_FITTED): the program also holds ``ddp_user_rollout_fit``, the rollout on a fitted time-varying affine model
+    ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` (the tables ``fit_dynamics`` returns) under the problem's own cost:
+    ``forward_pass(..., model=(fx, fu, fc))`` runs it and ``kl.iLQGkl(..., fitted=True)`` plans on that model throughout; every other
+    entry point ignores the flag.  Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False):
+                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False):
         self.clock = bool(clock)
         self.sample = bool(sample)
+        self.fitted = bool(fitted)
         self.nc = int(constraints)
         if self.nc < 0:
             raise DDPError("DeviceProblem: constraints = %d (the number of constraints, 0 for none)" % self.nc)
@@ -219,7 +226,8 @@ class DeviceProblem:
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
                       (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
-                      (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0))
+                      (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0) |
+                      (_lib.USER_FITTED if self.fitted else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -536,16 +544,22 @@ def _check_problem(problem, n, m, N, B):
 
 
 # ------------------------------------------------------------------------------- forward_pass
-def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None, t0=None, multipliers=None):
+def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=None, params=None, t0=None, multipliers=None, model=None):
     """Drop-in for ``forward_pass(traj_new,x0,u,x,α,f,costfun,lims,diff)`` (forward_pass.jl:9) with a
     registered ``problem`` standing in for the closures ``f``/``costfun``; ``diff``: ``None`` (``-``) or a ``WrappedDiff``.
     ``traj_new`` may be an empty ``GaussianPolicy`` (then ``x`` is ignored, iLQG.jl:185).
     A vector ``α`` rolls all step sizes out concurrently (outputs get a trailing α axis).
     A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in; made with ``clock=True`` it takes ``t0``, made
-    with ``constraints=nc`` it takes ``multipliers=(λ, μ)`` (the augmented cost).
+    with ``constraints=nc`` it takes ``multipliers=(λ, μ)`` (the augmented cost); made with ``fitted=True`` it takes
+    ``model=(fx, fu, fc)``, the tables ``fit_dynamics`` returns (``(n,n,N)``, ``(n,m,N)``, ``(n,N)`` [+ batch axis]): the rollout then runs
+    ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` under the problem's cost (``ddp_user_rollout_fit``; slot ``N-1`` of the tables is not read).
+    With ``traj_new=None`` that is the open-loop rollout which makes ``(x, u)`` consistent with the fit before ``kl.iLQGkl(..., fitted=True)``.
     Returns ``(xnew, unew, cnew)``."""
     if isinstance(problem, DeviceProblem):
-        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0, multipliers=multipliers)
+        return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0, multipliers=multipliers,
+                                  model=model)
+    if model is not None:
+        raise DDPError("model= needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
     h = handle or default_handle()
     _no_clock(t0)
     _no_multipliers(multipliers)
@@ -626,9 +640,29 @@ def _user_batch(x_or_x0, u, problem, x0_has_time=False):
     return u, batched, n, m, N, B
 
 
-def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None, t0=None, multipliers=None):
-    h = handle or default_handle()
+def _fitted_tables(problem, model, n, m, N, B, batched, who):
+    """``(fx, fu, fc)`` of a ``model=`` keyword as the library takes them, ``[.,.,N,B]``; refused by name on a problem made without
+    ``fitted=True`` or on a malformed shape, before anything is launched"""
+    if not problem.fitted:
+        raise DDPError("%s: a fitted model needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)" % who)
+    try:
+        fx, fu, fc = model
+    except (TypeError, ValueError):
+        raise DDPError("%s: the fitted model should be a triple (fx, fu, fc)" % who)
+    if fx is None or fu is None or fc is None:
+        raise DDPError("%s: the fitted model needs fx, fu and fc (fc is None?)" % who if fc is None else "%s: the fitted model needs fx, fu and fc" % who)
+    fx, fu, fc = _lib.f64(fx), _lib.f64(fu), _lib.f64(fc)
+    tb = (B,) if batched else ()
+    if fx.shape != (n, n, N) + tb or fu.shape != (n, m, N) + tb or fc.shape != (n, N) + tb:
+        raise DDPError("%s: fx, fu, fc should be (n,n,N), (n,m,N), (n,N) = (%d,%d,%d), (%d,%d,%d), (%d,%d)%s, got %s, %s, %s"
+                       % (who, n, n, N, n, m, N, n, N, " + (B = %d,)" % B if batched else "", fx.shape, fu.shape, fc.shape))
+    return fx, fu, fc
+
+
+def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=None, params=None, t0=None, multipliers=None, model=None):
     u, batched, n, m, N, B = _user_batch(x0, u, problem)
+    tables = None if model is None else _fitted_tables(problem, model, n, m, N, B, batched, "forward_pass")
+    h = handle or default_handle()                         # (behind the checks that need no device)
     x0 = _lib.f64(x0)
     if x0.shape != ((n, B) if batched else (n,)) and not (not batched and x0.shape == (n, 1)):
         raise DDPError("x0 should be (n,) — (n, B) with a batched u")
@@ -655,9 +689,14 @@ def _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, *, handle=No
     cnew = _lib.result_array((CL, B, na)); csum = np.zeros((B, na), order="F")
     up = problem._ptr(h)
     with problem._clock(h, t0), problem._multipliers(h, multipliers, N, B, batched):
-        _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
-                                                        _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
-                                                        _lib.ptr(cnew), _lib.ptr(csum)))
+        if tables is not None:
+            _lib.check(_lib.lib().ddp_user_rollout_fit_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
+                                                           _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), *map(_lib.ptr, tables),
+                                                           _lib.ptr(xnew), _lib.ptr(unew), _lib.ptr(cnew), _lib.ptr(csum)))
+        else:
+            _lib.check(_lib.lib().ddp_user_forward_pass_f64(h.raw, up, N, B, _lib.ptr(P), pb, _lib.ptr(K), _lib.ptr(k), _lib.ptr(x0), _lib.ptr(u),
+                                                            _lib.ptr(xx), _lib.ptr(alphas), na, _lib.ptr(L), _lib.ptr(xnew), _lib.ptr(unew),
+                                                            _lib.ptr(cnew), _lib.ptr(csum)))
     if not batched:
         xnew, unew, cnew = xnew[:, :, 0], unew[:, :, 0], cnew[:, 0]
     if np.ndim(α) == 0:

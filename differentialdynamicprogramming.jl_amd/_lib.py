@@ -39,10 +39,12 @@ EXPORTS = [
     "ddp_al_default_opts", "ddp_user_ilqg_al_f64_dev", "ddp_user_ilqg_al_f64",
     "ddp_normal_f64_dev", "ddp_normal_f64", "ddp_user_sample_f64_dev", "ddp_user_sample_f64",
     "ddp_fit_dynamics_f64_dev", "ddp_fit_dynamics_f64",
+    "ddp_user_rollout_fit_f64_dev", "ddp_user_rollout_fit_f64", "ddp_user_ilqgkl_fit_f64_dev", "ddp_user_ilqgkl_fit_f64",
 ]
-FIT_EXPORTS = tuple(EXPORTS[-2:])              # fit_dynamics: absent from A/B builds of the library from before it
-SAMPLE_EXPORTS = tuple(EXPORTS[-6:-2])         # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-14:-6])      # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+FITTED_EXPORTS = tuple(EXPORTS[-4:])           # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-6:-4])            # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-10:-6])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-18:-10])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -86,6 +88,7 @@ class ALOpts(C.Structure):
 
 
 ILQGKL_NSTATS = 12
+USER_FITTED = 4096             # DDP_USER_FITTED: the flag of DeviceProblem(..., fitted=True)
 USER_SAMPLE = 2048             # DDP_USER_SAMPLE: the flag of DeviceProblem(..., sample=True)
 USER_CONSTRAINTS = 1024        # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(..., constraints=nc)
 USER_MAX_NC = 16               # DDP_USER_MAX_NC
@@ -200,6 +203,12 @@ def lib():
             fit_args = [vp] + [ci] * 5 + [cd, cd, C.c_double, cd, cd, C.c_double, C.c_double, ci] + [cd] * 4 + [vp]
             L.ddp_fit_dynamics_f64.argtypes = fit_args
             L.ddp_fit_dynamics_f64_dev.argtypes = fit_args
+        if hasattr(L, "ddp_user_rollout_fit_f64"):            # DDP_USER_FITTED; absent from A/B builds of the library from before the flag
+            L.ddp_user_rollout_fit_f64.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 6 + [ci, cd] + [cd] * 3 + [cd] * 4
+            L.ddp_user_rollout_fit_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 6 + [ci, cd, vp] + [cd] * 3 + [cd] * 4
+            klfit_args = [vp, vp, ci, ci, cd, ci, vp] + [cd] * 7 + [ci] + [cd] * 3 + [cd] * 3 + [cd] * 10 + [vp]
+            L.ddp_user_ilqgkl_fit_f64.argtypes = klfit_args
+            L.ddp_user_ilqgkl_fit_f64_dev.argtypes = klfit_args
         if hasattr(L, "ddp_user_program_text_c"):            # unlisted debug hook (tests), with the flag
             L.ddp_user_program_text_c.restype = C.c_char_p
             L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
@@ -209,7 +218,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

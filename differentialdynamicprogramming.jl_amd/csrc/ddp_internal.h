@@ -113,6 +113,10 @@ struct ddp_family {
     bool const_hessian, has_plant, second_order = false;
     const int32_t *t0 = nullptr;
     mutable const int32_t *clk = nullptr;
+    // DDP_USER_FITTED (else NULL): fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] of a fitted time-varying affine model on the device.  While they
+    // are set, rollout() runs x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i in place of the family's dynamics (ddp_user_rollout_fit); an entry sets
+    // them for the time of its call (FitScope)
+    mutable const double *fit_fx = nullptr, *fit_fu = nullptr, *fit_fc = nullptr;
     virtual ~ddp_family() {}
     virtual int back_pass(ddp_handle h, const BPCall &c) const { ddp_set_error("back_pass: the family has no backward pass of its own"); return -1; }
     virtual int df(ddp_handle h, int B, const int32_t *map, const double *x, const double *u, const int32_t *active, double *fx,
@@ -136,6 +140,18 @@ struct ClockScope {
     explicit ClockScope(const ddp_family *f_) : f(f_), was(f_ ? f_->clk : nullptr) {}
     ~ClockScope() { if (f) f->clk = was; }
 };
+// sets the family's fitted tables for the time of a call and puts back what was there (every way out)
+struct FitScope {
+    const ddp_family *f;
+    const double *was[3];
+    FitScope(const ddp_family *f_, const double *fx, const double *fu, const double *fc) : f(f_), was{nullptr, nullptr, nullptr}   // f_ == NULL: nothing to set
+    {
+        if (!f) return;
+        was[0] = f->fit_fx; was[1] = f->fit_fu; was[2] = f->fit_fc;
+        f->fit_fx = fx; f->fit_fu = fu; f->fit_fc = fc;
+    }
+    ~FitScope() { if (f) { f->fit_fx = was[0]; f->fit_fu = was[1]; f->fit_fc = was[2]; } }
+};
 // the device-resident iLQG of ilqg.hip for such a family (arguments as ddp_ilqg_ex_f64_dev)
 int ddp_ilqg_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_opts *o, const double *x0, int x0_prerolled, const double *u0,
                         const double *cost0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
@@ -146,11 +162,14 @@ int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_
                               const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                               double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters);
 
-// the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev; model_fx == NULL: the family's own fx of STEP 1)
+// the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev; model_fx == NULL: the family's own fx of STEP 1).
+// fit_fx, fit_fu, fit_fc [.,.,N,B] (all three or none): the loop plans on that fitted model — back_pass_gps takes fit_fx, fit_fu, the
+// rollouts run on the family with the tables set (FitScope), model_fx == NULL means fit_fx
 int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
                           const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
                           int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
-                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters);
+                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
+                          const double *fit_fx = nullptr, const double *fit_fu = nullptr, const double *fit_fc = nullptr);
 
 // sample.hip: the lower Cholesky factors L[m,m,N,B] of Sigma[m,m,N,B] and status[B] (0, or i + 1 of the first step that is not positive
 // definite), and the moments xmean[n,N,B] / xcov[n,n,N,B] (either may be NULL) of xs[n,N,S,B] over its samples; the device is current

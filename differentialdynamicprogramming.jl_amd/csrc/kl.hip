@@ -945,8 +945,10 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
                        const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
                        const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
                        double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
-                       double *dV, double *stats, int *iters_out)
+                       double *dV, double *stats, int *iters_out, const double *fit_fx = nullptr, const double *fit_fu = nullptr,
+                       const double *fit_fc = nullptr)
 {
+    DDP_CHECK((!fit_fx && !fit_fu && !fit_fc) || (f && fit_fx && fit_fu && fit_fc), "ilqgkl: a fitted model is fx, fu and fc, with a user problem");
     DDP_CHECK((p || f) && x0 && Kp && kp && Sp && Sip && (model_fx || f) && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV &&
               stats, "ilqgkl: null argument");
     ddp_ilqgkl_opts od;
@@ -1028,7 +1030,9 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
     }
-    const double *fx = fx_own ? fxw : p->A, *fu = fx_own ? fuw : p->Bm;
+    // a fitted model: the plan is made on its fx, fu (the fxw, fuw STEP 1 wrote stay in scratch) and every rollout below runs on its tables
+    const double *fx = fit_fx ? fit_fx : (fx_own ? fxw : p->A), *fu = fit_fx ? fit_fu : (fx_own ? fuw : p->Bm);
+    FitScope fit_scope(fit_fx ? f : nullptr, fit_fx, fit_fu, fit_fc);
     if (!f) {
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * N), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * N), 0, p->Q, cxx);
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * N), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * N), 0, (const double *)nullptr, cxu);
@@ -1039,7 +1043,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
         if ((rc = M.costfun(h, (int)B, nullptr, x0, kp, nullptr, cost, c0buf))) return rc;
         cost0 = c0buf;
     }
-    if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56)
+    if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56); a fitted model: its fx
     const BPCall gps = {d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, kp, nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
     auto poll = [&](int *out) -> int {
         DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
@@ -1096,14 +1100,15 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
 int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
                           const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
                           int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
-                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters)
+                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
+                          const double *fit_fx, const double *fit_fu, const double *fit_fc)
 {
     DDP_DEVICE(h);
     DDP_CHECK(f, "ilqgkl: null problem");
     DDP_CHECK(!f->second_order, "ilqgkl: a DDP_USER_SECOND_ORDER problem is refused (back_pass_gps has no second-order variant); make the "
                                 "problem without the flag for the KL loop");
     return ilqgkl_impl(h, nullptr, f, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                       Vxx, cost, dV, stats, iters);
+                       Vxx, cost, dV, stats, iters, fit_fx, fit_fu, fit_fc);
 }
 
 extern "C" {

@@ -19,6 +19,7 @@
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
 #include "user_sample_kernels.h"
+#include "user_fitted_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 #include "back_pass_wide_kernel.h"   // BPWArgs, WLds, bpw_fill: the wide kernel's step, shared with ddp_user_back_pass2_wave
 #include "philox_text.h"         // kPhiloxText: the text of philox.h (written by build.py)
@@ -29,6 +30,7 @@ DDP_USER_ABI2
 DDP_USER_ABI3
 DDP_USER_ABI_C
 DDP_USER_ABI_SAMPLE
+DDP_USER_ABI_FIT
 
 namespace {
 
@@ -74,9 +76,17 @@ std::string g_log;                                          // log of the last c
 
 // LDS budgets of the generated kernels (per 64-lane work-group): the rollout keeps several waves per CU (its time loop is a
 // dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
-constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024;
+constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024, FIT_LDS = 48 * 1024;
 
-struct Layout { int chunk, rlanes, dflanes, adj, adh, wg, schunk, slanes; };
+struct Layout { int chunk, rlanes, dflanes, adj, adh, wg, schunk, slanes, fchunk, flanes; };
+
+// bytes of LDS of ddp_user_rollout_fit with `lanes` rollouts per work-group and `chunk` steps per chunk: u, x, k, K and the tables fx, fu,
+// fc per rollout at odd strides, and the two slot arrays
+size_t fit_lds(int n, int m, int lanes, int chunk)
+{
+    const int ps = 2 * m + m * n + n, ts = n * n + n * m + n;
+    return (size_t)lanes * (((chunk * ps) | 1) + ((chunk * ts) | 1) + 1) * 8;
+}
 
 // chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit.
 // DDP_USER_WAVE: rlanes and dflanes are the same two counts of the wave kernels (the launch geometry reads nothing else), wg the group.
@@ -107,6 +117,17 @@ Layout layout_of(int n, int m, int flags)
     L.schunk = (ROLL_LDS / 8 - L.slanes) / (L.slanes * (n + m + 1) + m + n + m * n + m * m);
     if (L.schunk > 16) L.schunk = 16;
     if (L.schunk < 1) L.schunk = 1;
+    // ddp_user_rollout_fit (DDP_USER_FITTED): the time loop is a chain of chunks, each a round trip to memory, so the chunk counts more
+    // than the lanes: 64 rollouts per work-group where four steps of operands and tables fit FIT_LDS, else 32, else 16 with the chunk that
+    // fits; a shape whose single step does not fit at 16 (n = 32, m = 8: 12.9 KB a rollout) takes one step and the rollouts that fit 64 KB
+    L.flanes = 64;
+    auto fit_chunk = [&](int lanes) { int c = 0; while (c < 8 && fit_lds(n, m, lanes, c + 1) <= (size_t)FIT_LDS) ++c; return c; };
+    L.fchunk = fit_chunk(L.flanes);
+    while (L.fchunk < 4 && L.flanes > 16) { L.flanes /= 2; L.fchunk = fit_chunk(L.flanes); }
+    if (L.fchunk < 1) {
+        L.fchunk = 1;
+        while (L.flanes > 1 && fit_lds(n, m, L.flanes, 1) > (size_t)MAX_LDS) --L.flanes;
+    }
     L.wg = 0;
     if (flags & DDP_USER_WAVE) {
         // ddp_user_rollout_wave: a group of wg lanes (the power of two >= m, 8 at least) per rollout, 64 / wg rollouts per work-group;
@@ -223,7 +244,7 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE | DDP_USER_FITTED)) == 0,
               "user problem: unknown flags 0x%x", flags);
     if (flags & DDP_USER_SAMPLE) {
         // deferred, not impossible: ddp_user_sample is a lane-per-sample kernel with the state in registers (n <= 32, m <= 8) and hands
@@ -235,6 +256,18 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
         DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_SAMPLE | DDP_USER_CLOCK is refused (deferred: ddp_user_sample takes no clock)");
         DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_SAMPLE | DDP_USER_CONSTRAINTS is refused (deferred: ddp_user_sample "
                                                    "takes no multipliers)");
+    }
+    if (flags & DDP_USER_FITTED) {
+        // deferred, not impossible: ddp_user_rollout_fit is a lane-per-rollout kernel with the state in registers (n <= 32, m <= 8) and hands
+        // the user's cost neither a clock nor multipliers
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER_WAVE), "user problem: DDP_USER_FITTED | DDP_USER_SECOND_ORDER_WAVE is refused (deferred: "
+                                                         "ddp_user_rollout_fit is sized for n <= %d, m <= %d)", DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!wave, "user problem: DDP_USER_FITTED | DDP_USER_WAVE is refused (deferred: ddp_user_rollout_fit is sized for n <= %d, m <= %d)",
+                  DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_FITTED | DDP_USER_CLOCK is refused (deferred: ddp_user_rollout_fit takes no "
+                                             "clock)");
+        DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_FITTED | DDP_USER_CONSTRAINTS is refused (deferred: "
+                                                   "ddp_user_rollout_fit takes no multipliers)");
     }
     if (flags & DDP_USER_CONSTRAINTS) {
         // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
@@ -288,6 +321,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     const Layout L = layout_of(n, m, flags);
     const int ps = 2 * m + m * n + n;
     DDP_CHECK((size_t)L.rlanes * ((L.chunk * ps) | 1) * 8 <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the rollout's LDS", n, m);
+    if (flags & DDP_USER_FITTED)
+        DDP_CHECK(fit_lds(n, m, L.flanes, L.fchunk) <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the LDS of ddp_user_rollout_fit", n, m);
     return 0;
 }
 
@@ -397,6 +432,13 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += "\n";
         s += kUserKernelsSample;
     }
+    if (flags & DDP_USER_FITTED) {                               // a problem without the flag: the text above, nothing more; this tail goes last
+        snprintf(head, sizeof head, "\n#define DDP_FLANES %d\n#define DDP_FCHUNK %d\n#line 1 \"ddp_user_kernels_fit\"\n", L.flanes, L.fchunk);
+        s += head;
+        s += DDP_USER_ABI_FIT_TEXT;
+        s += "\n";
+        s += kUserKernelsFit;
+    }
     return s;
 }
 
@@ -463,6 +505,7 @@ struct Module {
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
     hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
     hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE)
+    hipFunction_t rollfit = nullptr;                             // ddp_user_rollout_fit (DDP_USER_FITTED)
     hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
     const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
@@ -582,6 +625,20 @@ struct UserProblem final : ddp_family {
         DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
         DDP_CHECK((K == nullptr) == (k == nullptr), "forward_pass: K and k must both be given or both NULL");
         DDP_CHECK(!K || x, "forward_pass: a non-empty policy needs the nominal trajectory x");
+        if (fit_fx) {                                            // the fitted model of the call in place of `dynamics` (FitScope)
+            DDP_CHECK(mod->rollfit, "forward_pass: the problem was made without DDP_USER_FITTED");
+            UserRollFitArgs a;
+            a.N = N; a.B = Bc; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr; a.params_batched = params_batched;
+            a.params = params; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active; a.map = map;
+            a.xnew = xnew; a.unew = unew; a.cnew = cnew; a.csum = csum; a.fx = fit_fx; a.fu = fit_fu; a.fc = fit_fc;
+            for (int i = 0; i < 16; ++i) a.alpha[i] = i < nalpha ? alpha[i] : 0.0;
+            void *args[] = {&a};
+            const long total = (long)Bc * nalpha;
+            DDP_HIP(hipModuleLaunchKernel(mod->rollfit, (unsigned)((total + mod->L.flanes - 1) / mod->L.flanes), 1, 1, 64, 1, 1, 0, hh->stream,
+                                          args, nullptr));
+            hh->last_kernel[1] = "ddp_user_rollout_fit";
+            return 0;
+        }
         UserRollArgs a;
         a.N = N; a.B = Bc; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr; a.params_batched = params_batched;
         a.params = params; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active; a.map = map;
@@ -801,7 +858,8 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
                           hipModuleGetFunction(&M.vhess, M.mod, "ddp_user_vhess") == hipSuccess)) &&
                         (!(flags & DDP_USER_CONSTRAINTS) || (hipModuleGetFunction(&M.con, M.mod, "ddp_user_constraints") == hipSuccess &&
                                                              hipModuleGetFunction(&M.alup, M.mod, "ddp_user_al_update") == hipSuccess)) &&
-                        (!(flags & DDP_USER_SAMPLE) || hipModuleGetFunction(&M.sample, M.mod, "ddp_user_sample") == hipSuccess);
+                        (!(flags & DDP_USER_SAMPLE) || hipModuleGetFunction(&M.sample, M.mod, "ddp_user_sample") == hipSuccess) &&
+                        (!(flags & DDP_USER_FITTED) || hipModuleGetFunction(&M.rollfit, M.mod, "ddp_user_rollout_fit") == hipSuccess);
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -1426,6 +1484,93 @@ int ddp_user_sample_f64(ddp_handle h, void *up, int N, int B, int S, const doubl
     if ((rc = St.commit())) return rc;
     return St.finish(ddp_user_sample_f64_dev(h, up, N, B, S, dp, params_batched, dK, dSg, dx0, du, dx, dl, dno, seed_lo, seed_hi, sample0,
                                              traj0, use_plant, dxs, dus, dcs, dcsum, dmean, dcov, dst));
+}
+
+// ---- DDP_USER_FITTED: the rollout and the KL loop on the tables of ddp_fit_dynamics.  The tables ride on the family for the time of the
+// call (FitScope): rollout() then launches ddp_user_rollout_fit.
+int ddp_user_rollout_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                                 const double *K, const double *k, const double *x0, const double *u, const double *x,
+                                 const double *alpha, int nalpha, const double *lims, const int32_t *active,
+                                 const double *fx, const double *fu, const double *fc,
+                                 double *xnew, double *unew, double *cnew, double *csum)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(x0 && u && alpha && fx && fu && fc && xnew && unew && cnew && csum, "rollout_fit: null argument");
+    FitScope fit(P, fx, fu, fc);
+    return P->rollout(h, B, nullptr, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
+}
+
+int ddp_user_rollout_fit_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                             const double *K, const double *k, const double *x0, const double *u, const double *x,
+                             const double *alpha, int nalpha, const double *lims,
+                             const double *fx, const double *fu, const double *fc,
+                             double *xnew, double *unew, double *cnew, double *csum)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
+    if (rc) return rc;
+    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(x0 && u && alpha && fx && fu && fc && xnew && unew && cnew && csum, "rollout_fit: null argument");
+    DDP_CHECK(nalpha >= 1 && nalpha <= 16, "forward_pass: nalpha=%d out of [1,16]", nalpha);
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, na = nalpha;
+    const double *dp, *dK, *dk, *dx0, *du, *dx, *dl, *dfx, *dfu, *dfc;
+    double *dxn, *dun, *dcn, *dcs;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); S.in(&dK, K, m * n * T); S.in(&dk, k, m * T); S.in(&dx0, x0, n * B);
+    S.in(&du, u, m * T); S.in(&dx, x, n * T); S.in(&dl, lims, 2 * m);
+    S.in(&dfx, fx, n * n * T); S.in(&dfu, fu, n * m * T); S.in(&dfc, fc, n * T);
+    S.out(&dxn, xnew, n * T * na); S.out(&dun, unew, m * T * na); S.out(&dcn, cnew, (size_t)P->CL * B * na); S.out(&dcs, csum, (size_t)B * na);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_user_rollout_fit_f64_dev(h, up, N, B, dp, params_batched, dK, dk, dx0, du, dx, alpha, nalpha, dl, nullptr, dfx, dfu,
+                                                 dfc, dxn, dun, dcn, dcs));
+}
+
+int ddp_user_ilqgkl_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                                const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                                const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                                double *etab, const double *fx, const double *fu, const double *fc,
+                                double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                                double *cost, double *dV, double *stats, int *iters)
+{
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
+    if (rc) return rc;
+    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(fx && fu && fc, "ilqgkl_fit: null argument");
+    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
+                                 Vxx, cost, dV, stats, iters, fx, fu, fc);
+}
+
+int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                            const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                            const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                            double *etab, const double *fx, const double *fu, const double *fc,
+                            double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                            double *cost, double *dV, double *stats, int *iters)
+{
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
+    if (rc) return rc;
+    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && fx && fu && fc && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats,
+              "ilqgkl_fit: null argument");
+    const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;
+    const double *dp, *dx0, *dc0, *dKp, *dkp, *dSp, *dSip, *dmf, *dR1, *dl, *dfx, *dfu, *dfc;
+    double *det, *dx, *du, *dK, *dS, *dSi, *dVx, *dVxx, *dc, *ddV, *ds;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)U->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * T); S.in(&dc0, cost0, (size_t)B); S.in(&dKp, Kp, m * n * T);
+    S.in(&dkp, kp, m * T); S.in(&dSp, Sp, m * m * T); S.in(&dSip, Sip, m * m * T);
+    S.in(&dmf, model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)); S.in(&dR1, R1, n * n); S.in(&dl, lims, 2 * m);
+    S.in(&dfx, fx, n * n * T); S.in(&dfu, fu, n * m * T); S.in(&dfc, fc, n * T);
+    S.inout(&det, etab, (size_t)3 * B); S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dS, Sigma, m * m * T);
+    S.out(&dSi, Sigmai, m * m * T); S.out(&dVx, Vx, n * T); S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * B); S.out(&ddV, dV, (size_t)2 * B);
+    S.out(&ds, stats, (size_t)DDP_ILQGKL_NSTATS * B);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_user_ilqgkl_fit_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
+                                                det, dfx, dfu, dfc, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters));
 }
 
 }   // extern "C"

@@ -550,6 +550,7 @@ const USER_CLOCK = 512                 # DDP_USER_CLOCK: the flag of DeviceProbl
 const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(...; constraints=nc)
 const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
 const USER_SAMPLE = 2048               # DDP_USER_SAMPLE: the flag of DeviceProblem(...; sample=true)
+const USER_FITTED = 4096               # DDP_USER_FITTED: the flag of DeviceProblem(...; fitted=true)
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
@@ -983,6 +984,9 @@ end
 # second_order_wave; iLQG_queue, iLQG_mpc and iLQGkl refuse such a problem.  The loop itself (ddp_user_ilqg_al_f64) is not bound here yet.
 # sample=true (DDP_USER_SAMPLE): the program also holds ddp_user_sample, and sample_policy runs S closed-loop rollouts per trajectory of a
 # linear-Gaussian policy on the model or, with plant=true, on the plant.  Not together with wave, second_order_wave, clock or constraints.
+# fitted=true (DDP_USER_FITTED): the program also holds ddp_user_rollout_fit, the rollout on a fitted time-varying affine model
+# x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i (the tables of fit_dynamics) under the problem's cost: forward_pass(...; model=(fx, fu, fc)) runs it,
+# iLQGkl(...; fitted=true, fu_model, fc_model) plans on it throughout.  Not together with wave, second_order_wave, clock or constraints.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -996,12 +1000,13 @@ mutable struct DeviceProblem
 end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
-                       second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false)
+                       second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false,
+                       fitted::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
             (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0) |
-            (sample ? USER_SAMPLE : 0)
+            (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1090,7 +1095,19 @@ function _user_params(p::DeviceProblem, B, params)
     throw(DDPError(-1, "DeviceProblem: params must be [nparam] or [nparam, B]"))
 end
 
-function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff=-; handle::Handle=default_handle(), params=nothing, t0=nothing)
+# the tables (fx, fu, fc) of a fitted model as [.,.,N,B] arrays, checked against the call's sizes and the problem's flag
+function _fitted_tables(problem::DeviceProblem, model, n, m, N, B, who)
+    (problem.flags & USER_FITTED) != 0 || throw(DDPError(-1, who * ": a fitted model needs a DeviceProblem made with fitted=true (DDP_USER_FITTED)"))
+    length(model) == 3 || throw(DDPError(-1, who * ": the fitted model should be a triple (fx, fu, fc)"))
+    fx, fu, fc = _f64(model[1]), _f64(model[2]), _f64(model[3])
+    (size(fx) in ((n, n, N), (n, n, N, B)) && size(fu) in ((n, m, N), (n, m, N, B)) && size(fc) in ((n, N), (n, N, B)) &&
+     length(fx) == n * n * N * B && length(fu) == n * m * N * B && length(fc) == n * N * B) ||
+        throw(DDPError(-1, who * ": fx, fu, fc should be [n,n,N], [n,m,N], [n,N] with one set per trajectory"))
+    return fx, fu, fc
+end
+
+function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff=-; handle::Handle=default_handle(), params=nothing, t0=nothing,
+                      model=nothing)
     batched = ndims(u) == 3
     m, N = size(u, 1), size(u, 2)
     n = size(x0, 1)
@@ -1107,7 +1124,19 @@ function forward_pass(traj_new, x0, u, x, α, problem::DeviceProblem, lims, diff
     x0 = _f64(x0); u = _f64(u)
     Kh = empty ? Float64[] : _f64(traj_new.K); kh = empty ? Float64[] : _f64(traj_new.k); xh = empty ? Float64[] : _f64(x)
     limsp = _lims(lims)
+    tabs = model === nothing ? nothing : _fitted_tables(problem, model, n, m, N, B, "forward_pass")
     up = _user_ptr(problem, handle)
+    if tabs !== nothing                                        # the rollout on the fitted model (ddp_user_rollout_fit_f64)
+        tfx, tfu, tfc = tabs
+        GC.@preserve problem P Kh kh xh x0 u al limsp tfx tfu tfc xnew unew cnew csum begin
+            check(@ccall libddp.ddp_user_rollout_fit_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, _ptr_or_null(Kh)::Ptr{Float64}, _ptr_or_null(kh)::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64},
+                _ptr_or_null(xh)::Ptr{Float64}, al::Ptr{Float64}, na::Cint, _ptr_or_null(limsp)::Ptr{Float64},
+                tfx::Ptr{Float64}, tfu::Ptr{Float64}, tfc::Ptr{Float64},
+                xnew::Ptr{Float64}, unew::Ptr{Float64}, cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+        end
+        return xnew_r, unew_r, cnew_r
+    end
     _with_clock(problem, handle, t0) do
         GC.@preserve problem P Kh kh xh x0 u al limsp xnew unew cnew csum begin
             check(@ccall libddp.ddp_user_forward_pass_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
@@ -1406,10 +1435,13 @@ function iLQG_mpc(problem::DeviceProblem, x0::AbstractMatrix, u0::AbstractArray{
 end
 
 # iLQGkl with the user's closures (`ddp_user_ilqgkl_f64`): as the method for registered problems; `fx_model = nothing` means the
-# problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B]
+# problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B].  fitted=true (a problem made with fitted=true;
+# fx_model, fu_model, fc_model the tables of fit_dynamics, one set per trajectory): the whole loop plans on the fitted model
+# (`ddp_user_ilqgkl_fit_f64`); fitted=false: on the problem's own model, fx_model only shapes the state covariance
 function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, t0=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
                 ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
-                wide::Bool=false)
+                fitted::Bool=false, fu_model=nothing, fc_model=nothing, wide::Bool=false)
+    fitted && wide && throw(DDPError(-1, "iLQGkl: fitted=true together with wide=true is refused (deferred)"))
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
     isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
     batched = ndims(x0) == 3
@@ -1438,8 +1470,28 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
     Vx, Vx_r = result_pair((n, N, B), (n, N, bt...)); Vxx, Vxx_r = result_pair((n, n, N, B), (n, n, N, bt...))
     cnew, cnew_r = result_pair((CL, B), (CL, bt...)); dV = zeros(2, B); st = zeros(12, B)
     its = Ref{Cint}(0)
+    tabs = nothing
+    if fitted
+        (fx_model === nothing || fu_model === nothing || fc_model === nothing) &&
+            throw(DDPError(-1, "iLQGkl: fitted=true needs fx_model, fu_model and fc_model (the tables of fit_dynamics)"))
+        tabs = _fitted_tables(problem, (fx_model, fu_model, fc_model), n, m, N, B, "iLQGkl")
+        all(isfinite, tabs[1]) && all(isfinite, tabs[2]) && all(isfinite, tabs[3]) ||
+            throw(DDPError(-1, "iLQGkl: fitted=true needs finite tables (a step fit_dynamics rejected is NaN: see its status)"))
+    end
     up = _user_ptr(problem, handle)
-    _with_clock(problem, handle, t0) do
+    if tabs !== nothing
+        tfx, tfu, tfc = tabs
+        GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab tfx tfu tfc x u K S Si Vx Vxx cnew dV st begin
+            check(@ccall libddp.ddp_user_ilqgkl_fit_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
+                Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
+                R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, tfx::Ptr{Float64}, tfu::Ptr{Float64}, tfc::Ptr{Float64},
+                x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+                S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
+                its::Ptr{Cint})::Cint)
+        end
+    end
+    tabs === nothing && _with_clock(problem, handle, t0) do
         _with_kl_wide(handle, wide) do
             GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
                 check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
@@ -1508,6 +1560,26 @@ function user_ilqgkl_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::I
         Sp::Ptr{Float64}, Sip::Ptr{Float64}, model_fx::Ptr{Float64}, model_fx_batched::Cint, R1::Ptr{Float64}, lims::Ptr{Float64},
         etab::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64}, Sigma::Ptr{Float64}, Sigmai::Ptr{Float64}, Vx::Ptr{Float64},
         Vxx::Ptr{Float64}, cost::Ptr{Float64}, dV::Ptr{Float64}, stats::Ptr{Float64}, its::Ptr{Cint})::Cint)
+    return Int(its[])
+end
+
+# DDP_USER_FITTED on device-resident arrays: the rollout and the KL loop on the tables fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B]
+user_rollout_fit_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, K, k, x0, u, x, al::Vector{Float64}, lims, active, fx, fu, fc, xnew,
+                      unew, cnew, csum; handle::Handle=default_handle()) =
+    GC.@preserve al check(@ccall libddp.ddp_user_rollout_fit_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint,
+        B::Cint, params::Ptr{Float64}, pb::Cint, K::Ptr{Float64}, k::Ptr{Float64}, x0::Ptr{Float64}, u::Ptr{Float64}, x::Ptr{Float64},
+        al::Ptr{Float64}, length(al)::Cint, lims::Ptr{Float64}, active::Ptr{Int32}, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64},
+        xnew::Ptr{Float64}, unew::Ptr{Float64}, cnew::Ptr{Float64}, csum::Ptr{Float64})::Cint)
+function user_ilqgkl_fit_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQGKLOpts, x0, cost0, Kp, kp, Sp, Sip, model_fx,
+                              model_fx_batched, R1, lims, etab, fx, fu, fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats;
+                              handle::Handle=default_handle())
+    its = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqgkl_fit_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, cost0::Ptr{Float64}, Kp::Ptr{Float64}, kp::Ptr{Float64},
+        Sp::Ptr{Float64}, Sip::Ptr{Float64}, model_fx::Ptr{Float64}, model_fx_batched::Cint, R1::Ptr{Float64}, lims::Ptr{Float64},
+        etab::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+        Sigma::Ptr{Float64}, Sigmai::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cost::Ptr{Float64}, dV::Ptr{Float64},
+        stats::Ptr{Float64}, its::Ptr{Cint})::Cint)
     return Int(its[])
 end
 

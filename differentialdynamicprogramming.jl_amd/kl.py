@@ -32,7 +32,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from . import DDPError, DeviceProblem, GaussianPolicy, _clock, _DevProblem, _lims, _user_shapes, default_handle, df, forward_pass
+from . import DDPError, DeviceProblem, GaussianPolicy, _clock, _DevProblem, _fitted_tables, _lims, _user_shapes, default_handle, df, forward_pass
 
 __all__ = ["Model", "grad_kl", "∇kl", "back_pass_gps", "forward_covariance", "kl_div_wiki", "calc_η", "geom", "iLQGkl",
            "model_covariance", "demo_linear_kl"]
@@ -43,6 +43,7 @@ class Model:
     fx: np.ndarray          # [n,n,N] or [n,n,N,B]
     fu: np.ndarray          # [n,m,N] or [n,m,N,B]  (only used by model_covariance)
     R1: np.ndarray          # [n,n]
+    fc: np.ndarray = None   # [n,N] or [n,N,B]: the offsets of a fitted model x[i+1] = fx x + fu u + fc (``iLQGkl(..., fitted=True)``)
 
 
 MAX_N, MAX_M, MAX_N_WIDE, MAX_M_WIDE = 32, 8, 64, 32      # DDP_MAX_N_GENERIC, DDP_MAX_M; with the switch: 64, DDP_MAX_M_WIDE
@@ -207,7 +208,7 @@ def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, ha
 
 
 def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50, cost=None, ηbracket=(1e-8, 1.0, 1e16),
-           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False, t0=None):
+           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False, t0=None, fitted=False):
     """``iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step, lims, max_iter, cost, ηbracket, del0)`` with a registered
     ``problem`` or a ``DeviceProblem`` (the user's closures as device source; ``params`` as in ``iLQG``) standing in for the three
     closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the pre-rolled trajectory (the reference errors otherwise,
@@ -218,7 +219,19 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     The loop runs inside ONE library call (``ddp_ilqgkl_f64``); ``DDP_KL_HOSTLOOP=1`` selects the loop on host arrays instead.
     ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``.
     ``t0``: the clock of every trajectory of a ``DeviceProblem`` made with ``clock=True`` (an int or B ints, default 0): STEP 1 and
-    every rollout evaluate the model at the absolute step ``t0 + i``."""
+    every rollout evaluate the model at the absolute step ``t0 + i``.
+    ``fitted=True`` (a ``DeviceProblem`` made with ``fitted=True``, ``model = Model(fx, fu, R1, fc)`` from ``fit_dynamics``): the whole
+    loop plans on the fitted time-varying affine model ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` under the problem's cost — back_pass_gps
+    takes ``model.fx, model.fu``, every rollout runs ``ddp_user_rollout_fit`` on the tables, forward_covariance takes ``model.fx``; the
+    problem's ``dynamics`` and the fx, fu of its ``derivatives`` are not used.  ``x0`` should be the rollout of ``traj_prev.k`` on the
+    tables (``forward_pass(None, x0, u, None, 1.0, problem, lims, model=(fx, fu, fc))``).  The tables must be finite at every step (a step
+    ``fit_dynamics`` rejected is NaN).  ``fitted=False`` (default): the plan is made on the problem's own model, ``model.fx`` only shapes
+    the state covariance."""
+    if fitted:
+        if wide:
+            raise DDPError("iLQGkl: fitted=True together with wide=True is refused (deferred: ddp_user_rollout_fit is sized for n <= 32, m <= 8)")
+        if not isinstance(problem, DeviceProblem):
+            raise DDPError("iLQGkl: fitted=True needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
     if constrain_per_step:
         raise NotImplementedError("constrain_per_step (iLQGkl.jl:180-232) is not offloaded")
     if isinstance(problem, DeviceProblem) and problem.second_order_wave:
@@ -229,7 +242,6 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
                        "make the problem without the flag for the KL loop")
     if cost is None or np.size(cost) == 0:
         raise ValueError("Initial trajectory supplied, initial cost must also be supplied")                     # :69
-    h = handle or default_handle()
     x0 = _lib.f64(x0)
     batched = x0.ndim == 3
     x = _b(x0, 2)
@@ -242,18 +254,49 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     prev0 = GaussianPolicy(N, n, m, _b(traj_prev.K, 3), np.zeros_like(u), _b(traj_prev.Σ, 3), _b(traj_prev.Σi, 3))   # k *= 0 (:51)
     user = isinstance(problem, DeviceProblem)
     prm = _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched) if user else None
+    tables = _fitted_kl_tables(problem, model, n, m, N, B) if fitted else None
+    h = handle or default_handle()                         # (behind every check that needs no device)
     etab = np.asarray(ηbracket, dtype=np.float64)
     etab = etab.copy() if etab.shape == (3, B) else np.repeat(etab.reshape(3)[:, None], B, 1)                    # copy (:52); [3,B]: one bracket per trajectory
     del0 = np.full(B, float(del0))
     import os as _os
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
         with _wide(h, wide), _clock(problem, h, t0):
-            return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm)
+            return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm,
+                                tables)
     with _wide(h, wide), _clock(problem, h, t0):           # (the clocks are checked here; the array calls below set their own)
-        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0)
+        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0,
+                                tables)
 
 
-def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0=None):
+def _fitted_kl_tables(problem, model, n, m, N, B):
+    """``fitted=True``: the tables of ``model`` as [.,.,N,B] arrays; every missing condition is refused by name before any launch"""
+    if not problem.fitted:
+        raise DDPError("iLQGkl: fitted=True needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
+    if model.fx is None or model.fu is None:
+        raise DDPError("iLQGkl: fitted=True needs model.fx, model.fu and model.fc (Model(fx, fu, R1, fc) from fit_dynamics)")
+    if model.fc is None:
+        raise DDPError("iLQGkl: fitted=True needs model.fc (Model(fx, fu, R1, fc)); fc=None is the model of fitted=False")
+    b4 = np.ndim(model.fx) == 4
+    tabs = _fitted_tables(problem, (model.fx, model.fu, model.fc), n, m, N, B, b4, "iLQGkl")
+    if not b4:                                             # one set of tables for the batch (B = 1 of an unbatched call)
+        if B != 1:
+            raise DDPError("iLQGkl: fitted=True takes one set of tables per trajectory: fx, fu, fc should be (n,n,N,B), (n,m,N,B), (n,N,B) "
+                           "with B = %d, got %s" % (B, np.shape(model.fx)))
+        tabs = tuple(_lib.f64(a[..., None]) for a in tabs)
+    for name, a in zip(("fx", "fu", "fc"), tabs):
+        bad = ~np.isfinite(a)
+        if bad.any():
+            flat = bad.reshape(-1, N, B).any(axis=0)       # [N, B]
+            b = int(np.flatnonzero(flat.any(axis=0))[0])
+            i = int(np.flatnonzero(flat[:, b])[0])
+            raise DDPError("iLQGkl: fitted=True needs finite tables: model.%s is not finite at step %d of trajectory %d (a step "
+                           "fit_dynamics rejected is NaN: see its status)" % (name, i, b))
+    return tabs
+
+
+def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0=None,
+                     tables=None):
     """DDP_KL_HOSTLOOP=1 (the body of iLQGkl on host arrays)"""
     n, N, B = x.shape
     m = u.shape[0]
@@ -263,6 +306,10 @@ def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, et
         fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h, params=prm[0], t0=t0)
         hb = problem.const_hessian                             # constant Hessians [.,.,B]: the time axis back_pass_gps wants
         cxx, cxu, cuu = _tv(cxx, N, hb), _tv(cxu, N, hb), _tv(cuu, N, hb)
+        if tables is not None:                                 # fitted=True: the plan is made on the tables (the fx, fu of STEP 1 are dropped)
+            fx, fu = tables[0], tables[1]
+            if model.fx is None or np.ndim(model.fx) == 3:
+                model = Model(fx, fu, model.R1)
         if model.fx is None:
             model = Model(fx, fu, model.R1)
     else:
@@ -316,7 +363,8 @@ def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, et
         pb = _SubProblem(problem, idx, B, prm[0]) if user else (problem if allB else _SubProblem(problem, idx, B))
         xs = sel(x)
         ts = t0 if (t0 is None or np.size(t0) == 1) else np.asarray(t0)[idx]      # the clocks of the trajectories rolled out
-        xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h, t0=ts)           # :132
+        mt = None if tables is None else tuple(sel(a) for a in tables)
+        xnew, unew, cnew = forward_pass(new, xs[:, 0, :], sel(u), xs, 1.0, pb, lims, diff_fun, handle=h, t0=ts, model=mt)           # :132
         del pb                                                 # (a DeviceProblem slice frees its compiled-problem pointer here)
         mdl = Model(model.fx if (np.ndim(model.fx) == 3 or allB) else model.fx[..., idx], model.fu, model.R1)
         sig = forward_covariance(mdl, xs, sel(u), new, handle=h, wide=wide)                                     # :133
@@ -377,7 +425,7 @@ def _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, bat
     return problem._params(B, params)
 
 
-def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None, prm=None):
+def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None, prm=None, tables=None):
     """the whole loop of iLQGkl (iLQGkl.jl:91-178) as ONE library call: ``ddp_ilqgkl_f64`` / ``ddp_user_ilqgkl_f64`` (csrc/kl.hip)"""
     n, N, B = x.shape
     m = u.shape[0]
@@ -399,7 +447,12 @@ def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, 
     Vxx = _lib.result_array((n, n, N, B)); co = _lib.result_array((CL, B)); dV = np.zeros((2, B), order="F")
     st = np.zeros((_lib.ILQGKL_NSTATS, B), order="F")
     mb = int(mfx is not None and mfx.ndim == 4)
-    if user:
+    if tables is not None:                                 # fitted=True: ddp_user_ilqgkl_fit_f64, the same arguments and the three tables
+        _lib.check(_lib.lib().ddp_user_ilqgkl_fit_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm[0]), prm[1], _C.byref(o), _lib.ptr(x), _lib.ptr(c0),
+                                                      _lib.ptr(Kp), _lib.ptr(u), _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1),
+                                                      _lib.ptr(Lh), _lib.ptr(eb), *map(_lib.ptr, tables),
+                                                      *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None))
+    elif user:
         _lib.check(_lib.lib().ddp_user_ilqgkl_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm[0]), prm[1], _C.byref(o), _lib.ptr(x), _lib.ptr(c0),
                                                   _lib.ptr(Kp), _lib.ptr(u), _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1),
                                                   _lib.ptr(Lh), _lib.ptr(eb), *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None))

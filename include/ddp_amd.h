@@ -648,13 +648,28 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * trajectory, u_i, x_i, K_i, L_i through LDS once per work-group (broadcast reads), the state in registers, results out through LDS in
  * contiguous runs; n <= 32, m <= 8.  Legal with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT,
  * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
- * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did. */
+ * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did.
+ *
+ * DDP_USER_FITTED: the rollout, and the whole KL-constrained loop, on a fitted time-varying affine model in place of `dynamics` and
+ * `derivatives` (ddp_user_rollout_fit_*, ddp_user_ilqgkl_fit_*, below; every other entry point ignores the flag): the tables
+ * fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] that ddp_fit_dynamics_* returns, column-major, one set per trajectory,
+ *   u^_i = clamp(u_i + alpha k_i + K_i diff(x^_i, x_i));  c_i = stage_cost(x^_i, u^_i, i, p);
+ *   x^_{i+1} = fc_i + sum_j fx_i[:,j] x^_i[j] + sum_q fu_i[:,q] u^_i[q],  i < N-1
+ * with the user's own cost (and terminal cost).  The affine map acts on raw coordinates: diff_wrap applies in the policy term only.
+ * Slot N-1 of the tables is never read.  Per component the sum runs fc, j = 0..n-1, q = 0..m-1: nothing depends on B, nalpha or the
+ * launch geometry, and a call on a slice of the trajectories reproduces that slice of the full call bit for bit.  Kernel
+ * ddp_user_rollout_fit (ddp_last_kernel(h, 1)): one lane per rollout, the state in registers, the tables staged through LDS in
+ * contiguous runs per trajectory and chunk of steps, shared by the alpha candidates of a trajectory that sit in one work-group;
+ * n <= 32, m <= 8.  Legal with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SAMPLE,
+ * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
+ * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did;
+ * the tail of the flag goes last in the program. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
        DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
-       DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048 };                              /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048, DDP_USER_FITTED = 4096 };      /* 64: not assigned, refused as unknown (256 too) */
 #define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
@@ -842,6 +857,36 @@ int ddp_fit_dynamics_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, co
 int ddp_fit_dynamics_f64(ddp_handle h, int n, int m, int N, int S, int B, const double *xs, const double *us, double ridge,
                          const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
                          double *fc, double *cov, int32_t *status);
+
+/* DDP_USER_FITTED problems only (a problem made without the flag is refused by name).  The rollout of ddp_user_forward_pass_f64(_dev),
+ * arguments and outputs alike, on the fitted model fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] (see DDP_USER_FITTED above).                  */
+int ddp_user_rollout_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                                 const double *K, const double *k, const double *x0, const double *u, const double *x,
+                                 const double *alpha, int nalpha, const double *lims, const int32_t *active,
+                                 const double *fx, const double *fu, const double *fc,
+                                 double *xnew, double *unew, double *cnew, double *csum);
+int ddp_user_rollout_fit_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
+                             const double *K, const double *k, const double *x0, const double *u, const double *x,
+                             const double *alpha, int nalpha, const double *lims,
+                             const double *fx, const double *fu, const double *fc,
+                             double *xnew, double *unew, double *cnew, double *csum);
+/* iLQGkl planning on the fitted model: arguments and outputs as ddp_user_ilqgkl_f64(_dev), then the tables.  The backward pass takes the
+ * fitted fx, fu, every rollout of the loop runs ddp_user_rollout_fit, and model_fx == NULL means the fitted fx.  STEP 1 still evaluates
+ * the problem's derivatives once at (x0, kp) for the derivatives of the cost; the fx, fu it writes are not used.  The tables must be
+ * finite at every step (a step ddp_fit_dynamics_* rejected is NaN: the caller checks its status).  x0 is expected to be the rollout of kp
+ * on the tables (ddp_user_rollout_fit_* without a policy), as iLQGkl expects a trajectory consistent with its model.                */
+int ddp_user_ilqgkl_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                                const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                                const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                                double *etab, const double *fx, const double *fu, const double *fc,
+                                double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                                double *cost, double *dV, double *stats, int *iters);
+int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                            const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                            const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                            double *etab, const double *fx, const double *fu, const double *fc,
+                            double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                            double *cost, double *dV, double *stats, int *iters);
 
 #ifdef __cplusplus
 }
