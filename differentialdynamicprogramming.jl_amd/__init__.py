@@ -31,7 +31,7 @@ from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
            "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
-           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics"]
+           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics", "GMM", "fit_gmm", "gmm_prior"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -935,6 +935,99 @@ def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
     if not batched:
         return fx[..., 0], fu[..., 0], fc[..., 0], cov[..., 0], status[..., 0]
     return fx, fu, fc, cov, status
+
+
+# ------------------------------------------------------------------------------ fit_gmm, gmm_prior
+@dataclass
+class GMM:
+    """A Gaussian mixture over the transition tuples ``w = [x̂_i; û_i; x̂_{i+1}]`` (``p = 2n + m``), as ``fit_gmm`` returns it:
+    ``pi[K,G]``, ``mu[p,K,G]``, ``Sigma[p,p,K,G]``, ``ll[iters,G]``, ``status[G]``; ``G = 1`` with ``pool=True``, else one mixture per
+    trajectory."""
+    pi: np.ndarray
+    mu: np.ndarray
+    Sigma: np.ndarray
+    ll: np.ndarray
+    status: np.ndarray
+    pool: bool = True
+
+
+def _gmm_points(who, xs, us):
+    xs, us = _lib.f64(xs), _lib.f64(us)
+    if xs.ndim not in (3, 4) or us.ndim != xs.ndim:
+        raise DDPError("%s: xs, us should be (n, N, S), (m, N, S) [+ batch axis], got %s, %s" % (who, xs.shape, us.shape))
+    batched = xs.ndim == 4
+    if not batched:
+        xs, us = xs[..., None], us[..., None]
+    if us.shape[1:] != xs.shape[1:]:
+        raise DDPError("%s: us (m, %s) does not match xs (n, %s) in N, S [, B]" % (who, us.shape[1:], xs.shape[1:]))
+    return xs, us, batched
+
+
+def _gmm_mixture(who, pi, mu, Sigma, p, K, G):
+    pi, mu, Sigma = _lib.f64(pi), _lib.f64(mu), _lib.f64(Sigma)
+    if G == 1 and pi.ndim == 1:
+        pi, mu, Sigma = pi[..., None], mu[..., None], Sigma[..., None]
+    if pi.shape != (K, G) or mu.shape != (p, K, G) or Sigma.shape != (p, p, K, G):
+        raise DDPError("%s: π, μ, Σ should be (K, G), (p, K, G), (p, p, K, G) with p = 2n + m = %d, K = %d, G = %d, got %s, %s, %s"
+                       % (who, p, K, G, pi.shape, mu.shape, Sigma.shape))
+    return _lib.f64(pi), _lib.f64(mu), _lib.f64(Sigma)
+
+
+def fit_gmm(xs, us, K, *, iters=20, reg=1e-6, seed=0, init=None, pool=True, traj0=0, handle=None):
+    """A ``K``-cluster Gaussian mixture fitted by EM on the device to the transition tuples ``w = [x̂_i; û_i; x̂_{i+1}]`` of all steps and
+    samples of the rollouts ``xs[n,N,S(,B)]``, ``us[m,N,S(,B)]`` that ``sample_policy`` returns — the dynamics prior of the
+    guided-policy-search round (Levine & Abbeel 2014; the formulas are in include/ddp_amd.h).  ``pool=True``: one mixture over all
+    trajectories; ``False``: one per trajectory.  ``init=(π, μ, Σ)`` or a ``GMM`` (the mixture of the last round) is the start; without
+    it an M-step from a hard assignment drawn from ``seed`` (Philox counter ``(i, s, traj0 + b, 0x80000000)``: not the sampler's
+    stream).  ``reg >= 0`` is added to the diagonal of every ``Σ_k``.  Returns a ``GMM``; ``status[g]`` is 0, or ``k + 1`` for the first
+    cluster that emptied or whose ``Σ_k`` is not positive definite (that mixture is NaN).  1 <= n <= 32, 1 <= m <= 8, 1 <= K <= 32.
+    Two calls give the same bits; with ``pool=False`` a call on some of the trajectories (with its ``traj0``) gives their slice."""
+    xs, us, _ = _gmm_points("fit_gmm", xs, us)
+    n, N, S, B = xs.shape
+    m, p, K, iters, pool = us.shape[0], 2 * n + us.shape[0], int(K), int(iters), bool(pool)
+    G = 1 if pool else B
+    if not 1 <= K <= 32 or iters < 0:
+        raise DDPError("fit_gmm: K = %d out of [1, 32] or iters = %d < 0" % (K, iters))
+    pi0 = mu0 = Sg0 = None
+    if init is not None:
+        if isinstance(init, GMM):
+            init = (init.pi, init.mu, init.Sigma)
+        pi0, mu0, Sg0 = _gmm_mixture("fit_gmm: init", *init, p, K, G)
+    lo, hi = _seed_words(seed)
+    h = handle or default_handle()
+    pi = np.zeros((K, G), order="F"); mu = np.zeros((p, K, G), order="F"); Sigma = _lib.result_array((p, p, K, G))
+    ll = np.zeros((iters, G), order="F"); status = np.zeros(G, dtype=np.int32)
+    _lib.check(_lib.lib().ddp_gmm_fit_f64(h.raw, n, m, N, S, B, K, iters, int(pool), int(traj0), _lib.ptr(xs), _lib.ptr(us), float(reg), lo, hi,
+                                          _lib.ptr(pi0), _lib.ptr(mu0), _lib.ptr(Sg0), _lib.ptr(pi), _lib.ptr(mu), _lib.ptr(Sigma),
+                                          _lib.ptr(ll) if iters > 0 else None, status.ctypes.data_as(_lib.vp)))
+    return GMM(pi, mu, Sigma, ll, status, pool)
+
+
+def gmm_prior(gmm, xs, us, *, m0=1.0, n0=1.0, handle=None):
+    """The normal-inverse-Wishart prior of every step from a mixture of ``fit_gmm``: with ``r_sk`` the responsibilities of the step's
+    ``S`` points, ``ω_k = mean_s r_sk``, ``μ0 = Σ_k ω_k μ_k``, ``Φ = n0 Σ_k ω_k (Σ_k + (μ_k - μ0)(μ_k - μ0)ᵀ)``.  Returns
+    ``(Φ[p,p,N(,B)], μ0[p,N(,B)], m0, n0)``, which ``fit_dynamics(xs, us, prior=...)`` takes as it is:
+
+        gmm = fit_gmm(xs, us, K)
+        fx, fu, fc, cov, status = fit_dynamics(xs, us, prior=gmm_prior(gmm, xs, us))
+
+    A step with a point that is not finite, or a mixture that is not usable (``gmm.status != 0``), gives NaN in that step's ``Φ``,
+    ``μ0``, which ``fit_dynamics`` reports in its status.  Slot ``N-1`` has no transition: zeros."""
+    if not isinstance(gmm, GMM):
+        raise DDPError("gmm_prior: a GMM (the result of fit_gmm) is needed")
+    xs, us, batched = _gmm_points("gmm_prior", xs, us)
+    n, N, S, B = xs.shape
+    m = us.shape[0]
+    p, K, pool = 2 * n + m, int(np.shape(gmm.pi)[0]) if np.ndim(gmm.pi) else 0, bool(gmm.pool)
+    pi, mu, Sigma = _gmm_mixture("gmm_prior", gmm.pi, gmm.mu, gmm.Sigma, p, K, 1 if pool else B)
+    h = handle or default_handle()
+    Phi = _lib.result_array((p, p, N, B)); mu0 = _lib.result_array((p, N, B)); status = np.zeros((N, B), dtype=np.int32, order="F")
+    _lib.check(_lib.lib().ddp_gmm_prior_f64(h.raw, n, m, N, S, B, K, int(pool), _lib.ptr(xs), _lib.ptr(us), _lib.ptr(pi), _lib.ptr(mu),
+                                            _lib.ptr(Sigma), float(m0), float(n0), _lib.ptr(Phi), _lib.ptr(mu0),
+                                            status.ctypes.data_as(_lib.vp)))
+    if not batched:
+        return Phi[..., 0], mu0[..., 0], float(m0), float(n0)
+    return Phi, mu0, float(m0), float(n0)
 
 
 # ---------------------------------------------------------------------------------------- iLQG

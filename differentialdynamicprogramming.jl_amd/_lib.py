@@ -40,11 +40,13 @@ EXPORTS = [
     "ddp_normal_f64_dev", "ddp_normal_f64", "ddp_user_sample_f64_dev", "ddp_user_sample_f64",
     "ddp_fit_dynamics_f64_dev", "ddp_fit_dynamics_f64",
     "ddp_user_rollout_fit_f64_dev", "ddp_user_rollout_fit_f64", "ddp_user_ilqgkl_fit_f64_dev", "ddp_user_ilqgkl_fit_f64",
+    "ddp_gmm_fit_f64_dev", "ddp_gmm_fit_f64", "ddp_gmm_prior_f64_dev", "ddp_gmm_prior_f64",
 ]
-FITTED_EXPORTS = tuple(EXPORTS[-4:])           # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
-FIT_EXPORTS = tuple(EXPORTS[-6:-4])            # fit_dynamics: absent from A/B builds of the library from before it
-SAMPLE_EXPORTS = tuple(EXPORTS[-10:-6])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-18:-10])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+GMM_EXPORTS = tuple(EXPORTS[-4:])              # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
+FITTED_EXPORTS = tuple(EXPORTS[-8:-4])         # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-10:-8])            # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-14:-10])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-22:-14])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -209,6 +211,13 @@ def lib():
             klfit_args = [vp, vp, ci, ci, cd, ci, vp] + [cd] * 7 + [ci] + [cd] * 3 + [cd] * 3 + [cd] * 10 + [vp]
             L.ddp_user_ilqgkl_fit_f64.argtypes = klfit_args
             L.ddp_user_ilqgkl_fit_f64_dev.argtypes = klfit_args
+        if hasattr(L, "ddp_gmm_fit_f64"):                     # absent from A/B builds of the library from before it
+            gmm_args = [vp] + [ci] * 9 + [cd, cd, C.c_double, ci, ci] + [cd] * 7 + [vp]
+            L.ddp_gmm_fit_f64.argtypes = gmm_args
+            L.ddp_gmm_fit_f64_dev.argtypes = gmm_args
+            prior_args = [vp] + [ci] * 7 + [cd] * 5 + [C.c_double, C.c_double, cd, cd, vp]
+            L.ddp_gmm_prior_f64.argtypes = prior_args
+            L.ddp_gmm_prior_f64_dev.argtypes = prior_args
         if hasattr(L, "ddp_user_program_text_c"):            # unlisted debug hook (tests), with the flag
             L.ddp_user_program_text_c.restype = C.c_char_p
             L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
@@ -218,7 +227,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

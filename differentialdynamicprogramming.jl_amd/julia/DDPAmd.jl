@@ -1343,6 +1343,81 @@ function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, handle::Handle=def
     return fx, fu, fc, cov, status
 end
 
+"""
+    fit_gmm(xs, us, K; iters=20, reg=1e-6, seed=0, init=nothing, pool=true, traj0=0, handle) -> (pi, mu, Sigma, ll, status, pool)
+
+A `K`-cluster Gaussian mixture fitted by EM on the device to the transition tuples `w = [x̂_i; û_i; x̂_{i+1}]` (`p = 2n + m`) of all steps
+and samples of the rollouts `xs[n,N,S(,B)]`, `us[m,N,S(,B)]` of `sample_policy` (ddp_gmm_fit_f64; the formulas are in include/ddp_amd.h):
+the dynamics prior of the guided-policy-search round.  `pool=true`: one mixture over all trajectories (`G = 1`), `false`: one per
+trajectory (`G = B`).  `init = (pi[K,G], mu[p,K,G], Sigma[p,p,K,G])`, or the named tuple an earlier call returned, is the start; without
+it an M-step from a hard assignment drawn from `seed`.  Returns a named tuple with `pi[K,G]`, `mu[p,K,G]`, `Sigma[p,p,K,G]`, `ll[iters,G]`,
+`status[G]` (0, or `k` for the first cluster, counted from 1, that emptied or whose `Sigma` is not positive definite: that mixture is NaN).
+"""
+function fit_gmm(xs, us, K::Integer; iters::Integer=20, reg::Real=1e-6, seed::Integer=0, init=nothing, pool::Bool=true, traj0::Integer=0,
+                 handle::Handle=default_handle())
+    batched = ndims(xs) == 4
+    n, N, S = size(xs, 1), size(xs, 2), size(xs, 3)
+    m = size(us, 1)
+    B = batched ? size(xs, 4) : 1
+    bt = batched ? (B,) : ()
+    size(us) == (m, N, S, bt...) || throw(DDPError(-1, "fit_gmm: us does not match xs in N, S [, B]"))
+    p = 2n + m
+    G = pool ? 1 : B
+    pi0 = Float64[]; mu0 = Float64[]; Sg0 = Float64[]
+    if init !== nothing
+        pi0 = _f64(init[1]); mu0 = _f64(init[2]); Sg0 = _f64(init[3])
+        (length(pi0) == K * G && length(mu0) == p * K * G && length(Sg0) == p * p * K * G) ||
+            throw(DDPError(-1, "fit_gmm: init should be (pi[K,G], mu[p,K,G], Sigma[p,p,K,G]), p = 2n + m"))
+    end
+    xs = _f64(xs); us = _f64(us)
+    lo, hi = _seed_words(seed)
+    pik = zeros(max(K, 0), G); mu = zeros(p, max(K, 0), G); Sigma = zeros(p, p, max(K, 0), G); ll = zeros(max(iters, 0), G)
+    status = zeros(Int32, G)
+    rg = Float64(reg)
+    pl = pool ? 1 : 0
+    GC.@preserve xs us pi0 mu0 Sg0 pik mu Sigma ll status begin
+        check(@ccall libddp.ddp_gmm_fit_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, K::Cint, iters::Cint, pl::Cint,
+            traj0::Cint, xs::Ptr{Float64}, us::Ptr{Float64}, rg::Cdouble, lo::Cint, hi::Cint, _ptr_or_null(pi0)::Ptr{Float64},
+            _ptr_or_null(mu0)::Ptr{Float64}, _ptr_or_null(Sg0)::Ptr{Float64}, pik::Ptr{Float64}, mu::Ptr{Float64}, Sigma::Ptr{Float64},
+            _ptr_or_null(ll)::Ptr{Float64}, status::Ptr{Int32})::Cint)
+    end
+    return (pi=pik, mu=mu, Sigma=Sigma, ll=ll, status=status, pool=pool)
+end
+
+"""
+    gmm_prior(gmm, xs, us; m0=1.0, n0=1.0, handle) -> (Φ, μ0, m0, n0)
+
+The normal-inverse-Wishart prior of every step from a mixture of `fit_gmm` (ddp_gmm_prior_f64): with `r` the responsibilities of the
+step's `S` points, `ω_k = mean_s r_sk`, `μ0 = Σ_k ω_k μ_k`, `Φ = n0 Σ_k ω_k (Σ_k + (μ_k - μ0)(μ_k - μ0)')`.  The tuple `Φ[p,p,N(,B)]`,
+`μ0[p,N(,B)]`, `m0`, `n0` is what `fit_dynamics(xs, us; prior=...)` takes.  A step with a point that is not finite, or a mixture that is
+not usable, gives NaN in that step's `Φ`, `μ0`; slot `N` has no transition and is zeros.
+"""
+function gmm_prior(gmm, xs, us; m0::Real=1.0, n0::Real=1.0, handle::Handle=default_handle())
+    batched = ndims(xs) == 4
+    n, N, S = size(xs, 1), size(xs, 2), size(xs, 3)
+    m = size(us, 1)
+    B = batched ? size(xs, 4) : 1
+    bt = batched ? (B,) : ()
+    size(us) == (m, N, S, bt...) || throw(DDPError(-1, "gmm_prior: us does not match xs in N, S [, B]"))
+    p = 2n + m
+    K = size(gmm.pi, 1)
+    G = gmm.pool ? 1 : B
+    pik = _f64(gmm.pi); mu = _f64(gmm.mu); Sigma = _f64(gmm.Sigma)
+    (length(pik) == K * G && length(mu) == p * K * G && length(Sigma) == p * p * K * G) ||
+        throw(DDPError(-1, "gmm_prior: the mixture should be pi[K,G], mu[p,K,G], Sigma[p,p,K,G], p = 2n + m"))
+    xs = _f64(xs); us = _f64(us)
+    Phi = result_array(p, p, N, bt...); mu0 = result_array(p, N, bt...)
+    status = zeros(Int32, N, bt...)
+    m0f = Float64(m0); n0f = Float64(n0)
+    pl = gmm.pool ? 1 : 0
+    GC.@preserve xs us pik mu Sigma Phi mu0 status begin
+        check(@ccall libddp.ddp_gmm_prior_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, K::Cint, pl::Cint,
+            xs::Ptr{Float64}, us::Ptr{Float64}, pik::Ptr{Float64}, mu::Ptr{Float64}, Sigma::Ptr{Float64}, m0f::Cdouble, n0f::Cdouble,
+            Phi::Ptr{Float64}, mu0::Ptr{Float64}, status::Ptr{Int32})::Cint)
+    end
+    return Phi, mu0, m0f, n0f
+end
+
 function iLQG(problem::DeviceProblem, x0, u0; lims=[], α=DEFAULT_ALPHA, tol_fun=1e-7, tol_grad=1e-4, max_iter=500, λ=1.0, dλ=1.0,
               λfactor=1.6, λmax=1e10, λmin=1e-6, regType=1, reduce_ratio_min=0, cost=[], handle::Handle=default_handle(),
               params=nothing, t0=nothing, policy=GaussianPolicy{Float64})

@@ -888,6 +888,53 @@ int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *
                             double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
                             double *cost, double *dV, double *stats, int *iters);
 
+/* The dynamics prior of the guided-policy-search round (Levine & Abbeel 2014): a Gaussian mixture over the transition tuples of all
+ * steps and samples, and from it the normal-inverse-Wishart prior (Phi, mu0) of every step that ddp_fit_dynamics_* takes with
+ * prior_layout = 1.  From xs[n,N,S,B], us[m,N,S,B] the point of (step i < N - 1, sample s, trajectory b) is w = [xs_i; us_i; xs_{i+1}],
+ * p = 2n + m entries (the w of ddp_fit_dynamics).  pool = 1: one mixture over all trajectories, G = 1, P = (N - 1) S B points;
+ * pool = 0: one per trajectory, G = B, P = (N - 1) S points each.
+ *
+ * ddp_gmm_fit: K clusters, `iters` EM iterations, reg >= 0 absolute.
+ *   M-step from r[j,k]:  N_k = sum_j r_jk,  pi_k = N_k / P,  mu_k = sum_j r_jk w_j / N_k,
+ *                        Sigma_k = sum_j r_jk (w_j - mu_k)(w_j - mu_k)' / N_k + reg I   (the products are centred on the new mu_k);
+ *   E-step:  Sigma_k = L_k L_k',  lo_jk = log pi_k - (p/2) log 2 pi - sum_c log L_k,cc - |L_k^-1 (w_j - mu_k)|^2 / 2,
+ *            lse_j = logsumexp_k lo_jk,  r_jk = exp(lo_jk - lse_j),  ll = sum_j lse_j.
+ *   Start: pi0[K,G], mu0[p,K,G], Sigma0[p,p,K,G] when they are given (all three, or all NULL; the lower triangle of Sigma0 is read) —
+ *   the warm start of the next round; else an M-step from a hard assignment: the cluster of point (i, s, b) is the first output word of
+ *   Philox4x32-10 mod K with counter (i, s, traj0 + b, 0x80000000) and key (seed_lo, seed_hi) (the fourth word keeps the draw off the
+ *   sampler's noise stream, whose fourth word is a pair index < 4): independent of the launch geometry and of B.  Then `iters` times
+ *   (E-step, M-step); ll[t,g] is the log-likelihood the E-step of iteration t sees; iters = 0 returns the start (ll may be NULL).
+ *   Outputs pi[K,G], mu[p,K,G], Sigma[p,p,K,G] (both triangles, exactly symmetric), ll[iters,G], status[G].  Every mixture that is
+ *   formed, the start included, is tested: status[g] is 0, or k + 1 for the smallest k whose N_k (pi_k of a start that is given) is
+ *   not a positive finite number, whose mu_k of a given start is not finite, or for which a pivot of Sigma_k's factorisation is not a
+ *   positive finite number (the pivot test of ddp_user_sample's factorisation).  The first iteration where this happens sets the
+ *   status; that mixture's pi, mu, Sigma and the ll of the iterations after it are NaN, and no other mixture is touched.
+ *
+ * ddp_gmm_prior: per step i < N - 1 and trajectory b, with mixture g = pool ? 0 : b: r_sk of the step's S points by the E-step above,
+ *   omega_k = (1/S) sum_s r_sk,  mu0 = sum_k omega_k mu_k,  Phi = n0 sum_k omega_k (Sigma_k + (mu_k - mu0)(mu_k - mu0)'), exactly
+ *   symmetric (the lower triangle of Sigma is read) -> Phi[p,p,N,B], mu0[p,N,B], status[N,B]; slot N - 1: zeros, status 0.  status 2:
+ *   the mixture is not usable (the test above on the mixture as given); else 1: a point of the step is not finite.  In both cases that
+ *   step's Phi, mu0 are NaN and no other step is touched.  m0 is only validated: it goes to ddp_fit_dynamics_* with n0.
+ *
+ * 1 <= n <= 32, 1 <= m <= 8, 1 <= K <= 32, N >= 2, S >= 1, P >= 2, iters >= 0, reg, m0, n0 finite and >= 0, pool 0 or 1; anything else
+ * is refused by name before any launch.  Every sum has a fixed order: two calls give the same bits; with pool = 0 a call on a slice of
+ * the trajectories (with its traj0) gives the bits of that slice of the full call, for ddp_gmm_prior in both modes; with pool = 1 the
+ * split of the points over work-groups and the order of the final reduction depend on (n, m, K, N, S, B) alone.  The responsibilities
+ * (K P doubles), L_k^-1 and the per-work-group partial sums live in the handle's scratch.  Kernels: gmm.hip, the Mahalanobis terms and
+ * the weighted Gram matrices on v_mfma_f64_16x16x4.                                                                                 */
+int ddp_gmm_fit_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, int K, int iters, int pool, int traj0, const double *xs,
+                        const double *us, double reg, int seed_lo, int seed_hi, const double *pi0, const double *mu0, const double *Sigma0,
+                        double *pi, double *mu, double *Sigma, double *ll, int32_t *status);
+int ddp_gmm_fit_f64(ddp_handle h, int n, int m, int N, int S, int B, int K, int iters, int pool, int traj0, const double *xs,
+                    const double *us, double reg, int seed_lo, int seed_hi, const double *pi0, const double *mu0, const double *Sigma0,
+                    double *pi, double *mu, double *Sigma, double *ll, int32_t *status);
+int ddp_gmm_prior_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, int K, int pool, const double *xs, const double *us,
+                          const double *pi, const double *mu, const double *Sigma, double m0, double n0, double *Phi, double *mu0,
+                          int32_t *status);
+int ddp_gmm_prior_f64(ddp_handle h, int n, int m, int N, int S, int B, int K, int pool, const double *xs, const double *us,
+                      const double *pi, const double *mu, const double *Sigma, double m0, double n0, double *Phi, double *mu0,
+                      int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif
