@@ -31,7 +31,7 @@ from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
            "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
-           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics", "GMM", "fit_gmm", "gmm_prior"]
+           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics", "GMM", "fit_gmm", "gmm_prior", "fit_cost"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -208,12 +208,17 @@ class DeviceProblem:
     ``fitted=True`` (DDP_USER_FITTED): the program also holds ``ddp_user_rollout_fit``, the rollout on a fitted time-varying affine model
     ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` (the tables ``fit_dynamics`` returns) under the problem's own cost:
     ``forward_pass(..., model=(fx, fu, fc))`` runs it and ``kl.iLQGkl(..., fitted=True)`` plans on that model throughout; every other
-    entry point ignores the flag.  Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
+    entry point ignores the flag.  Not together with ``wave``, ``second_order_wave``, ``clock`` or ``constraints`` (deferred).
+    ``cost_fit=True`` (DDP_USER_COST_FIT): the program also holds ``ddp_user_cost_fit``, and ``fit_cost`` fits the quadratic cost model of
+    a guided-policy-search round to the samples ``sample_policy`` returns — the cost expanded at every sample, moved to the nominal and
+    averaged; ``kl.iLQGkl(..., cost_model=...)`` plans on it.  Every other entry point ignores the flag.  Not together with ``wave``,
+    ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False):
+                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False, cost_fit=False):
         self.clock = bool(clock)
+        self.cost_fit = bool(cost_fit)
         self.sample = bool(sample)
         self.fitted = bool(fitted)
         self.nc = int(constraints)
@@ -227,7 +232,7 @@ class DeviceProblem:
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
                       (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
                       (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0) |
-                      (_lib.USER_FITTED if self.fitted else 0))
+                      (_lib.USER_FITTED if self.fitted else 0) | (_lib.USER_COST_FIT if self.cost_fit else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -935,6 +940,51 @@ def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
     if not batched:
         return fx[..., 0], fu[..., 0], fc[..., 0], cov[..., 0], status[..., 0]
     return fx, fu, fc, cov, status
+
+
+# ------------------------------------------------------------------------------ fit_cost
+def fit_cost(problem, xs, us, x, u, *, params=None, handle=None):
+    """The quadratic cost model of a guided-policy-search round, fitted on the device to the rollouts ``xs[n,N,S(,B)]``, ``us[m,N,S(,B)]``
+    that ``sample_policy`` returns, around the nominal ``x[n,N(,B)]``, ``u[m,N(,B)]``, for a ``DeviceProblem`` made with
+    ``cost_fit=True``: the problem's cost is expanded to second order at every sample ``(x̂_s, û_s)``, the expansion is moved to the
+    nominal (``δx = diff(x̂_s, x_i)`` with the problem's ``diff``, ``δu = û_s - u_i``) and the results are averaged over the samples,
+    ``cxx = mean cxx_s`` (``cxu``, ``cuu`` alike), ``cx = mean (cx_s - cxx_s δx - cxu_s δu)``, ``cu = mean (cu_s - cxu_sᵀ δx - cuu_s δu)``,
+    ``c0 = mean (c_s - cx_s·δx - cu_s·δu + ½ [δx; δu]ᵀ H_s [δx; δu])``.  Returns ``(cx[n,N(,B)], cu[m,N(,B)], cxx[n,n,N(,B)],
+    cxu[n,m,N(,B)], cuu[m,m,N(,B)], c0[N(,B)])`` — the first five are what ``kl.iLQGkl(..., cost_model=...)`` takes; they are
+    time-varying also with ``const_hessian``.  With ``terminal`` the last step holds the terminal cost as ``derivatives`` does.  Two calls
+    give the same bits, and a call on some of the trajectories gives the bits of their slice of the full call; a non-finite sample makes
+    the outputs of its own step and trajectory non-finite and touches nothing else."""
+    if not isinstance(problem, DeviceProblem):
+        raise TypeError("fit_cost: a DeviceProblem is needed")
+    if not problem.cost_fit:
+        raise DDPError("fit_cost: a DeviceProblem made with cost_fit=True (DDP_USER_COST_FIT) is needed")
+    xs, us, x, u = _lib.f64(xs), _lib.f64(us), _lib.f64(x), _lib.f64(u)
+    if xs.ndim not in (3, 4) or us.ndim != xs.ndim:
+        raise DDPError("fit_cost: xs, us should be (n, N, S), (m, N, S) [+ batch axis], got %s, %s" % (xs.shape, us.shape))
+    batched = xs.ndim == 4
+    if x.ndim != xs.ndim - 1 or u.ndim != xs.ndim - 1:
+        raise DDPError("fit_cost: x, u should be (n, N), (m, N)%s, got %s, %s" % (" + (B,)" if batched else "", x.shape, u.shape))
+    if not batched:
+        xs, us, x, u = (_lib.f64(a[..., None]) for a in (xs, us, x, u))
+    n, N, S, B = xs.shape
+    m = us.shape[0]
+    _user_shapes(problem, n, m)
+    if us.shape[1:] != (N, S, B):
+        raise DDPError("fit_cost: us (m, %s) does not match xs (n, %s) in N, S [, B]" % (us.shape[1:], xs.shape[1:]))
+    if x.shape != (n, N, B) or u.shape != (m, N, B):
+        raise DDPError("fit_cost: x, u should be (n, N), (m, N) = (%d, %d), (%d, %d)%s, got %s, %s"
+                       % (n, N, m, N, " + (B = %d,)" % B if batched else "", x.shape if batched else x.shape[:-1],
+                          u.shape if batched else u.shape[:-1]))
+    if S < 1:
+        raise DDPError("fit_cost: S = %d (>= 1)" % S)
+    P, pb = problem._params(B, params)
+    h = handle or default_handle()                         # (behind the checks that need no device)
+    cx = _lib.result_array((n, N, B)); cu = _lib.result_array((m, N, B)); cxx = _lib.result_array((n, n, N, B))
+    cxu = _lib.result_array((n, m, N, B)); cuu = _lib.result_array((m, m, N, B)); c0 = _lib.result_array((N, B))
+    _lib.check(_lib.lib().ddp_user_cost_fit_f64(h.raw, problem._ptr(h), N, S, B, _lib.ptr(P), pb, *map(_lib.ptr, (xs, us, x, u)),
+                                                *map(_lib.ptr, (cx, cu, cxx, cxu, cuu, c0))))
+    out = (cx, cu, cxx, cxu, cuu, c0)
+    return out if batched else tuple(a[..., 0] for a in out)
 
 
 # ------------------------------------------------------------------------------ fit_gmm, gmm_prior

@@ -41,12 +41,14 @@ EXPORTS = [
     "ddp_fit_dynamics_f64_dev", "ddp_fit_dynamics_f64",
     "ddp_user_rollout_fit_f64_dev", "ddp_user_rollout_fit_f64", "ddp_user_ilqgkl_fit_f64_dev", "ddp_user_ilqgkl_fit_f64",
     "ddp_gmm_fit_f64_dev", "ddp_gmm_fit_f64", "ddp_gmm_prior_f64_dev", "ddp_gmm_prior_f64",
+    "ddp_user_cost_fit_f64_dev", "ddp_user_cost_fit_f64", "ddp_user_ilqgkl_cost_f64_dev", "ddp_user_ilqgkl_cost_f64",
 ]
-GMM_EXPORTS = tuple(EXPORTS[-4:])              # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
-FITTED_EXPORTS = tuple(EXPORTS[-8:-4])         # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
-FIT_EXPORTS = tuple(EXPORTS[-10:-8])            # fit_dynamics: absent from A/B builds of the library from before it
-SAMPLE_EXPORTS = tuple(EXPORTS[-14:-10])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-22:-14])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+COST_FIT_EXPORTS = tuple(EXPORTS[-4:])         # the entries of DDP_USER_COST_FIT and of a cost model: absent from A/B builds of the library from before them
+GMM_EXPORTS = tuple(EXPORTS[-8:-4])            # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
+FITTED_EXPORTS = tuple(EXPORTS[-12:-8])        # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-14:-12])           # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-18:-14])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-26:-18])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -90,6 +92,7 @@ class ALOpts(C.Structure):
 
 
 ILQGKL_NSTATS = 12
+USER_COST_FIT = 8192           # DDP_USER_COST_FIT: the flag of DeviceProblem(..., cost_fit=True)
 USER_FITTED = 4096             # DDP_USER_FITTED: the flag of DeviceProblem(..., fitted=True)
 USER_SAMPLE = 2048             # DDP_USER_SAMPLE: the flag of DeviceProblem(..., sample=True)
 USER_CONSTRAINTS = 1024        # DDP_USER_CONSTRAINTS: the flag of DeviceProblem(..., constraints=nc)
@@ -211,6 +214,12 @@ def lib():
             klfit_args = [vp, vp, ci, ci, cd, ci, vp] + [cd] * 7 + [ci] + [cd] * 3 + [cd] * 3 + [cd] * 10 + [vp]
             L.ddp_user_ilqgkl_fit_f64.argtypes = klfit_args
             L.ddp_user_ilqgkl_fit_f64_dev.argtypes = klfit_args
+        if hasattr(L, "ddp_user_cost_fit_f64"):               # DDP_USER_COST_FIT; absent from A/B builds of the library from before the flag
+            cost_fit_args = [vp, vp, ci, ci, ci, cd, ci] + [cd] * 4 + [cd] * 6
+            L.ddp_user_cost_fit_f64.argtypes = cost_fit_args
+            L.ddp_user_cost_fit_f64_dev.argtypes = cost_fit_args
+            L.ddp_user_ilqgkl_cost_f64.argtypes = klfit_args + [cd] * 5
+            L.ddp_user_ilqgkl_cost_f64_dev.argtypes = klfit_args + [cd] * 5
         if hasattr(L, "ddp_gmm_fit_f64"):                     # absent from A/B builds of the library from before it
             gmm_args = [vp] + [ci] * 9 + [cd, cd, C.c_double, ci, ci] + [cd] * 7 + [vp]
             L.ddp_gmm_fit_f64.argtypes = gmm_args
@@ -227,7 +236,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS + COST_FIT_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

@@ -164,12 +164,16 @@ int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_
 
 // the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev; model_fx == NULL: the family's own fx of STEP 1).
 // fit_fx, fit_fu, fit_fc [.,.,N,B] (all three or none): the loop plans on that fitted model — back_pass_gps takes fit_fx, fit_fu, the
-// rollouts run on the family with the tables set (FitScope), model_fx == NULL means fit_fx
+// rollouts run on the family with the tables set (FitScope), model_fx == NULL means fit_fx.
+// cm_cx[n,N,B], cm_cu[m,N,B], cm_cxx[n,n,N,B], cm_cxu[n,m,N,B], cm_cuu[m,m,N,B] (all five or none): a cost model — the backward passes
+// take these arrays in place of the cost derivatives STEP 1 wrote; nothing else of the loop changes
 int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
                           const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
                           int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
                           double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
-                          const double *fit_fx = nullptr, const double *fit_fu = nullptr, const double *fit_fc = nullptr);
+                          const double *fit_fx = nullptr, const double *fit_fu = nullptr, const double *fit_fc = nullptr,
+                          const double *cm_cx = nullptr, const double *cm_cu = nullptr, const double *cm_cxx = nullptr,
+                          const double *cm_cxu = nullptr, const double *cm_cuu = nullptr);
 
 // sample.hip: the lower Cholesky factors L[m,m,N,B] of Sigma[m,m,N,B] and status[B] (0, or i + 1 of the first step that is not positive
 // definite), and the moments xmean[n,N,B] / xcov[n,n,N,B] (either may be NULL) of xs[n,N,S,B] over its samples; the device is current

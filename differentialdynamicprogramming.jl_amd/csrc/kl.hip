@@ -946,9 +946,14 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
                        const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
                        double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
                        double *dV, double *stats, int *iters_out, const double *fit_fx = nullptr, const double *fit_fu = nullptr,
-                       const double *fit_fc = nullptr)
+                       const double *fit_fc = nullptr, const double *cm_cx = nullptr, const double *cm_cu = nullptr,
+                       const double *cm_cxx = nullptr, const double *cm_cxu = nullptr, const double *cm_cuu = nullptr)
 {
     DDP_CHECK((!fit_fx && !fit_fu && !fit_fc) || (f && fit_fx && fit_fu && fit_fc), "ilqgkl: a fitted model is fx, fu and fc, with a user problem");
+    // a cost model: cx[n,N,B], cu[m,N,B], cxx[n,n,N,B], cxu[n,m,N,B], cuu[m,m,N,B] in place of the cost derivatives of STEP 1
+    const bool cm = cm_cx != nullptr;
+    DDP_CHECK((!cm_cx && !cm_cu && !cm_cxx && !cm_cxu && !cm_cuu) || (f && cm_cx && cm_cu && cm_cxx && cm_cxu && cm_cuu),
+              "ilqgkl: a cost model is cx, cu, cxx, cxu and cuu, with a user problem");
     DDP_CHECK((p || f) && x0 && Kp && kp && Sp && Sip && (model_fx || f) && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV &&
               stats, "ilqgkl: null argument");
     ddp_ilqgkl_opts od;
@@ -965,7 +970,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     const bool fx_b = f || pend || p->dyn_batched, fx_rep = !f && !pend && !p->dyn_tv, fx_own = f || pend || fx_rep;
     // cost Hessians: [.,.,N] of the registered problem, [.,.,N,B] of a family; constant Hessians of a family [.,.,B], repeated along time
     // for every kernel but mid (the others want time-varying operands)
-    const bool cst = f && f->const_hessian;
+    const bool cst = f && f->const_hessian && !cm;         // (a cost model is time-varying and per trajectory, whatever the problem's own is)
     ddp_bp_desc d;
     d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = f != nullptr;
     d.regType = 1; d.has_lims = lims != nullptr;
@@ -1020,7 +1025,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     hipLaunchKernelGGL(kl_first_col_kernel, grid(n * B), dim3(256), 0, st, (int)n, (int)N, (int)B, x0, x0c);
     // STEP 1 (:86): derivs(x, u) with u = copy(traj_prev.k) (:45); a family evaluates every trajectory (no slot map: the loop recomputes all)
     if ((rc = M.df(h, (int)B, nullptr, x0, kp, nullptr, fxw, fuw, cx, cu, cxx, cxu, cuu))) return rc;
-    if ((rc = M.hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;      // const_hessian only
+    if (!cm && (rc = M.hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;      // const_hessian only
     if (hrep) {
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * NB), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * NB), 1, (const double *)hxx, cxx);
         hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * NB), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * NB), 1, (const double *)hxu, cxu);
@@ -1044,7 +1049,10 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
         cost0 = c0buf;
     }
     if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56); a fitted model: its fx
-    const BPCall gps = {d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, kp, nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
+    // a cost model: the backward passes take the caller's arrays (the cost derivatives STEP 1 wrote stay in scratch); cost0, the rollouts'
+    // user cost and the loop are as without one
+    const BPCall gps = {d, cm ? cm_cx : cx, cm ? cm_cu : cu, cm ? cm_cxx : cxx, cm ? cm_cxu : cxu, cm ? cm_cuu : cuu, fx, fu, nullptr, lims, kp,
+                        nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
     auto poll = [&](int *out) -> int {
         DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
         DDP_HIP(hipStreamSynchronize(st));
@@ -1101,14 +1109,15 @@ int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_op
                           const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
                           int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
                           double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
-                          const double *fit_fx, const double *fit_fu, const double *fit_fc)
+                          const double *fit_fx, const double *fit_fu, const double *fit_fc, const double *cm_cx, const double *cm_cu,
+                          const double *cm_cxx, const double *cm_cxu, const double *cm_cuu)
 {
     DDP_DEVICE(h);
     DDP_CHECK(f, "ilqgkl: null problem");
     DDP_CHECK(!f->second_order, "ilqgkl: a DDP_USER_SECOND_ORDER problem is refused (back_pass_gps has no second-order variant); make the "
                                 "problem without the flag for the KL loop");
     return ilqgkl_impl(h, nullptr, f, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                       Vxx, cost, dV, stats, iters, fit_fx, fit_fu, fit_fc);
+                       Vxx, cost, dV, stats, iters, fit_fx, fit_fu, fit_fc, cm_cx, cm_cu, cm_cxx, cm_cxu, cm_cuu);
 }
 
 extern "C" {

@@ -20,6 +20,7 @@
 #include "user_problem_wave_kernels.h"
 #include "user_sample_kernels.h"
 #include "user_fitted_kernels.h"
+#include "user_cost_fit_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 #include "back_pass_wide_kernel.h"   // BPWArgs, WLds, bpw_fill: the wide kernel's step, shared with ddp_user_back_pass2_wave
 #include "philox_text.h"         // kPhiloxText: the text of philox.h (written by build.py)
@@ -31,6 +32,7 @@ DDP_USER_ABI3
 DDP_USER_ABI_C
 DDP_USER_ABI_SAMPLE
 DDP_USER_ABI_FIT
+DDP_USER_ABI_COST_FIT
 
 namespace {
 
@@ -76,9 +78,9 @@ std::string g_log;                                          // log of the last c
 
 // LDS budgets of the generated kernels (per 64-lane work-group): the rollout keeps several waves per CU (its time loop is a
 // dependency chain, latency is hidden by more rollouts in flight), the derivative kernel is a stream of stores
-constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024, FIT_LDS = 48 * 1024;
+constexpr int ROLL_LDS = 32 * 1024, DF_LDS = 64 * 1024, MAX_LDS = 64 * 1024, FIT_LDS = 48 * 1024, COST_FIT_LDS = 48 * 1024;
 
-struct Layout { int chunk, rlanes, dflanes, adj, adh, wg, schunk, slanes, fchunk, flanes; };
+struct Layout { int chunk, rlanes, dflanes, adj, adh, wg, schunk, slanes, fchunk, flanes, clanes, cchunk, csb; };
 
 // bytes of LDS of ddp_user_rollout_fit with `lanes` rollouts per work-group and `chunk` steps per chunk: u, x, k, K and the tables fx, fu,
 // fc per rollout at odd strides, and the two slot arrays
@@ -86,6 +88,14 @@ size_t fit_lds(int n, int m, int lanes, int chunk)
 {
     const int ps = 2 * m + m * n + n, ts = n * n + n * m + n;
     return (size_t)lanes * (((chunk * ps) | 1) + ((chunk * ts) | 1) + 1) * 8;
+}
+
+// bytes of LDS of ddp_user_cost_fit with `lanes` (step, trajectory) pairs per work-group and `csb` sample indices per round: per lane the
+// derivatives and the sums (cx, cu, cxx, cxu, cuu each), c0, the nominal and csb samples at an odd stride, and the slot array
+size_t cost_fit_lds(int n, int m, int lanes, int csb)
+{
+    const int dc = n + m + n * n + n * m + m * m;
+    return (size_t)lanes * (((2 * dc + 1 + (csb + 1) * (n + m)) | 1) + 1) * 8;
 }
 
 // chunk length and rollouts per work-group of ddp_user_rollout, (step, trajectory) pairs per work-group of ddp_user_df; 0 lanes = no fit.
@@ -128,6 +138,14 @@ Layout layout_of(int n, int m, int flags)
         L.fchunk = 1;
         while (L.flanes > 1 && fit_lds(n, m, L.flanes, 1) > (size_t)MAX_LDS) --L.flanes;
     }
+    // ddp_user_cost_fit (DDP_USER_COST_FIT): one lane per (step, trajectory) with two slots of the cost derivatives in LDS, so the lanes
+    // are what fits 64 KB (car 4x2: 64, lq 10x2: 16, lq 32x8: 2, as ddp_user_df); up to 8 consecutive steps of a trajectory per work-group
+    // (the contiguous run of a sample), and the sample indices per round that keep the work-group within COST_FIT_LDS, one at least
+    L.clanes = 64;
+    while (L.clanes > 1 && cost_fit_lds(n, m, L.clanes, 1) > (size_t)MAX_LDS) L.clanes /= 2;
+    L.cchunk = L.clanes < 8 ? L.clanes : 8;
+    L.csb = 1;
+    while (L.csb < 8 && cost_fit_lds(n, m, L.clanes, L.csb + 1) <= (size_t)COST_FIT_LDS) ++L.csb;
     L.wg = 0;
     if (flags & DDP_USER_WAVE) {
         // ddp_user_rollout_wave: a group of wg lanes (the power of two >= m, 8 at least) per rollout, 64 / wg rollouts per work-group;
@@ -244,7 +262,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK(nparam >= 0 && nparam <= DDP_USER_MAX_NPARAM, "user problem: nparam = %d out of [0, %d] (DDP_USER_MAX_NPARAM)", nparam,
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
-                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE | DDP_USER_FITTED)) == 0,
+                         DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE | DDP_USER_FITTED |
+                         DDP_USER_COST_FIT)) == 0,
               "user problem: unknown flags 0x%x", flags);
     if (flags & DDP_USER_SAMPLE) {
         // deferred, not impossible: ddp_user_sample is a lane-per-sample kernel with the state in registers (n <= 32, m <= 8) and hands
@@ -268,6 +287,18 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
                                              "clock)");
         DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_FITTED | DDP_USER_CONSTRAINTS is refused (deferred: "
                                                    "ddp_user_rollout_fit takes no multipliers)");
+    }
+    if (flags & DDP_USER_COST_FIT) {
+        // deferred, not impossible: ddp_user_cost_fit is a lane-per-(step, trajectory) kernel with the cost derivatives of a lane in LDS
+        // (n <= 32, m <= 8) and hands the user's functions neither a clock nor multipliers
+        DDP_CHECK(!(flags & DDP_USER_SECOND_ORDER_WAVE), "user problem: DDP_USER_COST_FIT | DDP_USER_SECOND_ORDER_WAVE is refused (deferred: "
+                                                         "ddp_user_cost_fit is sized for n <= %d, m <= %d)", DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!wave, "user problem: DDP_USER_COST_FIT | DDP_USER_WAVE is refused (deferred: ddp_user_cost_fit is sized for n <= %d, m <= %d)",
+                  DDP_MAX_N_USER, DDP_MAX_M);
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_COST_FIT | DDP_USER_CLOCK is refused (deferred: ddp_user_cost_fit takes no "
+                                             "clock)");
+        DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_COST_FIT | DDP_USER_CONSTRAINTS is refused (deferred: "
+                                                   "ddp_user_cost_fit takes no multipliers)");
     }
     if (flags & DDP_USER_CONSTRAINTS) {
         // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
@@ -323,6 +354,8 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
     DDP_CHECK((size_t)L.rlanes * ((L.chunk * ps) | 1) * 8 <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the rollout's LDS", n, m);
     if (flags & DDP_USER_FITTED)
         DDP_CHECK(fit_lds(n, m, L.flanes, L.fchunk) <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the LDS of ddp_user_rollout_fit", n, m);
+    if (flags & DDP_USER_COST_FIT)
+        DDP_CHECK(cost_fit_lds(n, m, L.clanes, L.csb) <= (size_t)MAX_LDS, "user problem: n = %d, m = %d does not fit the LDS of ddp_user_cost_fit", n, m);
     return 0;
 }
 
@@ -439,6 +472,14 @@ std::string program_text(const char *source, int n, int m, int nparam, int flags
         s += "\n";
         s += kUserKernelsFit;
     }
+    if (flags & DDP_USER_COST_FIT) {                             // a problem without the flag: the text above, nothing more; behind the fitted tail
+        snprintf(head, sizeof head, "\n#define DDP_CLANES %d\n#define DDP_CCHUNK %d\n#define DDP_CSB %d\n#line 1 \"ddp_user_kernels_cost_fit\"\n",
+                 L.clanes, L.cchunk, L.csb);
+        s += head;
+        s += DDP_USER_ABI_COST_FIT_TEXT;
+        s += "\n";
+        s += kUserKernelsCostFit;
+    }
     return s;
 }
 
@@ -506,6 +547,7 @@ struct Module {
     hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
     hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE)
     hipFunction_t rollfit = nullptr;                             // ddp_user_rollout_fit (DDP_USER_FITTED)
+    hipFunction_t costfit = nullptr;                             // ddp_user_cost_fit (DDP_USER_COST_FIT)
     hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
     const char *roll_name = nullptr;                             // ddp_user_rollout, or ddp_user_rollout_wave (DDP_USER_WAVE)
@@ -859,7 +901,8 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
                         (!(flags & DDP_USER_CONSTRAINTS) || (hipModuleGetFunction(&M.con, M.mod, "ddp_user_constraints") == hipSuccess &&
                                                              hipModuleGetFunction(&M.alup, M.mod, "ddp_user_al_update") == hipSuccess)) &&
                         (!(flags & DDP_USER_SAMPLE) || hipModuleGetFunction(&M.sample, M.mod, "ddp_user_sample") == hipSuccess) &&
-                        (!(flags & DDP_USER_FITTED) || hipModuleGetFunction(&M.rollfit, M.mod, "ddp_user_rollout_fit") == hipSuccess);
+                        (!(flags & DDP_USER_FITTED) || hipModuleGetFunction(&M.rollfit, M.mod, "ddp_user_rollout_fit") == hipSuccess) &&
+                        (!(flags & DDP_USER_COST_FIT) || hipModuleGetFunction(&M.costfit, M.mod, "ddp_user_cost_fit") == hipSuccess);
         if (!ok) {
             hipModuleUnload(M.mod);
             ddp_set_error("user problem: a kernel of the compiled program is missing");
@@ -1571,6 +1614,116 @@ int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *
     if ((rc = S.commit())) return rc;
     return S.finish(ddp_user_ilqgkl_fit_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
                                                 det, dfx, dfu, dfc, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters));
+}
+
+// ---- DDP_USER_COST_FIT: the quadratic cost model fitted to sampled rollouts (ddp_user_cost_fit), and the KL loop on a cost model
+// what both flavours of ddp_user_cost_fit refuse, before anything is staged or launched
+static int cost_fit_check(const UserProblem *P, int S, const double *xs, const double *us, const double *x, const double *u, const double *cx,
+                          const double *cu, const double *cxx, const double *cxu, const double *cuu, const double *c0)
+{
+    DDP_CHECK(P->mod->costfit, "cost_fit: the problem was made without DDP_USER_COST_FIT");
+    DDP_CHECK(S >= 1, "cost_fit: S = %d (>= 1)", S);
+    DDP_CHECK(xs && us && x && u && cx && cu && cxx && cxu && cuu && c0, "cost_fit: null argument");
+    return 0;
+}
+
+int ddp_user_cost_fit_f64_dev(ddp_handle h, void *up, int N, int S, int B, const double *params, int params_batched, const double *xs,
+                              const double *us, const double *x, const double *u, double *cx, double *cu, double *cxx, double *cxu,
+                              double *cuu, double *c0)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P, true);
+    if (rc) return rc;
+    if ((rc = cost_fit_check(P, S, xs, us, x, u, cx, cu, cxx, cxu, cuu, c0))) return rc;
+    const Layout &L = P->mod->L;
+    const long chunks = ((long)N + L.cchunk - 1) / L.cchunk, ctraj = L.clanes / L.cchunk, groups = ((long)B + ctraj - 1) / ctraj;
+    DDP_CHECK(chunks * groups <= 0x7fffffffL, "cost_fit: N = %d, B = %d is too large for one launch", N, B);
+    UserCostFitArgs a;
+    a.N = N; a.S = S; a.B = B; a.params_batched = P->params_batched;
+    a.params = P->params; a.xs = xs; a.us = us; a.x = x; a.u = u;
+    a.cx = cx; a.cu = cu; a.cxx = cxx; a.cxu = cxu; a.cuu = cuu; a.c0 = c0;
+    void *args[] = {&a};
+    DDP_HIP(hipModuleLaunchKernel(P->mod->costfit, (unsigned)(chunks * groups), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
+    h->last_kernel[1] = "ddp_user_cost_fit";
+    return 0;
+}
+
+int ddp_user_cost_fit_f64(ddp_handle h, void *up, int N, int S, int B, const double *params, int params_batched, const double *xs,
+                          const double *us, const double *x, const double *u, double *cx, double *cu, double *cxx, double *cxu,
+                          double *cuu, double *c0)
+{
+    UserProblem *P;
+    int rc = enter(h, up, N, B, params, params_batched, &P);
+    if (rc) return rc;
+    if ((rc = cost_fit_check(P, S, xs, us, x, u, cx, cu, cxx, cxu, cuu, c0))) return rc;
+    const size_t n = P->n, m = P->m, T = (size_t)N * B, R = (size_t)S * T;
+    const double *dp, *dxs, *dus, *dx, *du;
+    double *dcx, *dcu, *dcxx, *dcxu, *dcuu, *dc0;
+    Staging St(h, Staging::OWNED, "user problem");
+    St.in(&dp, params, (size_t)P->nparam * (params_batched ? B : 1)); St.in(&dxs, xs, n * R); St.in(&dus, us, m * R);
+    St.in(&dx, x, n * T); St.in(&du, u, m * T);
+    St.out(&dcx, cx, n * T); St.out(&dcu, cu, m * T); St.out(&dcxx, cxx, n * n * T); St.out(&dcxu, cxu, n * m * T);
+    St.out(&dcuu, cuu, m * m * T); St.out(&dc0, c0, T);
+    if ((rc = St.commit())) return rc;
+    return St.finish(ddp_user_cost_fit_f64_dev(h, up, N, S, B, dp, params_batched, dxs, dus, dx, du, dcx, dcu, dcxx, dcxu, dcuu, dc0));
+}
+
+// what both flavours of ddp_user_ilqgkl_cost refuse
+static int ilqgkl_cost_check(const UserProblem *U, const double *fx, const double *fu, const double *fc, const double *cx, const double *cu,
+                             const double *cxx, const double *cxu, const double *cuu)
+{
+    DDP_CHECK((fx && fu && fc) || (!fx && !fu && !fc), "ilqgkl_cost: fx, fu and fc are given all three (the plan is made on the tables) or all "
+                                                       "three NULL (on the problem's own model)");
+    DDP_CHECK(!fx || U->mod->rollfit, "ilqgkl_cost: the problem was made without DDP_USER_FITTED (the tables fx, fu, fc need it)");
+    DDP_CHECK(cx && cu && cxx && cxu && cuu, "ilqgkl_cost: a cost model is cx, cu, cxx, cxu and cuu (null argument)");
+    return 0;
+}
+
+int ddp_user_ilqgkl_cost_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                                 const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                                 const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                                 double *etab, const double *fx, const double *fu, const double *fc,
+                                 double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                                 double *cost, double *dV, double *stats, int *iters,
+                                 const double *cx, const double *cu, const double *cxx, const double *cxu, const double *cuu)
+{
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
+    if (rc) return rc;
+    if ((rc = ilqgkl_cost_check(U, fx, fu, fc, cx, cu, cxx, cxu, cuu))) return rc;
+    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
+                                 Vxx, cost, dV, stats, iters, fx, fu, fc, cx, cu, cxx, cxu, cuu);
+}
+
+int ddp_user_ilqgkl_cost_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                             const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                             const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                             double *etab, const double *fx, const double *fu, const double *fc,
+                             double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                             double *cost, double *dV, double *stats, int *iters,
+                             const double *cx, const double *cu, const double *cxx, const double *cxu, const double *cuu)
+{
+    UserProblem *U;
+    int rc = enter(h, up, N, B, params, params_batched, &U, false, "ilqgkl");
+    if (rc) return rc;
+    if ((rc = ilqgkl_cost_check(U, fx, fu, fc, cx, cu, cxx, cxu, cuu))) return rc;
+    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl_cost: null argument");
+    const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;
+    const double *dp, *dx0, *dc0, *dKp, *dkp, *dSp, *dSip, *dmf, *dR1, *dl, *dfx, *dfu, *dfc, *dmx, *dmu, *dmxx, *dmxu, *dmuu;
+    double *det, *dx, *du, *dK, *dS, *dSi, *dVx, *dVxx, *dc, *ddV, *ds;
+    Staging S(h, Staging::OWNED, "user problem");
+    S.in(&dp, params, (size_t)U->nparam * (params_batched ? B : 1)); S.in(&dx0, x0, n * T); S.in(&dc0, cost0, (size_t)B); S.in(&dKp, Kp, m * n * T);
+    S.in(&dkp, kp, m * T); S.in(&dSp, Sp, m * m * T); S.in(&dSip, Sip, m * m * T);
+    S.in(&dmf, model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)); S.in(&dR1, R1, n * n); S.in(&dl, lims, 2 * m);
+    S.in(&dfx, fx, n * n * T); S.in(&dfu, fu, n * m * T); S.in(&dfc, fc, n * T);
+    S.in(&dmx, cx, n * T); S.in(&dmu, cu, m * T); S.in(&dmxx, cxx, n * n * T); S.in(&dmxu, cxu, n * m * T); S.in(&dmuu, cuu, m * m * T);
+    S.inout(&det, etab, (size_t)3 * B); S.out(&dx, x, n * T); S.out(&du, u, m * T); S.out(&dK, K, m * n * T); S.out(&dS, Sigma, m * m * T);
+    S.out(&dSi, Sigmai, m * m * T); S.out(&dVx, Vx, n * T); S.out(&dVxx, Vxx, n * n * T); S.out(&dc, cost, CL * B); S.out(&ddV, dV, (size_t)2 * B);
+    S.out(&ds, stats, (size_t)DDP_ILQGKL_NSTATS * B);
+    if ((rc = S.commit())) return rc;
+    return S.finish(ddp_user_ilqgkl_cost_f64_dev(h, up, N, B, dp, params_batched, o, dx0, dc0, dKp, dkp, dSp, dSip, dmf, model_fx_batched, dR1, dl,
+                                                 det, dfx, dfu, dfc, dx, du, dK, dS, dSi, dVx, dVxx, dc, ddV, ds, iters, dmx, dmu, dmxx, dmxu,
+                                                 dmuu));
 }
 
 }   // extern "C"

@@ -551,6 +551,7 @@ const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of Devic
 const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
 const USER_SAMPLE = 2048               # DDP_USER_SAMPLE: the flag of DeviceProblem(...; sample=true)
 const USER_FITTED = 4096               # DDP_USER_FITTED: the flag of DeviceProblem(...; fitted=true)
+const USER_COST_FIT = 8192             # DDP_USER_COST_FIT: the flag of DeviceProblem(...; cost_fit=true)
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
 
@@ -987,6 +988,9 @@ end
 # fitted=true (DDP_USER_FITTED): the program also holds ddp_user_rollout_fit, the rollout on a fitted time-varying affine model
 # x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i (the tables of fit_dynamics) under the problem's cost: forward_pass(...; model=(fx, fu, fc)) runs it,
 # iLQGkl(...; fitted=true, fu_model, fc_model) plans on it throughout.  Not together with wave, second_order_wave, clock or constraints.
+# cost_fit=true (DDP_USER_COST_FIT): the program also holds ddp_user_cost_fit, and fit_cost fits the quadratic cost model of a
+# guided-policy-search round to the samples of sample_policy; iLQGkl(...; cost_model=(cx, cu, cxx, cxu, cuu)) plans on it.  Not together
+# with wave, second_order_wave, clock or constraints.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -1001,12 +1005,12 @@ end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
                        second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false,
-                       fitted::Bool=false)
+                       fitted::Bool=false, cost_fit::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
             (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0) |
-            (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0)
+            (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0) | (cost_fit ? USER_COST_FIT : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1344,6 +1348,38 @@ function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, handle::Handle=def
 end
 
 """
+    fit_cost(problem, xs, us, x, u; params=nothing, handle) -> cx, cu, cxx, cxu, cuu, c0
+
+The quadratic cost model of a guided-policy-search round, fitted on the device to the rollouts `xs[n,N,S(,B)]`, `us[m,N,S(,B)]` of
+`sample_policy` around the nominal `x[n,N(,B)]`, `u[m,N(,B)]`, for a `DeviceProblem` made with `cost_fit=true` (ddp_user_cost_fit_f64; the
+formulas are in include/ddp_amd.h): the cost is expanded at every sample, the expansion is moved to the nominal and the results are
+averaged over the samples.  `cx[n,N(,B)]`, `cu[m,N(,B)]`, `cxx[n,n,N(,B)]`, `cxu[n,m,N(,B)]`, `cuu[m,m,N(,B)]` are what
+`iLQGkl(...; cost_model=...)` takes; `c0[N(,B)]` is the model's value at the nominal.
+"""
+function fit_cost(problem::DeviceProblem, xs, us, x, u; params=nothing, handle::Handle=default_handle())
+    (problem.flags & USER_COST_FIT) != 0 || throw(DDPError(-1, "fit_cost: a DeviceProblem made with cost_fit=true (DDP_USER_COST_FIT) is needed"))
+    batched = ndims(xs) == 4
+    n, N, S = size(xs, 1), size(xs, 2), size(xs, 3)
+    m = size(us, 1)
+    B = batched ? size(xs, 4) : 1
+    bt = batched ? (B,) : ()
+    (n, m) == (problem.n, problem.m) || throw(DDPError(-1, "DeviceProblem: n, m of the arrays differ from the compiled ones"))
+    size(us) == (m, N, S, bt...) || throw(DDPError(-1, "fit_cost: us does not match xs in N, S [, B]"))
+    size(x) == (n, N, bt...) && size(u) == (m, N, bt...) || throw(DDPError(-1, "fit_cost: x, u should be (n, N), (m, N) [+ batch axis]"))
+    P, pb = _user_params(problem, B, params)
+    xs = _f64(xs); us = _f64(us); x = _f64(x); u = _f64(u)
+    cx = result_array(n, N, bt...); cu = result_array(m, N, bt...); cxx = result_array(n, n, N, bt...); cxu = result_array(n, m, N, bt...)
+    cuu = result_array(m, m, N, bt...); c0 = result_array(N, bt...)
+    up = _user_ptr(problem, handle)
+    GC.@preserve problem P xs us x u cx cu cxx cxu cuu c0 begin
+        check(@ccall libddp.ddp_user_cost_fit_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, S::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+            pb::Cint, xs::Ptr{Float64}, us::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, cx::Ptr{Float64}, cu::Ptr{Float64},
+            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, c0::Ptr{Float64})::Cint)
+    end
+    return cx, cu, cxx, cxu, cuu, c0
+end
+
+"""
     fit_gmm(xs, us, K; iters=20, reg=1e-6, seed=0, init=nothing, pool=true, traj0=0, handle) -> (pi, mu, Sigma, ll, status, pool)
 
 A `K`-cluster Gaussian mixture fitted by EM on the device to the transition tuples `w = [x̂_i; û_i; x̂_{i+1}]` (`p = 2n + m`) of all steps
@@ -1512,11 +1548,14 @@ end
 # iLQGkl with the user's closures (`ddp_user_ilqgkl_f64`): as the method for registered problems; `fx_model = nothing` means the
 # problem's own linearisation (the fx of STEP 1), `params` [nparam] or [nparam, B].  fitted=true (a problem made with fitted=true;
 # fx_model, fu_model, fc_model the tables of fit_dynamics, one set per trajectory): the whole loop plans on the fitted model
-# (`ddp_user_ilqgkl_fit_f64`); fitted=false: on the problem's own model, fx_model only shapes the state covariance
+# (`ddp_user_ilqgkl_fit_f64`); fitted=false: on the problem's own model, fx_model only shapes the state covariance.
+# cost_model=(cx, cu, cxx, cxu, cuu) ([n,N(,B)], [m,N(,B)], [n,n,N(,B)], [n,m,N(,B)], [m,m,N(,B)], e.g. from fit_cost): every backward pass
+# takes these arrays in place of the cost derivatives of STEP 1 (`ddp_user_ilqgkl_cost_f64`), with and without fitted=true
 function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, t0=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
                 ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
-                fitted::Bool=false, fu_model=nothing, fc_model=nothing, wide::Bool=false)
+                fitted::Bool=false, fu_model=nothing, fc_model=nothing, cost_model=nothing, wide::Bool=false)
     fitted && wide && throw(DDPError(-1, "iLQGkl: fitted=true together with wide=true is refused (deferred)"))
+    cost_model !== nothing && wide && throw(DDPError(-1, "iLQGkl: cost_model together with wide=true is refused (deferred)"))
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
     isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
     batched = ndims(x0) == 3
@@ -1554,7 +1593,23 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
             throw(DDPError(-1, "iLQGkl: fitted=true needs finite tables (a step fit_dynamics rejected is NaN: see its status)"))
     end
     up = _user_ptr(problem, handle)
-    if tabs !== nothing
+    if cost_model !== nothing
+        length(cost_model) == 5 || throw(DDPError(-1, "iLQGkl: cost_model should be five arrays (cx, cu, cxx, cxu, cuu)"))
+        mcx, mcu, mcxx, mcxu, mcuu = map(_f64, cost_model)
+        (size(mcx), size(mcu), size(mcxx), size(mcxu), size(mcuu)) == ((n, N, bt...), (m, N, bt...), (n, n, N, bt...), (n, m, N, bt...), (m, m, N, bt...)) ||
+            throw(DDPError(-1, "iLQGkl: cost_model cx, cu, cxx, cxu, cuu should be (n,N), (m,N), (n,n,N), (n,m,N), (m,m,N) [+ batch axis]"))
+        all(a -> all(isfinite, a), (mcx, mcu, mcxx, mcxu, mcuu)) || throw(DDPError(-1, "iLQGkl: cost_model needs finite arrays"))
+        tfx, tfu, tfc = tabs === nothing ? (Float64[], Float64[], Float64[]) : tabs
+        GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab tfx tfu tfc x u K S Si Vx Vxx cnew dV st mcx mcu mcxx mcxu mcuu begin
+            check(@ccall libddp.ddp_user_ilqgkl_cost_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
+                pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, c0::Ptr{Float64}, Kp::Ptr{Float64}, u0::Ptr{Float64}, Sp::Ptr{Float64},
+                Sip::Ptr{Float64}, _ptr_or_null(fxm)::Ptr{Float64}, (ndims(fxm) == 4)::Cint,
+                R1::Ptr{Float64}, _ptr_or_null(limsp)::Ptr{Float64}, etab::Ptr{Float64}, _ptr_or_null(tfx)::Ptr{Float64},
+                _ptr_or_null(tfu)::Ptr{Float64}, _ptr_or_null(tfc)::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+                S::Ptr{Float64}, Si::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cnew::Ptr{Float64}, dV::Ptr{Float64}, st::Ptr{Float64},
+                its::Ptr{Cint}, mcx::Ptr{Float64}, mcu::Ptr{Float64}, mcxx::Ptr{Float64}, mcxu::Ptr{Float64}, mcuu::Ptr{Float64})::Cint)
+        end
+    elseif tabs !== nothing
         tfx, tfu, tfc = tabs
         GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab tfx tfu tfc x u K S Si Vx Vxx cnew dV st begin
             check(@ccall libddp.ddp_user_ilqgkl_fit_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
@@ -1566,7 +1621,7 @@ function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=noth
                 its::Ptr{Cint})::Cint)
         end
     end
-    tabs === nothing && _with_clock(problem, handle, t0) do
+    tabs === nothing && cost_model === nothing && _with_clock(problem, handle, t0) do
         _with_kl_wide(handle, wide) do
             GC.@preserve problem P x0 c0 Kp u0 Sp Sip fxm R1 limsp etab x u K S Si Vx Vxx cnew dV st begin
                 check(@ccall libddp.ddp_user_ilqgkl_f64(handle.ptr::Ptr{Cvoid}, up::Ptr{Cvoid}, N::Cint, B::Cint, _ptr_or_null(P)::Ptr{Float64},
@@ -1655,6 +1710,26 @@ function user_ilqgkl_fit_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, 
         etab::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
         Sigma::Ptr{Float64}, Sigmai::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cost::Ptr{Float64}, dV::Ptr{Float64},
         stats::Ptr{Float64}, its::Ptr{Cint})::Cint)
+    return Int(its[])
+end
+
+# DDP_USER_COST_FIT on device-resident arrays: the cost model of xs[n,N,S,B], us[m,N,S,B] around x[n,N,B], u[m,N,B], and the KL loop on a
+# cost model cx[n,N,B], cu[m,N,B], cxx[n,n,N,B], cxu[n,m,N,B], cuu[m,m,N,B] (fx, fu, fc: the tables, or three C_NULL)
+user_cost_fit_dev!(p::DeviceProblem, N, S, B, params::Ptr{Float64}, pb, xs, us, x, u, cx, cu, cxx, cxu, cuu, c0; handle::Handle=default_handle()) =
+    check(@ccall libddp.ddp_user_cost_fit_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, S::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, xs::Ptr{Float64}, us::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, cx::Ptr{Float64},
+        cu::Ptr{Float64}, cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, c0::Ptr{Float64})::Cint)
+function user_ilqgkl_cost_dev!(p::DeviceProblem, N, B, params::Ptr{Float64}, pb, o::ILQGKLOpts, x0, cost0, Kp, kp, Sp, Sip, model_fx,
+                               model_fx_batched, R1, lims, etab, fx, fu, fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats, cx, cu, cxx,
+                               cxu, cuu; handle::Handle=default_handle())
+    its = Ref{Cint}(0)
+    check(@ccall libddp.ddp_user_ilqgkl_cost_f64_dev(handle.ptr::Ptr{Cvoid}, _user_ptr(p, handle)::Ptr{Cvoid}, N::Cint, B::Cint,
+        params::Ptr{Float64}, pb::Cint, Ref(o)::Ptr{ILQGKLOpts}, x0::Ptr{Float64}, cost0::Ptr{Float64}, Kp::Ptr{Float64}, kp::Ptr{Float64},
+        Sp::Ptr{Float64}, Sip::Ptr{Float64}, model_fx::Ptr{Float64}, model_fx_batched::Cint, R1::Ptr{Float64}, lims::Ptr{Float64},
+        etab::Ptr{Float64}, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, K::Ptr{Float64},
+        Sigma::Ptr{Float64}, Sigmai::Ptr{Float64}, Vx::Ptr{Float64}, Vxx::Ptr{Float64}, cost::Ptr{Float64}, dV::Ptr{Float64},
+        stats::Ptr{Float64}, its::Ptr{Cint}, cx::Ptr{Float64}, cu::Ptr{Float64}, cxx::Ptr{Float64}, cxu::Ptr{Float64},
+        cuu::Ptr{Float64})::Cint)
     return Int(its[])
 end
 

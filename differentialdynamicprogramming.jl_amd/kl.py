@@ -208,7 +208,8 @@ def calc_η(xnew, xold, sigmanew, ηbracket, traj_new, traj_prev, kl_step, *, ha
 
 
 def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50, cost=None, ηbracket=(1e-8, 1.0, 1e16),
-           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False, t0=None, fitted=False):
+           del0=1e-4, constrain_per_step=False, diff_fun=None, handle=None, params=None, wide=False, t0=None, fitted=False,
+           cost_model=None):
     """``iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step, lims, max_iter, cost, ηbracket, del0)`` with a registered
     ``problem`` or a ``DeviceProblem`` (the user's closures as device source; ``params`` as in ``iLQG``) standing in for the three
     closures (single KL constraint, iLQGkl.jl:91-178).  ``x0[n,N(,B)]`` is the pre-rolled trajectory (the reference errors otherwise,
@@ -226,7 +227,16 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     problem's ``dynamics`` and the fx, fu of its ``derivatives`` are not used.  ``x0`` should be the rollout of ``traj_prev.k`` on the
     tables (``forward_pass(None, x0, u, None, 1.0, problem, lims, model=(fx, fu, fc))``).  The tables must be finite at every step (a step
     ``fit_dynamics`` rejected is NaN).  ``fitted=False`` (default): the plan is made on the problem's own model, ``model.fx`` only shapes
-    the state covariance."""
+    the state covariance.
+    ``cost_model=(cx, cu, cxx, cxu, cuu)`` (a ``DeviceProblem``; ``[n,N(,B)]``, ``[m,N(,B)]``, ``[n,n,N(,B)]``, ``[n,m,N(,B)]``,
+    ``[m,m,N(,B)]``, e.g. the first five arrays ``fit_cost`` returns): every backward pass of the loop takes these arrays in place of the
+    cost derivatives STEP 1 evaluates at ``(x0, traj_prev.k)``; ``cost``, the problem's own cost of the rollouts (what the loop compares
+    and returns) and the loop itself are as without it.  With and without ``fitted=True``; the arrays must be finite."""
+    if cost_model is not None:
+        if wide:
+            raise DDPError("iLQGkl: cost_model= together with wide=True is refused (deferred: a cost model is sized for n <= 32, m <= 8)")
+        if not isinstance(problem, DeviceProblem):
+            raise DDPError("iLQGkl: cost_model= needs a DeviceProblem (the registered problems bring their own quadratic cost)")
     if fitted:
         if wide:
             raise DDPError("iLQGkl: fitted=True together with wide=True is refused (deferred: ddp_user_rollout_fit is sized for n <= 32, m <= 8)")
@@ -255,6 +265,7 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     user = isinstance(problem, DeviceProblem)
     prm = _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched) if user else None
     tables = _fitted_kl_tables(problem, model, n, m, N, B) if fitted else None
+    ctabs = _cost_model_tables(cost_model, n, m, N, B) if cost_model is not None else None
     h = handle or default_handle()                         # (behind every check that needs no device)
     etab = np.asarray(ηbracket, dtype=np.float64)
     etab = etab.copy() if etab.shape == (3, B) else np.repeat(etab.reshape(3)[:, None], B, 1)                    # copy (:52); [3,B]: one bracket per trajectory
@@ -263,10 +274,39 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
         with _wide(h, wide), _clock(problem, h, t0):
             return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm,
-                                tables)
+                                tables, ctabs)
     with _wide(h, wide), _clock(problem, h, t0):           # (the clocks are checked here; the array calls below set their own)
         return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0,
-                                tables)
+                                tables, ctabs)
+
+
+def _cost_model_tables(cost_model, n, m, N, B):
+    """``cost_model=``: the five arrays as [.,.,N,B]; a malformed tuple, shape or a non-finite entry is refused by name before any launch"""
+    try:
+        cx, cu, cxx, cxu, cuu = cost_model
+    except (TypeError, ValueError):
+        raise DDPError("iLQGkl: cost_model should be five arrays (cx, cu, cxx, cxu, cuu), e.g. fit_cost(...)[:5]")
+    if any(a is None for a in (cx, cu, cxx, cxu, cuu)):
+        raise DDPError("iLQGkl: cost_model needs cx, cu, cxx, cxu and cuu (one of them is None)")
+    tabs = tuple(_lib.f64(a) for a in (cx, cu, cxx, cxu, cuu))
+    want = ((n, N), (m, N), (n, n, N), (n, m, N), (m, m, N))
+    b4 = tabs[0].ndim == 3
+    tb = (B,) if b4 else ()
+    if any(a.shape != w + tb for a, w in zip(tabs, want)):
+        raise DDPError("iLQGkl: cost_model cx, cu, cxx, cxu, cuu should be (n,N), (m,N), (n,n,N), (n,m,N), (m,m,N) = %s%s, got %s"
+                       % (", ".join(str(w) for w in want), " + (B = %d,)" % B if b4 else "", ", ".join(str(a.shape) for a in tabs)))
+    if not b4:                                             # one cost model for the batch (B = 1 of an unbatched call)
+        if B != 1:
+            raise DDPError("iLQGkl: cost_model takes one cost model per trajectory: cx should be (n,N,B) with B = %d, got %s" % (B, tabs[0].shape))
+        tabs = tuple(_lib.f64(a[..., None]) for a in tabs)
+    for name, a in zip(("cx", "cu", "cxx", "cxu", "cuu"), tabs):
+        bad = ~np.isfinite(a)
+        if bad.any():
+            flat = bad.reshape(-1, N, B).any(axis=0)       # [N, B]
+            b = int(np.flatnonzero(flat.any(axis=0))[0])
+            i = int(np.flatnonzero(flat[:, b])[0])
+            raise DDPError("iLQGkl: cost_model needs finite arrays: %s is not finite at step %d of trajectory %d" % (name, i, b))
+    return tabs
 
 
 def _fitted_kl_tables(problem, model, n, m, N, B):
@@ -296,7 +336,7 @@ def _fitted_kl_tables(problem, model, n, m, N, B):
 
 
 def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0=None,
-                     tables=None):
+                     tables=None, ctabs=None):
     """DDP_KL_HOSTLOOP=1 (the body of iLQGkl on host arrays)"""
     n, N, B = x.shape
     m = u.shape[0]
@@ -306,6 +346,8 @@ def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, et
         fx, fu, _, _, _, cx, cu, cxx, cxu, cuu = df(problem, x, u, handle=h, params=prm[0], t0=t0)
         hb = problem.const_hessian                             # constant Hessians [.,.,B]: the time axis back_pass_gps wants
         cxx, cxu, cuu = _tv(cxx, N, hb), _tv(cxu, N, hb), _tv(cuu, N, hb)
+        if ctabs is not None:                                  # cost_model=: the backward passes take the caller's cost arrays
+            cx, cu, cxx, cxu, cuu = ctabs
         if tables is not None:                                 # fitted=True: the plan is made on the tables (the fx, fu of STEP 1 are dropped)
             fx, fu = tables[0], tables[1]
             if model.fx is None or np.ndim(model.fx) == 3:
@@ -425,7 +467,7 @@ def _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, bat
     return problem._params(B, params)
 
 
-def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None, prm=None, tables=None):
+def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, del0, batched, diff_fun=None, prm=None, tables=None, ctabs=None):
     """the whole loop of iLQGkl (iLQGkl.jl:91-178) as ONE library call: ``ddp_ilqgkl_f64`` / ``ddp_user_ilqgkl_f64`` (csrc/kl.hip)"""
     n, N, B = x.shape
     m = u.shape[0]
@@ -447,7 +489,12 @@ def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, 
     Vxx = _lib.result_array((n, n, N, B)); co = _lib.result_array((CL, B)); dV = np.zeros((2, B), order="F")
     st = np.zeros((_lib.ILQGKL_NSTATS, B), order="F")
     mb = int(mfx is not None and mfx.ndim == 4)
-    if tables is not None:                                 # fitted=True: ddp_user_ilqgkl_fit_f64, the same arguments and the three tables
+    if ctabs is not None:                                  # cost_model=: ddp_user_ilqgkl_cost_f64, the tables (or three NULLs) and the five cost arrays
+        _lib.check(_lib.lib().ddp_user_ilqgkl_cost_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm[0]), prm[1], _C.byref(o), _lib.ptr(x), _lib.ptr(c0),
+                                                       _lib.ptr(Kp), _lib.ptr(u), _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1),
+                                                       _lib.ptr(Lh), _lib.ptr(eb), *map(_lib.ptr, tables if tables is not None else (None,) * 3),
+                                                       *map(_lib.ptr, (xo, uo, K, S, Si, Vx, Vxx, co, dV, st)), None, *map(_lib.ptr, ctabs)))
+    elif tables is not None:                               # fitted=True: ddp_user_ilqgkl_fit_f64, the same arguments and the three tables
         _lib.check(_lib.lib().ddp_user_ilqgkl_fit_f64(h.raw, problem._ptr(h), N, B, _lib.ptr(prm[0]), prm[1], _C.byref(o), _lib.ptr(x), _lib.ptr(c0),
                                                       _lib.ptr(Kp), _lib.ptr(u), _lib.ptr(Sp), _lib.ptr(Sip), _lib.ptr(mfx), mb, _lib.ptr(R1),
                                                       _lib.ptr(Lh), _lib.ptr(eb), *map(_lib.ptr, tables),

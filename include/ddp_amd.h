@@ -663,13 +663,34 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * n <= 32, m <= 8.  Legal with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SAMPLE,
  * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
  * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did;
- * the tail of the flag goes last in the program. */
+ * the tail of the flag goes last in the program.
+ *
+ * DDP_USER_COST_FIT: the quadratic cost model of a guided-policy-search round (Levine & Abbeel 2014), fitted to the samples the
+ * dynamics model is fitted to (ddp_user_cost_fit_*, below; every other entry point ignores the flag).  For every step i and trajectory b,
+ * over the samples s = 0..S-1 of xs[n,N,S,B], us[m,N,S,B] around the nominal x[n,N,B], u[m,N,B], with dx = diff(x^_s, x_i) (diff_wrap,
+ * as in the rollout's policy term), du = u^_s - u_i and (c, cx, cu, cxx, cxu, cuu) the user's cost and its derivatives at
+ * (x^_s, u^_s, i) — `derivatives`, forward-mode AD of the cost alone with DDP_USER_AUTODIFF, `cost_hessians` with
+ * DDP_USER_CONST_HESSIAN, at i = N-1 whatever `derivatives` adds there and c = stage_cost + terminal_cost (DDP_USER_TERMINAL):
+ *   cxx_i = mean_s cxx,  cxu_i = mean_s cxu,  cuu_i = mean_s cuu,
+ *   cx_i = mean_s (cx - cxx dx - cxu du),  cu_i = mean_s (cu - cxu' dx - cuu du),
+ *   c0_i = mean_s (c - cx.dx - cu.du + 1/2 [dx; du]' H [dx; du]),
+ * every expansion moved to the nominal before it is averaged.  Every sum runs s = 0..S-1 in that order and is divided by S at the end;
+ * inside a sample the sums run j = 0..n-1, then q = 0..m-1: nothing depends on S, B or the launch geometry, two calls give the same
+ * bits and a call on a slice of the trajectories reproduces that slice of the full call bit for bit.  A non-finite sample makes the
+ * outputs of its own (i, b) non-finite and touches nothing else.  Kernel ddp_user_cost_fit (ddp_last_kernel(h, 1)): one lane per
+ * (step, trajectory), the derivatives of a sample and the running sums in the lane's LDS slots, the samples staged through LDS in
+ * contiguous runs over the steps of a work-group; no per-sample array exists in memory; n <= 32, m <= 8.  Legal with
+ * DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SAMPLE, DDP_USER_FITTED,
+ * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
+ * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did;
+ * the tail of the flag goes last in the program, behind that of DDP_USER_FITTED. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
        DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
-       DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048, DDP_USER_FITTED = 4096 };      /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048, DDP_USER_FITTED = 4096,
+       DDP_USER_COST_FIT = 8192 };                                                         /* 64: not assigned, refused as unknown (256 too) */
 #define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
@@ -887,6 +908,38 @@ int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *
                             double *etab, const double *fx, const double *fu, const double *fc,
                             double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
                             double *cost, double *dV, double *stats, int *iters);
+
+/* DDP_USER_COST_FIT problems only (a problem made without the flag is refused by name).  The cost model of DDP_USER_COST_FIT above:
+ * xs[n,N,S,B], us[m,N,S,B] (what ddp_user_sample_* returns), the nominal x[n,N,B], u[m,N,B]; outputs in the layouts of
+ * ddp_user_df_f64(_dev), always time-varying and per trajectory (also with DDP_USER_CONST_HESSIAN): cx[n,N,B], cu[m,N,B],
+ * cxx[n,n,N,B], cxu[n,m,N,B], cuu[m,m,N,B], and c0[N,B], the model's value at the nominal (sum(c0[:,b]) is comparable with a rollout's
+ * csum).  S >= 1.  The host flavour stages its arrays like every host-pointer entry; both give the same bits.                          */
+int ddp_user_cost_fit_f64_dev(ddp_handle h, void *up, int N, int S, int B, const double *params, int params_batched, const double *xs,
+                              const double *us, const double *x, const double *u, double *cx, double *cu, double *cxx, double *cxu,
+                              double *cuu, double *c0);
+int ddp_user_cost_fit_f64(ddp_handle h, void *up, int N, int S, int B, const double *params, int params_batched, const double *xs,
+                          const double *us, const double *x, const double *u, double *cx, double *cu, double *cxx, double *cxu,
+                          double *cuu, double *c0);
+/* iLQGkl with a cost model: arguments and outputs as ddp_user_ilqgkl_fit_f64(_dev), then cx[n,N,B], cu[m,N,B], cxx[n,n,N,B],
+ * cxu[n,m,N,B], cuu[m,m,N,B] (all five, time-varying and batched), which every backward pass of the loop takes in place of the cost
+ * derivatives STEP 1 evaluates at (x0, kp).  fx, fu, fc: all three given — the loop plans on the tables as ddp_user_ilqgkl_fit_* does
+ * (a DDP_USER_FITTED problem) — or all three NULL — on the problem's own model, as ddp_user_ilqgkl_* does.  Everything else is as
+ * without a cost model: cost0, the user's cost of the rollouts (the cost the loop compares and reports) and the loop itself.  The
+ * tables need not come from ddp_user_cost_fit_* and the problem needs no DDP_USER_COST_FIT; non-finite tables are the caller's to check. */
+int ddp_user_ilqgkl_cost_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                                 const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                                 const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                                 double *etab, const double *fx, const double *fu, const double *fc,
+                                 double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                                 double *cost, double *dV, double *stats, int *iters,
+                                 const double *cx, const double *cu, const double *cxx, const double *cxu, const double *cuu);
+int ddp_user_ilqgkl_cost_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
+                             const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
+                             const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims,
+                             double *etab, const double *fx, const double *fu, const double *fc,
+                             double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx,
+                             double *cost, double *dV, double *stats, int *iters,
+                             const double *cx, const double *cu, const double *cxx, const double *cxu, const double *cuu);
 
 /* The dynamics prior of the guided-policy-search round (Levine & Abbeel 2014): a Gaussian mixture over the transition tuples of all
  * steps and samples, and from it the normal-inverse-Wishart prior (Phi, mu0) of every step that ddp_fit_dynamics_* takes with
