@@ -958,7 +958,7 @@ int ddp_user_df_f64_dev(ddp_handle h, void *up, int N, int B, const double *para
     rc = P->df(h, B, nullptr, x, u, active, fx, fu, cx, cu, P->const_hessian ? nullptr : cxx, P->const_hessian ? nullptr : cxu,
                P->const_hessian ? nullptr : cuu);
     if (rc) return rc;
-    if (P->const_hessian && cxx && cxu && cuu) return P->hessians(h, B, nullptr, nullptr, cxx, cxu, cuu);
+    if (P->const_hessian && cxx && cxu && cuu) return P->hessians(h, B, nullptr, active, cxx, cxu, cuu);
     return 0;
 }
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import par_map, relerr
+from user_lane_cases import car_closures                # noqa: F401  (the car's closures live with the lane cases; imported from here by other tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,40 +55,6 @@ def car_params(rng, B):
     P[5] = 0.6 + rng.uniform(0, 0.3, B); P[6] = rng.uniform(5.0, 20.0, B)                 # radius, weight
     P[7] = 0.1; P[8] = rng.uniform(5.0, 20.0, B)                                           # control, terminal weights
     return P
-
-
-def car_closures(p):
-    h, gx, gy, ox, oy, r, wo, wu, wt = p
-
-    def f(x, u, i):
-        return np.array([x[0] + h * x[3] * np.cos(x[2]), x[1] + h * x[3] * np.sin(x[2]), x[2] + h * u[1], x[3] + h * u[0]])
-
-    def costfun(x, u):
-        dx, dy = x[0] - ox, x[1] - oy
-        c = 0.5 * wu * (u[0] ** 2 + u[1] ** 2) + wo * np.exp(-(dx * dx + dy * dy) / r ** 2)
-        e = x[:, -1]
-        return np.concatenate([c, [0.5 * wt * ((e[0] - gx) ** 2 + (e[1] - gy) ** 2 + e[3] ** 2)]])
-
-    def df(x, u):
-        n, N = x.shape
-        fx = np.zeros((4, 4, N)); fu = np.zeros((4, 2, N))
-        for j in range(4):
-            fx[j, j] = 1.0
-        c, s = np.cos(x[2]), np.sin(x[2])
-        fx[0, 2] = -h * x[3] * s; fx[0, 3] = h * c; fx[1, 2] = h * x[3] * c; fx[1, 3] = h * s
-        fu[3, 0] = h; fu[2, 1] = h
-        dx, dy = x[0] - ox, x[1] - oy
-        phi = wo * np.exp(-(dx * dx + dy * dy) / r ** 2); k = -2.0 / r ** 2
-        cx = np.zeros((4, N)); cxx = np.zeros((4, 4, N))
-        cx[0] = phi * k * dx; cx[1] = phi * k * dy
-        cxx[0, 0] = phi * (k + k * k * dx * dx); cxx[1, 1] = phi * (k + k * k * dy * dy); cxx[0, 1] = cxx[1, 0] = phi * k * k * dx * dy
-        cx[0, -1] += wt * (x[0, -1] - gx); cx[1, -1] += wt * (x[1, -1] - gy); cx[3, -1] += wt * x[3, -1]
-        cxx[0, 0, -1] += wt; cxx[1, 1, -1] += wt; cxx[3, 3, -1] += wt
-        cu = wu * u
-        cuu = np.zeros((2, 2, N)); cuu[0, 0] = cuu[1, 1] = wu
-        return fx, fu, cx, cu, cxx, np.zeros((4, 2, N)), cuu
-
-    return f, costfun, df
 
 
 # ------------------------------------------------------------------------------------------------------------------ rollouts
