@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libddp_amd.so")
 SOURCES = ["capi.hip", "back_pass.hip", "back_pass_dpp.hip", "back_pass_dppw.hip", "back_pass_row.hip", "back_pass_row_hi.hip", "back_pass_mid.hip", "back_pass_big.hip", "back_pass_gps_lane.hip", "back_pass_mfma.hip", "back_pass_mfma_lims.hip", "back_pass_mf2.hip", "back_pass_mf2_lims.hip", "back_pass_mx.hip", "back_pass_mxg.hip", "back_pass_mx2.hip", "back_pass_sh.hip", "back_pass_q4.hip", "back_pass_wide.hip",
-           "forward_pass.hip", "forward_pass_dpp.hip", "forward_pass_row.hip", "forward_pass_pipe.hip", "forward_pass_big.hip", "forward_pass_wide.hip", "df.hip", "ilqg.hip", "kl.hip", "kl_wide.hip", "comm.hip", "boxqp_big.hip", "user_problem.hip", "sample.hip", "fit.hip", "gmm.hip"]
+           "forward_pass.hip", "forward_pass_dpp.hip", "forward_pass_row.hip", "forward_pass_pipe.hip", "forward_pass_big.hip", "forward_pass_wide.hip", "df.hip", "ilqg.hip", "kl.hip", "kl_wide.hip", "comm.hip", "boxqp_big.hip", "user_program.hip", "user_problem.hip", "sample.hip", "fit.hip", "gmm.hip"]
 HEADERS = ["ddp_internal.h", "boxqp_dev.h", "boxqp_rows.h", "staging.h", os.path.join("..", "..", "include", "ddp_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-Wall", "-Wno-unused-function",
          "-Wno-unused-but-set-variable", "-Wno-unused-variable"]
@@ -35,52 +35,37 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "kl_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "fit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gmm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-               "user_problem.hip": ["-I", OBJ]}                  # build/boxqp_dev_text.h (_boxqp_text), build/wide_kernel_text.h (_wide_text), build/philox_text.h (_philox_text)
+               "user_program.hip": ["-I", OBJ]}                  # the headers of PROGRAM_TEXTS, written to build/
 
 
-EXTRA_DEPS = {"user_problem.hip": ["user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"], "sample.hip": ["philox.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
+EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
+              "user_problem.hip": ["user_program.h", "user_problem_kernels.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "wide_tile.h", "back_pass_wide_kernel.h"], "sample.hip": ["philox.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
               "ilqg.hip": ["ilqg_model.h"], "kl.hip": ["ilqg_model.h"], "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"], "fit.hip": ["wide_tile.h"], "gmm.hip": ["wide_tile.h", "philox.h"]}
 
 
-def _boxqp_text():
-    """csrc/boxqp_dev.h as program text for hiprtc -> build/boxqp_dev_text.h (kBoxqpDevText).  ddp_user_back_pass2, compiled at run time
-    (user_problem_kernels.h), factorises and solves with the routines the precompiled backward kernels include: one definition for both
-    compilers.  The header's own #include lines and #pragma once are left out (hiprtc has no include path to them; ddp_rsqrt, the one
-    thing boxqp_dev.h takes from ddp_internal.h, is part of the program text)."""
-    src = open(os.path.join(CSRC, "boxqp_dev.h")).read()
-    body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
-    assert ')DDPQ"' not in body
-    text = "// written by build.py from csrc/boxqp_dev.h\nstatic const char *kBoxqpDevText = R\"DDPQ(\n" + body + ")DDPQ\";\n"
-    out = os.path.join(OBJ, "boxqp_dev_text.h")
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
+# Headers of csrc/ as program text for hiprtc (user_program.hip): output file -> [(symbol, header)].  The kernels compiled at run time take
+# the definitions the precompiled ones include, one definition for both compilers: ddp_user_back_pass2 factorises and solves with
+# boxqp_dev.h, ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE) is the step of back_pass_wide.hip, ddp_user_sample (DDP_USER_SAMPLE)
+# draws its normals with the philox.h of sample.hip.
+PROGRAM_TEXTS = {"boxqp_dev_text.h": [("kBoxqpDevText", "boxqp_dev.h")],
+                 "wide_kernel_text.h": [("kWideTileText", "wide_tile.h"), ("kWideKernelText", "back_pass_wide_kernel.h")],
+                 "philox_text.h": [("kPhiloxText", "philox.h")]}
 
 
-def _wide_text():
-    """csrc/wide_tile.h and csrc/back_pass_wide_kernel.h as program text -> build/wide_kernel_text.h (kWideTileText, kWideKernelText), the
-    same way: ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE) is the step of back_pass_wide.hip compiled by hiprtc, not a copy."""
-    text = "// written by build.py from csrc/wide_tile.h and csrc/back_pass_wide_kernel.h\n"
-    for name, header in (("kWideTileText", "wide_tile.h"), ("kWideKernelText", "back_pass_wide_kernel.h")):
-        src = open(os.path.join(CSRC, header)).read()
-        body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
-        assert ')DDPQ"' not in body
-        text += "static const char *%s = R\"DDPQ(\n" % name + body + ")DDPQ\";\n"
-    out = os.path.join(OBJ, "wide_kernel_text.h")
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
-
-
-def _philox_text():
-    """csrc/philox.h as program text -> build/philox_text.h (kPhiloxText), the same way: ddp_user_sample (DDP_USER_SAMPLE), compiled at run
-    time, draws its normals with the definition that sample.hip includes for ddp_normal_fill."""
-    src = open(os.path.join(CSRC, "philox.h")).read()
-    body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
-    assert ')DDPQ"' not in body
-    text = "// written by build.py from csrc/philox.h\nstatic const char *kPhiloxText = R\"DDPQ(\n" + body + ")DDPQ\";\n"
-    out = os.path.join(OBJ, "philox_text.h")
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
+def _program_texts():
+    """PROGRAM_TEXTS -> build/.  A header's own #include lines and #pragma once are left out (hiprtc has no include path to them; ddp_rsqrt,
+    the one thing boxqp_dev.h takes from ddp_internal.h, is part of the program text)."""
+    for out, parts in PROGRAM_TEXTS.items():
+        text = "// written by build.py from " + " and ".join("csrc/" + header for _, header in parts) + "\n"
+        for name, header in parts:
+            src = open(os.path.join(CSRC, header)).read()
+            body = "".join(l for l in src.splitlines(True) if not l.startswith("#include") and not l.startswith("#pragma once"))
+            assert ')DDPQ"' not in body
+            text += "static const char *%s = R\"DDPQ(\n" % name + body + ")DDPQ\";\n"
+        out = os.path.join(OBJ, out)
+        if not os.path.exists(out) or open(out).read() != text:
+            open(out, "w").write(text)
 
 
 def _stale(target, deps):
@@ -143,9 +128,7 @@ def build(force=False, verbose=True):
     if force:
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
-    _boxqp_text()
-    _wide_text()
-    _philox_text()
+    _program_texts()
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         results = list(ex.map(_compile, srcs))

@@ -452,3 +452,41 @@ def test_user_drivers(lib, user):
     ok.max_iter = 3
     for etab in (np.repeat(np.array([1e-8, 1.0, 1e16])[:, None], B, 1), None):
         pair(lib, h, "ddp_user_ilqgkl_f64", [Raw(up), Raw(N), Raw(B), In(prm), Raw(0)] + ilqgkl_args(lib, d, q, ok, etab, None))
+
+
+@pytest.fixture(scope="module")
+def user_fit(lib):
+    """the same example made with DDP_USER_FITTED | DDP_USER_COST_FIT, on a handle of the module's own"""
+    import ddp_amd
+    hd = lib.Handle()
+    p = ddp_amd.DeviceProblem(ddp_amd.example_source("lq_ad"), n, m, nparam=28, autodiff=True, fitted=True, cost_fit=True)
+    yield hd, p._ptr(hd)
+    hd.close()
+
+
+def test_user_fitted_and_cost_model_entries(lib, user_fit):
+    """ddp_user_rollout_fit, ddp_user_ilqgkl_fit and ddp_user_ilqgkl_cost (with the tables and with the three tables NULL): the tables are
+    the model's own A, Bm with a small offset fc, the cost model the Hessians Q, R of the example and gradients at the nominal"""
+    h, up = user_fit
+    d, q = lq_data(), kl_inputs()
+    prm = user_params(d)
+    r = np.random.default_rng(12)
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a.reshape(a.shape + (1, 1)), a.shape + (N, B)))
+    tabs = [rep(d["A"]) * (1.0 + 0.01 * r.standard_normal((n, n, N, B))), rep(d["Bm"]), 0.01 * r.standard_normal((n, N, B))]
+    model = [np.einsum("ij,jtb->itb", d["Q"], d["x"]), np.einsum("ij,jtb->itb", d["R"], d["u"]), rep(d["Q"]), 0.01 * r.standard_normal((n, m, N, B)),
+             rep(d["R"])]
+    alpha = np.array([1.0, 0.5])
+    pair(lib, h, "ddp_user_rollout_fit_f64", [Raw(up), Raw(N), Raw(B), In(prm), Raw(0), In(d["K"]), In(d["k"]), In(d["x0"]), In(d["u"]), In(d["x"]),
+                                              Raw(lib_ptr(alpha)), Raw(2), In(d["lims"]), DevOnly(None)] + [In(a) for a in tabs] +
+         [Out((n, N, B, 2)), Out((m, N, B, 2)), Out((N, B, 2)), Out((B, 2))])
+    ok = lib.ILQGKLOpts()
+    lib.lib().ddp_ilqgkl_default_opts(C.byref(ok))
+    ok.max_iter = 3
+    base = ilqgkl_args(lib, d, q, ok, np.repeat(np.array([1e-8, 1.0, 1e16])[:, None], B, 1), None)
+    cut = next(i for i, a in enumerate(base) if isinstance(a, InOut)) + 1      # the tables go behind etab, the cost model behind iters
+    head = [Raw(up), Raw(N), Raw(B), In(prm), Raw(0)]
+    fit = pair(lib, h, "ddp_user_ilqgkl_fit_f64", head + base[:cut] + [In(a) for a in tabs] + base[cut:])
+    assert (fit[-1][1] >= 1).all()
+    for tables in (tabs, [None] * 3):
+        out = pair(lib, h, "ddp_user_ilqgkl_cost_f64", head + base[:cut] + [In(a) for a in tables] + base[cut:] + [In(a) for a in model])
+        assert (out[-1][1] >= 1).all()

@@ -1,7 +1,7 @@
 """Cases, references and device-call helpers of the contract tests of the default (lane) user-problem kernels: ddp_user_rollout,
 ddp_user_df / ddp_user_df_ad, ddp_user_cost and ddp_user_hessians (tests/test_user_lane_cpu.py, tests/test_gpu_user_lane.py).
 
-The launch geometry of these kernels is chosen per shape by layout_of (csrc/user_problem.hip): DDP_CHUNK time steps per LDS chunk and
+The launch geometry of these kernels is chosen per shape by layout_of (csrc/user_program.hip): DDP_CHUNK time steps per LDS chunk and
 DDP_RLANES rollouts per work-group of the rollout, DDP_DFLANES (step, trajectory) pairs per work-group of the derivatives.  SHAPES
 holds one shape per regime, EXPECT what layout_of gives them today (the CPU test pins it), and every size below is read from the
 layout the library reports, so that the cases stay on the edges (a partial last chunk, a work-group over an α boundary or over two
