@@ -914,3 +914,15 @@ extern "C" const char *ddp_bp_choice(const ddp_bp_desc *d, unsigned al16, int si
     const BPChoiceIn q = {al16, sink != 0, d->has_lims && lims_active != 0, backpass, sh_min_b, mx2, dppw};
     return bp_kernel_name[bp_choose(*d, q, true)];
 }
+
+// Unlisted debug hook (not in ddp_amd.h): the element strides bp_kargs gives the kernels for this descriptor, callable without a GPU
+// (tests/test_bp_choice.py).  out: fx_t, fx_b, fu_t, fu_b, cxx_t, cxx_b, cxu_t, cxu_b, cuu_t, cuu_b
+extern "C" void ddp_bp_strides(const ddp_bp_desc *d, long long *out)
+{
+    ddp_handle_s hs = {};
+    BPCall c = {};
+    c.d = *d;
+    const BPKArgs a = bp_kargs(&hs, c);
+    const long st[10] = {a.fx_t, a.fx_b, a.fu_t, a.fu_b, a.cxx_t, a.cxx_b, a.cxu_t, a.cxu_b, a.cuu_t, a.cuu_b};
+    for (int i = 0; i < 10; ++i) out[i] = st[i];
+}

@@ -19,15 +19,6 @@
 
 namespace {
 
-struct BPBArgs {
-    int n, m, N, B;
-    int fx_tv, fx_batched, cost_tv, cost_batched, regType, has_lims;
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
-    const int32_t *active;
-    double *K, *k, *Quu, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-};
-
 typedef double d2 __attribute__((ext_vector_type(2)));
 constexpr int NT = 256, MMAX = 8;
 
@@ -56,7 +47,7 @@ struct BigLds {            // offsets in doubles (all even)
     }
 };
 
-__global__ __launch_bounds__(NT) void back_pass_big_kernel(BPBArgs a)
+__global__ __launch_bounds__(NT) void back_pass_big_kernel(BPKArgs a)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (a.active && a.active[b] == 0) return;
@@ -343,13 +334,7 @@ __global__ __launch_bounds__(NT) void back_pass_big_kernel(BPBArgs a)
 int ddp_launch_back_pass_big(ddp_handle h, const BPCall &c)
 {
     const ddp_bp_desc *d = &c.d;
-    BPBArgs a;
-    a.n = d->n; a.m = d->m; a.N = d->N; a.B = d->B;
-    a.fx_tv = d->fx_tv; a.fx_batched = d->fx_batched; a.cost_tv = d->cost_tv; a.cost_batched = d->cost_batched;
-    a.regType = d->regType; a.has_lims = d->has_lims;
-    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
-    a.u = c.u; a.active = c.active;
-    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    const BPKArgs a = bp_kargs(h, c);
     const BigLds L(d->n, d->m);
     const size_t shmem = (size_t)L.total * sizeof(double);
     if (int rc = ddp_raise_lds(h, (const void *)back_pass_big_kernel, 160 * 1024)) return rc;

@@ -24,15 +24,6 @@
 
 namespace {
 
-struct BPDArgs {
-    int N, B;
-    int fx_batched, cost_batched, regType;
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
-    const int32_t *active;
-    double *K, *k, *Quu, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-};
-
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 template <int L>
@@ -60,7 +51,7 @@ __device__ __forceinline__ void dpp_fence(double (&v)[NN])
 }
 
 template <int NS, int MS, bool FXTV, bool CTV, bool LIMS>
-__global__ __launch_bounds__(DDP_WAVE) void back_pass_dpp_kernel(BPDArgs a)
+__global__ __launch_bounds__(DDP_WAVE) void back_pass_dpp_kernel(BPKArgs a)
 {
     constexpr int n = NS, m = MS, p = n + m, G = 16, GPW = DDP_WAVE / G, D = 8, LD = n + 2;   // LD even: 16-byte aligned columns
     static_assert(p + 1 <= G, "n + m + 1 lanes must fit one 16-lane DPP row");
@@ -453,7 +444,7 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_dpp_kernel(BPDArgs a)
 }
 
 template <int NS, int MS>
-int launch_dpp_bp(ddp_handle h, const ddp_bp_desc *d, const BPDArgs &a)
+int launch_dpp_bp(ddp_handle h, const ddp_bp_desc *d, const BPKArgs &a)
 {
     const int gpw = DDP_WAVE / 16;
     const dim3 grid((unsigned)((d->B + gpw - 1) / gpw)), block(DDP_WAVE);
@@ -483,11 +474,7 @@ int launch_dpp_bp(ddp_handle h, const ddp_bp_desc *d, const BPDArgs &a)
 int ddp_launch_back_pass_dpp(ddp_handle h, const BPCall &c)
 {
     const ddp_bp_desc *d = &c.d;
-    BPDArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.regType = d->regType;
-    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
-    a.u = c.u; a.active = c.active;
-    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    const BPKArgs a = bp_kargs(h, c);
     if (d->n == 10 && d->m == 2) return launch_dpp_bp<10, 2>(h, d, a);
     return launch_dpp_bp<4, 1>(h, d, a);
 }

@@ -32,15 +32,6 @@
 
 namespace {
 
-struct BPWArgs {
-    int N, B, regType;
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda;
-    const int32_t *active;
-    double *K, *k, *Quu, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-    double *sink;               // >= 64 x 16 B of device memory for the writer lanes without an item
-};
-
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 template <int L>
@@ -81,7 +72,7 @@ __device__ __forceinline__ int lds_load_flag(const int *p) { return *(const vola
 __device__ __forceinline__ void lds_store_flag(int *p, int v) { asm volatile("" ::: "memory"); *(volatile lds_int *)p = v; asm volatile("" ::: "memory"); }
 
 template <int NS, int MS>
-__global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(BPWArgs a)
+__global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(BPKArgs a)
 {
     constexpr int n = NS, m = MS, p = n + m, G = 16, GPW = DDP_WAVE / G;
     constexpr int nn = n * n, nm = n * m, mm = m * m;
@@ -477,10 +468,7 @@ __global__ __launch_bounds__(DDP_WAVE * (NCW + NWW)) void back_pass_dppw_kernel(
 int ddp_launch_back_pass_dppw(ddp_handle h, const BPCall &c)
 {
     const ddp_bp_desc *d = &c.d;
-    BPWArgs a;
-    a.N = d->N; a.B = d->B; a.regType = d->regType;
-    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.active = c.active;
-    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge; a.sink = (double *)h->sink;
+    const BPKArgs a = bp_kargs(h, c);          // a.sink: >= 64 x 16 B for the writer lanes without an item
     const dim3 grid((unsigned)((d->B + NCW * 4 - 1) / (NCW * 4))), block(DDP_WAVE * (NCW + NWW));
     hipLaunchKernelGGL((back_pass_dppw_kernel<10, 2>), grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());

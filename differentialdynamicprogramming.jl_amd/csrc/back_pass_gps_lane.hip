@@ -9,15 +9,6 @@
 
 namespace {
 
-struct GLArgs {
-    int N, B, fx_batched, cost_batched, eta_tv;
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lims, *u;
-    const double *cxkl, *cukl, *cxxkl, *cxukl, *cuukl, *eta;
-    const int32_t *active;
-    double *K, *k, *Quu, *Quui, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-};
-
 template <int MS>
 __device__ __forceinline__ void inv_sym(const double (&Q)[MS * MS], double (&Qi)[MS * MS])
 {
@@ -31,7 +22,7 @@ __device__ __forceinline__ void inv_sym(const double (&Q)[MS * MS], double (&Qi)
 }
 
 template <int NS, int MS, bool LIMS>
-__global__ __launch_bounds__(DDP_WAVE) void back_pass_gps_lane_kernel(GLArgs a)
+__global__ __launch_bounds__(DDP_WAVE) void back_pass_gps_lane_kernel(BPKArgs a)
 {
     constexpr int n = NS, m = MS, DR = 2;                      // DR: steps of operands in flight per lane
     constexpr size_t nn = (size_t)n * n, nm = (size_t)n * m, mm = (size_t)m * m;
@@ -46,8 +37,8 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_gps_lane_kernel(GLArgs a)
     const double *fx = a.fx + (a.fx_batched ? nn * N * b : 0), *fu = a.fu + (a.fx_batched ? nm * N * b : 0);
     const double *cxx = a.cxx + (a.cost_batched ? nn * N * b : 0), *cxu = a.cxu + (a.cost_batched ? nm * N * b : 0),
                  *cuu = a.cuu + (a.cost_batched ? mm * N * b : 0);
-    const double *cxkl = a.cxkl + (size_t)n * N * b, *cukl = a.cukl + (size_t)m * N * b, *cxxkl = a.cxxkl + nn * N * b,
-                 *cxukl = a.cxukl + nm * N * b, *cuukl = a.cuukl + mm * N * b;
+    const double *cxkl = a.kcx + (size_t)n * N * b, *cukl = a.kcu + (size_t)m * N * b, *cxxkl = a.kcxx + nn * N * b,
+                 *cxukl = a.kcxu + nm * N * b, *cuukl = a.kcuu + mm * N * b;
     const double *etag = a.eta + (a.eta_tv ? (size_t)N * b : b);
     double *Kg = a.K + nm * N * b, *kg = a.k + (size_t)m * N * b, *Quug = a.Quu + mm * N * b, *Quuig = a.Quui + mm * N * b,
            *Vxg = a.Vx + (size_t)n * N * b, *Vxxg = a.Vxx + nn * N * b;
@@ -308,13 +299,8 @@ int ddp_launch_back_pass_gps_lane(ddp_handle h, const BPCall &c)
 {
     const ddp_bp_desc *d = &c.d;
     if (!(d->n == 4 && (d->m == 1 || d->m == 2)) || d->N < 2 || !d->fx_tv || !d->cost_tv) return 1;
-    const ddp_kl_cost_terms *kl = c.kl;
-    GLArgs a;
-    a.N = d->N; a.B = d->B; a.fx_batched = d->fx_batched; a.cost_batched = d->cost_batched; a.eta_tv = kl->eta_tv;
-    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lims = c.lims; a.u = c.u;
-    a.cxkl = kl->cx; a.cukl = kl->cu; a.cxxkl = kl->cxx; a.cxukl = kl->cxu; a.cuukl = kl->cuu; a.eta = kl->eta;
-    a.active = c.active;
-    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Quui = c.Quui; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    BPKArgs a = bp_kargs(h, c);
+    a.regType = 1; a.lambda = nullptr;
     const dim3 grid((unsigned)((d->B + DDP_WAVE - 1) / DDP_WAVE)), block(DDP_WAVE);
     if (d->m == 1) {
         if (d->has_lims) hipLaunchKernelGGL((back_pass_gps_lane_kernel<4, 1, true>), grid, block, 0, h->stream, a);

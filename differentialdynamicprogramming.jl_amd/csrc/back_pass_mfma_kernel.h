@@ -37,15 +37,6 @@
 #include <type_traits>
 #include "boxqp_rows.h"
 
-struct BPMArgs {
-    int N, B;
-    int fx_tv, fx_batched, cost_tv, cost_batched, regType, has_lims;
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
-    const int32_t *active;
-    double *K, *k, *Quu, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-};
-
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -104,7 +95,7 @@ __device__ __forceinline__ void mfma_chain_shared(const double *sp, const double
 }
 
 template <bool LIMS, bool CTV>
-__global__ __launch_bounds__(NT) void back_pass_mfma_kernel(BPMArgs a)
+__global__ __launch_bounds__(NT) void back_pass_mfma_kernel(BPKArgs a)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
     if (a.active && a.active[b] == 0) return;
@@ -660,7 +651,7 @@ __global__ __launch_bounds__(NT) void back_pass_mfma_kernel(BPMArgs a)
 }   // namespace
 
 template <bool LIMS, bool CTV>
-static int ddp_bpm_launch_tv(ddp_handle h, const BPMArgs &a)
+static int ddp_bpm_launch_tv(ddp_handle h, const BPKArgs &a)
 {
     const size_t shmem = (size_t)oTot * sizeof(double);
     if (int rc = ddp_raise_lds(h, (const void *)back_pass_mfma_kernel<LIMS, CTV>, 160 * 1024)) return rc;
@@ -671,6 +662,6 @@ static int ddp_bpm_launch_tv(ddp_handle h, const BPMArgs &a)
 
 // time-invariant cost: its terms are loaded once, before the loop — no load (and no s_waitcnt on the in-order vmcnt) inside
 template <bool LIMS>
-static int ddp_bpm_launch(ddp_handle h, const BPMArgs &a) { return a.cost_tv ? ddp_bpm_launch_tv<LIMS, true>(h, a) : ddp_bpm_launch_tv<LIMS, false>(h, a); }
+static int ddp_bpm_launch(ddp_handle h, const BPKArgs &a) { return a.cost_tv ? ddp_bpm_launch_tv<LIMS, true>(h, a) : ddp_bpm_launch_tv<LIMS, false>(h, a); }
 
-int ddp_bpm_launch_lims(ddp_handle h, const BPMArgs &a);      // back_pass_mfma_lims.hip
+int ddp_bpm_launch_lims(ddp_handle h, const BPKArgs &a);      // back_pass_mfma_lims.hip

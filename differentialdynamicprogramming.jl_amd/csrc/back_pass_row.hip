@@ -20,16 +20,6 @@
 
 namespace {
 
-struct BPRArgs {
-    int n, m, N, B, regType;
-    long fx_t, fx_b, fu_t, fu_b, cxx_t, cxx_b, cxu_t, cxu_b, cuu_t, cuu_b;      // element strides per time step / per trajectory (0: shared)
-    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
-    const int32_t *active;
-    double *K, *k, *Quu, *Vx, *Vxx, *dV;
-    int32_t *diverge;
-    double *sink;                                   // >= 64 x 8 B that lanes without an output write to: no exec-mask branch around a store
-};
-
 template <int L>
 __device__ __forceinline__ void fmac_bc(double &acc, double src0, double src1)
 {   // acc += src0[lane L of this 16-lane row] * src1   (volatile: see back_pass_dpp.hip)
@@ -53,7 +43,7 @@ __device__ __forceinline__ void dpp_fence(double (&v)[NN])
 }
 
 template <int NP, int MP, bool LIMS>
-__global__ __launch_bounds__(DDP_WAVE) void back_pass_row_kernel(BPRArgs a)
+__global__ __launch_bounds__(DDP_WAVE) void back_pass_row_kernel(BPKArgs a)
 {
     constexpr int PP = NP + MP, G = 16, GPW = DDP_WAVE / G, D = 4, LD = NP + 1;
     static_assert(PP + 1 <= G && NP % 2 == 0, "NP + MP + 1 lanes must fit one 16-lane DPP row");
@@ -393,11 +383,11 @@ __global__ __launch_bounds__(DDP_WAVE) void back_pass_row_kernel(BPRArgs a)
 }
 
 template <int NP, int MP>
-int launch_row(ddp_handle h, const ddp_bp_desc *d, const BPRArgs &a)
+int launch_row(ddp_handle h, const BPKArgs &a)
 {
     const int gpw = DDP_WAVE / 16;
-    const dim3 grid((unsigned)((d->B + gpw - 1) / gpw)), block(DDP_WAVE);
-    if (d->has_lims) hipLaunchKernelGGL((back_pass_row_kernel<NP, MP, true>), grid, block, 0, h->stream, a);
+    const dim3 grid((unsigned)((a.B + gpw - 1) / gpw)), block(DDP_WAVE);
+    if (a.has_lims) hipLaunchKernelGGL((back_pass_row_kernel<NP, MP, true>), grid, block, 0, h->stream, a);
     else hipLaunchKernelGGL((back_pass_row_kernel<NP, MP, false>), grid, block, 0, h->stream, a);
     DDP_HIP(hipGetLastError());
     return 0;
@@ -412,46 +402,32 @@ int launch_row(ddp_handle h, const ddp_bp_desc *d, const BPRArgs &a)
 // The padded sizes compiled here: NP in {4, 6, 8, 10, 12, 14}, MP in {1, 2, 4} (3 at NP = 12, 1 at NP = 14: NP + MP + 1 <= 16).
 // (back_pass.hip chooses this kernel for n <= 14, m <= 4, n + m <= 15, m <= 3 above n = 10, m = 1 above n = 12, with a sink)
 #if DDP_ROW_PART == 0
-int ddp_launch_back_pass_row_hi(ddp_handle h, const ddp_bp_desc *d, const void *args);
+int ddp_launch_back_pass_row_hi(ddp_handle h, const BPKArgs &a);
 int ddp_launch_back_pass_row(ddp_handle h, const BPCall &c)
 {
-    const ddp_bp_desc *d = &c.d;
-    const int n = d->n, m = d->m;
-    const long N = d->N;
-    BPRArgs a;
-    a.n = n; a.m = m; a.N = d->N; a.B = d->B; a.regType = d->regType;
-    const long nn = (long)n * n, nm = (long)n * m, mm = (long)m * m;
-    a.fx_t = d->fx_tv ? nn : 0; a.fx_b = d->fx_batched ? nn * (d->fx_tv ? N : 1) : 0;
-    a.fu_t = d->fx_tv ? nm : 0; a.fu_b = d->fx_batched ? nm * (d->fx_tv ? N : 1) : 0;
-    a.cxx_t = d->cost_tv ? nn : 0; a.cxx_b = d->cost_batched ? nn * (d->cost_tv ? N : 1) : 0;
-    a.cxu_t = d->cost_tv ? nm : 0; a.cxu_b = d->cost_batched ? nm * (d->cost_tv ? N : 1) : 0;
-    a.cuu_t = d->cost_tv ? mm : 0; a.cuu_b = d->cost_batched ? mm * (d->cost_tv ? N : 1) : 0;
-    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
-    a.u = c.u; a.active = c.active;
-    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
-    a.sink = (double *)h->sink;
+    const BPKArgs a = bp_kargs(h, c);               // a.sink: >= 64 x 8 B that lanes without an output write to
+    const int n = a.n, m = a.m;
     const int np = n <= 4 ? 4 : (n + 1) & ~1;
-    if (np > 8) return ddp_launch_back_pass_row_hi(h, d, &a);
+    if (np > 8) return ddp_launch_back_pass_row_hi(h, a);
     const int mp = m <= 2 ? m : 4;
-#define ROW_CASE(NP_, MP_) if (np == NP_ && mp == MP_) return launch_row<NP_, MP_>(h, d, a);
+#define ROW_CASE(NP_, MP_) if (np == NP_ && mp == MP_) return launch_row<NP_, MP_>(h, a);
     ROW_CASE(4, 1) ROW_CASE(4, 2) ROW_CASE(4, 4)
     ROW_CASE(6, 1) ROW_CASE(6, 2) ROW_CASE(6, 4)
     ROW_CASE(8, 1) ROW_CASE(8, 2) ROW_CASE(8, 4)
 #undef ROW_CASE
-    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", d->n, d->m);
+    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", n, m);
 }
 #else
 // second translation unit (back_pass_row_hi.hip): the larger padded sizes, compiled beside the first
-int ddp_launch_back_pass_row_hi(ddp_handle h, const ddp_bp_desc *d, const void *args)
+int ddp_launch_back_pass_row_hi(ddp_handle h, const BPKArgs &a)
 {
-    const BPRArgs &a = *(const BPRArgs *)args;
-    const int n = d->n, m = d->m;
+    const int n = a.n, m = a.m;
     const int np = (n + 1) & ~1;
-#define ROW_CASE(NP_, MP_) return launch_row<NP_, MP_>(h, d, a);
+#define ROW_CASE(NP_, MP_) return launch_row<NP_, MP_>(h, a);
     if (np == 10) { if (m == 1) ROW_CASE(10, 1) if (m == 2) ROW_CASE(10, 2) ROW_CASE(10, 4) }
     if (np == 12) { if (m == 1) ROW_CASE(12, 1) if (m == 2) ROW_CASE(12, 2) ROW_CASE(12, 3) }
     if (np == 14) { ROW_CASE(14, 1) }
 #undef ROW_CASE
-    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", d->n, d->m);
+    DDP_CHECK(false, "back_pass_row: no kernel for n=%d m=%d", n, m);
 }
 #endif

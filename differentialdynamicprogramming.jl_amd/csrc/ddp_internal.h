@@ -198,6 +198,47 @@ struct BPCall {
     const int32_t *map = nullptr;               // ddp_family::back_pass only: slot -> trajectory map of the working set (may be NULL)
 };
 
+// The kernel argument of the dpp, dppw, row, big, mfma and gps_lane families (the general, mx, mxg, mid, mf2, q4, wide and shared-operand
+// kernels keep structs of their own): the descriptor, the element strides it implies, the call's pointers in BPCall's order, the KL terms
+// of back_pass_gps and the handle's sink.  bp_kargs fills it; a launcher changes only what is particular to its kernel.  (The field
+// order keeps every field the row kernels read at the offset it had in their own struct: their compiler records are the ones they had.)
+struct BPKArgs {
+    int n, m, N, B, regType, has_lims;
+    long fx_t, fx_b, fu_t, fu_b, cxx_t, cxx_b, cxu_t, cxu_b, cuu_t, cuu_b;      // element strides per time step / per trajectory (0: shared)
+    const double *cx, *cu, *cxx, *cxu, *cuu, *fx, *fu, *lambda, *lims, *u;
+    const int32_t *active;
+    double *K, *k, *Quu, *Vx, *Vxx, *dV;
+    int32_t *diverge;
+    double *sink;               // the handle's 4 KB that lanes without an output may write (stores without an exec-mask branch); may be NULL
+    // back_pass_gps (backward_pass.jl:259-350): ∇kl [n,N,B] [m,N,B] [n,n,N,B] [m,n,N,B] [m,m,N,B], η [B] or [N,B] (eta_tv), Quui = inv(Quu)
+    const double *kcx, *kcu, *kcxx, *kcxu, *kcuu;
+    int eta_tv, fx_tv;
+    const double *eta;
+    double *Quui;
+    int fx_batched, cost_tv, cost_batched;
+};
+inline BPKArgs bp_kargs(ddp_handle h, const BPCall &c)
+{
+    BPKArgs a = {};
+    const ddp_bp_desc &d = c.d;
+    a.n = d.n; a.m = d.m; a.N = d.N; a.B = d.B; a.regType = d.regType; a.has_lims = d.has_lims;
+    a.fx_tv = d.fx_tv; a.fx_batched = d.fx_batched; a.cost_tv = d.cost_tv; a.cost_batched = d.cost_batched;
+    const long N = d.N, nn = (long)d.n * d.n, nm = (long)d.n * d.m, mm = (long)d.m * d.m;
+    auto set = [N](long &t, long &b, long len, int tv, int batched) { t = tv ? len : 0; b = batched ? len * (tv ? N : 1) : 0; };
+    set(a.fx_t, a.fx_b, nn, d.fx_tv, d.fx_batched);
+    set(a.fu_t, a.fu_b, nm, d.fx_tv, d.fx_batched);
+    set(a.cxx_t, a.cxx_b, nn, d.cost_tv, d.cost_batched);
+    set(a.cxu_t, a.cxu_b, nm, d.cost_tv, d.cost_batched);
+    set(a.cuu_t, a.cuu_b, mm, d.cost_tv, d.cost_batched);
+    a.cx = c.cx; a.cu = c.cu; a.cxx = c.cxx; a.cxu = c.cxu; a.cuu = c.cuu; a.fx = c.fx; a.fu = c.fu; a.lambda = c.lambda; a.lims = c.lims;
+    a.u = c.u; a.active = c.active;
+    a.K = c.K; a.k = c.k; a.Quu = c.Quu; a.Vx = c.Vx; a.Vxx = c.Vxx; a.dV = c.dV; a.diverge = c.diverge;
+    if (c.kl) { a.kcx = c.kl->cx; a.kcu = c.kl->cu; a.kcxx = c.kl->cxx; a.kcxu = c.kl->cxu; a.kcuu = c.kl->cuu; a.eta = c.kl->eta; a.eta_tv = c.kl->eta_tv; }
+    a.Quui = c.Quui;
+    a.sink = (double *)h->sink;
+    return a;
+}
+
 // the dispatcher (back_pass.hip) and back_pass_gps (run-time sizes n <= 32, m <= 8)
 int ddp_launch_back_pass(ddp_handle h, const BPCall &c);
 int ddp_launch_back_pass_gps(ddp_handle h, const BPCall &c);

@@ -1,6 +1,8 @@
 """Which backward-pass kernel a call gets (csrc/back_pass.hip, bp_choose).  One table of calls pins every threshold edge, each family's
 shapes, misaligned operands and each DDP_BACKPASS letter.  The CPU test asks the library's choice through its unlisted debug hook
-(ddp_bp_choice, no GPU needed); the GPU test makes each call through ddp_back_pass_f64_dev and reads ddp_last_kernel(h, 0)."""
+(ddp_bp_choice, no GPU needed); the GPU test makes each call through ddp_back_pass_f64_dev and reads ddp_last_kernel(h, 0).
+The operand strides bp_kargs (csrc/ddp_internal.h) computes for the kernels that take a BPKArgs are checked the same way, through
+ddp_bp_strides; the families that keep an argument struct of their own compute theirs in their launchers."""
 import ctypes as C
 import os
 
@@ -115,6 +117,51 @@ def test_kernel_choice_without_a_sink(choice):
     assert ask(10, 2, 6144, 0, b"1000000") == DPP
     assert ask(13, 1, 64, 0) == MID
     assert ask(65, 1, 8, 1) == ""                 # no kernel: the dispatcher reports the error
+
+
+def _strides(L, n, m, N, fx_tv, fx_batched, cost_tv, cost_batched):
+    """the ten element strides the kernels get (bp_kargs through its unlisted debug hook ddp_bp_strides), as
+    {"fx": (per step, per trajectory), ...}"""
+    from ddp_amd import _lib
+    out = (C.c_longlong * 10)(*([-1] * 10))
+    L.ddp_bp_strides.restype = None
+    L.ddp_bp_strides.argtypes = [C.c_void_p, C.c_void_p]
+    L.ddp_bp_strides(C.byref(_lib.BPDesc(n, m, N, 4, fx_tv, fx_batched, cost_tv, cost_batched, 1, 0)), out)
+    return {k: (out[2 * i], out[2 * i + 1]) for i, k in enumerate(("fx", "fu", "cxx", "cxu", "cuu"))}
+
+
+def _strides_expected(n, m, N, fx_tv, fx_batched, cost_tv, cost_batched):
+    """an array [len] / [len, N] / [len, B] / [len, N, B] (column-major, batch slowest): a step is len elements further when the array
+    has the time axis, a trajectory len * (N when it has the time axis) further when it has the batch axis; 0 where the axis is missing"""
+    want = {}
+    for k, ln, tv, batched in (("fx", n * n, fx_tv, fx_batched), ("fu", n * m, fx_tv, fx_batched), ("cxx", n * n, cost_tv, cost_batched),
+                               ("cxu", n * m, cost_tv, cost_batched), ("cuu", m * m, cost_tv, cost_batched)):
+        shape = [ln] + ([N] if tv else []) + ([4] if batched else [])
+        el = np.cumprod([1] + shape[:-1])                   # column-major element strides of the axes
+        want[k] = (int(el[1]) if tv else 0, int(el[-1]) if batched else 0)
+    return want
+
+
+FLAGS16 = [tuple((i >> s) & 1 for s in (3, 2, 1, 0)) for i in range(16)]
+
+
+@pytest.mark.parametrize("n,m,N", [(3, 1, 2), (64, 8, 300)])
+def test_kernel_argument_strides(choice, n, m, N):
+    """every combination of fx_tv, fx_batched, cost_tv, cost_batched against the strides of the arrays' own shapes"""
+    L = C.CDLL(LIB)
+    for flags in FLAGS16:
+        assert _strides(L, n, m, N, *flags) == _strides_expected(n, m, N, *flags), flags
+
+
+def test_kernel_argument_strides_stay_exact_in_64_bits(choice):
+    """n = 64, N = 400 000: a trajectory of fx is 64 * 64 * 400 000 = 1 638 400 000 elements, 13 107 200 000 bytes, past 2^32; the
+    expected values are Python integers (exact)"""
+    n, m, N = 64, 8, 400000
+    got = _strides(C.CDLL(LIB), n, m, N, 1, 1, 1, 1)
+    assert got == {"fx": (n * n, n * n * N), "fu": (n * m, n * m * N), "cxx": (n * n, n * n * N), "cxu": (n * m, n * m * N),
+                   "cuu": (m * m, m * m * N)}
+    assert got["fx"][1] == 1638400000 and got["fx"][1] * 8 > 2 ** 32
+    assert got == _strides_expected(n, m, N, 1, 1, 1, 1)
 
 
 def run_row(h, r):
