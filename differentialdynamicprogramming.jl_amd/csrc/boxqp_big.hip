@@ -127,7 +127,13 @@ __global__ __launch_bounds__(QT) void boxqp_big_kernel(QPBig a)
         }
         __syncthreads();
         nfree = flags[2];
-        if (all_clamped) { result = 6; break; }                                                     // :98-101
+        if (all_clamped) {                                                                          // :98-101
+            // the returned set has no free coordinate, so Hfree is all zero (ddp_amd.h): drop the factor an earlier iteration left
+            if (iter > 1)
+                for (size_t e = tid; e < mm; e += QT) R[e] = 0.0;
+            result = 6;
+            break;
+        }
         // ---- factorize if the clamped set has changed (:104-117)
         if (iter == 1 || changed) {
             for (size_t e = tid; e < mm; e += QT) R[e] = 0.0;

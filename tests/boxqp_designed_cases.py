@@ -67,18 +67,21 @@ def ref_boxqp(H, g, lo, up, x0, dtype=LD, opts=OPTS):
     """boxQP.jl:46-169 in `dtype`.  Returns x, result, free, iters (the value of `iter` at the exit) and the trace:
     events   set of strings: exit<r>, exit<r>_iter<1|2|3+>, exit6_later, iters3 / iters4 / iters6 (the value of `iter` at the exit), q12,
              armijo_pinned_closed / armijo_pinned_slow / armijo_inside (a line search that fails at step 1), warm_below / warm_above
-             (x0 outside the box, clamped at :58), warm_on_bound_inward (x0 on a bound, the gradient pointing into the box)
+             (x0 outside the box, clamped at :58), warm_on_bound_inward (x0 on a bound, the gradient pointing into the box),
+             factor_reused (an iteration after the first whose clamped set is the previous one's: :104 keeps the factor),
+             factor_reused_solve (such an iteration that goes on to the search direction: :127-129 solve with the kept factor)
     margin   the smallest relative distance between a tested quantity and its threshold over every comparison of the run
     guard    for every line search that failed at step 1 with all moving coordinates pinned: |max_j r_j - 0.59| / 0.59, r_j = the step
              at which coordinate j re-enters the box over s* = (old - v(pinned)) / (Armijo |s'g|); the kernels' closed-form back-off
              takes the step iff every r_j <= 0.59
+    changes  the number of iterations after the first that found another clamped set and factorised again
     L        lower Cholesky factor of H[free, free] for the RETURNED free set (Q12: on exit 4 both are the previous iteration's)
     A matrix that is not positive definite gives result 0 (backward_pass.jl:48-52 swallows the exception)."""
     H, g, lo, up, x0 = (np.asarray(a, dtype) for a in (H, g, lo, up, x0))
     n = len(g)
     ev, margin, guard = set(), _Margin(), []
     clamped = np.zeros(n, bool); free = np.ones(n, bool)
-    oldvalue = dtype(0); result = 0; L = np.zeros((0, 0), dtype)
+    oldvalue = dtype(0); result = 0; L = np.zeros((0, 0), dtype); changes = 0
     x = _clamp(x0, lo, up)                                                                  # :58
     if (x0 < lo).any():
         ev.add("warm_below")
@@ -108,16 +111,22 @@ def ref_boxqp(H, g, lo, up, x0, dtype=LD, opts=OPTS):
         if clamped.all():                                                                   # :98-101
             result = 6
             break
-        if it == 1 or (old_clamped != clamped).any():                                       # :104-117
+        reused = not (it == 1 or (old_clamped != clamped).any())
+        if not reused:                                                                      # :104-117
+            changes += it > 1
             try:
                 L = chol_lower(H[np.ix_(free, free)])
             except ValueError:
-                return x, 0, free, it, dict(events=ev, margin=margin.v, where=margin.where, guard=guard, L=L)
+                return x, 0, free, it, dict(events=ev, margin=margin.v, where=margin.where, guard=guard, L=L, changes=changes)
+        else:
+            ev.add("factor_reused")
         gnorm = np.sqrt(np.sum(grad[free] ** 2))                                            # :120-124
         margin(abs(gnorm - dtype(opts["minGrad"])) / dtype(opts["minGrad"]), ("gnorm", it))
         if gnorm < opts["minGrad"]:
             result = 5
             break
+        if reused:
+            ev.add("factor_reused_solve")
         grad_clamped = g + H @ (x * clamped)                                                # :127-129
         search = np.zeros(n, dtype)
         search[free] = -chol_solve(L, grad_clamped[free]) - x[free]
@@ -166,7 +175,7 @@ def ref_boxqp(H, g, lo, up, x0, dtype=LD, opts=OPTS):
         ev.add("iters6")
     if result == 4 and (free & ((x == lo) | (x == up)) & (lo < up)).any():
         ev.add("q12")                                # the last step put a coordinate on its bound; the returned set still has it free
-    return x, result, free, it, dict(events=ev, margin=margin.v, where=margin.where, guard=guard, L=L)
+    return x, result, free, it, dict(events=ev, margin=margin.v, where=margin.where, guard=guard, L=L, changes=changes)
 
 
 _MEMO = {}
