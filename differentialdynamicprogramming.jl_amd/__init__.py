@@ -31,7 +31,7 @@ from ._lib import DDPError, Handle, default_handle  # noqa: F401
 
 __all__ = ["GaussianPolicy", "LQProblem", "PendcartProblem", "back_pass", "boxQP", "forward_pass", "iLQG", "print_timing", "mpc_shift", "demo_linear", "demo_pendcart", "demoQP",
            "df", "costfun", "Handle", "DDPError", "DEFAULT_ALPHA", "WrappedDiff", "DeviceProblem", "example_source", "vhess", "back_pass_ddp",
-           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics", "GMM", "fit_gmm", "gmm_prior", "fit_cost"]
+           "constraints", "iLQG_al", "normal", "sample_policy", "fit_dynamics", "GMM", "fit_gmm", "gmm_prior", "fit_cost", "expected_cost"]
 
 DEFAULT_ALPHA = 10.0 ** np.linspace(0, -3, 11)     # iLQG.jl:145
 
@@ -985,6 +985,98 @@ def fit_cost(problem, xs, us, x, u, *, params=None, handle=None):
                                                 *map(_lib.ptr, (cx, cu, cxx, cxu, cuu, c0))))
     out = (cx, cu, cxx, cxu, cuu, c0)
     return out if batched else tuple(a[..., 0] for a in out)
+
+
+# ------------------------------------------------------------------------------ expected_cost
+def expected_cost(traj, x0, x, u, model, cost_model, *, Sigma0=None, moments=False, handle=None):
+    """Moments and expected cost of the linear-Gaussian policy ``traj`` (``K[m,n,N(,B)]``, ``Σ[m,m,N(,B)]``; ``Σ=None``: deterministic)
+    around the nominal ``x[n,N(,B)]``, ``u[m,N(,B)]`` under ``model = (fx, fu, fc, cov)`` — the first four results of ``fit_dynamics``
+    as they are, ``cov=None``: zeros — and ``cost_model = (cx, cu, cxx, cxu, cuu, c0)``, the six results of ``fit_cost``: the step
+    that closes a guided-policy-search round (``kl.kl_step_adjust`` takes three of its results).  The policy is the one
+    ``sample_policy`` runs, ``û_i = u_i + K_i (x̂_i − x_i) + L_i ξ``; with ``G = [fx fu]``, ``H = [[cxx, cxu], [cxuᵀ, cuu]]``::
+
+        μx_0 = x0 (None: x[:, 0]),  Sx_0 = Sigma0 (None: 0)
+        δx_i = μx_i − x_i,  δu_i = K_i δx_i,  δz_i = [δx_i; δu_i],  Σz_i = [[Sx_i, Sx_i K_iᵀ], [K_i Sx_i, K_i Sx_i K_iᵀ + Σ_i]]
+        ec_i = c0_i + cx_i·δx_i + cu_i·δu_i + ½ δz_iᵀ H_i δz_i + ½ tr(H_i Σz_i)
+        μx_{i+1} = fx_i μx_i + fu_i (u_i + δu_i) + fc_i,  Sx_{i+1} = G_i Σz_i G_iᵀ + cov_i
+
+    Plain subtraction for ``δx`` (no ``diff`` wrap: the function takes arrays and no problem); ``lims`` play no part; slot ``N−1`` of
+    the dynamics tables is not used.  ``model`` and ``cost_model`` may each carry the batch axis or, with a batched policy, be shared
+    by the batch (``[..., N]``).  ``cxx``, ``cuu``, ``cov``, ``Σ`` and ``Sigma0[n,n(,B)]`` are taken as symmetric; the result on input
+    that is not is undefined.  Returns ``(ec[N(,B)], status[(B)])`` and, with ``moments=True``, ``mu[n+m,N(,B)]`` holding
+    ``[μx_i; u_i + δu_i]`` and ``sigma[n+m,n+m,N(,B)]`` holding ``Σz_i`` in the layout of ``kl.forward_covariance``, symmetric to the
+    bit and filled at every step.  ``status`` is 0, or ``i + 1`` for the first step whose ``ec`` is not finite: from that step on the
+    trajectory's outputs are NaN (also when the value that was not finite, a ``c0_i`` say, does not enter the chain of moments), and
+    no other trajectory is touched.  1 <= n <= 32, 1 <= m <= 8.  Two calls give the same bits, and a call on some of the trajectories
+    gives the bits of their slice of the full call."""
+    x, u, K = _lib.f64(x), _lib.f64(u), _lib.f64(traj.K)
+    if x.ndim not in (2, 3) or u.ndim != x.ndim:
+        raise DDPError("expected_cost: x, u should be (n, N), (m, N) [+ batch axis], got %s, %s" % (x.shape, u.shape))
+    batched = x.ndim == 3
+    if not batched:
+        x, u = _lib.f64(x[..., None]), _lib.f64(u[..., None])
+    n, N, B = x.shape
+    m = u.shape[0]
+    tb = (B,) if batched else ()
+    if not (1 <= n <= 32 and 1 <= m <= 8):
+        raise DDPError("expected_cost: n = %d, m = %d out of the box 1 <= n <= 32, 1 <= m <= 8" % (n, m))
+    if N < 1 or u.shape[1:] != (N, B):
+        raise DDPError("expected_cost: u (m, %s) does not match x (n, %s) in N [, B]" % (u.shape[1:], x.shape[1:]))
+    if K.shape != (m, n, N) + tb:
+        raise DDPError("expected_cost: traj.K should be (m,n,N) = (%d,%d,%d)%s, got %s" % (m, n, N, " + (B = %d,)" % B if batched else "", K.shape))
+    Sg = getattr(traj, "Σ", None)
+    Sg = None if Sg is None or np.size(Sg) == 0 else _lib.f64(Sg)
+    if Sg is not None and Sg.shape != (m, m, N) + tb:
+        raise DDPError("expected_cost: traj.Σ should be (m,m,N) [+ batch axis] or None, got %s" % (Sg.shape,))
+    if x0 is not None:
+        x0 = _lib.f64(x0)
+        if x0.shape != (n,) + tb and not (not batched and x0.shape == (n, 1)):
+            raise DDPError("expected_cost: x0 should be (n,) — (n, B) with a batched x — or None, got %s" % (x0.shape,))
+    if Sigma0 is not None:
+        Sigma0 = _lib.f64(Sigma0)
+        if Sigma0.shape == (n, n) and batched:
+            Sigma0 = _lib.f64(np.repeat(Sigma0[:, :, None], B, 2))
+        if Sigma0.shape != (n, n) + tb:
+            raise DDPError("expected_cost: Sigma0 should be (n, n) [+ batch axis] or None, got %s" % (Sigma0.shape,))
+        if not np.all(np.isfinite(Sigma0)):
+            raise DDPError("expected_cost: Sigma0 is not finite")
+
+    def tables(name, tabs, want, optional):
+        """the arrays of one model as the library takes them, and whether they carry the batch axis"""
+        tabs = [None if a is None else _lib.f64(a) for a in tabs]
+        for a, w, nm in zip(tabs, want, name):
+            if a is None and nm not in optional:
+                raise DDPError("expected_cost: %s is None" % nm)
+        nd = tabs[0].ndim - len(want[0])
+        own = batched and nd == 1
+        for a, w, nm in zip(tabs, want, name):
+            if a is not None and a.shape != w + ((B,) if own else ()):
+                raise DDPError("expected_cost: %s should be %s%s, got %s" % (nm, w, " [+ (B = %d,)]" % B if batched else "", a.shape))
+        return tabs, own
+
+    try:
+        fx, fu, fc, cov = model
+    except (TypeError, ValueError):
+        raise DDPError("expected_cost: model should be four arrays (fx, fu, fc, cov), e.g. fit_dynamics(...)[:4]")
+    try:
+        cx, cu, cxx, cxu, cuu, c0 = cost_model
+    except (TypeError, ValueError):
+        raise DDPError("expected_cost: cost_model should be six arrays (cx, cu, cxx, cxu, cuu, c0), the results of fit_cost")
+    (fx, fu, fc, cov), mb = tables(("fx", "fu", "fc", "cov"), (fx, fu, fc, cov), ((n, n, N), (n, m, N), (n, N), (n, n, N)), ("cov",))
+    (cx, cu, cxx, cxu, cuu, c0), cb = tables(("cx", "cu", "cxx", "cxu", "cuu", "c0"), (cx, cu, cxx, cxu, cuu, c0),
+                                             ((n, N), (m, N), (n, n, N), (n, m, N), (m, m, N), (N,)), ())
+    h = handle or default_handle()                         # (behind the checks that need no device)
+    p = n + m
+    ec = _lib.result_array((N, B)); status = np.zeros(B, dtype=np.int32)
+    mu = _lib.result_array((p, N, B)) if moments else None
+    sigma = _lib.result_array((p, p, N, B)) if moments else None
+    _lib.check(_lib.lib().ddp_expected_cost_f64(h.raw, n, m, N, B, *map(_lib.ptr, (K, Sg, x0, x, u, fx, fu, fc, cov)), int(mb),
+                                                *map(_lib.ptr, (cx, cu, cxx, cxu, cuu, c0)), int(cb), _lib.ptr(Sigma0), _lib.ptr(ec),
+                                                status.ctypes.data_as(_lib.vp), _lib.ptr(mu), _lib.ptr(sigma)))
+    out = (ec, status) + ((mu, sigma) if moments else ())
+    if not batched:
+        return (ec[..., 0], int(status[0])) + ((mu[..., 0], sigma[..., 0]) if moments else ())
+    return out
 
 
 # ------------------------------------------------------------------------------ fit_gmm, gmm_prior

@@ -42,13 +42,15 @@ EXPORTS = [
     "ddp_user_rollout_fit_f64_dev", "ddp_user_rollout_fit_f64", "ddp_user_ilqgkl_fit_f64_dev", "ddp_user_ilqgkl_fit_f64",
     "ddp_gmm_fit_f64_dev", "ddp_gmm_fit_f64", "ddp_gmm_prior_f64_dev", "ddp_gmm_prior_f64",
     "ddp_user_cost_fit_f64_dev", "ddp_user_cost_fit_f64", "ddp_user_ilqgkl_cost_f64_dev", "ddp_user_ilqgkl_cost_f64",
+    "ddp_expected_cost_f64_dev", "ddp_expected_cost_f64", "ddp_kl_step_adjust_f64_dev", "ddp_kl_step_adjust_f64", "ddp_kl_set_steps_f64_dev", "ddp_kl_set_steps_f64",
 ]
-COST_FIT_EXPORTS = tuple(EXPORTS[-4:])         # the entries of DDP_USER_COST_FIT and of a cost model: absent from A/B builds of the library from before them
-GMM_EXPORTS = tuple(EXPORTS[-8:-4])            # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
-FITTED_EXPORTS = tuple(EXPORTS[-12:-8])        # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
-FIT_EXPORTS = tuple(EXPORTS[-14:-12])           # fit_dynamics: absent from A/B builds of the library from before it
-SAMPLE_EXPORTS = tuple(EXPORTS[-18:-14])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-26:-18])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+EXPECT_EXPORTS = tuple(EXPORTS[-6:])           # expected_cost, kl_step_adjust, the table of kl_steps: absent from A/B builds of the library from before them
+COST_FIT_EXPORTS = tuple(EXPORTS[-10:-6])      # the entries of DDP_USER_COST_FIT and of a cost model: absent from A/B builds of the library from before them
+GMM_EXPORTS = tuple(EXPORTS[-14:-10])          # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
+FITTED_EXPORTS = tuple(EXPORTS[-18:-14])       # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-20:-18])           # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-24:-20])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-32:-24])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -227,6 +229,15 @@ def lib():
             prior_args = [vp] + [ci] * 7 + [cd] * 5 + [C.c_double, C.c_double, cd, cd, vp]
             L.ddp_gmm_prior_f64.argtypes = prior_args
             L.ddp_gmm_prior_f64_dev.argtypes = prior_args
+        if hasattr(L, "ddp_expected_cost_f64"):               # absent from A/B builds of the library from before it
+            expect_args = [vp] + [ci] * 4 + [cd] * 9 + [ci] + [cd] * 6 + [ci, cd, cd, vp, cd, cd]
+            L.ddp_expected_cost_f64.argtypes = expect_args
+            L.ddp_expected_cost_f64_dev.argtypes = expect_args
+            adjust_args = [vp, ci, ci] + [cd] * 4 + [C.c_double, C.c_double, cd, cd]
+            L.ddp_kl_step_adjust_f64.argtypes = adjust_args
+            L.ddp_kl_step_adjust_f64_dev.argtypes = adjust_args
+            L.ddp_kl_set_steps_f64.argtypes = [vp, ci, cd]
+            L.ddp_kl_set_steps_f64_dev.argtypes = [vp, ci, cd]
         if hasattr(L, "ddp_user_program_text_c"):            # unlisted debug hook (tests), with the flag
             L.ddp_user_program_text_c.restype = C.c_char_p
             L.ddp_user_program_text_c.argtypes = [C.c_char_p, ci, ci, ci, ci, ci, ci]
@@ -236,7 +247,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS + COST_FIT_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS + COST_FIT_EXPORTS + EXPECT_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

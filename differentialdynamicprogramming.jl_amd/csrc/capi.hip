@@ -100,6 +100,7 @@ int ddp_destroy(ddp_handle h)
     if (h->sink) hipFree(h->sink);
     if (h->pad) hipFree(h->pad);
     if (h->sh) hipFree(h->sh);
+    if (h->kl_steps) hipFree(h->kl_steps);
     if (h->sched_aux) { hipStreamDestroy(h->sched_aux); hipEventDestroy(h->sched_ev[0]); hipEventDestroy(h->sched_ev[1]); }
     if (h->tev_ok) for (int e = 0; e < 4; ++e) hipEventDestroy(h->tev[e]);
     ddp_user_release(h);

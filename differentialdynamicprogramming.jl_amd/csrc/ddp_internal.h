@@ -49,6 +49,8 @@ struct ddp_handle_s {
     bool         tev_ok;
     int          kl_wide;         // ddp_kl_set_wide: the KL functions take n <= 64, m <= DDP_MAX_M_WIDE
     void        *user_cache;      // user_problem.hip: the modules of the user problems compiled for this handle (unloaded by ddp_destroy)
+    double      *kl_steps = nullptr;   // ddp_kl_set_steps: one kl_step per trajectory, the handle's own device copy (NULL: the scalar of the call)
+    int          kl_steps_B = 0;
 };
 
 void ddp_set_error(const char *fmt, ...);

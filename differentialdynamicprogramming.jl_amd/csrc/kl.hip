@@ -6,6 +6,7 @@
 // the n = 4 ones of back_pass_q4.hip and back_pass_gps_lane.hip; gps_dispatch below chooses) and the iLQGkl driver for registered and
 // user problems.
 // None of this is on the benchmarked path; the kernels are written for clarity and coalescing, not tuned.
+#include <float.h>
 #include <stdlib.h>
 #include <vector>
 #include <type_traits>
@@ -521,8 +522,9 @@ __global__ __launch_bounds__(DDP_WAVE) void kl_div_lds_kernel(int n, int m, int 
 
 // ---- the dual variable of the KL constraint, one thread per trajectory (calc_η klutils.jl:112-133, the bracket/exit logic of
 // iLQGkl.jl:91-178).  op 0: start of an iteration, 1: after a back pass, 2: after the divergence of the new trajectory is known.
-__global__ void kl_dual_kernel(int op, int B, int it, double kl_step, ddp_kl_dual s, const int32_t *__restrict__ diverge,
-                               const double *__restrict__ klmean, int32_t *__restrict__ count)
+// steps (ddp_kl_set_steps, else NULL): one kl_step per trajectory in place of the scalar.
+__global__ void kl_dual_kernel(int op, int B, int it, double kl_step_all, ddp_kl_dual s, const int32_t *__restrict__ diverge,
+                               const double *__restrict__ klmean, int32_t *__restrict__ count, const double *__restrict__ steps)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     int one = 0;
@@ -546,6 +548,7 @@ __global__ void kl_dual_kernel(int op, int B, int it, double kl_step, ddp_kl_dua
         } else if (s.live[b]) {                                               // :141 calc_η, :169-177
             bool sat = true;
             double dv = 0.0;
+            const double kl_step = steps ? steps[b] : kl_step_all;
             if (kl_step > 0) {                                                // klutils.jl:113
                 dv = klmean[b];
                 const double viol = dv - kl_step;                             // :116
@@ -901,8 +904,9 @@ static int kl_dual_launch(ddp_handle h, int op, int B, int it, double kl_step, c
     int rc = ddp_scratch(h, 256, &cnt);
     if (rc) return rc;
     DDP_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t), h->stream));
+    DDP_CHECK(!h->kl_steps || h->kl_steps_B == B, "kl_dual: B = %d, the table of ddp_kl_set_steps holds %d steps", B, h->kl_steps_B);
     hipLaunchKernelGGL(kl_dual_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, op, B, it, kl_step, *s, diverge, klmean,
-                       (int32_t *)cnt);
+                       (int32_t *)cnt, (const double *)h->kl_steps);
     DDP_HIP(hipGetLastError());
     DDP_HIP(hipMemcpyAsync(h->h_pinned, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     DDP_HIP(hipStreamSynchronize(h->stream));
@@ -925,6 +929,102 @@ int ddp_kl_dual_update_f64_dev(ddp_handle h, int B, double kl_step, const ddp_kl
 {
     DDP_CHECK(klmean, "kl_dual_update: null argument");
     return kl_dual_launch(h, 2, B, 0, kl_step, s, nullptr, klmean, n_live);
+}
+
+// ---- one kl_step per trajectory: the handle keeps its own device copy, kl_dual_kernel reads it in place of the scalar of the call
+static int kl_steps_finite(int B, const double *steps)
+{
+    for (int b = 0; b < B; ++b)
+        DDP_CHECK(fabs(steps[b]) <= DBL_MAX, "kl_set_steps: steps[%d] = %g is not finite", b, steps[b]);
+    return 0;
+}
+static int kl_steps_store(ddp_handle h, int B, const double *steps, hipMemcpyKind kind)
+{
+    DDP_HIP(hipStreamSynchronize(h->stream));
+    if (h->kl_steps) { DDP_HIP(hipFree(h->kl_steps)); h->kl_steps = nullptr; h->kl_steps_B = 0; }
+    if (!steps) return 0;
+    DDP_HIP(hipMalloc((void **)&h->kl_steps, (size_t)B * sizeof(double)));
+    h->kl_steps_B = B;
+    DDP_HIP(hipMemcpy(h->kl_steps, steps, (size_t)B * sizeof(double), kind));
+    return 0;
+}
+int ddp_kl_set_steps_f64(ddp_handle h, int B, const double *steps)
+{
+    if (steps) {
+        DDP_CHECK(B >= 1, "kl_set_steps: B = %d (>= 1)", B);
+        const int rc = kl_steps_finite(B, steps);
+        if (rc) return rc;
+    }
+    DDP_DEVICE(h);
+    return kl_steps_store(h, B, steps, hipMemcpyHostToDevice);
+}
+int ddp_kl_set_steps_f64_dev(ddp_handle h, int B, const double *steps)
+{
+    DDP_CHECK(!steps || B >= 1, "kl_set_steps: B = %d (>= 1)", B);
+    DDP_DEVICE(h);
+    if (steps) {                                           // (a setter, not a hot path: the test needs the values on the host)
+        std::vector<double> host((size_t)B);
+        DDP_HIP(hipStreamSynchronize(h->stream));
+        DDP_HIP(hipMemcpy(host.data(), steps, (size_t)B * sizeof(double), hipMemcpyDeviceToHost));
+        const int rc = kl_steps_finite(B, host.data());
+        if (rc) return rc;
+    }
+    return kl_steps_store(h, B, steps, hipMemcpyDeviceToDevice);
+}
+
+// ---- the step rule of the round, one thread per trajectory: J = sum_i ec[i, b] in ascending i of the three expected costs,
+// mult = clip(pred / (2 max(1e-4, pred - act)), 0.1, 5) (a non-finite J: 0.1), kl_step_new = clip(kl_step mult, step_min, step_max)
+__global__ __launch_bounds__(256) void kl_step_adjust_kernel(int N, int B, const double *__restrict__ ec_prev, const double *__restrict__ ec_pred,
+                                                             const double *__restrict__ ec_act, const double *__restrict__ kl_step,
+                                                             double step_min, double step_max, double *__restrict__ kl_step_new,
+                                                             double *__restrict__ mult)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    double Jp = 0.0, Jd = 0.0, Ja = 0.0;
+    for (int i = 0; i < N; ++i) { const size_t e = (size_t)N * b + i; Jp += ec_prev[e]; Jd += ec_pred[e]; Ja += ec_act[e]; }
+    double mu = 0.1;
+    if (fabs(Jp) <= DBL_MAX && fabs(Jd) <= DBL_MAX && fabs(Ja) <= DBL_MAX) {
+        const double pred = Jp - Jd, act = Jp - Ja;
+        mu = pred / (2.0 * fmax(1e-4, pred - act));
+        mu = mu < 0.1 ? 0.1 : (mu > 5.0 ? 5.0 : mu);
+    }
+    const double s = kl_step[b] * mu;
+    mult[b] = mu;
+    kl_step_new[b] = s < step_min ? step_min : (s > step_max ? step_max : s);
+}
+static int kl_step_adjust_validate(int N, int B, const void *ec_prev, const void *ec_pred, const void *ec_act, const void *kl_step,
+                                   double step_min, double step_max, const void *kl_step_new, const void *mult)
+{
+    DDP_CHECK(N >= 1 && B >= 1, "kl_step_adjust: N = %d, B = %d (both >= 1)", N, B);
+    DDP_CHECK(step_min > 0.0 && step_min <= step_max && step_max <= DBL_MAX, "kl_step_adjust: step_min = %g, step_max = %g should be finite with 0 < step_min <= step_max", step_min, step_max);
+    DDP_CHECK(ec_prev && ec_pred && ec_act && kl_step && kl_step_new && mult, "kl_step_adjust: null argument");
+    return 0;
+}
+int ddp_kl_step_adjust_f64_dev(ddp_handle h, int N, int B, const double *ec_prev, const double *ec_pred, const double *ec_act,
+                               const double *kl_step, double step_min, double step_max, double *kl_step_new, double *mult)
+{
+    { const int rc = kl_step_adjust_validate(N, B, ec_prev, ec_pred, ec_act, kl_step, step_min, step_max, kl_step_new, mult); if (rc) return rc; }
+    DDP_DEVICE(h);
+    hipLaunchKernelGGL(kl_step_adjust_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, N, B, ec_prev, ec_pred, ec_act, kl_step,
+                       step_min, step_max, kl_step_new, mult);
+    DDP_HIP(hipGetLastError());
+    return 0;
+}
+int ddp_kl_step_adjust_f64(ddp_handle h, int N, int B, const double *ec_prev, const double *ec_pred, const double *ec_act,
+                           const double *kl_step, double step_min, double step_max, double *kl_step_new, double *mult)
+{
+    { const int rc = kl_step_adjust_validate(N, B, ec_prev, ec_pred, ec_act, kl_step, step_min, step_max, kl_step_new, mult); if (rc) return rc; }
+    DDP_DEVICE(h);
+    const size_t nb = (size_t)N * B;
+    const double *d0, *d1, *d2, *ds;
+    double *o0, *o1;
+    Staging S(h, Staging::SCRATCH, "kl_step_adjust");
+    S.in(&d0, ec_prev, nb); S.in(&d1, ec_pred, nb); S.in(&d2, ec_act, nb); S.in(&ds, kl_step, (size_t)B);
+    S.out(&o0, kl_step_new, (size_t)B); S.out(&o1, mult, (size_t)B);
+    const int rc = S.commit();
+    if (rc) return rc;
+    return S.finish(ddp_kl_step_adjust_f64_dev(h, N, B, d0, d1, d2, ds, step_min, step_max, o0, o1));
 }
 
 
@@ -962,6 +1062,7 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     DDP_CHECK(x0 != x && kp != u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
     const Model M(p, f);
     const size_t n = M.n, m = M.m, N = M.N, B = M.B, NB = N * B, P2 = (n + m) * (n + m);
+    DDP_CHECK(!h->kl_steps || (size_t)h->kl_steps_B == B, "ilqgkl: B = %zu, the table of ddp_kl_set_steps holds %d steps", B, h->kl_steps_B);
     const bool pend = M.pw.kind == DDP_PROBLEM_PENDCART;
     const int wide = kl_shape(h, (int)n, (int)m);          // 1: back_pass_gps, ∇kl, forward_covariance and kl_div_wiki on the wide kernels
     DDP_CHECK(wide >= 0, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m,
@@ -1061,7 +1162,8 @@ static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, 
     };
     auto dual = [&](int op, int it) -> int {
         DDP_HIP(hipMemsetAsync(counter, 0, 4, st));
-        hipLaunchKernelGGL(kl_dual_kernel, dim3(gB), dim3(256), 0, st, op, (int)B, it, oo->kl_step, s, (const int32_t *)div, (const double *)klm, counter);
+        hipLaunchKernelGGL(kl_dual_kernel, dim3(gB), dim3(256), 0, st, op, (int)B, it, oo->kl_step, s, (const int32_t *)div, (const double *)klm, counter,
+                           (const double *)h->kl_steps);
         DDP_HIP(hipGetLastError());
         return 0;
     };

@@ -1380,6 +1380,92 @@ function fit_cost(problem::DeviceProblem, xs, us, x, u; params=nothing, handle::
 end
 
 """
+    expected_cost(K, Σ, x0, x, u, model, cost_model; Sigma0=nothing, moments=false, handle) -> ec, status[, mu, sigma]
+
+Moments and expected cost of the linear-Gaussian policy `K[m,n,N(,B)]`, `Σ[m,m,N(,B)]` (`nothing`: deterministic) around the nominal
+`x[n,N(,B)]`, `u[m,N(,B)]` under `model = (fx, fu, fc, cov)`, the first four results of `fit_dynamics` (`cov = nothing`: zeros), and
+`cost_model = (cx, cu, cxx, cxu, cuu, c0)`, the results of `fit_cost` (ddp_expected_cost_f64; the recursion is in include/ddp_amd.h): the
+step that closes a guided-policy-search round.  `x0 = nothing` starts at `x[:,1]`, `Sigma0 = nothing` at zero covariance.  `model` and
+`cost_model` carry the batch axis or, with a batched policy, are shared by the batch.  `ec[N(,B)]`; `status` is 0, or `i` (counted from
+1) for the first step whose `ec` is not finite, from which on the trajectory's outputs are NaN; with `moments=true` also
+`mu[n+m,N(,B)] = [μx_i; u_i + δu_i]` and `sigma[n+m,n+m,N(,B)] = Σz_i`, symmetric to the bit.
+"""
+function expected_cost(K, Σ, x0, x, u, model, cost_model; Sigma0=nothing, moments::Bool=false, handle::Handle=default_handle())
+    batched = ndims(x) == 3
+    n, N = size(x, 1), size(x, 2)
+    m = size(u, 1)
+    B = batched ? size(x, 3) : 1
+    bt = batched ? (B,) : ()
+    size(u) == (m, N, bt...) && size(K) == (m, n, N, bt...) || throw(DDPError(-1, "expected_cost: K, x, u should be (m,n,N), (n,N), (m,N) [+ batch axis]"))
+    length(model) == 4 && length(cost_model) == 6 || throw(DDPError(-1, "expected_cost: model is (fx, fu, fc, cov), cost_model (cx, cu, cxx, cxu, cuu, c0)"))
+    mb = batched && ndims(model[1]) == 4
+    cb = batched && ndims(cost_model[1]) == 3
+    K = _f64(K); x = _f64(x); u = _f64(u)
+    Sg = Σ === nothing ? Float64[] : _f64(Σ)
+    x0h = x0 === nothing ? Float64[] : _f64(x0)
+    S0 = Sigma0 === nothing ? Float64[] : _f64(Sigma0)
+    fx = _f64(model[1]); fu = _f64(model[2]); fc = _f64(model[3]); cov = model[4] === nothing ? Float64[] : _f64(model[4])
+    cx = _f64(cost_model[1]); cu = _f64(cost_model[2]); cxx = _f64(cost_model[3]); cxu = _f64(cost_model[4]); cuu = _f64(cost_model[5])
+    c0 = _f64(cost_model[6])
+    ec = result_array(N, bt...); status = zeros(Int32, B)
+    mu = moments ? result_array(n + m, N, bt...) : Float64[]
+    sigma = moments ? result_array(n + m, n + m, N, bt...) : Float64[]
+    mbi = Int(mb); cbi = Int(cb)
+    GC.@preserve K Sg x0h x u fx fu fc cov cx cu cxx cxu cuu c0 S0 ec status mu sigma begin
+        check(@ccall libddp.ddp_expected_cost_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, B::Cint, K::Ptr{Float64},
+            _ptr_or_null(Sg)::Ptr{Float64}, _ptr_or_null(x0h)::Ptr{Float64}, x::Ptr{Float64}, u::Ptr{Float64}, fx::Ptr{Float64},
+            fu::Ptr{Float64}, fc::Ptr{Float64}, _ptr_or_null(cov)::Ptr{Float64}, mbi::Cint, cx::Ptr{Float64}, cu::Ptr{Float64},
+            cxx::Ptr{Float64}, cxu::Ptr{Float64}, cuu::Ptr{Float64}, c0::Ptr{Float64}, cbi::Cint, _ptr_or_null(S0)::Ptr{Float64},
+            ec::Ptr{Float64}, status::Ptr{Int32}, _ptr_or_null(mu)::Ptr{Float64}, _ptr_or_null(sigma)::Ptr{Float64})::Cint)
+    end
+    st = batched ? status : Int(status[1])
+    return moments ? (ec, st, mu, sigma) : (ec, st)
+end
+
+"""
+    kl_step_adjust(ec_prev, ec_pred, ec_act, kl_step; step_min=1e-2, step_max=1e2, handle) -> kl_step_new, mult
+
+The step rule of a guided-policy-search round per trajectory (ddp_kl_step_adjust_f64), from three results of `expected_cost`: the old
+policy on the old models, the new policy on the old models, the new policy on the new models, `ec[N(,B)]` each.  With `J` the sum of a
+column in ascending order, `pred = J_prev - J_pred`, `act = J_prev - J_act`: `mult = clamp(pred / (2 max(1e-4, pred - act)), 0.1, 5)`
+(0.1 when a `J` is not finite) and `kl_step_new = clamp(kl_step * mult, step_min, step_max)`; `kl_step` is a number or `B` values.
+"""
+function kl_step_adjust(ec_prev, ec_pred, ec_act, kl_step; step_min::Real=1e-2, step_max::Real=1e2, handle::Handle=default_handle())
+    N = size(ec_prev, 1)
+    B = ndims(ec_prev) == 2 ? size(ec_prev, 2) : 1
+    size(ec_pred) == size(ec_prev) && size(ec_act) == size(ec_prev) || throw(DDPError(-1, "kl_step_adjust: the three ec arrays should have one shape"))
+    e0 = _f64(ec_prev); e1 = _f64(ec_pred); e2 = _f64(ec_act)
+    ks = kl_step isa Real ? fill(Float64(kl_step), B) : _f64(kl_step)
+    length(ks) == B || throw(DDPError(-1, "kl_step_adjust: kl_step should be a number or B values"))
+    new = zeros(Float64, B); mult = zeros(Float64, B)
+    smin = Float64(step_min); smax = Float64(step_max)
+    GC.@preserve e0 e1 e2 ks new mult begin
+        check(@ccall libddp.ddp_kl_step_adjust_f64(handle.ptr::Ptr{Cvoid}, N::Cint, B::Cint, e0::Ptr{Float64}, e1::Ptr{Float64},
+            e2::Ptr{Float64}, ks::Ptr{Float64}, smin::Cdouble, smax::Cdouble, new::Ptr{Float64}, mult::Ptr{Float64})::Cint)
+    end
+    return new, mult
+end
+
+"""
+    kl_set_steps!(handle, steps)
+
+One `kl_step` per trajectory for the `iLQGkl` loops of `handle` (ddp_kl_set_steps_f64): `steps` holds `B` finite values, e.g. the first
+result of `kl_step_adjust`; `nothing` clears the table, after which the loops read their scalar `kl_step` again.
+"""
+function kl_set_steps!(handle::Handle, steps)
+    if steps === nothing
+        check(@ccall libddp.ddp_kl_set_steps_f64(handle.ptr::Ptr{Cvoid}, 0::Cint, C_NULL::Ptr{Float64})::Cint)
+        return nothing
+    end
+    s = _f64(vec(steps))
+    nB = length(s)
+    GC.@preserve s begin
+        check(@ccall libddp.ddp_kl_set_steps_f64(handle.ptr::Ptr{Cvoid}, nB::Cint, s::Ptr{Float64})::Cint)
+    end
+    return nothing
+end
+
+"""
     fit_gmm(xs, us, K; iters=20, reg=1e-6, seed=0, init=nothing, pool=true, traj0=0, handle) -> (pi, mu, Sigma, ll, status, pool)
 
 A `K`-cluster Gaussian mixture fitted by EM on the device to the transition tuples `w = [x̂_i; û_i; x̂_{i+1}]` (`p = 2n + m`) of all steps

@@ -35,7 +35,7 @@ from . import _lib
 from . import DDPError, DeviceProblem, GaussianPolicy, _clock, _DevProblem, _fitted_tables, _lims, _user_shapes, default_handle, df, forward_pass
 
 __all__ = ["Model", "grad_kl", "∇kl", "back_pass_gps", "forward_covariance", "kl_div_wiki", "calc_η", "geom", "iLQGkl",
-           "model_covariance", "demo_linear_kl"]
+           "model_covariance", "demo_linear_kl", "kl_step_adjust"]
 
 
 @dataclass
@@ -68,6 +68,20 @@ def _wide(h, on):
         yield
     finally:
         h.set_kl_wide(was)
+
+
+@_contextlib.contextmanager
+def _steps(h, steps):
+    """``kl_step`` with one value per trajectory: the handle's table (ddp_kl_set_steps) holds them inside the block and is cleared on
+    every way out"""
+    if steps is None:
+        yield
+        return
+    _lib.check(_lib.lib().ddp_kl_set_steps_f64(h.raw, int(steps.size), _lib.ptr(steps)))
+    try:
+        yield
+    finally:
+        _lib.check(_lib.lib().ddp_kl_set_steps_f64(h.raw, 0, None))
 
 
 def _b(a, nd):
@@ -231,7 +245,11 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     ``cost_model=(cx, cu, cxx, cxu, cuu)`` (a ``DeviceProblem``; ``[n,N(,B)]``, ``[m,N(,B)]``, ``[n,n,N(,B)]``, ``[n,m,N(,B)]``,
     ``[m,m,N(,B)]``, e.g. the first five arrays ``fit_cost`` returns): every backward pass of the loop takes these arrays in place of the
     cost derivatives STEP 1 evaluates at ``(x0, traj_prev.k)``; ``cost``, the problem's own cost of the rollouts (what the loop compares
-    and returns) and the loop itself are as without it.  With and without ``fitted=True``; the arrays must be finite."""
+    and returns) and the loop itself are as without it.  With and without ``fitted=True``; the arrays must be finite.
+    ``kl_step``: a scalar, or with a batched call ``B`` values, ONE STEP PER TRAJECTORY (e.g. ``kl_step_adjust(...)[0]``): trajectory
+    ``b`` is held to ``kl_step[b]`` and runs as it does in a call with that scalar.  (The reference's per-time-step meaning of a
+    vector ``kl_step`` belongs to ``constrain_per_step``, which stays refused.)  The values are the handle's for the duration of the call
+    (``ddp_kl_set_steps``) and cleared on every way out; every loop variant reads them, ``DDP_KL_HOSTLOOP=1`` included."""
     if cost_model is not None:
         if wide:
             raise DDPError("iLQGkl: cost_model= together with wide=True is refused (deferred: a cost model is sized for n <= 32, m <= 8)")
@@ -261,6 +279,15 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     if x.shape[1] != u.shape[1]:
         raise ValueError("pre-rolled initial trajectory must be of correct length (size(x0,2) == N)")            # :72
     _kl_box("iLQGkl", n, m, wide)
+    steps = None
+    if np.ndim(kl_step) != 0:                              # one step per trajectory
+        steps = np.ascontiguousarray(kl_step, dtype=np.float64)
+        if not batched or steps.shape != (B,):
+            raise DDPError("iLQGkl: kl_step should be a scalar or, with a batched call, B = %d values (one step per trajectory), got shape %s"
+                           % (B, np.shape(kl_step)))
+        if not np.all(np.isfinite(steps)):
+            raise DDPError("iLQGkl: kl_step[%d] = %r is not finite" % (int(np.flatnonzero(~np.isfinite(steps))[0]), float(steps[~np.isfinite(steps)][0])))
+        kl_step = float(steps[0])                          # (the scalar of the call is not read while the table is set)
     prev0 = GaussianPolicy(N, n, m, _b(traj_prev.K, 3), np.zeros_like(u), _b(traj_prev.Σ, 3), _b(traj_prev.Σi, 3))   # k *= 0 (:51)
     user = isinstance(problem, DeviceProblem)
     prm = _user_kl_args(problem, model, prev0, x, u, cost, lims, params, diff_fun, batched) if user else None
@@ -272,11 +299,11 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     del0 = np.full(B, float(del0))
     import os as _os
     if _os.environ.get("DDP_KL_HOSTLOOP") != "1":
-        with _wide(h, wide), _clock(problem, h, t0):
+        with _wide(h, wide), _clock(problem, h, t0), _steps(h, steps):
             return _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, etab, float(del0[0]), batched, diff_fun, prm,
                                 tables, ctabs)
     with _wide(h, wide), _clock(problem, h, t0):           # (the clocks are checked here; the array calls below set their own)
-        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0,
+        return _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step if steps is None else steps, max_iter, x, u, etab, del0, batched, diff_fun, prm, user, wide, t0,
                                 tables, ctabs)
 
 
@@ -424,7 +451,7 @@ def _ilqgkl_hostloop(h, problem, model, prev0, lims, kl_step, max_iter, x, u, et
             out["K"][..., idx], out["S"][..., idx], out["Si"][..., idx] = new.K, new.Σ, new.Σi
             out["Vx"][..., idx], out["Vxx"][..., idx], out["dV"][..., idx] = acc[4], acc[5], acc[6]
         for j, b in enumerate(idx):                                                                             # :141, :169-177
-            eb, sat, dv = calc_η(None, None, None, etab[:, b], None, None, kl_step, _mean=mean[j])
+            eb, sat, dv = calc_η(None, None, None, etab[:, b], None, None, kl_step if np.ndim(kl_step) == 0 else kl_step[b], _mean=mean[j])
             etab[:, b] = eb
             divergence[b], satisfied[b] = dv, sat
             if sat:
@@ -515,6 +542,35 @@ def _ilqgkl_call(h, problem, model, prev0, lims, kl_step, max_iter, x, u, cost, 
         trace = {k_: (v[..., 0] if isinstance(v, np.ndarray) else v) for k_, v in trace.items()}
         return xo[..., 0], uo[..., 0], traj_new, Vx[..., 0], Vxx[..., 0], co[..., 0], trace
     return xo, uo, GaussianPolicy(N, n, m, K, uo.copy(), S, Si), Vx, Vxx, co, trace
+
+
+def kl_step_adjust(ec_prev, ec_pred, ec_act, kl_step, *, step_min=1e-2, step_max=1e2, handle=None):
+    """The step rule of a guided-policy-search round, per trajectory, from three results of ``expected_cost``: ``ec_prev[N(,B)]`` the old
+    policy on the old models, ``ec_pred`` the new policy on the old models, ``ec_act`` the new policy on the new models.  With
+    ``J = Σ_i ec[i, b]`` summed in ascending ``i``: ``pred = J_prev − J_pred``, ``act = J_prev − J_act``,
+    ``mult = clip(pred / (2 max(1e-4, pred − act)), 0.1, 5)`` (0.1 when a ``J`` is not finite) and
+    ``kl_step_new = clip(kl_step · mult, step_min, step_max)``; ``kl_step`` is a scalar or ``B`` values.  Returns
+    ``(kl_step_new[B], mult[B])`` (``ddp_kl_step_adjust_f64``, one thread per trajectory); ``iLQGkl(..., kl_step=kl_step_new)`` takes
+    the first as it is."""
+    ecs = [_lib.f64(a) for a in (ec_prev, ec_pred, ec_act)]
+    if ecs[0].ndim not in (1, 2) or any(a.shape != ecs[0].shape for a in ecs):
+        raise DDPError("kl_step_adjust: ec_prev, ec_pred, ec_act should be three (N,) or (N, B) arrays, got %s" % ", ".join(str(a.shape) for a in ecs))
+    if ecs[0].ndim == 1:
+        ecs = [_lib.f64(a[:, None]) for a in ecs]
+    N, B = ecs[0].shape
+    if N < 1 or B < 1:
+        raise DDPError("kl_step_adjust: N = %d, B = %d (both >= 1)" % (N, B))
+    ks = np.asarray(kl_step, dtype=np.float64)
+    if ks.ndim != 0 and ks.shape != (B,):
+        raise DDPError("kl_step_adjust: kl_step should be a scalar or B = %d values, got shape %s" % (B, ks.shape))
+    ks = np.ascontiguousarray(np.broadcast_to(ks, (B,)))
+    if not (0 < step_min <= step_max < np.inf):
+        raise DDPError("kl_step_adjust: step_min = %r, step_max = %r should be finite with 0 < step_min <= step_max" % (step_min, step_max))
+    h = handle or default_handle()                         # (behind the checks that need no device)
+    new, mult = np.zeros(B), np.zeros(B)
+    _lib.check(_lib.lib().ddp_kl_step_adjust_f64(h.raw, N, B, *map(_lib.ptr, ecs), _lib.ptr(ks), float(step_min), float(step_max),
+                                                 _lib.ptr(new), _lib.ptr(mult)))
+    return new, mult
 
 
 def _tv(a, N, batched=False):

@@ -452,6 +452,26 @@ int ddp_kl_dual_begin_f64_dev(ddp_handle h, int B, int it, const ddp_kl_dual *s,
 int ddp_kl_dual_retry_f64_dev(ddp_handle h, int B, const ddp_kl_dual *s, const int32_t *diverge, int *n_pending);
 int ddp_kl_dual_update_f64_dev(ddp_handle h, int B, double kl_step, const ddp_kl_dual *s, const double *klmean, int *n_live);
 
+/* One kl_step per trajectory for every iLQGkl loop of the handle (registered and user problems, fitted tables, a cost model) and for
+ * ddp_kl_dual_update_f64_dev: steps[B], finite (a non-finite entry is refused by name); the handle keeps its own device copy, and
+ * while it is set the update of the dual variable reads steps[b] in place of the scalar kl_step of the call — also in calc_η's
+ * `kl_step > 0` test.  steps == NULL clears the table (B is not read).  A loop whose B differs from the table's is refused by name
+ * before any launch.  This is one step per TRAJECTORY; the reference's per-time-step meaning of a vector kl_step belongs to
+ * constrain_per_step, which is not offloaded.  No struct changes its layout.                                                   */
+int ddp_kl_set_steps_f64(ddp_handle h, int B, const double *steps);
+int ddp_kl_set_steps_f64_dev(ddp_handle h, int B, const double *steps);
+
+/* The step rule of a guided-policy-search round, per trajectory, from three results of ddp_expected_cost_* (below): ec_prev[N,B] the
+ * old policy on the old models, ec_pred[N,B] the new policy on the old models, ec_act[N,B] the new policy on the new models.  With
+ * J = sum_i ec[i,b] in ascending i:  pred = J_prev - J_pred,  act = J_prev - J_act,
+ *   mult[b] = clip(pred / (2 max(1e-4, pred - act)), 0.1, 5)   (0.1 when one of the three J is not finite),
+ *   kl_step_new[b] = clip(kl_step[b] mult[b], step_min, step_max),   kl_step[B], 0 < step_min <= step_max finite.
+ * One thread per trajectory (kl.hip): a device-resident round reads nothing back here; kl_step_new goes to ddp_kl_set_steps_*_dev. */
+int ddp_kl_step_adjust_f64_dev(ddp_handle h, int N, int B, const double *ec_prev, const double *ec_pred, const double *ec_act,
+                               const double *kl_step, double step_min, double step_max, double *kl_step_new, double *mult);
+int ddp_kl_step_adjust_f64(ddp_handle h, int N, int B, const double *ec_prev, const double *ec_pred, const double *ec_act,
+                           const double *kl_step, double step_min, double step_max, double *kl_step_new, double *mult);
+
 /* ---- iLQGkl — replaces iLQGkl(dynamics,costfun,derivs,x0,traj_prev,model; kl_step,lims,max_iter,cost,ηbracket,del0) ------------
  * reference: src/iLQGkl.jl:25-178,234-252 (single KL constraint; the per-time-step branch :180-232 cannot run upstream), called from
  * src/demo_linear.jl:124.  The whole loop — derivs, ∇kl, back_pass_gps until the KL-regularised Quu is positive definite (η += del;
@@ -987,6 +1007,44 @@ int ddp_gmm_prior_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, int K
 int ddp_gmm_prior_f64(ddp_handle h, int n, int m, int N, int S, int B, int K, int pool, const double *xs, const double *us,
                       const double *pi, const double *mu, const double *Sigma, double m0, double n0, double *Phi, double *mu0,
                       int32_t *status);
+
+/* The moments and the expected cost of a linear-Gaussian policy under a fitted linear-Gaussian model and a fitted quadratic cost, the
+ * step that closes the guided-policy-search round (sample -> fit -> iLQGkl -> expected cost -> ddp_kl_step_adjust_*).  The policy is
+ * the one ddp_user_sample_* runs, u^_i = u_i + K_i (x^_i - x_i) + L_i xi with L_i L_i' = Sigma_i; the dynamics
+ * x^_{i+1} = fx_i x^_i + fu_i u^_i + fc_i + w_i, w_i ~ N(0, cov_i), are the first four results of ddp_fit_dynamics_*; the cost of step i
+ * is the quadratic model (cx, cu, cxx, cxu, cuu, c0) of ddp_user_cost_fit_* around (x_i, u_i).  With p = n + m, G_i = [fx_i fu_i],
+ * H_i = [cxx_i cxu_i; cxu_i' cuu_i]:
+ *   mux_0 = x0 (NULL: x[:,0]),  Sx_0 = Sigma0 (NULL: 0)
+ *   dx_i = mux_i - x_i,   du_i = K_i dx_i,   dz_i = [dx_i; du_i]            (plain subtraction; lims play no part)
+ *   Sz_i = [Sx_i, Sx_i K_i'; K_i Sx_i, K_i Sx_i K_i' + Sigma_i]
+ *   ec_i = c0_i + cx_i.dx_i + cu_i.du_i + dz_i' H_i dz_i / 2 + tr(H_i Sz_i) / 2                       i = 0 .. N - 1
+ *   mux_{i+1} = fx_i mux_i + fu_i (u_i + du_i) + fc_i,   Sx_{i+1} = G_i Sz_i G_i' + cov_i             i = 0 .. N - 2
+ * inputs : K[m,n,N,B], Sigma[m,m,N,B] (NULL: a deterministic policy), x0[n,B] or NULL, x[n,N,B], u[m,N,B];
+ *          fx[n,n,N(,B)], fu[n,m,N(,B)], fc[n,N(,B)], cov[n,n,N(,B)] (NULL: zeros) with the batch axis iff model_batched = 1 (slot N - 1
+ *          is not read by the kernel); cx[n,N(,B)], cu[m,N(,B)], cxx[n,n,N(,B)], cxu[n,m,N(,B)], cuu[m,m,N(,B)], c0[N(,B)] with the batch
+ *          axis iff cost_batched = 1; Sigma0[n,n,B] or NULL.
+ * outputs: ec[N,B], status[B], and (each may be NULL) mu[p,N,B] = [mux_i; u_i + du_i], sigma[p,p,N,B] = Sz_i in the layout of
+ *          ddp_forward_covariance_*'s sigmanew, filled at every step including N - 1.
+ * cxx, cuu, cov, Sigma and Sigma0 are taken as symmetric (their upper triangles are what Sigma, Sigma0 and cov contribute); the
+ * result on input that is not symmetric is undefined.  Sx and Sz are computed on their upper blocks and mirrored: sigma is symmetric to
+ * the bit.  status[b] is 0, or i + 1 for the first step whose ec is not finite; from that step on the trajectory's ec, mu and sigma
+ * are NaN — also when the value that was not finite (a c0_i, say) does not enter the chain of moments — and no other trajectory is
+ * touched.  1 <= n <= 32, 1 <= m <= 8, N >= 1, B >= 1; anything else — a null required pointer, a *_batched flag other than 0 or 1,
+ * for the host flavour a Sigma0 that is not finite (the _dev flavour cannot see it: it ends in status 1) — is refused by name before any
+ * launch and before the handle is looked at.  Every sum has a fixed order that does not depend on B: two calls give the same bits, a
+ * call on a slice of the trajectories gives the bits of that slice, and the host flavour (which stages its arrays like every
+ * host-pointer entry) gives the bits of the _dev one.  Kernel ddp_expected_cost (expect.hip): one work-group of four waves per
+ * trajectory, the matrix products on v_mfma_f64_16x16x4, the operands of step i + 1 fetched while step i computes.                 */
+int ddp_expected_cost_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *K, const double *Sigma, const double *x0,
+                              const double *x, const double *u, const double *fx, const double *fu, const double *fc, const double *cov,
+                              int model_batched, const double *cx, const double *cu, const double *cxx, const double *cxu,
+                              const double *cuu, const double *c0, int cost_batched, const double *Sigma0, double *ec, int32_t *status,
+                              double *mu, double *sigma);
+int ddp_expected_cost_f64(ddp_handle h, int n, int m, int N, int B, const double *K, const double *Sigma, const double *x0,
+                          const double *x, const double *u, const double *fx, const double *fu, const double *fc, const double *cov,
+                          int model_batched, const double *cx, const double *cu, const double *cxx, const double *cxu,
+                          const double *cuu, const double *c0, int cost_batched, const double *Sigma0, double *ec, int32_t *status,
+                          double *mu, double *sigma);
 
 #ifdef __cplusplus
 }
