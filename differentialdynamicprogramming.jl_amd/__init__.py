@@ -163,7 +163,8 @@ def example_source(name):
     """Source text of a bundled example problem: ``"lq"``, ``"pendcart"`` or ``"car"`` (``user_examples/<name>.hip``), or the same
     model written for ``autodiff=True``: ``"lq_ad"``, ``"pendcart_ad"``, ``"car_ad"``; ``"car_plant"``: the car with a plant for the
     closed loop (``plant=True``); ``"bicycle_ad"``: a kinematic bicycle whose dynamics have mixed and control curvature, for
-    ``second_order=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
+    ``second_order=True``; ``"chain_plant_ad"``: ``chain_ad`` with a plant (per-joint actuator gain and another damping, 9 parameters),
+    for ``plant=True`` at the sizes of ``wave=True``; ``"chain_ad"``: a chain of ``m`` coupled pendulums (``n = 2 m``, 7 parameters at every size), the large model
     for ``wave=True``; ``"chain_ddp_ad"``: the same chain with the torque entering as ``g tanh(u_j) cos(q_j)`` (curvature in x, u
     and mixed; ``n = 2 m``, 8 parameters), for ``second_order_wave=True``; ``"car_track"``, ``"car_track_ad"``, ``"car_track_plant"``: the
     car following a sampled reference past a moving obstacle (``7 + 4 L`` parameters, the plant ``7 + 6 L``), for ``clock=True``;
@@ -212,12 +213,19 @@ class DeviceProblem:
     ``cost_fit=True`` (DDP_USER_COST_FIT): the program also holds ``ddp_user_cost_fit``, and ``fit_cost`` fits the quadratic cost model of
     a guided-policy-search round to the samples ``sample_policy`` returns — the cost expanded at every sample, moved to the nominal and
     averaged; ``kl.iLQGkl(..., cost_model=...)`` plans on it.  Every other entry point ignores the flag.  Not together with ``wave``,
-    ``second_order_wave``, ``clock`` or ``constraints`` (deferred)."""
+    ``second_order_wave``, ``clock`` or ``constraints`` (deferred).
+    ``sample_wave=True`` (DDP_USER_SAMPLE_WAVE, needs ``wave=True``): the sampler at the shapes of ``wave=True``, ``n <= 64`` and
+    ``m <= 32`` — the program also holds ``ddp_user_sample_wave`` (a group of lanes per sample, the vectors in LDS) and ``sample_policy``
+    takes the problem, with the semantics of ``sample=True`` word for word; every other entry point ignores the flag.  Legal with
+    ``terminal``, ``const_hessian``, ``autodiff``, ``plant``, ``second_order_wave`` and ``diff``; not with ``clock`` or ``constraints``
+    (deferred).  ``sample=True`` stays the flag of a problem without ``wave``."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
-                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False, cost_fit=False):
+                 second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False, cost_fit=False,
+                 sample_wave=False):
         self.clock = bool(clock)
+        self.sample_wave = bool(sample_wave)
         self.cost_fit = bool(cost_fit)
         self.sample = bool(sample)
         self.fitted = bool(fitted)
@@ -226,13 +234,17 @@ class DeviceProblem:
             raise DDPError("DeviceProblem: constraints = %d (the number of constraints, 0 for none)" % self.nc)
         self.second_order_wave = bool(second_order_wave)
         self.second_order, self.wave = bool(second_order), bool(wave) or self.second_order_wave
+        if self.sample_wave and not self.wave:
+            raise DDPError("DeviceProblem: DDP_USER_SAMPLE_WAVE needs DDP_USER_WAVE (sample_wave=True needs wave=True; without wave the "
+                           "sampler is sample=True)")
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
                       (8 if self.plant else 0) | (16 if self.second_order else 0) | (_lib.USER_WAVE if self.wave else 0) |
                       (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
                       (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0) |
-                      (_lib.USER_FITTED if self.fitted else 0) | (_lib.USER_COST_FIT if self.cost_fit else 0))
+                      (_lib.USER_FITTED if self.fitted else 0) | (_lib.USER_COST_FIT if self.cost_fit else 0) |
+                      (_lib.USER_SAMPLE_WAVE if self.sample_wave else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -838,7 +850,8 @@ def normal(seed, m, N, S, B=None, *, sample0=0, traj0=0, handle=None):
 def sample_policy(problem, traj, x0, x, u, S, *, seed=0, noise=None, lims=None, plant=False, params=None, moments=False, sample0=0,
                   traj0=0, handle=None):
     """``S`` closed-loop rollouts per trajectory of the policy ``traj`` (``K``, ``Σ``; a solve's ``traj_new``) around the nominal
-    ``(x, u)`` from ``x0``, on a ``DeviceProblem`` made with ``sample=True``: at step ``i``
+    ``(x, u)`` from ``x0``, on a ``DeviceProblem`` made with ``sample=True`` (``n <= 32``, ``m <= 8``) or with ``wave=True,
+    sample_wave=True`` (``n <= 64``, ``m <= 32``): at step ``i``
     ``û = u[:, i] + L_i ξ_i + K[:, :, i] diff(x̂, x[:, i])``, clamped to ``lims``, with ``L_i`` the lower Cholesky factor of ``Σ[:, :, i]``
     (the reference's docstring uses the upper one, whose samples do not have covariance ``Σ`` for m > 1) — the sampling step of the
     guided-policy-search loop.  ``ξ`` is generated on the device from ``seed`` (an int in [0, 2^64); see ``normal``), or taken from

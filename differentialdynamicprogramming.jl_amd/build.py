@@ -39,7 +39,7 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "user_program.hip": ["-I", OBJ]}                  # the headers of PROGRAM_TEXTS, written to build/
 
 
-EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
+EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_sample_wave_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
               "user_problem.hip": ["user_program.h", "user_problem_kernels.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "wide_tile.h", "back_pass_wide_kernel.h"], "sample.hip": ["philox.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
               "ilqg.hip": ["ilqg_model.h"], "kl.hip": ["ilqg_model.h"], "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"], "fit.hip": ["wide_tile.h"], "gmm.hip": ["wide_tile.h", "philox.h"], "expect.hip": ["wide_tile.h"]}
@@ -48,7 +48,7 @@ EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "
 # Headers of csrc/ as program text for hiprtc (user_program.hip): output file -> [(symbol, header)].  The kernels compiled at run time take
 # the definitions the precompiled ones include, one definition for both compilers: ddp_user_back_pass2 factorises and solves with
 # boxqp_dev.h, ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE) is the step of back_pass_wide.hip, ddp_user_sample (DDP_USER_SAMPLE)
-# draws its normals with the philox.h of sample.hip.
+# and ddp_user_sample_wave (DDP_USER_SAMPLE_WAVE) draw their normals with the philox.h of sample.hip.
 PROGRAM_TEXTS = {"boxqp_dev_text.h": [("kBoxqpDevText", "boxqp_dev.h")],
                  "wide_kernel_text.h": [("kWideTileText", "wide_tile.h"), ("kWideKernelText", "back_pass_wide_kernel.h")],
                  "philox_text.h": [("kPhiloxText", "philox.h")]}

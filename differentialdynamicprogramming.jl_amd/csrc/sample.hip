@@ -6,6 +6,8 @@
 //                        positive finite number (an atomic min over the steps, then ddp_policy_status turns "none" into 0).
 //                        The reference's docstring says chol(Σ)*randn(m): Julia's chol is the UPPER factor U, and U ξ has covariance
 //                        U U', which is not Σ for m > 1.  The lower factor is used here on purpose (L ξ has covariance Σ).
+//   ddp_policy_factor_wide  the same contract for 8 < m <= 32 (DDP_USER_SAMPLE_WAVE): a half-wave per matrix, a row per lane, out of LDS;
+//                        the m <= 8 kernel is untouched.
 //   ddp_sample_moments   xs[n,N,S,B] -> xmean[n,N,B] and the unbiased xcov[n,n,N,B] over the samples: one wave per (step, trajectory),
 //                        two passes (the mean, then the centred products).  Lane l sums s = l, l + 64, ..., then a fixed butterfly:
 //                        two runs give the same bits.  S = 1: the covariance is 0/0 = NaN.
@@ -55,6 +57,46 @@ __global__ __launch_bounds__(64) void ddp_policy_factor(int N, int B, const doub
     if (factor_lower<M>(Sigma + (size_t)M * M * r, L + (size_t)M * M * r)) atomicMin(status + b, i + 1);
 }
 
+// 8 < m <= 32: two matrices per wave, a half-wave each, lane q of the half owning row q of the factor; the matrix lives in LDS, column-major
+// at stride m (the lanes of a half read consecutive addresses, the pivot row is a broadcast), and is factored in place.  The order is
+// factor_lower's, left-looking: column c = 0..m-1; d = S[c,c] - Σ_k l[c,k]² and s = S[q,c] - Σ_k l[q,k] l[c,k] with k = 0..c-1 ascending;
+// l[c,c] = sqrt(d), l[q,c] = s / l[c,c].  Every lane forms d itself from the broadcast row (the same bits in every lane).  Entries above
+// the diagonal come into LDS with the rest but enter no sum, and leave as zeros.
+__global__ __launch_bounds__(64) void ddp_policy_factor_wide(int m, int N, int B, const double *Sigma, double *L, int32_t *status)
+{
+    __shared__ double lds[2][DDP_MAX_M_WIDE * DDP_MAX_M_WIDE];
+    const int half = threadIdx.x >> 5, q = threadIdx.x & 31, mm = m * m;
+    const long r = (long)blockIdx.x * 2 + half;
+    const bool act = r < (long)N * B;
+    double *l = lds[half];
+    if (act)
+        for (int e = q; e < mm; e += 32) l[e] = Sigma[(size_t)mm * r + e];
+    __syncthreads();
+    int fail = 0;
+    for (int c = 0; c < m; ++c) {
+        double lqc = 0.0;
+        if (act) {
+            double d = l[c + m * c];
+            for (int k = 0; k < c; ++k) d -= l[c + m * k] * l[c + m * k];
+            if (!(d > 0.0 && d <= DBL_MAX) && fail == 0) fail = c + 1;
+            const double rt = sqrt(d);
+            if (q == c) lqc = rt;
+            else if (q > c && q < m) {
+                double s = l[q + m * c];
+                for (int k = 0; k < c; ++k) s -= l[q + m * k] * l[c + m * k];
+                lqc = s / rt;
+            }
+        }
+        __syncthreads();                                         // (every read of column c's old values and of the diagonal is done)
+        if (act && q < m) l[q + m * c] = lqc;
+        __syncthreads();
+    }
+    if (act) {
+        for (int e = q; e < mm; e += 32) L[(size_t)mm * r + e] = l[e];
+        if (fail && q == 0) atomicMin(status + (int)(r / N), (int)(r % N) + 1);
+    }
+}
+
 __global__ void ddp_policy_status(int B, int32_t *status, int first)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,7 +112,7 @@ __device__ __forceinline__ double wave_sum(double v)            // a fixed butte
 
 __global__ __launch_bounds__(64) void ddp_sample_moments(int n, int N, int S, int B, const double *xs, double *xmean, double *xcov)
 {
-    __shared__ double mean[DDP_MAX_N_USER];
+    __shared__ double mean[DDP_MAX_N_USER_WAVE];
     const long r = blockIdx.x;                                  // (step, trajectory)
     const int lane = threadIdx.x, b = (int)(r / N), i = (int)(r - (long)b * N);
     const double *x = xs + (size_t)n * ((size_t)N * S * b + i);  // sample s: x + n N s
@@ -113,7 +155,8 @@ __global__ __launch_bounds__(256) void ddp_normal_fill(int seed_lo, int seed_hi,
 
 int ddp_policy_factor_dev(ddp_handle h, int m, int N, int B, const double *Sigma, double *L, int32_t *status)
 {
-    DDP_CHECK(m >= 1 && m <= DDP_MAX_M, "policy_factor: m = %d out of [1, %d]", m, DDP_MAX_M);
+    DDP_CHECK(m >= 1 && m <= DDP_MAX_M_WIDE, "policy_factor: m = %d out of [1, %d]", m, DDP_MAX_M_WIDE);
+    DDP_CHECK(((long)N * B + 63) / 64 <= 0x7fffffffL, "policy_factor: N = %d, B = %d is too large for one launch", N, B);
     const unsigned gb = (unsigned)((B + 255) / 256), gr = (unsigned)(((long)N * B + 63) / 64);
     hipLaunchKernelGGL(ddp_policy_status, dim3(gb), dim3(256), 0, h->stream, B, status, 1);
     switch (m) {
@@ -121,6 +164,8 @@ int ddp_policy_factor_dev(ddp_handle h, int m, int N, int B, const double *Sigma
         DDP_FACTOR_CASE(1) DDP_FACTOR_CASE(2) DDP_FACTOR_CASE(3) DDP_FACTOR_CASE(4) DDP_FACTOR_CASE(5) DDP_FACTOR_CASE(6) DDP_FACTOR_CASE(7)
         DDP_FACTOR_CASE(8)
 #undef DDP_FACTOR_CASE
+    default:                                                     // 8 < m <= 32
+        hipLaunchKernelGGL(ddp_policy_factor_wide, dim3((unsigned)(((long)N * B + 1) / 2)), dim3(64), 0, h->stream, m, N, B, Sigma, L, status);
     }
     hipLaunchKernelGGL(ddp_policy_status, dim3(gb), dim3(256), 0, h->stream, B, status, 0);
     DDP_HIP(hipGetLastError());
@@ -129,7 +174,7 @@ int ddp_policy_factor_dev(ddp_handle h, int m, int N, int B, const double *Sigma
 
 int ddp_sample_moments_dev(ddp_handle h, int n, int N, int S, int B, const double *xs, double *xmean, double *xcov)
 {
-    DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER, "sample_moments: n = %d out of [1, %d]", n, DDP_MAX_N_USER);
+    DDP_CHECK(n >= 1 && n <= DDP_MAX_N_USER_WAVE, "sample_moments: n = %d out of [1, %d]", n, DDP_MAX_N_USER_WAVE);
     DDP_CHECK((long)N * B <= 0x7fffffffL, "sample_moments: N = %d, B = %d is too large for one launch", N, B);
     hipLaunchKernelGGL(ddp_sample_moments, dim3((unsigned)((long)N * B)), dim3(64), 0, h->stream, n, N, S, B, xs, xmean, xcov);
     DDP_HIP(hipGetLastError());

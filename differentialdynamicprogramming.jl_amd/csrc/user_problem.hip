@@ -65,7 +65,9 @@ struct Module {
     hipModule_t mod = nullptr;
     hipFunction_t roll = nullptr, df = nullptr, cost = nullptr, hess = nullptr, plant = nullptr, bp2 = nullptr, vhess = nullptr;
     hipFunction_t bp2w = nullptr;                                // ddp_user_back_pass2_wave (DDP_USER_SECOND_ORDER_WAVE)
-    hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE)
+    hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE) or ddp_user_sample_wave (DDP_USER_SAMPLE_WAVE)
+    const char *sample_name = nullptr;
+    int sample_per = 0;                                          // samples per work-group of `sample`
     hipFunction_t rollfit = nullptr;                             // ddp_user_rollout_fit (DDP_USER_FITTED)
     hipFunction_t costfit = nullptr;                             // ddp_user_cost_fit (DDP_USER_COST_FIT)
     hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
@@ -385,6 +387,8 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
         const bool wave = (flags & DDP_USER_WAVE) != 0;
         M.df_name = (flags & DDP_USER_AUTODIFF) ? (wave ? "ddp_user_df_wave" : "ddp_user_df_ad") : "ddp_user_df";
         M.roll_name = wave ? "ddp_user_rollout_wave" : "ddp_user_rollout";
+        M.sample_name = (flags & DDP_USER_SAMPLE_WAVE) ? "ddp_user_sample_wave" : "ddp_user_sample";
+        M.sample_per = (flags & DDP_USER_SAMPLE_WAVE) ? 64 / M.L.wg : M.L.slanes;
         DDP_HIP(hipModuleLoadData(&M.mod, code.data()));
         // the kernels of the program: mask 0 = every program has it, else the flags (any of them) whose programs do
         const struct { int mask; const char *name; hipFunction_t Module::*fn; } kernels[] = {
@@ -394,7 +398,7 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
             {DDP_USER_SECOND_ORDER_WAVE, "ddp_user_back_pass2_wave", &Module::bp2w},
             {DDP_USER_SECOND_ORDER | DDP_USER_SECOND_ORDER_WAVE, "ddp_user_vhess", &Module::vhess},
             {DDP_USER_CONSTRAINTS, "ddp_user_constraints", &Module::con}, {DDP_USER_CONSTRAINTS, "ddp_user_al_update", &Module::alup},
-            {DDP_USER_SAMPLE, "ddp_user_sample", &Module::sample}, {DDP_USER_FITTED, "ddp_user_rollout_fit", &Module::rollfit},
+            {DDP_USER_SAMPLE | DDP_USER_SAMPLE_WAVE, M.sample_name, &Module::sample}, {DDP_USER_FITTED, "ddp_user_rollout_fit", &Module::rollfit},
             {DDP_USER_COST_FIT, "ddp_user_cost_fit", &Module::costfit}};
         bool ok = true;
         for (const auto &k : kernels)
@@ -836,7 +840,7 @@ static int sample_check(const UserProblem *P, int S, const double *K, const doub
                         int traj0, int use_plant, const double *xs, const double *cs, const double *csum, const double *xmean,
                         const double *xcov, const int32_t *status)
 {
-    DDP_CHECK(P->mod->sample, "sample: the problem was made without DDP_USER_SAMPLE");
+    DDP_CHECK(P->mod->sample, "sample: the problem was made without DDP_USER_SAMPLE (a DDP_USER_WAVE problem: without DDP_USER_SAMPLE_WAVE)");
     DDP_CHECK(use_plant == 0 || use_plant == 1, "sample: use_plant = %d (0 or 1)", use_plant);
     DDP_CHECK(!use_plant || (P->flags & DDP_USER_PLANT), "sample: use_plant = 1 but the problem was made without DDP_USER_PLANT");
     DDP_CHECK(S >= 1, "sample: S = %d (>= 1)", S);
@@ -856,7 +860,7 @@ int ddp_user_sample_f64_dev(ddp_handle h, void *up, int N, int B, int S, const d
     if (rc) return rc;
     if ((rc = sample_check(P, S, K, x0, u, x, sample0, traj0, use_plant, xs, cs, csum, xmean, xcov, status))) return rc;
     const int m = P->m;
-    const long groups = ((long)S + P->mod->L.slanes - 1) / P->mod->L.slanes;
+    const long groups = ((long)S + P->mod->sample_per - 1) / P->mod->sample_per;
     DDP_CHECK(groups * B <= 0x7fffffffL, "sample: S = %d, B = %d is too large for one launch", S, B);
     if (Sigma) {
         if ((rc = P->chol.reserve(h->stream, (size_t)m * m * N * B * sizeof(double)))) return rc;
@@ -871,7 +875,7 @@ int ddp_user_sample_f64_dev(ddp_handle h, void *up, int N, int B, int S, const d
     a.noise = Sigma ? noise : nullptr; a.status = status; a.xs = xs; a.us = us; a.cs = cs; a.csum = csum;
     void *args[] = {&a};
     DDP_HIP(hipModuleLaunchKernel(P->mod->sample, (unsigned)(groups * B), 1, 1, 64, 1, 1, 0, h->stream, args, nullptr));
-    h->last_kernel[1] = "ddp_user_sample";
+    h->last_kernel[1] = P->mod->sample_name;
     if (xmean || xcov) return ddp_sample_moments_dev(h, P->n, N, S, B, xs, xmean, xcov);
     return 0;
 }

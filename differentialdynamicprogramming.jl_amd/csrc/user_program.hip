@@ -15,6 +15,7 @@
 #include "user_problem_kernels.h"
 #include "user_problem_wave_kernels.h"
 #include "user_sample_kernels.h"
+#include "user_sample_wave_kernels.h"
 #include "user_fitted_kernels.h"
 #include "user_cost_fit_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
@@ -247,7 +248,7 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
                          DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE | DDP_USER_FITTED |
-                         DDP_USER_COST_FIT)) == 0,
+                         DDP_USER_COST_FIT | DDP_USER_SAMPLE_WAVE)) == 0,
               "user problem: unknown flags 0x%x", flags);
     // deferred, not impossible: the sampled kernels keep a lane's state in registers or its cost derivatives in LDS (n <= 32, m <= 8) and hand
     // the user's functions neither a clock nor multipliers
@@ -263,6 +264,16 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
         DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: %s | DDP_USER_CLOCK is refused (deferred: %s takes no clock)", s.name, s.kernel);
         DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: %s | DDP_USER_CONSTRAINTS is refused (deferred: %s takes no multipliers)",
                   s.name, s.kernel);
+    }
+    if (flags & DDP_USER_SAMPLE_WAVE) {
+        // the sampler at the wave sizes is a flag of its own (DDP_USER_SAMPLE | DDP_USER_WAVE stays refused, as it always was); deferred, not
+        // impossible: ddp_user_sample_wave hands the user's functions neither a clock nor multipliers, as ddp_user_sample
+        DDP_CHECK(wave, "user problem: DDP_USER_SAMPLE_WAVE needs DDP_USER_WAVE (ddp_user_sample_wave runs in the layout of "
+                        "ddp_user_rollout_wave; without DDP_USER_WAVE the sampler is DDP_USER_SAMPLE)");
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_SAMPLE_WAVE | DDP_USER_CLOCK is refused (deferred: ddp_user_sample_wave "
+                                             "takes no clock)");
+        DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_SAMPLE_WAVE | DDP_USER_CONSTRAINTS is refused (deferred: "
+                                                   "ddp_user_sample_wave takes no multipliers)");
     }
     if (flags & DDP_USER_CONSTRAINTS) {
         // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
@@ -429,6 +440,11 @@ static std::string program_text(const char *source, int n, int m, int nparam, in
     if (flags & DDP_USER_COST_FIT) {
         snprintf(head, sizeof head, "#define DDP_CLANES %d\n#define DDP_CCHUNK %d\n#define DDP_CSB %d\n", L.clanes, L.cchunk, L.csb);
         section(s, head, "ddp_user_kernels_cost_fit", DDP_USER_ABI_COST_FIT_TEXT, kUserKernelsCostFit);
+    }
+    if (flags & DDP_USER_SAMPLE_WAVE) {                          // (never next to DDP_USER_SAMPLE: one copy of philox.h and of the struct)
+        s += "\n#line 1 \"ddp_philox\"\n";
+        s += kPhiloxText;
+        section(s, "", "ddp_user_kernels_sample_wave", DDP_USER_ABI_SAMPLE_TEXT, kUserKernelsSampleWave);
     }
     return s;
 }

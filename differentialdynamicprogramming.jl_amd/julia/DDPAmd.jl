@@ -551,6 +551,7 @@ const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of Devic
 const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
 const USER_SAMPLE = 2048               # DDP_USER_SAMPLE: the flag of DeviceProblem(...; sample=true)
 const USER_FITTED = 4096               # DDP_USER_FITTED: the flag of DeviceProblem(...; fitted=true)
+const USER_SAMPLE_WAVE = 16384         # DDP_USER_SAMPLE_WAVE: the flag of DeviceProblem(...; wave=true, sample_wave=true)
 const USER_COST_FIT = 8192             # DDP_USER_COST_FIT: the flag of DeviceProblem(...; cost_fit=true)
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
 const MAX_M_WIDE = 32                  # DDP_MAX_M_WIDE: back_pass / forward_pass / iLQG of the LQ family (8 < m <= 32: the wide-control kernels)
@@ -991,6 +992,8 @@ end
 # cost_fit=true (DDP_USER_COST_FIT): the program also holds ddp_user_cost_fit, and fit_cost fits the quadratic cost model of a
 # guided-policy-search round to the samples of sample_policy; iLQGkl(...; cost_model=(cx, cu, cxx, cxu, cuu)) plans on it.  Not together
 # with wave, second_order_wave, clock or constraints.
+# sample_wave=true (DDP_USER_SAMPLE_WAVE, needs wave=true): the sampler at the shapes of wave=true, n <= 64 and m <= 32 — the program also
+# holds ddp_user_sample_wave, and sample_policy takes the problem with the semantics of sample=true.  Not together with clock or constraints.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -1005,12 +1008,14 @@ end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
                        second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false,
-                       fitted::Bool=false, cost_fit::Bool=false)
+                       fitted::Bool=false, cost_fit::Bool=false, sample_wave::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
+    sample_wave && !wave && error("DeviceProblem: DDP_USER_SAMPLE_WAVE needs DDP_USER_WAVE (sample_wave=true needs wave=true)")
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
             (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0) |
-            (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0) | (cost_fit ? USER_COST_FIT : 0)
+            (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0) | (cost_fit ? USER_COST_FIT : 0) |
+            (sample_wave ? USER_SAMPLE_WAVE : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1267,7 +1272,7 @@ end
                   sample0=0, traj0=0, handle) -> xs, us, cs, info
 
 `S` closed-loop rollouts per trajectory of the policy `traj` (`K`, `Σ`) around the nominal `(x, u)` from `x0`, on a `DeviceProblem` made
-with `sample=true` (ddp_user_sample_f64): `û = u[:,i] + L_i ξ_i + K[:,:,i] diff(x̂, x[:,i])`, clamped to `lims`, `L_i` the LOWER
+with `sample=true` (n <= 32, m <= 8) or with `wave=true, sample_wave=true` (n <= 64, m <= 32) (ddp_user_sample_f64): `û = u[:,i] + L_i ξ_i + K[:,:,i] diff(x̂, x[:,i])`, clamped to `lims`, `L_i` the LOWER
 Cholesky factor of `Σ[:,:,i]` (the docstring of the reference's iLQGkl uses the upper one, whose samples do not have covariance `Σ` for
 m > 1).  `ξ` is generated on the device from `seed`, or taken from `noise[m,N,S(,B)]`; `Σ` empty or all zero: the noise-free closed loop.
 `plant=true` runs the problem's `plant` instead of its `dynamics`.  Returns `xs[n,N,S(,B)]`, `us[m,N,S(,B)]`, `cs[CL,S(,B)]` and `info`

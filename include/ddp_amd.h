@@ -703,14 +703,29 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SAMPLE, DDP_USER_FITTED,
  * DDP_USER_SECOND_ORDER and diff_wrap.  Together with DDP_USER_WAVE (and so DDP_USER_SECOND_ORDER_WAVE), DDP_USER_CLOCK or
  * DDP_USER_CONSTRAINTS it is refused by name — deferred, not impossible.  A problem without the flag compiles the text it always did;
- * the tail of the flag goes last in the program, behind that of DDP_USER_FITTED. */
+ * the tail of the flag goes last in the program, behind that of DDP_USER_FITTED.
+ *
+ * DDP_USER_SAMPLE_WAVE: the sampled rollouts of DDP_USER_SAMPLE at the shapes of DDP_USER_WAVE, n <= 64, m <= 32 (ddp_user_sample_*,
+ * below; every other entry point ignores the flag).  A flag of its own, which needs DDP_USER_WAVE: DDP_USER_SAMPLE | DDP_USER_WAVE stays
+ * refused, as DDP_USER_SECOND_ORDER | DDP_USER_WAVE is next to DDP_USER_SECOND_ORDER_WAVE.  The step, the noise, the generator and its
+ * counter, the status and the NaN rows are those of DDP_USER_SAMPLE, word for word; nothing depends on the launch geometry, S or B.
+ * Kernel ddp_user_sample_wave (ddp_last_kernel(h, 1)): a group of lanes per sample (8, 16 or 32: the power of two >= m), 64 / group
+ * samples per one-wave work-group, every group of a work-group on one trajectory; x^, diff(x^, x_i), u^ and xi_i in LDS; lane q of
+ * the group draws the Philox pair q of the step and forms row q of u^ = u_i, + sum_c L_i[q,c] xi_c (c ascending), + sum_l K_i[q,l] dx_l
+ * (l ascending), clamp — the order of ddp_user_sample — streaming row q of K_i and L_i from memory; one lane of the group calls the
+ * user's stage_cost and dynamics (or plant) on the LDS vectors; results leave in contiguous runs written by the group.  The noise
+ * factor of 8 < m <= 32 is ddp_policy_factor_wide (one wave per Sigma_i, a row per lane, left-looking).  Legal with DDP_USER_TERMINAL,
+ * DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SECOND_ORDER_WAVE and diff_wrap.  Without DDP_USER_WAVE, or
+ * together with DDP_USER_CLOCK or DDP_USER_CONSTRAINTS, it is refused by name — the last two deferred, not impossible.  A problem
+ * without the flag compiles the text it always did; the tail of the flag goes last in the program.  user_examples/chain_plant_ad.hip is
+ * chain_ad.hip with a plant (an actuator gain per joint, another damping; 9 parameters), for use_plant = 1 at these sizes. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
        DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
        DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048, DDP_USER_FITTED = 4096,
-       DDP_USER_COST_FIT = 8192 };                                                         /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_COST_FIT = 8192, DDP_USER_SAMPLE_WAVE = 16384 };                           /* 64: not assigned, refused as unknown (256 too) */
 #define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
@@ -858,14 +873,14 @@ int ddp_user_ilqg_al_f64(ddp_handle h, void *up, int N, int B, const double *par
  * two seed words are the low and high 32 bits of a 64-bit seed, passed as int (their bits are what counts).  Kernel ddp_normal_fill. */
 int ddp_normal_f64_dev(ddp_handle h, int seed_lo, int seed_hi, int m, int N, int S, int B, int sample0, int traj0, double *xi);
 int ddp_normal_f64(ddp_handle h, int seed_lo, int seed_hi, int m, int N, int S, int B, int sample0, int traj0, double *xi);
-/* DDP_USER_SAMPLE problems only (others are refused by name).  K[m,n,N,B], Sigma[m,m,N,B] (lower triangle read), x0[n,B], u[m,N,B],
+/* DDP_USER_SAMPLE and DDP_USER_SAMPLE_WAVE problems only (others are refused by name).  K[m,n,N,B], Sigma[m,m,N,B] (lower triangle read), x0[n,B], u[m,N,B],
  * x[n,N,B], lims[m,2] or NULL -> xs[n,N,S,B], us[m,N,S,B], cs[CL,S,B], csum[S,B], status[B], and the moments over the samples
  * xmean[n,N,B], xcov[n,n,N,B] (unbiased; S = 1: NaN).  Sigma == NULL: no noise, the deterministic policy rollout (S is usually 1).
  * noise[m,N,S,B] != NULL overrides the seed (ignored without Sigma).  xs, us, xmean, xcov may be NULL; moments without xs are
  * refused by name.  status[b] is 0, or i + 1 for the smallest step whose Sigma_i is not positive definite (a pivot of its Cholesky
  * factorisation that is not a positive finite number): such a trajectory runs no rollout and its rows of every non-NULL output are
- * NaN.  use_plant = 1 on a problem without DDP_USER_PLANT is refused by name.  The noise factors (kernel ddp_policy_factor) live in a
- * buffer the problem owns; the moments are ddp_sample_moments, one wave per step and trajectory, a fixed summation order.        */
+ * NaN.  use_plant = 1 on a problem without DDP_USER_PLANT is refused by name.  The noise factors (kernel ddp_policy_factor, for m > 8
+ * ddp_policy_factor_wide) live in a buffer the problem owns; the moments are ddp_sample_moments, one wave per step and trajectory, a fixed summation order.        */
 int ddp_user_sample_f64_dev(ddp_handle h, void *up, int N, int B, int S, const double *params, int params_batched, const double *K,
                             const double *Sigma, const double *x0, const double *u, const double *x, const double *lims, const double *noise,
                             int seed_lo, int seed_hi, int sample0, int traj0, int use_plant, double *xs, double *us, double *cs, double *csum,
