@@ -164,18 +164,28 @@ int ddp_ilqg_sched_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqg_
                               const double *u0, const double *lims, double *x, double *u, double *K, double *k, double *Quu, double *Vx,
                               double *Vxx, double *cost, double *stats, double *xcl, double *ucl, double *stats_cl, int *global_iters);
 
-// the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev; model_fx == NULL: the family's own fx of STEP 1).
-// fit_fx, fit_fu, fit_fc [.,.,N,B] (all three or none): the loop plans on that fitted model — back_pass_gps takes fit_fx, fit_fu, the
-// rollouts run on the family with the tables set (FitScope), model_fx == NULL means fit_fx.
-// cm_cx[n,N,B], cm_cu[m,N,B], cm_cxx[n,n,N,B], cm_cxu[n,m,N,B], cm_cuu[m,m,N,B] (all five or none): a cost model — the backward passes
-// take these arrays in place of the cost derivatives STEP 1 wrote; nothing else of the loop changes
-int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
-                          const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
-                          int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
-                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
-                          const double *fit_fx = nullptr, const double *fit_fu = nullptr, const double *fit_fc = nullptr,
-                          const double *cm_cx = nullptr, const double *cm_cu = nullptr, const double *cm_cxx = nullptr,
-                          const double *cm_cxu = nullptr, const double *cm_cuu = nullptr);
+// One iLQGkl call as the C ABI passes it (ddp_ilqgkl_f64_dev, ddp_user_ilqgkl*_f64_dev): every entry fills one, the driver of kl.hip
+// takes it.  Optional members are NULL when the entry has none.
+struct KlCall {
+    const ddp_ilqgkl_opts *opts = nullptr;                                     // NULL: ddp_ilqgkl_default_opts
+    const double *x0 = nullptr, *cost0 = nullptr;                              // cost0 == NULL: costfun(x0, kp)
+    const double *Kp = nullptr, *kp = nullptr, *Sp = nullptr, *Sip = nullptr;   // the previous policy
+    const double *model_fx = nullptr;                                          // the model of forward_covariance; NULL (family only): the fx of STEP 1,
+    int model_fx_batched = 0;                                                  // or fit_fx
+    const double *R1 = nullptr, *lims = nullptr;
+    double *etab = nullptr;                                                    // NULL: the driver's own, from opts->etabracket
+    // a fitted model [.,.,N,B] (all three or none, family only): the loop plans on it — back_pass_gps takes fit_fx, fit_fu, the rollouts
+    // run on the family with the tables set (FitScope)
+    const double *fit_fx = nullptr, *fit_fu = nullptr, *fit_fc = nullptr;
+    // a cost model cx[n,N,B], cu[m,N,B], cxx[n,n,N,B], cxu[n,m,N,B], cuu[m,m,N,B] (all five or none, family only): the backward passes
+    // take these arrays in place of the cost derivatives STEP 1 wrote; nothing else of the loop changes
+    const double *cm_cx = nullptr, *cm_cu = nullptr, *cm_cxx = nullptr, *cm_cxu = nullptr, *cm_cuu = nullptr;
+    double *x = nullptr, *u = nullptr, *K = nullptr, *Sigma = nullptr, *Sigmai = nullptr, *Vx = nullptr, *Vxx = nullptr, *cost = nullptr,
+           *dV = nullptr, *stats = nullptr;
+    int *iters = nullptr;                                                      // may stay NULL
+};
+// the device-resident iLQGkl of kl.hip for such a family (arguments as ddp_ilqgkl_f64_dev)
+int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const KlCall &c);
 
 // sample.hip: the lower Cholesky factors L[m,m,N,B] of Sigma[m,m,N,B] and status[B] (0, or i + 1 of the first step that is not positive
 // definite), and the moments xmean[n,N,B] / xcov[n,n,N,B] (either may be NULL) of xs[n,N,S,B] over its samples; the device is current
@@ -274,9 +284,6 @@ int ddp_launch_fcov_wide(ddp_handle h, int n, int m, int N, int B, const double 
 int ddp_launch_kl_div_wide(ddp_handle h, int n, int m, int N, int B, const double *xnew, const double *xold, const double *sigmanew,
                            const double *Kn, const double *kn, const double *Sn, const double *Kp, const double *kp, const double *Sp,
                            const double *Sip, double *kldiv, double *klmean);
-// back_pass_gps dispatch (kl.hip): the user-problem KL driver (`user`) tries q4, lane, mid, generic; every other call q4, lane, generic.
-// DDP_GPS_MID=1 puts mid first for every call, =0 keeps it out.  Records the kernel in ddp_last_kernel(h, 0).
-int ddp_dispatch_back_pass_gps(ddp_handle h, const BPCall &c, bool user);
 // shared time-invariant operands (n=10, m=2, no limits): the matrix recursion once per distinct λ, an affine chain per trajectory
 // (back_pass_sh.hip); the trajectories it left out are flagged in *fb_active
 extern "C" int ddp_sh_max_tiles(int B, int ncu);      // capacity of its work-item list: the most consumer tiles any grouping of B trajectories can make

@@ -1,16 +1,8 @@
 // ilqg_model.h — the problem as the iLQG drivers (ilqg.hip) and the iLQGkl driver (kl.hip) see it, and the derivative workspace they
 // hand to it.  A driver runs a registered ddp_problem kind or a ddp_family (a user problem); Model is the only place that asks which.
 #pragma once
+#include "carver.h"
 #include "ddp_internal.h"
-
-// One device block handed out in 256-byte-aligned pieces (the backward-pass dispatcher tests the alignment of its operands).  A layout is
-// written once, as a function of a Carver: run from address 0 it measures the block, run from the block's base it places the pieces.
-struct Carver {
-    uintptr_t p;
-    explicit Carver(void *base = nullptr) : p((uintptr_t)base) {}
-    template <class T> T *take(size_t count) { T *r = (T *)p; p += (count * sizeof(T) + 255) & ~(size_t)255; return r; }
-    template <class T> T *take_if(bool want, size_t count) { return want ? take<T>(count) : nullptr; }
-};
 
 struct Model;
 // workspace of STEPS 1-2 for `slots` trajectories: what df writes (fxw, fuw: dynamics of the problem's own; hxx, hxu, huu: the cost

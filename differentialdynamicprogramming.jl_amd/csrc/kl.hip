@@ -3,7 +3,7 @@
 //   forward_covariance src/forward_pass.jl:37-56 one wave per trajectory, the discrete Lyapunov chain Σ⁺ = fx Σ fx' + R1
 //   kl_div_wiki        src/klutils.jl:70-103     one wave per trajectory, lanes over time, mean over time in the wave
 // plus the C-ABI entry points of the four KL calls (the back_pass_gps kernels: the GPS variants of back_pass.hip and back_pass_mid.hip,
-// the n = 4 ones of back_pass_q4.hip and back_pass_gps_lane.hip; gps_dispatch below chooses) and the iLQGkl driver for registered and
+// the n = 4 ones of back_pass_q4.hip and back_pass_gps_lane.hip; gps_choose below chooses) and the iLQGkl driver for registered and
 // user problems.
 // None of this is on the benchmarked path; the kernels are written for clarity and coalescing, not tuned.
 #include <float.h>
@@ -12,6 +12,7 @@
 #include <type_traits>
 #include "ddp_internal.h"
 #include "ilqg_model.h"
+#include "kl_workspace.h"
 #include "staging.h"
 
 namespace {
@@ -636,74 +637,107 @@ __global__ __launch_bounds__(DDP_WAVE) void kl_summary_kernel(int m, int N, ddp_
 
 size_t fcov_lds(int n, int m) { return ((size_t)3 * n * n + 2 * (size_t)n * m) * sizeof(double); }
 
-// ---- back_pass_gps kernel choice.  q4: n = 4, m = 1, one η per trajectory (back_pass_q4.hip); lane: n = 4, m <= 2 (back_pass_gps_lane.hip);
-// mid: any n <= 32, m <= 8 on the matrix cores behind a combine prepass (back_pass_mid.hip); generic: the 64-lane run-time-sized kernel
-// (back_pass.hip).  The user-problem KL driver takes q4, lane, mid, generic; the stand-alone call and the registered families' driver
-// q4, lane, generic as before.  DDP_GPS_MID=1 puts mid first in every call, =0 keeps it out of all of them (A/B timing, tests).
-// wide: any n <= 64, m <= DDP_MAX_M_WIDE on the GPS instantiation of back_pass_wide.hip — the shapes beyond n <= 32, m <= 8 when the
-// handle's ddp_kl_set_wide switch is on, every shape with DDP_GPS_WIDE=1 (gps_choose2).
+// ---- kernel choice of the four KL entry points, host facts only.  Each entry point fills a KlChoiceIn, asks its *_choose function and
+// launches what that returns; the unlisted hooks ddp_gps_choice .. ddp_kl_div_choice are wrappers over the same functions.
+// back_pass_gps.  q4: n = 4, m = 1, one η per trajectory (back_pass_q4.hip); lane: n = 4, m <= 2 (back_pass_gps_lane.hip); mid: any
+// n <= 32, m <= 8 on the matrix cores behind a combine prepass (back_pass_mid.hip); generic: the 64-lane run-time-sized kernel
+// (back_pass.hip), also every call whose `kl` argument is incomplete (the generic launcher words that refusal).  The user-problem KL
+// driver takes q4, lane, mid, generic; the stand-alone call and the registered families' driver q4, lane, generic.  DDP_GPS_MID=1 puts
+// mid first in every call, =0 keeps it out of all of them (A/B timing, tests).  wide: the GPS instantiation of back_pass_wide.hip, see
+// kl_shape.
 enum GpsKernel { GPS_Q4, GPS_LANE, GPS_MID, GPS_GENERIC, GPS_WIDE, GPS_NONE };
 const char *const gps_kernel_name[] = {"back_pass_gps_q4", "back_pass_gps_lane", "back_pass_gps_mid", "back_pass_gps", "back_pass_gps_wide", "none"};
 enum GpsCaller { GPS_STANDALONE = 0, GPS_REGISTERED = 1, GPS_USER = 2 };
 
-// host facts only (the same tests the launchers make before they return 1)
-GpsKernel gps_choose(const ddp_bp_desc &d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane)
+// What a choice depends on besides the sizes.  caller, eta_tv, complete: back_pass_gps (complete: every pointer of `kl` is there, and
+// lims and u with has_lims); al16: forward_covariance, its fx, K, Sigma and sigmanew are 16-byte aligned; sink: the handle has its sink
+// buffer; wide_on: ddp_kl_set_wide; the switches as strings (NULL: unset)
+struct KlChoiceIn {
+    int caller = GPS_STANDALONE, eta_tv = 0;
+    bool complete = true, al16 = false, sink = false;
+    int wide_on = 0;
+    const char *gps_mid = nullptr, *gps_q4 = nullptr, *gps_lane = nullptr, *gps_wide = nullptr, *fcov_q4 = nullptr, *fcov_q4l = nullptr,
+               *kl_lds = nullptr;
+};
+KlChoiceIn kl_choice_in(ddp_handle h, const BPCall *c = nullptr)
 {
-    const char mid = gps_mid ? gps_mid[0] : 0;
-    const bool mid_ok = d.n >= 1 && d.n <= NMAXK && d.m >= 1 && d.m <= 8;
-    if (mid == '1' && mid_ok) return GPS_MID;
-    const bool fast = caller != GPS_STANDALONE || !(gps_lane && gps_lane[0] == '0');    // stand-alone DDP_GPS_LANE=0: the generic kernel
+    KlChoiceIn q;
+    q.sink = h->sink != nullptr; q.wide_on = h->kl_wide;
+    q.gps_mid = ddp_env(h, ENV_GPS_MID); q.gps_q4 = ddp_env(h, ENV_GPS_Q4); q.gps_lane = ddp_env(h, ENV_GPS_LANE);
+    q.gps_wide = ddp_env(h, ENV_GPS_WIDE); q.fcov_q4 = ddp_env(h, ENV_FCOV_Q4); q.fcov_q4l = ddp_env(h, ENV_FCOV_Q4L);
+    q.kl_lds = ddp_env(h, ENV_KL_LDS);
+    if (c) {
+        const ddp_kl_cost_terms *kl = c->kl;
+        q.eta_tv = kl ? kl->eta_tv : 0;
+        q.complete = kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!c->d.has_lims || (c->lims && c->u));
+    }
+    return q;
+}
+
+// The KL shape box: 0 the kernels of n <= 32, m <= 8; 1 the wide kernels of n <= 64, m <= DDP_MAX_M_WIDE (the switch is on and the shape
+// is beyond the box, or DDP_GPS_WIDE=1 inside it); -1 no kernel.
+int kl_shape(int n, int m, const KlChoiceIn &q)
+{
+    const bool small = n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK, wide_ok = n >= 1 && n <= KL_WIDE_MAX_N && m >= 1 && m <= DDP_MAX_M_WIDE;
+    if (small) return (q.gps_wide && q.gps_wide[0] == '1') ? 1 : 0;
+    return (q.wide_on && wide_ok) ? 1 : -1;
+}
+// The one shape check: every KL entry point and the iLQGkl driver call it before anything else depends on the sizes
+// (`kernel`: what the entry has no kernel for — "back_pass_gps" for that entry and the loop around it, as the wrappers word it, "KL" else)
+int kl_check_shape(ddp_handle h, const char *who, const char *kernel, int n, int m, int N, int B)
+{
+    DDP_CHECK(kl_shape(n, m, kl_choice_in(h)) >= 0, "%s: n=%d m=%d has no %s kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): "
+              "n <= %d, m <= %d)", who, n, m, kernel, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
+    DDP_CHECK(N >= 1 && B >= 1, "%s: bad sizes N=%d B=%d (both >= 1)", who, N, B);
+    return 0;
+}
+
+GpsKernel gps_choose(const ddp_bp_desc &d, const KlChoiceIn &q)
+{
+    const int sh = kl_shape(d.n, d.m, q);
+    if (sh < 0) return GPS_NONE;
+    if (!q.complete) return GPS_GENERIC;
+    if (sh) return GPS_WIDE;
+    const char mid = q.gps_mid ? q.gps_mid[0] : 0;
+    if (mid == '1') return GPS_MID;
+    const bool fast = q.caller != GPS_STANDALONE || !(q.gps_lane && q.gps_lane[0] == '0');    // stand-alone DDP_GPS_LANE=0: the generic kernel
     const bool tv = d.N >= 2 && d.fx_tv && d.cost_tv;
-    if (fast && tv && d.n == 4 && d.m == 1 && !eta_tv && !(gps_q4 && gps_q4[0] == '0')) return GPS_Q4;
+    if (fast && tv && d.n == 4 && d.m == 1 && !q.eta_tv && !(q.gps_q4 && q.gps_q4[0] == '0')) return GPS_Q4;
     if (fast && tv && d.n == 4 && (d.m == 1 || d.m == 2)) return GPS_LANE;
-    if (caller == GPS_USER && mid != '0' && mid_ok) return GPS_MID;
+    if (q.caller == GPS_USER && mid != '0') return GPS_MID;
     return GPS_GENERIC;
 }
 
-// The KL shape box: 0 the kernels of n <= 32, m <= 8; 1 the wide kernels (the switch is on and the shape is beyond the box, or
-// DDP_GPS_WIDE=1); -1 no kernel.  Host facts only.
-int kl_shape(int n, int m, int wide_on, const char *gps_wide)
+// ∇kl: the small kernel or the wide one
+enum KlTermsKernel { KLTERMS_SMALL, KLTERMS_WIDE, KLTERMS_NONE };
+KlTermsKernel kl_terms_choose(int n, int m, const KlChoiceIn &q)
 {
-    const bool small = n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK, wide_ok = n >= 1 && n <= KL_WIDE_MAX_N && m >= 1 && m <= DDP_MAX_M_WIDE;
-    if (small) return (gps_wide && gps_wide[0] == '1') ? 1 : 0;
-    return (wide_on && wide_ok) ? 1 : -1;
-}
-int kl_shape(ddp_handle h, int n, int m) { return kl_shape(n, m, h->kl_wide, ddp_env(h, ENV_GPS_WIDE)); }
-#define DDP_KL_SHAPE(h, who, n, m)                                                                                                   \
-    DDP_CHECK(kl_shape(h, n, m) >= 0, "%s: n=%d m=%d has no kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", who, n, \
-              m, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE)
-
-GpsKernel gps_choose2(const ddp_bp_desc &d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane, int wide_on,
-                      const char *gps_wide)
-{
-    const int sh = kl_shape(d.n, d.m, wide_on, gps_wide);
-    if (sh < 0) return GPS_NONE;
-    return sh ? GPS_WIDE : gps_choose(d, eta_tv, caller, gps_mid, gps_q4, gps_lane);
+    const int sh = kl_shape(n, m, q);
+    return sh < 0 ? KLTERMS_NONE : sh ? KLTERMS_WIDE : KLTERMS_SMALL;
 }
 
-// ---- forward_covariance and kl_div_wiki kernel choice, host facts only (fcov_choose, kl_div_choose: what the two entry points launch;
-// the names are what ddp_last_kernel(h, 5) and (h, 6) report).
-// forward_covariance.  q4<M>: n = 4, m = M <= 2 on the matrix cores, four trajectories per wave (needs the handle's sink buffer;
-// DDP_FCOV_Q4=0: not); q4l: its m = 1 variant with chunks of eight steps through the LDS — N a multiple of 8 and >= 16, fx, K, Sigma and
-// sigmanew 16-byte aligned, B <= 6144 (DDP_FCOV_Q4L=0: not); generic: the run-time-sized kernel, every n <= 32, m <= 8; wide: kl_shape.
+// forward_covariance (the names are what ddp_last_kernel(h, 5) reports).  q4<M>: n = 4, m = M <= 2 on the matrix cores, four
+// trajectories per wave (needs the handle's sink buffer; DDP_FCOV_Q4=0: not); q4l: its m = 1 variant with chunks of eight steps through
+// the LDS — N a multiple of 8 and >= 16, fx, K, Sigma and sigmanew 16-byte aligned, B <= 6144 (DDP_FCOV_Q4L=0: not); generic: the
+// run-time-sized kernel, every n <= 32, m <= 8; wide: kl_shape.
 enum FcovKernel { FCOV_GENERIC, FCOV_Q4_1, FCOV_Q4_2, FCOV_Q4L, FCOV_WIDE, FCOV_NONE };
 const char *const fcov_kernel_name[] = {"fcov_kernel", "fcov_q4_kernel<1>", "fcov_q4_kernel<2>", "fcov_q4l_kernel", "fcov_wide_kernel", "none"};
 
-FcovKernel fcov_choose(int n, int m, int N, int B, bool al16, bool sink, int wide_on, const char *gps_wide, const char *fcov_q4,
-                       const char *fcov_q4l)
+FcovKernel fcov_choose(int n, int m, int N, int B, const KlChoiceIn &q)
 {
-    const int sh = kl_shape(n, m, wide_on, gps_wide);
+    const int sh = kl_shape(n, m, q);
     if (sh < 0 || N < 1 || B < 1) return FCOV_NONE;
     if (sh) return FCOV_WIDE;
-    if (n == 4 && (m == 1 || m == 2) && sink && !(fcov_q4 && fcov_q4[0] == '0')) {
-        if (m == 1 && N % FQL_CH == 0 && N >= 2 * FQL_CH && al16 && B <= 6144 && !(fcov_q4l && fcov_q4l[0] == '0')) return FCOV_Q4L;
+    if (n == 4 && (m == 1 || m == 2) && q.sink && !(q.fcov_q4 && q.fcov_q4[0] == '0')) {
+        if (m == 1 && N % FQL_CH == 0 && N >= 2 * FQL_CH && q.al16 && B <= 6144 && !(q.fcov_q4l && q.fcov_q4l[0] == '0')) return FCOV_Q4L;
         return m == 1 ? FCOV_Q4_1 : FCOV_Q4_2;
     }
     return FCOV_GENERIC;
 }
 
-// kl_div_wiki.  lds: the operands of 64 steps through an LDS image when that fits 48 KB (DDP_KL_LDS=0: not) — <4,1> and <4,2> with
-// compile-time sizes, <0,0> the run-time-sized staging loop; direct: every n <= 32, m <= 8 from global memory; wide: kl_shape.
+// kl_div_wiki (ddp_last_kernel(h, 6)).  lds: the operands of 64 steps through an LDS image when that fits 48 KB (DDP_KL_LDS=0: not) —
+// <4,1> and <4,2> with compile-time sizes, <0,0> the run-time-sized staging loop; direct: every n <= 32, m <= 8 from global memory;
+// wide: kl_shape.
 enum KlDivKernel { KLDIV_DIRECT, KLDIV_LDS41, KLDIV_LDS42, KLDIV_LDS00, KLDIV_WIDE, KLDIV_NONE };
 const char *const kl_div_kernel_name[] = {"kl_div_kernel", "kl_div_lds_kernel<4,1>", "kl_div_lds_kernel<4,2>", "kl_div_lds_kernel<0,0>",
                                           "kl_div_wide_kernel", "none"};
@@ -717,43 +751,38 @@ size_t kl_div_image(int n, int m)
     return image;
 }
 
-KlDivKernel kl_div_choose(int n, int m, int N, int B, int wide_on, const char *gps_wide, const char *kl_lds)
+KlDivKernel kl_div_choose(int n, int m, int N, int B, const KlChoiceIn &q)
 {
-    const int sh = kl_shape(n, m, wide_on, gps_wide);
+    const int sh = kl_shape(n, m, q);
     if (sh < 0 || N < 1 || B < 1) return KLDIV_NONE;
     if (sh) return KLDIV_WIDE;
-    if (kl_div_image(n, m) <= 48 * 1024 && !(kl_lds && kl_lds[0] == '0'))
+    if (kl_div_image(n, m) <= 48 * 1024 && !(q.kl_lds && q.kl_lds[0] == '0'))
         return (n == 4 && m == 1) ? KLDIV_LDS41 : (n == 4 && m == 2) ? KLDIV_LDS42 : KLDIV_LDS00;
     return KLDIV_DIRECT;
 }
 
-int gps_dispatch(ddp_handle h, const BPCall &c, int caller)
+// Launches the kernel gps_choose returned for the call.  A launcher returns 1 to decline, and the next of q4 -> lane -> generic takes the
+// call.  What they test is what gps_choose has tested already — q4: n = 4, m = 1, N >= 2, time-varying fx and cost, one η per
+// trajectory, DDP_GPS_Q4; lane: n = 4, m <= 2, N >= 2, time-varying fx and cost; mid: the box, a `kl` and a Quui — so behind gps_choose
+// only mid can decline, on a BPCall without Quui (no entry point builds one).  ddp_last_kernel(h, 0) names the kernel that ran.
+int gps_launch(ddp_handle h, const BPCall &c, GpsKernel k)
 {
-    const ddp_kl_cost_terms *kl = c.kl;
-    const bool complete = kl && kl->cx && kl->cu && kl->cxx && kl->cxu && kl->cuu && kl->eta && (!c.d.has_lims || (c.lims && c.u));
-    GpsKernel k = complete ? gps_choose(c.d, kl->eta_tv, caller, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE))
-                           : GPS_GENERIC;
-    if (complete && kl_shape(h, c.d.n, c.d.m) == 1) {
-        DDP_DEVICE(h);
-        const int rcw = ddp_launch_back_pass_gps_wide(h, c);
-        if (!rcw) h->last_kernel[0] = gps_kernel_name[GPS_WIDE];
-        return rcw;
-    }
     int rc = 1;
-    if (k == GPS_MID) rc = ddp_launch_back_pass_gps_mid(h, c);
-    if (k == GPS_Q4) {
+    if (k == GPS_WIDE) {
+        rc = ddp_launch_back_pass_gps_wide(h, c);           // 0 or < 0: it never declines (nothing else takes a wide shape)
+    } else if (k == GPS_MID) {
+        rc = ddp_launch_back_pass_gps_mid(h, c);
+    } else if (k == GPS_Q4) {
         rc = ddp_launch_back_pass_gps_q4(h, c);
         if (rc > 0) k = GPS_LANE;
     }
     if (k == GPS_LANE) rc = ddp_launch_back_pass_gps_lane(h, c);
     if (rc > 0) { k = GPS_GENERIC; rc = ddp_launch_back_pass_gps(h, c); }
-    h->last_kernel[0] = gps_kernel_name[k];
+    if (!rc || k != GPS_WIDE) h->last_kernel[0] = gps_kernel_name[k];      // (a wide launch that failed ran nothing; the others as ever)
     return rc;
 }
 
 }   // namespace
-
-int ddp_dispatch_back_pass_gps(ddp_handle h, const BPCall &c, bool user) { return gps_dispatch(h, c, user ? GPS_USER : GPS_REGISTERED); }
 
 extern "C" {
 
@@ -761,10 +790,9 @@ int ddp_kl_terms_f64_dev(ddp_handle h, int n, int m, int N, int B, const double 
                          double *cx, double *cu, double *cxx, double *cxu, double *cuu)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && K && k && Sigmai && cx && cu && cxx && cxu && cuu, "kl_terms: null argument");
-    if (kl_shape(h, n, m) == 1 && N >= 1 && B >= 1) return ddp_launch_kl_terms_wide(h, n, m, N, B, K, k, Sigmai, cx, cu, cxx, cxu, cuu);
-    DDP_CHECK(n >= 1 && n <= NMAXK && m >= 1 && m <= MMAXK && N >= 1 && B >= 1, "kl_terms: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
-              "after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
+    DDP_CHECK(K && k && Sigmai && cx && cu && cxx && cxu && cuu, "kl_terms: null argument");
+    if (int rc = kl_check_shape(h, "kl_terms", "KL", n, m, N, B)) return rc;
+    if (kl_terms_choose(n, m, kl_choice_in(h)) == KLTERMS_WIDE) return ddp_launch_kl_terms_wide(h, n, m, N, B, K, k, Sigmai, cx, cu, cxx, cxu, cuu);
     const long NB = (long)N * B;
     hipLaunchKernelGGL(kl_terms_kernel, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, h->stream, n, m, NB, K, k, Sigmai, cx, cu, cxx, cxu, cuu);
     DDP_HIP(hipGetLastError());
@@ -779,43 +807,47 @@ int ddp_back_pass_gps_f64_dev(ddp_handle h, const ddp_bp_desc *d,
                               int32_t *diverge)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && d && cx && cu && cxx && cxu && cuu && fx && fu && kl && K && k && Quu && Quui && Vx && Vxx && dV && diverge,
+    DDP_CHECK(d && cx && cu && cxx && cxu && cuu && fx && fu && kl && K && k && Quu && Quui && Vx && Vxx && dV && diverge,
               "back_pass_gps: null argument");
-    DDP_CHECK(d->n >= 1 && d->m >= 1 && d->N >= 1 && d->B >= 1, "back_pass_gps: bad sizes n=%d m=%d N=%d B=%d", d->n, d->m, d->N, d->B);
-    DDP_KL_SHAPE(h, "back_pass_gps", d->n, d->m);
+    if (int rc = kl_check_shape(h, "back_pass_gps", "back_pass_gps", d->n, d->m, d->N, d->B)) return rc;
     DDP_HIP(hipMemsetAsync(Quui, 0, sizeof(double) * (size_t)d->m * d->m * d->N * d->B, h->stream));
-    // q4 (n = 4, m = 1, one η per trajectory; DDP_GPS_Q4=0: not), lane (n = 4, m <= 2), generic; DDP_GPS_LANE=0: always the run-time-sized
-    // kernel (cross-check in the tests); DDP_GPS_MID=1: the mid kernel for every shape it takes
     const BPCall c = {*d, cx, cu, cxx, cxu, cuu, fx, fu, nullptr, lims, u, active, K, k, Quu, Vx, Vxx, dV, diverge, kl, Quui};
-    return gps_dispatch(h, c, GPS_STANDALONE);
+    return gps_launch(h, c, gps_choose(c.d, kl_choice_in(h, &c)));
 }
 
-// Unlisted debug hook (not in ddp_amd.h): the name ddp_last_kernel(h, 0) reports after a back_pass_gps with these facts — the choice of
-// gps_dispatch, callable without a GPU.  caller: 0 stand-alone ddp_back_pass_gps_*, 1 ddp_ilqgkl_* (registered problems), 2 ddp_user_ilqgkl_*;
-// the switches DDP_GPS_MID, DDP_GPS_Q4, DDP_GPS_LANE as strings (NULL: unset)
-const char *ddp_gps_choice(const ddp_bp_desc *d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane)
+// Unlisted debug hooks (not in ddp_amd.h): the kernel names ddp_last_kernel(h, 0) / (h, 5) / (h, 6) report after a back_pass_gps /
+// forward_covariance / kl_div_wiki with these facts (the fields of KlChoiceIn; the switches as strings, NULL: unset) — gps_choose,
+// fcov_choose and kl_div_choose, the functions the entry points call, callable without a GPU.  "none": the call is refused.
+// ddp_gps_choice3 takes every fact of back_pass_gps; ddp_gps_choice2 is a complete call, ddp_gps_choice one with the wide switch off too.
+const char *ddp_gps_choice3(const ddp_bp_desc *d, int eta_tv, int caller, int complete, const char *gps_mid, const char *gps_q4,
+                            const char *gps_lane, int wide_on, const char *gps_wide)
 {
-    return gps_kernel_name[gps_choose(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane)];
+    KlChoiceIn q;
+    q.caller = caller; q.eta_tv = eta_tv; q.complete = complete != 0; q.wide_on = wide_on;
+    q.gps_mid = gps_mid; q.gps_q4 = gps_q4; q.gps_lane = gps_lane; q.gps_wide = gps_wide;
+    return gps_kernel_name[gps_choose(*d, q)];
 }
-// Its twin with the two facts of the large shapes: the handle's ddp_kl_set_wide switch and DDP_GPS_WIDE.  "none": the call is refused.
 const char *ddp_gps_choice2(const ddp_bp_desc *d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane,
                             int wide_on, const char *gps_wide)
 {
-    return gps_kernel_name[gps_choose2(*d, eta_tv, caller, gps_mid, gps_q4, gps_lane, wide_on, gps_wide)];
+    return ddp_gps_choice3(d, eta_tv, caller, 1, gps_mid, gps_q4, gps_lane, wide_on, gps_wide);
 }
-
-// Unlisted debug hooks (not in ddp_amd.h): the names ddp_last_kernel(h, 5) / (h, 6) report after a forward_covariance / kl_div_wiki with
-// these facts — fcov_choose and kl_div_choose, the functions the entry points call, callable without a GPU.  al16: fx, K, Sigma and sigmanew
-// are 16-byte aligned; sink: the handle has its sink buffer; wide_on: ddp_kl_set_wide; the switches DDP_GPS_WIDE, DDP_FCOV_Q4, DDP_FCOV_Q4L,
-// DDP_KL_LDS as strings (NULL: unset).  "none": the call is refused.
+const char *ddp_gps_choice(const ddp_bp_desc *d, int eta_tv, int caller, const char *gps_mid, const char *gps_q4, const char *gps_lane)
+{
+    return ddp_gps_choice3(d, eta_tv, caller, 1, gps_mid, gps_q4, gps_lane, 0, nullptr);
+}
 const char *ddp_fcov_choice(int n, int m, int N, int B, int al16, int sink, int wide_on, const char *gps_wide, const char *fcov_q4,
                             const char *fcov_q4l)
 {
-    return fcov_kernel_name[fcov_choose(n, m, N, B, al16 != 0, sink != 0, wide_on, gps_wide, fcov_q4, fcov_q4l)];
+    KlChoiceIn q;
+    q.al16 = al16 != 0; q.sink = sink != 0; q.wide_on = wide_on; q.gps_wide = gps_wide; q.fcov_q4 = fcov_q4; q.fcov_q4l = fcov_q4l;
+    return fcov_kernel_name[fcov_choose(n, m, N, B, q)];
 }
 const char *ddp_kl_div_choice(int n, int m, int N, int B, int wide_on, const char *gps_wide, const char *kl_lds)
 {
-    return kl_div_kernel_name[kl_div_choose(n, m, N, B, wide_on, gps_wide, kl_lds)];
+    KlChoiceIn q;
+    q.wide_on = wide_on; q.gps_wide = gps_wide; q.kl_lds = kl_lds;
+    return kl_div_kernel_name[kl_div_choose(n, m, N, B, q)];
 }
 
 int ddp_kl_set_wide(ddp_handle h, int on)
@@ -830,20 +862,17 @@ int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, con
                                    const double *R1, const double *K, const double *Sigma, double *sigmanew)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && fx && R1 && K && Sigma && sigmanew, "forward_covariance: null argument");
-    const bool al16 = ((((uintptr_t)fx | (uintptr_t)K | (uintptr_t)Sigma | (uintptr_t)sigmanew) & 15) == 0);
+    DDP_CHECK(fx && R1 && K && Sigma && sigmanew, "forward_covariance: null argument");
+    int rc = kl_check_shape(h, "forward_covariance", "KL", n, m, N, B);
+    if (rc) return rc;
+    KlChoiceIn q = kl_choice_in(h);
+    q.al16 = ((((uintptr_t)fx | (uintptr_t)K | (uintptr_t)Sigma | (uintptr_t)sigmanew) & 15) == 0);
     // DDP_FCOV_Q4=0: the run-time-sized kernel for every shape; DDP_FCOV_Q4L=0: the step-by-step q4 kernel (cross-checks in the tests)
-    const FcovKernel kern = fcov_choose(n, m, N, B, al16, h->sink != nullptr, h->kl_wide, ddp_env(h, ENV_GPS_WIDE), ddp_env(h, ENV_FCOV_Q4),
-                                        ddp_env(h, ENV_FCOV_Q4L));
-    if (kern == FCOV_WIDE) {
-        const int rc = ddp_launch_fcov_wide(h, n, m, N, B, fx, fx_batched, R1, K, Sigma, sigmanew);
-        if (!rc) h->last_kernel[5] = fcov_kernel_name[kern];
-        return rc;
-    }
-    DDP_CHECK(kern != FCOV_NONE, "forward_covariance: bad sizes n=%d m=%d N=%d B=%d (n <= %d, "
-              "m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
+    const FcovKernel kern = fcov_choose(n, m, N, B, q);
     const dim3 grid4((unsigned)((B + 3) / 4)), block(DDP_WAVE);
-    if (kern == FCOV_Q4L)
+    if (kern == FCOV_WIDE)
+        rc = ddp_launch_fcov_wide(h, n, m, N, B, fx, fx_batched, R1, K, Sigma, sigmanew);
+    else if (kern == FCOV_Q4L)
         hipLaunchKernelGGL(fcov_q4l_kernel, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
     else if (kern == FCOV_Q4_1)
         hipLaunchKernelGGL(fcov_q4_kernel<1>, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
@@ -851,6 +880,7 @@ int ddp_forward_covariance_f64_dev(ddp_handle h, int n, int m, int N, int B, con
         hipLaunchKernelGGL(fcov_q4_kernel<2>, grid4, block, 0, h->stream, N, B, fx, fx_batched, R1, K, Sigma, sigmanew, (double *)h->sink);
     else
         hipLaunchKernelGGL(fcov_kernel, dim3(B), block, fcov_lds(n, m), h->stream, n, m, N, fx, fx_batched, R1, K, Sigma, sigmanew);
+    if (rc) return rc;
     DDP_HIP(hipGetLastError());
     h->last_kernel[5] = fcov_kernel_name[kern];
     return 0;
@@ -862,17 +892,14 @@ int ddp_kl_div_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *x
                        double *kldiv, double *klmean)
 {
     DDP_DEVICE(h);
-    DDP_CHECK(h && xnew && xold && sigmanew && Kn && kn && Sn && Kp && kp && Sp && Sip && kldiv && klmean, "kl_div: null argument");
-    const KlDivKernel kern = kl_div_choose(n, m, N, B, h->kl_wide, ddp_env(h, ENV_GPS_WIDE), ddp_env(h, ENV_KL_LDS));
-    if (kern == KLDIV_WIDE) {
-        const int rc = ddp_launch_kl_div_wide(h, n, m, N, B, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip, kldiv, klmean);
-        if (!rc) h->last_kernel[6] = kl_div_kernel_name[kern];
-        return rc;
-    }
-    DDP_CHECK(kern != KLDIV_NONE, "kl_div: bad sizes n=%d m=%d N=%d B=%d (n <= %d, m <= %d; "
-              "after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m, N, B, NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
+    DDP_CHECK(xnew && xold && sigmanew && Kn && kn && Sn && Kp && kp && Sp && Sip && kldiv && klmean, "kl_div: null argument");
+    int rc = kl_check_shape(h, "kl_div", "KL", n, m, N, B);
+    if (rc) return rc;
+    const KlDivKernel kern = kl_div_choose(n, m, N, B, kl_choice_in(h));
     // operands through an LDS image of 64 steps when that fits (DDP_KL_LDS=0: the direct kernel, cross-check in the tests)
-    if (kern != KLDIV_DIRECT) {
+    if (kern == KLDIV_WIDE) {
+        rc = ddp_launch_kl_div_wide(h, n, m, N, B, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip, kldiv, klmean);
+    } else if (kern != KLDIV_DIRECT) {
         const int lens[10] = {n, n, (n + m) * (n + m), n * m, m, m * m, n * m, m, m * m, m * m};
         const size_t image = kl_div_image(n, m);
         const double *ptr[10] = {xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip};
@@ -888,11 +915,30 @@ int ddp_kl_div_f64_dev(ddp_handle h, int n, int m, int N, int B, const double *x
         hipLaunchKernelGGL(kl_div_kernel, dim3(B), dim3(DDP_WAVE), 0, h->stream, n, m, N, xnew, xold, sigmanew, Kn, kn, Sn, Kp, kp, Sp, Sip,
                            kldiv, klmean);
     }
+    if (rc) return rc;
     DDP_HIP(hipGetLastError());
     h->last_kernel[6] = kl_div_kernel_name[kern];
     return 0;
 }
 
+// one dual step on the stream: clears `count`, then kl_dual_kernel counts into it (the stand-alone entries and the driver)
+static int kl_dual_enqueue(ddp_handle h, int op, int B, int it, double kl_step, const ddp_kl_dual &s, const int32_t *diverge,
+                           const double *klmean, int32_t *count)
+{
+    DDP_HIP(hipMemsetAsync(count, 0, sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(kl_dual_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, op, B, it, kl_step, s, diverge, klmean, count,
+                       (const double *)h->kl_steps);
+    DDP_HIP(hipGetLastError());
+    return 0;
+}
+// reads a count of kl_dual_kernel back (the one synchronisation of a dual step)
+static int kl_dual_poll(ddp_handle h, const int32_t *count, int *out)
+{
+    DDP_HIP(hipMemcpyAsync(h->h_pinned, count, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    DDP_HIP(hipStreamSynchronize(h->stream));
+    *out = h->h_pinned[0];
+    return 0;
+}
 static int kl_dual_launch(ddp_handle h, int op, int B, int it, double kl_step, const ddp_kl_dual *s, const int32_t *diverge,
                           const double *klmean, int *count)
 {
@@ -900,18 +946,11 @@ static int kl_dual_launch(ddp_handle h, int op, int B, int it, double kl_step, c
     DDP_CHECK(s && count && B >= 1, "kl_dual: null argument");
     DDP_CHECK(s->etab && s->eta && s->del && s->divergence && s->satisfied && s->status && s->live && s->pend && s->iters && s->nback,
               "kl_dual: null state array");
+    DDP_CHECK(!h->kl_steps || h->kl_steps_B == B, "kl_dual: B = %d, the table of ddp_kl_set_steps holds %d steps", B, h->kl_steps_B);
     void *cnt = nullptr;
     int rc = ddp_scratch(h, 256, &cnt);
-    if (rc) return rc;
-    DDP_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t), h->stream));
-    DDP_CHECK(!h->kl_steps || h->kl_steps_B == B, "kl_dual: B = %d, the table of ddp_kl_set_steps holds %d steps", B, h->kl_steps_B);
-    hipLaunchKernelGGL(kl_dual_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, op, B, it, kl_step, *s, diverge, klmean,
-                       (int32_t *)cnt, (const double *)h->kl_steps);
-    DDP_HIP(hipGetLastError());
-    DDP_HIP(hipMemcpyAsync(h->h_pinned, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    DDP_HIP(hipStreamSynchronize(h->stream));
-    *count = h->h_pinned[0];
-    return 0;
+    if (rc || (rc = kl_dual_enqueue(h, op, B, it, kl_step, *s, diverge, klmean, (int32_t *)cnt))) return rc;
+    return kl_dual_poll(h, (const int32_t *)cnt, count);
 }
 
 int ddp_kl_dual_begin_f64_dev(ddp_handle h, int B, int it, const ddp_kl_dual *s, int *n_live)
@@ -1037,159 +1076,119 @@ void ddp_ilqgkl_default_opts(ddp_ilqgkl_opts *o)
     o->kl_step = 1.0; o->max_iter = 50; o->etabracket[0] = 1e-8; o->etabracket[1] = 1.0; o->etabracket[2] = 1e16; o->del0 = 1e-4;
 }
 
-// The body of ddp_ilqgkl_f64_dev and ddp_user_ilqgkl_f64_dev: the registered problem `p`, or the family `f` (a user problem) with its
+// The body of ddp_ilqgkl_f64_dev and ddp_user_ilqgkl*_f64_dev: the registered problem `p`, or the family `f` (a user problem) with its
 // derivatives [.,.,N,B] (constant Hessians [.,.,B]), its costfun and its rollout — the three calls go through Model (ilqg_model.h); the
-// operand layouts below are back_pass_gps's own.  model_fx == NULL (family only): the model is the
-// problem itself, forward_covariance takes the fx of STEP 1.
-static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, const ddp_ilqgkl_opts *oo, const double *x0,
-                       const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
-                       const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
-                       double *x, double *u, double *K, double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost,
-                       double *dV, double *stats, int *iters_out, const double *fit_fx = nullptr, const double *fit_fu = nullptr,
-                       const double *fit_fc = nullptr, const double *cm_cx = nullptr, const double *cm_cu = nullptr,
-                       const double *cm_cxx = nullptr, const double *cm_cxu = nullptr, const double *cm_cuu = nullptr)
+// operand layouts (kl_workspace.h) are back_pass_gps's own.  c.model_fx == NULL (family only): the model is the problem itself,
+// forward_covariance takes the fx of STEP 1.
+static int ilqgkl_impl(ddp_handle h, const ddp_problem *p, const ddp_family *f, const KlCall &c)
 {
-    DDP_CHECK((!fit_fx && !fit_fu && !fit_fc) || (f && fit_fx && fit_fu && fit_fc), "ilqgkl: a fitted model is fx, fu and fc, with a user problem");
-    // a cost model: cx[n,N,B], cu[m,N,B], cxx[n,n,N,B], cxu[n,m,N,B], cuu[m,m,N,B] in place of the cost derivatives of STEP 1
-    const bool cm = cm_cx != nullptr;
-    DDP_CHECK((!cm_cx && !cm_cu && !cm_cxx && !cm_cxu && !cm_cuu) || (f && cm_cx && cm_cu && cm_cxx && cm_cxu && cm_cuu),
+    const bool fit = c.fit_fx || c.fit_fu || c.fit_fc, cm = c.cm_cx || c.cm_cu || c.cm_cxx || c.cm_cxu || c.cm_cuu;
+    DDP_CHECK(!fit || (f && c.fit_fx && c.fit_fu && c.fit_fc), "ilqgkl: a fitted model is fx, fu and fc, with a user problem");
+    DDP_CHECK(!cm || (f && c.cm_cx && c.cm_cu && c.cm_cxx && c.cm_cxu && c.cm_cuu),
               "ilqgkl: a cost model is cx, cu, cxx, cxu and cuu, with a user problem");
-    DDP_CHECK((p || f) && x0 && Kp && kp && Sp && Sip && (model_fx || f) && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV &&
-              stats, "ilqgkl: null argument");
+    DDP_CHECK((p || f) && c.x0 && c.Kp && c.kp && c.Sp && c.Sip && (c.model_fx || f) && c.R1 && c.x && c.u && c.K && c.Sigma && c.Sigmai && c.Vx &&
+              c.Vxx && c.cost && c.dV && c.stats, "ilqgkl: null argument");
     ddp_ilqgkl_opts od;
+    const ddp_ilqgkl_opts *oo = c.opts;
     if (!oo) { ddp_ilqgkl_default_opts(&od); oo = &od; }
     DDP_CHECK(oo->max_iter >= 1, "ilqgkl: max_iter=%d (the reference returns undefined arrays without an iteration)", oo->max_iter);
-    DDP_CHECK(x0 != x && kp != u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
+    DDP_CHECK(c.x0 != c.x && c.kp != c.u, "ilqgkl: x0 / traj_prev.k must not alias the outputs x / u");
     const Model M(p, f);
-    const size_t n = M.n, m = M.m, N = M.N, B = M.B, NB = N * B, P2 = (n + m) * (n + m);
+    int rc = kl_check_shape(h, "ilqgkl", "back_pass_gps", M.n, M.m, M.N, M.B);
+    if (rc) return rc;
+    const size_t n = M.n, m = M.m, N = M.N, B = M.B, NB = N * B;
     DDP_CHECK(!h->kl_steps || (size_t)h->kl_steps_B == B, "ilqgkl: B = %zu, the table of ddp_kl_set_steps holds %d steps", B, h->kl_steps_B);
     const bool pend = M.pw.kind == DDP_PROBLEM_PENDCART;
-    const int wide = kl_shape(h, (int)n, (int)m);          // 1: back_pass_gps, ∇kl, forward_covariance and kl_div_wiki on the wide kernels
-    DDP_CHECK(wide >= 0, "ilqgkl: n=%zu m=%zu has no back_pass_gps kernel (n <= %d, m <= %d; after ddp_kl_set_wide(h, 1): n <= %d, m <= %d)", n, m,
-              NMAXK, MMAXK, KL_WIDE_MAX_N, DDP_MAX_M_WIDE);
     // dynamics as back_pass_gps wants them: [n,n,N] or [n,n,N,B]
     const bool fx_b = f || pend || p->dyn_batched, fx_rep = !f && !pend && !p->dyn_tv, fx_own = f || pend || fx_rep;
     // cost Hessians: [.,.,N] of the registered problem, [.,.,N,B] of a family; constant Hessians of a family [.,.,B], repeated along time
-    // for every kernel but mid (the others want time-varying operands)
+    // (hrep) for every kernel but mid and wide, which read every operand layout
     const bool cst = f && f->const_hessian && !cm;         // (a cost model is time-varying and per trajectory, whatever the problem's own is)
-    ddp_bp_desc d;
-    d.n = (int)n; d.m = (int)m; d.N = (int)N; d.B = (int)B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = f != nullptr;
-    d.regType = 1; d.has_lims = lims != nullptr;
-    // (the wide kernel reads every operand layout too)
-    const bool hrep = cst && !wide && gps_choose(d, 0, GPS_USER, ddp_env(h, ENV_GPS_MID), ddp_env(h, ENV_GPS_Q4), ddp_env(h, ENV_GPS_LANE)) != GPS_MID;
+    ddp_kl_cost_terms t = {};
+    BPCall gps = {};
+    ddp_bp_desc &d = gps.d;
+    d.n = M.n; d.m = M.m; d.N = M.N; d.B = M.B; d.fx_tv = 1; d.fx_batched = fx_b; d.cost_tv = 1; d.cost_batched = f != nullptr;
+    d.regType = 1; d.has_lims = c.lims != nullptr;
+    // the kernel of every back pass below, chosen once, for time-varying operands (the loop's call is complete: one η per trajectory,
+    // lims with kp)
+    KlChoiceIn q = kl_choice_in(h);
+    q.caller = f ? GPS_USER : GPS_REGISTERED;
+    const GpsKernel kern = gps_choose(d, q);
+    const bool hrep = cst && kern != GPS_MID && kern != GPS_WIDE;
     if (cst && !hrep) d.cost_tv = 0;
-    const size_t hc = f ? (cst && !hrep ? B : NB) : N;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t fxc = N * (fx_b ? B : 1);
-    const size_t s_fx = fx_own ? al(n * n * fxc * 8) : 0, s_fu = fx_own ? al(n * m * fxc * 8) : 0;
-    const size_t s_h = hrep ? al(n * n * B * 8) + al(n * m * B * 8) + al(m * m * B * 8) : 0;
-    const size_t sz[] = {al(n * NB * 8), al(m * NB * 8),                                       // cx, cu
-                         al(n * n * hc * 8), al(n * m * hc * 8), al(m * m * hc * 8),           // cxx, cxu, cuu
-                         al(n * NB * 8), al(m * NB * 8), al(n * n * NB * 8), al(m * n * NB * 8), al(m * m * NB * 8),   // ∇kl
-                         al(m * NB * 8), al(m * NB * 8),                                       // k (new policy), zeros (traj_prev.k *= 0)
-                         al(P2 * NB * 8), al(NB * 8), al(B * 8), al(B * 8), al(n * B * 8),     // sigmanew, kldiv, klmean, csum, x0[:,1]
-                         al(3 * B * 8), 4 * al(B * 8), 6 * al(B * 4), al(B * 4), 256};         // dual state (+ sum(cost0)), diverge, counters
-    size_t bytes = s_fx + s_fu + s_h;
-    for (size_t v : sz) bytes += v;
+
+    KlWork W;
+    const KlWorkIn wi = {n, m, N, B, f != nullptr, fx_own, fx_b, cst, hrep};
     void *base;
-    int rc = ddp_scratch(h, bytes, &base);
-    if (rc) return rc;
-    char *q = (char *)base;
-    auto take = [&](size_t b) { void *r = q; q += al(b); return r; };
-    int32_t *counter = (int32_t *)take(256);               // first: the stand-alone ddp_kl_dual_* entry points keep theirs at the scratch base
-    double *cx = (double *)take(n * NB * 8), *cu = (double *)take(m * NB * 8), *cxx = (double *)take(n * n * hc * 8),
-           *cxu = (double *)take(n * m * hc * 8), *cuu = (double *)take(m * m * hc * 8);
-    ddp_kl_cost_terms t;
-    double *kcx = (double *)take(n * NB * 8), *kcu = (double *)take(m * NB * 8), *kcxx = (double *)take(n * n * NB * 8),
-           *kcxu = (double *)take(m * n * NB * 8), *kcuu = (double *)take(m * m * NB * 8);
-    double *k = (double *)take(m * NB * 8), *kzero = (double *)take(m * NB * 8), *sig = (double *)take(P2 * NB * 8),
-           *kld = (double *)take(NB * 8), *klm = (double *)take(B * 8), *cs = (double *)take(B * 8), *x0c = (double *)take(n * B * 8);
-    ddp_kl_dual s;
-    double *etab_own = (double *)take(3 * B * 8);
-    s.etab = etab ? etab : etab_own;
-    s.eta = (double *)take(B * 8); s.del = (double *)take(B * 8); s.divergence = (double *)take(B * 8);
-    s.satisfied = (int32_t *)take(B * 4); s.status = (int32_t *)take(B * 4); s.live = (int32_t *)take(B * 4);
-    s.pend = (int32_t *)take(B * 4); s.iters = (int32_t *)take(B * 4); s.nback = (int32_t *)take(B * 4);
-    int32_t *div = (int32_t *)take(B * 4);
-    double *c0buf = (double *)take(B * 8);
-    double *fxw = fx_own ? (double *)take(n * n * fxc * 8) : nullptr, *fuw = fx_own ? (double *)take(n * m * fxc * 8) : nullptr;
-    double *hxx = hrep ? (double *)take(n * n * B * 8) : nullptr, *hxu = hrep ? (double *)take(n * m * B * 8) : nullptr,
-           *huu = hrep ? (double *)take(m * m * B * 8) : nullptr;
-    t.cx = kcx; t.cu = kcu; t.cxx = kcxx; t.cxu = kcxu; t.cuu = kcuu; t.eta = s.eta; t.eta_tv = 0;
+    if ((rc = ddp_scratch(h, W.carve(Carver(), wi), &base))) return rc;
+    W.carve(Carver(base), wi);
+    const KlDeriv &dv = W.dv;
+    ddp_kl_dual &s = W.dual.s;
+    if (c.etab) s.etab = c.etab;
+    t.cx = W.kt.cx; t.cu = W.kt.cu; t.cxx = W.kt.cxx; t.cxu = W.kt.cxu; t.cuu = W.kt.cuu; t.eta = s.eta; t.eta_tv = 0;
 
     hipStream_t st = h->stream;
     const unsigned gB = (unsigned)((B + 255) / 256);
     auto grid = [](size_t tot) { return dim3((unsigned)((tot + 255) / 256)); };
     hipLaunchKernelGGL(kl_dual_init_kernel, dim3(gB), dim3(256), 0, st, (int)B, oo->etabracket[0], oo->etabracket[1], oo->etabracket[2],
-                       oo->del0, etab ? 0 : 1, s);
-    DDP_HIP(hipMemsetAsync(kzero, 0, m * NB * 8, st));
-    hipLaunchKernelGGL(kl_first_col_kernel, grid(n * B), dim3(256), 0, st, (int)n, (int)N, (int)B, x0, x0c);
+                       oo->del0, c.etab ? 0 : 1, s);
+    DDP_HIP(hipMemsetAsync(W.kzero, 0, m * NB * 8, st));
+    hipLaunchKernelGGL(kl_first_col_kernel, grid(n * B), dim3(256), 0, st, (int)n, (int)N, (int)B, c.x0, W.x0c);
     // STEP 1 (:86): derivs(x, u) with u = copy(traj_prev.k) (:45); a family evaluates every trajectory (no slot map: the loop recomputes all)
-    if ((rc = M.df(h, (int)B, nullptr, x0, kp, nullptr, fxw, fuw, cx, cu, cxx, cxu, cuu))) return rc;
-    if (!cm && (rc = M.hessians(h, (int)B, nullptr, nullptr, hrep ? hxx : cxx, hrep ? hxu : cxu, hrep ? huu : cuu))) return rc;      // const_hessian only
-    if (hrep) {
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * NB), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * NB), 1, (const double *)hxx, cxx);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * NB), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * NB), 1, (const double *)hxu, cxu);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * NB), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * NB), 1, (const double *)huu, cuu);
-    }
-    if (fx_rep) {                                          // (a registered LTI problem)
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * fxc), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * fxc), (int)fx_b, p->A, fxw);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * fxc), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * fxc), (int)fx_b, p->Bm, fuw);
-    }
+    if ((rc = M.df(h, (int)B, nullptr, c.x0, c.kp, nullptr, dv.fxw, dv.fuw, dv.cx, dv.cu, dv.cxx, dv.cxu, dv.cuu))) return rc;
+    if (!cm && (rc = M.hessians(h, (int)B, nullptr, nullptr, hrep ? dv.hxx : dv.cxx, hrep ? dv.hxu : dv.cxu, hrep ? dv.huu : dv.cuu))) return rc;      // const_hessian only
+    auto repeat = [&](size_t len, size_t cols, int batched, const double *src, double *dst) {      // dst[len, N, cols / N] = src[len (, b)]
+        hipLaunchKernelGGL(kl_repeat_kernel, grid(len * cols), dim3(256), 0, st, (int)len, (int)N, (long)(len * cols), batched, src, dst);
+    };
+    if (hrep) { repeat(n * n, NB, 1, dv.hxx, dv.cxx); repeat(n * m, NB, 1, dv.hxu, dv.cxu); repeat(m * m, NB, 1, dv.huu, dv.cuu); }
+    const size_t fxc = N * (fx_b ? B : 1);
+    if (fx_rep) { repeat(n * n, fxc, fx_b, p->A, dv.fxw); repeat(n * m, fxc, fx_b, p->Bm, dv.fuw); }      // (a registered LTI problem)
     // a fitted model: the plan is made on its fx, fu (the fxw, fuw STEP 1 wrote stay in scratch) and every rollout below runs on its tables
-    const double *fx = fit_fx ? fit_fx : (fx_own ? fxw : p->A), *fu = fit_fx ? fit_fu : (fx_own ? fuw : p->Bm);
-    FitScope fit_scope(fit_fx ? f : nullptr, fit_fx, fit_fu, fit_fc);
-    if (!f) {
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * n * N), dim3(256), 0, st, (int)(n * n), (int)N, (long)(n * n * N), 0, p->Q, cxx);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(n * m * N), dim3(256), 0, st, (int)(n * m), (int)N, (long)(n * m * N), 0, (const double *)nullptr, cxu);
-        hipLaunchKernelGGL(kl_repeat_kernel, grid(m * m * N), dim3(256), 0, st, (int)(m * m), (int)N, (long)(m * m * N), 0, p->R, cuu);
-    }
-    if ((rc = ddp_kl_terms_f64_dev(h, (int)n, (int)m, (int)N, (int)B, Kp, kzero, Sip, kcx, kcu, kcxx, kcxu, kcuu))) return rc;   // :90
+    const double *fx = fit ? c.fit_fx : (fx_own ? dv.fxw : p->A), *fu = fit ? c.fit_fu : (fx_own ? dv.fuw : p->Bm);
+    FitScope fit_scope(fit ? f : nullptr, c.fit_fx, c.fit_fu, c.fit_fc);
+    if (!f) { repeat(n * n, N, 0, p->Q, dv.cxx); repeat(n * m, N, 0, nullptr, dv.cxu); repeat(m * m, N, 0, p->R, dv.cuu); }
+    if ((rc = ddp_kl_terms_f64_dev(h, M.n, M.m, M.N, M.B, c.Kp, W.kzero, c.Sip, W.kt.cx, W.kt.cu, W.kt.cxx, W.kt.cxu, W.kt.cuu))) return rc;   // :90
+    const double *cost0 = c.cost0;
     if (!cost0) {                                          // the reference insists on `cost` (:69); a C caller may leave it to costfun(x0, u)
-        if ((rc = M.costfun(h, (int)B, nullptr, x0, kp, nullptr, cost, c0buf))) return rc;
-        cost0 = c0buf;
+        if ((rc = M.costfun(h, (int)B, nullptr, c.x0, c.kp, nullptr, c.cost, W.c0buf))) return rc;
+        cost0 = W.c0buf;
     }
-    if (!model_fx) { model_fx = fx; model_fx_batched = 1; }      // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56); a fitted model: its fx
+    // the problem's own linearisation: df(model, x, u) at (x0, kp) (forward_pass.jl:37-56); a fitted model: its fx
+    const double *model_fx = c.model_fx ? c.model_fx : fx;
+    const int model_fx_batched = c.model_fx ? c.model_fx_batched : 1;
     // a cost model: the backward passes take the caller's arrays (the cost derivatives STEP 1 wrote stay in scratch); cost0, the rollouts'
     // user cost and the loop are as without one
-    const BPCall gps = {d, cm ? cm_cx : cx, cm ? cm_cu : cu, cm ? cm_cxx : cxx, cm ? cm_cxu : cxu, cm ? cm_cuu : cuu, fx, fu, nullptr, lims, kp,
-                        nullptr, K, k, Sigmai, Vx, Vxx, dV, div, &t, Sigma};
-    auto poll = [&](int *out) -> int {
-        DDP_HIP(hipMemcpyAsync(h->h_pinned, counter, 4, hipMemcpyDeviceToHost, st));
-        DDP_HIP(hipStreamSynchronize(st));
-        *out = h->h_pinned[0];
-        return 0;
-    };
-    auto dual = [&](int op, int it) -> int {
-        DDP_HIP(hipMemsetAsync(counter, 0, 4, st));
-        hipLaunchKernelGGL(kl_dual_kernel, dim3(gB), dim3(256), 0, st, op, (int)B, it, oo->kl_step, s, (const int32_t *)div, (const double *)klm, counter,
-                           (const double *)h->kl_steps);
-        DDP_HIP(hipGetLastError());
-        return 0;
+    gps.cx = cm ? c.cm_cx : dv.cx; gps.cu = cm ? c.cm_cu : dv.cu; gps.cxx = cm ? c.cm_cxx : dv.cxx; gps.cxu = cm ? c.cm_cxu : dv.cxu;
+    gps.cuu = cm ? c.cm_cuu : dv.cuu; gps.fx = fx; gps.fu = fu; gps.lims = c.lims; gps.u = c.kp; gps.kl = &t;
+    gps.K = c.K; gps.k = W.k; gps.Quu = c.Sigmai; gps.Vx = c.Vx; gps.Vxx = c.Vxx; gps.dV = c.dV; gps.diverge = W.dual.div; gps.Quui = c.Sigma;
+    auto dual = [&](int op, int it, int *count) -> int {
+        const int rcd = kl_dual_enqueue(h, op, (int)B, it, oo->kl_step, s, W.dual.div, W.dual.klm, W.counter);
+        return rcd || !count ? rcd : kl_dual_poll(h, W.counter, count);
     };
     const double one = 1.0;
     int it = 0, live = (int)B;
     for (it = 1; it <= oo->max_iter && live > 0; ++it) {                                                  // :91
-        if ((rc = dual(0, it))) return rc;
+        if ((rc = dual(0, it, nullptr))) return rc;
         for (int guard = 0;; ++guard) {                    // back passes until the KL-regularised Quu is positive definite everywhere (:95-122)
-            DDP_HIP(hipMemsetAsync(Sigma, 0, m * m * NB * 8, st));
-            if ((rc = gps_dispatch(h, gps, f ? GPS_USER : GPS_REGISTERED))) return rc;
+            DDP_HIP(hipMemsetAsync(c.Sigma, 0, m * m * NB * 8, st));
+            if ((rc = gps_launch(h, gps, kern))) return rc;
             int pending = 0;
-            if ((rc = dual(1, it)) || (rc = poll(&pending))) return rc;                                    // :103-105
+            if ((rc = dual(1, it, &pending))) return rc;                                                   // :103-105
             if (!pending) break;
             DDP_CHECK(guard < 200, "ilqgkl: back_pass_gps keeps diverging (the reference would loop forever)");
         }
-        rc = M.rollout(h, (int)B, nullptr, K, k, x0c, kp, x0, &one, 1, lims, nullptr, x, u, cost, cs);                                      // :132
+        rc = M.rollout(h, (int)B, nullptr, c.K, W.k, W.x0c, c.kp, c.x0, &one, 1, c.lims, nullptr, c.x, c.u, c.cost, W.cs);                  // :132
         if (rc) return rc;
-        if ((rc = ddp_forward_covariance_f64_dev(h, (int)n, (int)m, (int)N, (int)B, model_fx, model_fx_batched, R1, K, Sigma, sig))) return rc;   // :133
-        if ((rc = ddp_kl_div_f64_dev(h, (int)n, (int)m, (int)N, (int)B, x, x0, sig, K, k, Sigma, Kp, kzero, Sp, Sip, kld, klm))) return rc;
-        if ((rc = dual(2, it)) || (rc = poll(&live))) return rc;                                           // :141, :169-177
+        if ((rc = ddp_forward_covariance_f64_dev(h, M.n, M.m, M.N, M.B, model_fx, model_fx_batched, c.R1, c.K, c.Sigma, W.sig))) return rc;      // :133
+        if ((rc = ddp_kl_div_f64_dev(h, M.n, M.m, M.N, M.B, c.x, c.x0, W.sig, c.K, W.k, c.Sigma, c.Kp, W.kzero, c.Sp, c.Sip, W.kld, W.dual.klm)))
+            return rc;
+        if ((rc = dual(2, it, &live))) return rc;                                                          // :141, :169-177
     }
-    hipLaunchKernelGGL(kl_summary_kernel, dim3((unsigned)B), dim3(DDP_WAVE), 0, st, (int)m, (int)N, s, (const double *)k, kp, (const double *)cs,
-                       cost0, (const double *)dV, stats);
+    hipLaunchKernelGGL(kl_summary_kernel, dim3((unsigned)B), dim3(DDP_WAVE), 0, st, (int)m, (int)N, s, (const double *)W.k, c.kp,
+                       (const double *)W.cs, cost0, (const double *)c.dV, c.stats);
     DDP_HIP(hipGetLastError());
     DDP_HIP(hipStreamSynchronize(st));
-    if (iters_out) *iters_out = it - 1;
+    if (c.iters) *c.iters = it - 1;
     return 0;
 }
 
@@ -1201,25 +1200,23 @@ int ddp_ilqgkl_f64_dev(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts
 {
     DDP_DEVICE(h);
     DDP_CHECK(p && model_fx, "ilqgkl: null argument");
-    return ilqgkl_impl(h, p, nullptr, oo, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                       Vxx, cost, dV, stats, iters_out);
+    KlCall c;
+    c.opts = oo; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters_out;
+    return ilqgkl_impl(h, p, nullptr, c);
 }
 
 }   // extern "C"
 
-int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const ddp_ilqgkl_opts *o, const double *x0, const double *cost0,
-                          const double *Kp, const double *kp, const double *Sp, const double *Sip, const double *model_fx,
-                          int model_fx_batched, const double *R1, const double *lims, double *etab, double *x, double *u, double *K,
-                          double *Sigma, double *Sigmai, double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters,
-                          const double *fit_fx, const double *fit_fu, const double *fit_fc, const double *cm_cx, const double *cm_cu,
-                          const double *cm_cxx, const double *cm_cxu, const double *cm_cuu)
+int ddp_ilqgkl_family_dev(ddp_handle h, const ddp_family *f, const KlCall &c)
 {
     DDP_DEVICE(h);
     DDP_CHECK(f, "ilqgkl: null problem");
     DDP_CHECK(!f->second_order, "ilqgkl: a DDP_USER_SECOND_ORDER problem is refused (back_pass_gps has no second-order variant); make the "
                                 "problem without the flag for the KL loop");
-    return ilqgkl_impl(h, nullptr, f, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                       Vxx, cost, dV, stats, iters, fit_fx, fit_fu, fit_fc, cm_cx, cm_cu, cm_cxx, cm_cxu, cm_cuu);
+    return ilqgkl_impl(h, nullptr, f, c);
 }
 
 extern "C" {

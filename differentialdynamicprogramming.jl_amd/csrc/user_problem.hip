@@ -327,8 +327,8 @@ int bind(UserProblem *P, int N, int B, const double *params, int params_batched,
 }
 
 // what every ddp_user_* entry does first: the handle's device made current, the problem checked against the handle, the sizes and
-// parameters of the call bound.  A host-pointer flavour binds twice, here (it needs CL to size its staging) and in its `_dev` twin, with
-// the device copy of the parameters; the second bind finds t0_count == B and leaves the clocks on the device alone.
+// parameters of the call bound.  A host-pointer flavour binds twice, here (it needs CL to size its staging) and in its `_dev` twin (the three
+// ddp_user_ilqgkl*: in their staging body, ilqgkl_host), with the device copy of the parameters; the second bind finds t0_count == B and leaves the clocks on the device alone.
 // DDP_USER_CONSTRAINTS: ON_DEVICE says that params is a device pointer (the `_dev` entries that take such a problem: the parameter block
 // is assembled from it); `deferred` names an entry that refuses such a problem.
 int enter(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, UserProblem **P, ParamsOn on = ON_HOST,
@@ -1029,8 +1029,9 @@ int ddp_user_rollout_fit_f64(ddp_handle h, void *up, int N, int B, const double 
 }
 
 // ---- the KL loop: ddp_user_ilqgkl on the problem's own model, _fit on the tables fx, fu, fc of ddp_fit_dynamics (DDP_USER_FITTED), _cost
-// on a cost model cx .. cuu as well (and on the tables or not).  One loop (ddp_ilqgkl_family_dev: NULL tables, a NULL cost model are none)
-// and one staging body for the host flavours; what differs between the entries is what each refuses.
+// on a cost model cx .. cuu as well (and on the tables or not).  Every entry fills one KlCall (absent tables, an absent cost model stay
+// NULL) for the one loop, ddp_ilqgkl_family_dev; the host flavours share one staging body; what differs between the entries is what
+// each refuses.
 int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
                             const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp, const double *Sip,
                             const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
@@ -1040,8 +1041,12 @@ int ddp_user_ilqgkl_f64_dev(ddp_handle h, void *up, int N, int B, const double *
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                                 Vxx, cost, dV, stats, iters);
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    return ddp_ilqgkl_family_dev(h, U, c);
 }
 
 int ddp_user_ilqgkl_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
@@ -1056,18 +1061,22 @@ int ddp_user_ilqgkl_fit_f64_dev(ddp_handle h, void *up, int N, int B, const doub
     if (rc) return rc;
     DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
     DDP_CHECK(fx && fu && fc, "ilqgkl_fit: null argument");
-    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                                 Vxx, cost, dV, stats, iters, fx, fu, fc);
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.fit_fx = fx; c.fit_fu = fu; c.fit_fc = fc;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    return ddp_ilqgkl_family_dev(h, U, c);
 }
 
 // what both flavours of ddp_user_ilqgkl_cost refuse
-static int ilqgkl_cost_check(const UserProblem *U, const double *fx, const double *fu, const double *fc, const double *cx, const double *cu,
-                             const double *cxx, const double *cxu, const double *cuu)
+static int ilqgkl_cost_check(const UserProblem *U, const KlCall &c)
 {
-    DDP_CHECK((fx && fu && fc) || (!fx && !fu && !fc), "ilqgkl_cost: fx, fu and fc are given all three (the plan is made on the tables) or all "
-                                                       "three NULL (on the problem's own model)");
-    DDP_CHECK(!fx || U->mod->rollfit, "ilqgkl_cost: the problem was made without DDP_USER_FITTED (the tables fx, fu, fc need it)");
-    DDP_CHECK(cx && cu && cxx && cxu && cuu, "ilqgkl_cost: a cost model is cx, cu, cxx, cxu and cuu (null argument)");
+    DDP_CHECK((c.fit_fx && c.fit_fu && c.fit_fc) || (!c.fit_fx && !c.fit_fu && !c.fit_fc),
+              "ilqgkl_cost: fx, fu and fc are given all three (the plan is made on the tables) or all three NULL (on the problem's own model)");
+    DDP_CHECK(!c.fit_fx || U->mod->rollfit, "ilqgkl_cost: the problem was made without DDP_USER_FITTED (the tables fx, fu, fc need it)");
+    DDP_CHECK(c.cm_cx && c.cm_cu && c.cm_cxx && c.cm_cxu && c.cm_cuu, "ilqgkl_cost: a cost model is cx, cu, cxx, cxu and cuu (null argument)");
     return 0;
 }
 
@@ -1082,41 +1091,38 @@ int ddp_user_ilqgkl_cost_f64_dev(ddp_handle h, void *up, int N, int B, const dou
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    if ((rc = ilqgkl_cost_check(U, fx, fu, fc, cx, cu, cxx, cxu, cuu))) return rc;
-    return ddp_ilqgkl_family_dev(h, U, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, x, u, K, Sigma, Sigmai, Vx,
-                                 Vxx, cost, dV, stats, iters, fx, fu, fc, cx, cu, cxx, cxu, cuu);
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.fit_fx = fx; c.fit_fu = fu; c.fit_fc = fc;
+    c.cm_cx = cx; c.cm_cu = cu; c.cm_cxx = cxx; c.cm_cxu = cxu; c.cm_cuu = cuu;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    if ((rc = ilqgkl_cost_check(U, c))) return rc;
+    return ddp_ilqgkl_family_dev(h, U, c);
 }
 
-// the host flavour of the three, behind the checks of each: the staging, then the `_dev` twin of the entry (a cost model: _cost; else
-// tables: _fit; else the plain one)
-static int ilqgkl_host(ddp_handle h, void *up, const UserProblem *U, int N, int B, const double *params, int params_batched,
-                       const ddp_ilqgkl_opts *o, const double *x0, const double *cost0, const double *Kp, const double *kp, const double *Sp,
-                       const double *Sip, const double *model_fx, int model_fx_batched, const double *R1, const double *lims, double *etab,
-                       const double *fx, const double *fu, const double *fc, double *x, double *u, double *K, double *Sigma, double *Sigmai,
-                       double *Vx, double *Vxx, double *cost, double *dV, double *stats, int *iters, const double *cx, const double *cu,
-                       const double *cxx, const double *cxu, const double *cuu)
+// the host flavour of the three, behind the checks of each (`who` words the null-argument refusal): the staging, the device copy of the
+// parameters bound as a `_dev` entry binds it, then the loop on the staged call
+static int ilqgkl_host(ddp_handle h, UserProblem *U, const char *who, int N, int B, const double *params, int params_batched, KlCall c)
 {
+    DDP_CHECK(c.x0 && c.Kp && c.kp && c.Sp && c.Sip && c.R1 && c.x && c.u && c.K && c.Sigma && c.Sigmai && c.Vx && c.Vxx && c.cost && c.dV && c.stats,
+              "%s: null argument", who);
     const size_t n = U->n, m = U->m, T = (size_t)N * B, CL = U->CL;
-    const bool tables = fx != nullptr, model = cx != nullptr;
     Staging S(h, Staging::OWNED, "user problem");
-    stage_params(S, U, &params, params_batched, B); S.in(&x0, x0, n * T); S.in(&cost0, cost0, (size_t)B); S.in(&Kp, Kp, m * n * T);
-    S.in(&kp, kp, m * T); S.in(&Sp, Sp, m * m * T); S.in(&Sip, Sip, m * m * T);
-    S.in(&model_fx, model_fx, n * n * (size_t)N * (model_fx_batched ? B : 1)); S.in(&R1, R1, n * n); S.in(&lims, lims, 2 * m);
-    S.in(&fx, fx, n * n * T); S.in(&fu, fu, n * m * T); S.in(&fc, fc, n * T);
-    S.in(&cx, cx, n * T); S.in(&cu, cu, m * T); S.in(&cxx, cxx, n * n * T); S.in(&cxu, cxu, n * m * T); S.in(&cuu, cuu, m * m * T);
-    S.inout(&etab, etab, (size_t)3 * B); S.out(&x, x, n * T); S.out(&u, u, m * T); S.out(&K, K, m * n * T); S.out(&Sigma, Sigma, m * m * T);
-    S.out(&Sigmai, Sigmai, m * m * T); S.out(&Vx, Vx, n * T); S.out(&Vxx, Vxx, n * n * T); S.out(&cost, cost, CL * B);
-    S.out(&dV, dV, (size_t)2 * B); S.out(&stats, stats, (size_t)DDP_ILQGKL_NSTATS * B);
-    const int rc = S.commit();
+    stage_params(S, U, &params, params_batched, B); S.in(&c.x0, c.x0, n * T); S.in(&c.cost0, c.cost0, (size_t)B); S.in(&c.Kp, c.Kp, m * n * T);
+    S.in(&c.kp, c.kp, m * T); S.in(&c.Sp, c.Sp, m * m * T); S.in(&c.Sip, c.Sip, m * m * T);
+    S.in(&c.model_fx, c.model_fx, n * n * (size_t)N * (c.model_fx_batched ? B : 1)); S.in(&c.R1, c.R1, n * n); S.in(&c.lims, c.lims, 2 * m);
+    S.in(&c.fit_fx, c.fit_fx, n * n * T); S.in(&c.fit_fu, c.fit_fu, n * m * T); S.in(&c.fit_fc, c.fit_fc, n * T);
+    S.in(&c.cm_cx, c.cm_cx, n * T); S.in(&c.cm_cu, c.cm_cu, m * T); S.in(&c.cm_cxx, c.cm_cxx, n * n * T); S.in(&c.cm_cxu, c.cm_cxu, n * m * T);
+    S.in(&c.cm_cuu, c.cm_cuu, m * m * T);
+    S.inout(&c.etab, c.etab, (size_t)3 * B); S.out(&c.x, c.x, n * T); S.out(&c.u, c.u, m * T); S.out(&c.K, c.K, m * n * T);
+    S.out(&c.Sigma, c.Sigma, m * m * T); S.out(&c.Sigmai, c.Sigmai, m * m * T); S.out(&c.Vx, c.Vx, n * T); S.out(&c.Vxx, c.Vxx, n * n * T);
+    S.out(&c.cost, c.cost, CL * B); S.out(&c.dV, c.dV, (size_t)2 * B); S.out(&c.stats, c.stats, (size_t)DDP_ILQGKL_NSTATS * B);
+    int rc = S.commit();
     if (rc) return rc;
-    if (model) return S.finish(ddp_user_ilqgkl_cost_f64_dev(h, up, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx,
-                                                            model_fx_batched, R1, lims, etab, fx, fu, fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost,
-                                                            dV, stats, iters, cx, cu, cxx, cxu, cuu));
-    if (tables) return S.finish(ddp_user_ilqgkl_fit_f64_dev(h, up, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx,
-                                                            model_fx_batched, R1, lims, etab, fx, fu, fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost,
-                                                            dV, stats, iters));
-    return S.finish(ddp_user_ilqgkl_f64_dev(h, up, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1,
-                                            lims, etab, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats, iters));
+    if (!(rc = bind(U, N, B, params, params_batched, ON_HOST))) rc = ddp_ilqgkl_family_dev(h, U, c);
+    return S.finish(rc);
 }
 
 int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
@@ -1128,10 +1134,12 @@ int ddp_user_ilqgkl_f64(ddp_handle h, void *up, int N, int B, const double *para
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl: null argument");
-    return ilqgkl_host(h, up, U, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab,
-                       nullptr, nullptr, nullptr, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats, iters, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    return ilqgkl_host(h, U, "ilqgkl", N, B, params, params_batched, c);
 }
 
 int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
@@ -1145,10 +1153,14 @@ int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
     DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
-    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && fx && fu && fc && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats,
-              "ilqgkl_fit: null argument");
-    return ilqgkl_host(h, up, U, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, fx, fu,
-                       fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats, iters, nullptr, nullptr, nullptr, nullptr, nullptr);
+    DDP_CHECK(fx && fu && fc, "ilqgkl_fit: null argument");
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.fit_fx = fx; c.fit_fu = fu; c.fit_fc = fc;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    return ilqgkl_host(h, U, "ilqgkl_fit", N, B, params, params_batched, c);
 }
 
 int ddp_user_ilqgkl_cost_f64(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
@@ -1162,10 +1174,15 @@ int ddp_user_ilqgkl_cost_f64(ddp_handle h, void *up, int N, int B, const double 
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    if ((rc = ilqgkl_cost_check(U, fx, fu, fc, cx, cu, cxx, cxu, cuu))) return rc;
-    DDP_CHECK(x0 && Kp && kp && Sp && Sip && R1 && x && u && K && Sigma && Sigmai && Vx && Vxx && cost && dV && stats, "ilqgkl_cost: null argument");
-    return ilqgkl_host(h, up, U, N, B, params, params_batched, o, x0, cost0, Kp, kp, Sp, Sip, model_fx, model_fx_batched, R1, lims, etab, fx, fu,
-                       fc, x, u, K, Sigma, Sigmai, Vx, Vxx, cost, dV, stats, iters, cx, cu, cxx, cxu, cuu);
+    KlCall c;
+    c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
+    c.model_fx_batched = model_fx_batched; c.R1 = R1; c.lims = lims; c.etab = etab;
+    c.fit_fx = fx; c.fit_fu = fu; c.fit_fc = fc;
+    c.cm_cx = cx; c.cm_cu = cu; c.cm_cxx = cxx; c.cm_cxu = cxu; c.cm_cuu = cuu;
+    c.x = x; c.u = u; c.K = K; c.Sigma = Sigma; c.Sigmai = Sigmai; c.Vx = Vx; c.Vxx = Vxx; c.cost = cost; c.dV = dV; c.stats = stats;
+    c.iters = iters;
+    if ((rc = ilqgkl_cost_check(U, c))) return rc;
+    return ilqgkl_host(h, U, "ilqgkl_cost", N, B, params, params_batched, c);
 }
 
 }   // extern "C"

@@ -2,6 +2,7 @@
     ∇kl                 src/klutils.jl:8-23
     forward_covariance  src/forward_pass.jl:37-56
     kl_div_wiki         src/klutils.jl:70-103
+and of back_pass_gps without limits (src/backward_pass.jl:259-350) for one trajectory.
 No tests here.  Every function takes the arrays of ONE trajectory or, with a trailing axis, of a batch (every trajectory is computed
 independently, in one vectorised sweep: the B = 6145 case of tests/kl_narrow_cases.py is one call).  Inputs are float64 values taken
 exactly; every operation on them is long double, so what comes back is the float64 problem's answer to ~1e-19 — the yardstick both the
@@ -112,3 +113,50 @@ def kl_div_wiki(xnew, xold, sig, Kn, kn, Sn, Kp, kp, Sp, Sip):
         kld = np.where(v <= 0, LD(0), v)                                                     # max.(0, kldiv): NaN propagates (:98)
         mean = np.where(threw, LD(np.inf), kld.sum(axis=0) / T)
     return (kld, mean, threw) if bt else (kld[:, 0], mean[0], bool(threw[0]))
+
+
+def _spd_solve(Q, rhs):
+    """Q \\ rhs for a symmetric positive definite Q by Cholesky, in long double (numpy.linalg has no long double)"""
+    m = Q.shape[0]
+    Lo = np.zeros((m, m), dtype=LD)
+    for j in range(m):
+        d = Q[j, j] - Lo[j, :j] @ Lo[j, :j]
+        assert d > 0, "the case is meant to be positive definite"
+        Lo[j, j] = np.sqrt(d)
+        for i in range(j + 1, m):
+            Lo[i, j] = (Q[i, j] - Lo[i, :j] @ Lo[j, :j]) / Lo[j, j]
+    y = np.array(rhs, dtype=LD)
+    for i in range(m):
+        y[i] = (y[i] - Lo[i, :i] @ y[:i]) / Lo[i, i]
+    for i in range(m - 1, -1, -1):
+        y[i] = (y[i] - Lo[i + 1:, i] @ y[i + 1:]) / Lo[i, i]
+    return y
+
+
+def back_pass_gps(cx, cu, cxx, cxu, cuu, fx, fu, terms, eta):
+    """back_pass_gps of one trajectory without limits, every Quu positive definite -> K, k, Quui, Quu, Vx, Vxx, dV.  terms: ∇kl of the
+    trajectory (cxu as [m,n,N]); eta: ηbracket[2], a scalar or [N]"""
+    cx, cu, cxx, cxu, cuu, fx, fu = [np.asarray(a, dtype=np.float64).astype(LD) for a in (cx, cu, cxx, cxu, cuu, fx, fu)]
+    kx, ku, kxx, kux, kuu = [np.asarray(a, dtype=np.float64).astype(LD) for a in terms]
+    eta = np.broadcast_to(np.asarray(eta, dtype=np.float64).astype(LD), (cx.shape[1],))
+    (n, N), m = cx.shape, cu.shape[0]
+    K, k = np.zeros((m, n, N), dtype=LD), np.zeros((m, N), dtype=LD)
+    Vx, Vxx = np.zeros((n, N), dtype=LD), np.zeros((n, n, N), dtype=LD)
+    Quu, Quui, dV = np.zeros((m, m, N), dtype=LD), np.zeros((m, m, N), dtype=LD), np.zeros(2, dtype=LD)
+    Vx[:, -1], Vxx[:, :, -1] = cx[:, -1], cxx[:, :, -1]
+    Quu[:, :, -1] = cuu[:, :, -1] / eta[-1] + kuu[:, :, -1]
+    Quui[:, :, -1] = _spd_solve(Quu[:, :, -1], np.eye(m))
+    for i in range(N - 2, -1, -1):
+        F, G, V, e = fx[:, :, i], fu[:, :, i], Vxx[:, :, i + 1], eta[i]
+        Qu = (cu[:, i] + G.T @ Vx[:, i + 1]) / e + ku[:, i]
+        Qx = (cx[:, i] + F.T @ Vx[:, i + 1]) / e + kx[:, i]
+        Qux = (cxu[:, :, i].T + G.T @ V @ F) / e + kux[:, :, i]
+        Q = (cuu[:, :, i] + G.T @ V @ G) / e + kuu[:, :, i]
+        Qxx = (cxx[:, :, i] + F.T @ V @ F) / e + kxx[:, :, i]
+        Q = (Q + Q.T) / 2
+        ki, Ki = -_spd_solve(Q, Qu), -_spd_solve(Q, Qux)
+        dV = dV + np.array([ki @ Qu, ki @ Q @ ki / 2])
+        Vx[:, i] = Qx + Ki.T @ Q @ ki + Ki.T @ Qu + Qux.T @ ki
+        M = Qxx + Ki.T @ Q @ Ki + Ki.T @ Qux + Qux.T @ Ki
+        Vxx[:, :, i], k[:, i], K[:, :, i], Quu[:, :, i], Quui[:, :, i] = (M + M.T) / 2, ki, Ki, Q, _spd_solve(Q, np.eye(m))
+    return dict(K=K, k=k, Quui=Quui, Quu=Quu, Vx=Vx, Vxx=Vxx, dV=dV)

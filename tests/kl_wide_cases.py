@@ -31,9 +31,8 @@ def _spd(rng, d, s=1.0):
 
 
 @functools.lru_cache(maxsize=None)
-def single_pass(n, m):
+def single_pass(n, m, N=N1, B=B1):
     rng = np.random.default_rng(100 * n + m)
-    N, B = N1, B1
     c = dict(n=n, m=m, N=N, B=B)
     c["fx"] = np.stack([np.stack([np.eye(n) + 0.1 * rng.standard_normal((n, n)) for _ in range(N)], -1) for _ in range(B)], -1)
     c["fu"] = 0.3 * rng.standard_normal((n, m, N, B))
@@ -55,7 +54,7 @@ def operands(c, cfg):
     N, B, m = c["N"], c["B"], c["m"]
     fx, fu = (c["fx"], c["fu"]) if fx_b else (c["fx"][..., 0], c["fu"][..., 0])
     cxx, cxu, cuu = (c["cxx"], c["cxu"], c["cuu"].copy()) if cost_b else (c["cxx"][..., 0], c["cxu"][..., 0], c["cuu"][..., 0].copy())
-    etab = np.stack([1e-8 * np.ones(B), np.array([1.0, 0.5, 2.0]), 1e16 * np.ones(B)])
+    etab = np.stack([1e-8 * np.ones(B), np.array([1.0, 0.5, 2.0])[:B], 1e16 * np.ones(B)])
     if eta_tv:
         etab = np.repeat(etab[:, None, :], N, 1) * (1.0 + 0.1 * np.arange(N))[None, :, None]
     if bad:                                       # Quu indefinite at step 6 of trajectory 1

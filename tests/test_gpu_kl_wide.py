@@ -356,3 +356,120 @@ def test_switch_is_off_again_after_a_wide_call(ddp, gps_wide):
     out = [np.zeros(s, order="F") for s in ((n, N, B), (m, N, B), (n, n, N, B), (m, n, N, B), (m, m, N, B))]
     rc = _lib.lib().ddp_kl_terms_f64(h.raw, n, m, N, B, *map(_lib.ptr, [_lib.f64(c["Kp"]), _lib.f64(c["kp"]), _lib.f64(c["Sip"])] + out))
     assert rc < 0 and b"ddp_kl_set_wide" in _lib.lib().ddp_last_error()
+
+
+# 8. --------------------------------------------------------------------------------------------- the hook is the dispatcher
+Q4, LANE, MID, GEN = "back_pass_gps_q4", "back_pass_gps_lane", "back_pass_gps_mid", "back_pass_gps"
+STANDALONE, USER = 0, 2
+TWO_WAYS = 1e-10                                             # two kernels of one shape (tests/test_gpu_kl.py)
+# (n, m, N, η per step, switches, wide=, expected kernel): the smallest shape that reaches each branch of gps_choose, B = 2
+BRANCHES = [(4, 1, 1, False, {}, False, GEN),                # below N >= 2 of q4 and lane
+            (4, 1, 2, False, {}, False, Q4), (4, 1, 2, True, {}, False, LANE), (4, 2, 2, False, {}, False, LANE),
+            (10, 2, 3, False, {}, False, GEN),
+            (33, 2, 3, False, {}, True, WIDE), (10, 9, 3, False, {}, True, WIDE), (10, 2, 3, False, {"DDP_GPS_WIDE": "1"}, False, WIDE)]
+
+
+@pytest.fixture
+def switches(ddp, monkeypatch):
+    names = ("DDP_GPS_WIDE", "DDP_GPS_MID", "DDP_GPS_LANE", "DDP_GPS_Q4")
+
+    def set_(env):
+        for k in names:
+            if k in env:
+                monkeypatch.setenv(k, env[k])
+            else:
+                monkeypatch.delenv(k, raising=False)
+        ddp.default_handle().raw                              # (re-reads the DDP_* switches when they changed)
+    set_({})
+    yield set_
+    set_({})
+
+
+def _hook(n, m, N, B, caller, eta_tv, env, wide_on, complete=1):
+    """ddp_gps_choice3 for a call with time-varying per-trajectory operands and no limits, the switches as the environment has them"""
+    from ddp_amd import _lib
+    f = C.CDLL(_lib.LIB_PATH).ddp_gps_choice3
+    f.restype = C.c_char_p
+    f.argtypes = [C.POINTER(_lib.BPDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    e = lambda k: env[k].encode() if k in env else None                                  # noqa: E731
+    return f(C.byref(_lib.BPDesc(n, m, N, B, 1, 1, 1, 1, 1, 0)), int(eta_tv), caller, complete, e("DDP_GPS_MID"), e("DDP_GPS_Q4"),
+             e("DDP_GPS_LANE"), int(wide_on), e("DDP_GPS_WIDE")).decode()
+
+
+def _flat(got):
+    div, pol, Vx, Vxx, dV = got
+    return dict(K=pol.K, k=pol.k, Quui=pol.Σ, Quu=pol.Σi, Vx=Vx, Vxx=Vxx, dV=dV), div
+
+
+@pytest.mark.parametrize("n,m,N,eta_tv,env,wide,want", BRANCHES)
+def test_hook_names_the_kernel_the_entry_point_runs(ddp, switches, n, m, N, eta_tv, env, wide, want):
+    """ddp_back_pass_gps_f64 with B = 2: ddp_last_kernel(h, 0) is what ddp_gps_choice3 answers for the same facts, and the results are
+    the long double reference's to 1e-8 (kl_reference.back_pass_gps; the project's bar for back_pass_gps).  Bit for bit with the
+    run-time-sized kernel holds where that kernel is the one that ran, whichever way it is reached: q4, lane and wide do the same
+    arithmetic in another order and cannot share its bits, so a small-box kernel that is not the run-time-sized one is held to 1e-10 of
+    it, the bar tests/test_gpu_kl.py sets for two kernels of one shape.  (The reference is long double, not the C oracle of
+    kl_wide_cases.gps_reference: that one is fixed to N = 12, B = 3 and is itself double arithmetic.)"""
+    import kl_reference as ref
+    ref.need_longdouble()
+    B = 2
+    c = kc.single_pass(n, m, N, B)
+    cfg = (1, 1, False, eta_tv, False)
+    o = kc.operands(c, cfg)
+    kw = dict(wide=True) if wide else {}
+    switches(env)
+    terms = ddp.kl.grad_kl(_prev(ddp, c), **kw)
+    got, div = _flat(_gps(ddp, c, o, terms, **kw))
+    ran = _last(ddp)
+    hook = _hook(n, m, N, B, STANDALONE, eta_tv, env, wide)
+    print("(%d, %d) N = %d: ran %s, hook %s" % (n, m, N, ran, hook))
+    assert ran == hook == want
+    assert not div.any()
+    for b in range(B):
+        tl = ref.grad_kl(c["Kp"][..., b], c["kp"][..., b], c["Sip"][..., b])
+        eb = o["etab"][1, :, b] if eta_tv else o["etab"][1, b]
+        want_b = ref.back_pass_gps(c["cx"][..., b], c["cu"][..., b], o["cxx"][..., b], o["cxu"][..., b], o["cuu"][..., b], o["fx"][..., b],
+                                   o["fu"][..., b], tl, eb)
+        for key, a in got.items():
+            e = relerr(a[..., b], want_b[key].astype(float), 0) if key == "dV" else relerr(a[..., b], want_b[key].astype(float))
+            print("    trajectory %d %-4s %.2e" % (b, key, e))
+            assert e < RTOL, (b, key, e)
+    if n <= 32 and m <= 8:                                   # the run-time-sized kernel of the same call: DDP_GPS_LANE=0, no other switch
+        switches({"DDP_GPS_LANE": "0"})
+        gen, gdiv = _flat(_gps(ddp, c, o, ddp.kl.grad_kl(_prev(ddp, c))))
+        assert _last(ddp) == GEN == _hook(n, m, N, B, STANDALONE, eta_tv, {"DDP_GPS_LANE": "0"}, False)
+        assert np.array_equal(div, gdiv)
+        for key, a in got.items():
+            if want == GEN:
+                assert np.array_equal(a, gen[key]), key
+            else:
+                assert relerr(a, gen[key]) < TWO_WAYS, (key, relerr(a, gen[key]))
+
+
+def test_hook_names_the_kernel_of_the_user_loop_with_constant_hessians(ddp, switches):
+    """ddp_user_ilqgkl on lq_ad with const_hessian, (10, 2), N = 3, B = 2: the mid kernel reads the [.,.,B] Hessians as they are; with
+    DDP_GPS_MID=0 the run-time-sized kernel gets them repeated along time.  Both are what the hook names for the driver's call, and
+    both loops are the registered problem's (1e-8, the bar of tests/test_gpu_user_kl.py), which never sees a constant Hessian"""
+    from test_gpu_user_kl import _lq_setup
+    from test_gpu_user_problem import lq_params
+    kl = ddp.kl
+    n, m, T, B = 10, 2, 3, 2
+    A, Bm, Q, R, u, x, cost0, eye = _lq_setup(np.random.default_rng(8), n, m, T, B)
+    prev = ddp.GaussianPolicy(T, n, m, np.zeros((m, n, T, B)), u, eye, eye.copy())
+    fx, fu, R1 = np.repeat(A[:, :, None], T, 2), np.repeat(Bm[:, :, None], T, 2), 1e-4 * np.eye(n)
+    kw = dict(kl_step=2e-4, max_iter=6, cost=cost0)
+    switches({})
+    reg = kl.iLQGkl(ddp.LQProblem(A, Bm, Q, R), x, prev, kl.Model(fx, fu, R1), **kw)
+    user = ddp.DeviceProblem(ddp.example_source("lq_ad"), n, m, nparam=2 * n * n + n * m + m * m, autodiff=True, const_hessian=True)
+    for env, want in (({}, MID), ({"DDP_GPS_MID": "0"}, GEN)):
+        switches(env)
+        got = kl.iLQGkl(user, x, prev, kl.Model(None, None, R1), params=lq_params(A, Bm, Q, R), **kw)
+        ran, hook = _last(ddp), _hook(n, m, T, B, USER, False, env, False)
+        print("DDP_GPS_MID %s: ran %s, hook %s" % (env.get("DDP_GPS_MID"), ran, hook))
+        assert ran == hook == want
+        for k_ in ("status", "iter", "n_backpass"):
+            assert np.array_equal(got[6][k_], reg[6][k_]), (want, k_, got[6][k_], reg[6][k_])
+        assert relerr(got[6]["η"], reg[6]["η"], 0) < RTOL, want
+        for i, nm in ((0, "x"), (1, "u"), (3, "Vx"), (4, "Vxx"), (5, "cost")):
+            assert relerr(got[i], reg[i]) < RTOL, (want, nm, relerr(got[i], reg[i]))
+        for nm in ("K", "Σ", "Σi"):
+            assert relerr(getattr(got[2], nm), getattr(reg[2], nm)) < RTOL, (want, nm)

@@ -1,5 +1,5 @@
 """The wide KL path (ddp_kl_set_wide, kl.*(wide=True): n <= 64, m <= 32) without a GPU: the switch is declared, exported and bound;
-ddp_gps_choice2 names the back_pass_gps kernel of every shape; out-of-range shapes are refused before anything touches the handle; the
+ddp_gps_choice2 names the back_pass_gps kernel of every shape (ddp_gps_choice3: and of an incomplete call); out-of-range shapes are refused before anything touches the handle; the
 keyword restores the switch; the cases of tests/kl_wide_cases.py are sound (two independent references agree, no loop case sits on a
 tie of the reference, the limits bind); the GPS instantiation of back_pass_wide_kernel carries no more scratch than its twin."""
 import ctypes as C
@@ -59,6 +59,14 @@ def _choice2(n, m, caller, wide_on, gps_wide=None, eta_tv=0):
     return f(C.byref(_desc(n, m)), eta_tv, caller, None, None, None, wide_on, None if gps_wide is None else gps_wide.encode()).decode()
 
 
+def _choice3(n, m, caller, complete, wide_on, gps_wide=None, eta_tv=0, N=100, mid=None):
+    f = C.CDLL(_lib.LIB_PATH).ddp_gps_choice3
+    f.restype = C.c_char_p
+    f.argtypes = [C.POINTER(_lib.BPDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    enc = lambda s: None if s is None else s.encode()                                   # noqa: E731
+    return f(C.byref(_lib.BPDesc(n, m, N, 16, 1, 1, 1, 1, 1, 0)), eta_tv, caller, complete, enc(mid), None, None, wide_on, enc(gps_wide)).decode()
+
+
 BEYOND = [(33, 1), (33, 8), (1, 9), (32, 9), (64, 32), (40, 20), (65, 1), (1, 33), (64, 33), (65, 32), (0, 1), (1, 0)]
 
 
@@ -81,6 +89,28 @@ def test_choice_table(caller):
     for n in range(1, 65):                                                                # wide exactly when n > 32 or m > 8
         for m in range(1, 33):
             assert (_choice2(n, m, caller, 1) == WIDE) == (n > 32 or m > 8), (n, m)
+
+
+@pytest.mark.parametrize("caller", [STANDALONE, REGISTERED, USER])
+def test_choice_with_an_incomplete_kl_argument(caller):
+    """ddp_gps_choice3 carries the fact the dispatcher has always looked at first: a `kl` with a pointer missing (or limits without lims
+    and u) goes to the generic kernel, whose launcher words the refusal — inside the box whatever the shape, the step sizes and the
+    switches say, and for the wide shapes too; a complete call answers as ddp_gps_choice2 does"""
+    for n in range(1, 33):
+        for m in range(1, 9):
+            for eta_tv in (0, 1):
+                for wide_on in (0, 1):
+                    for N in (1, 100):
+                        assert _choice3(n, m, caller, 0, wide_on, eta_tv=eta_tv, N=N) == "back_pass_gps", (n, m)
+                assert _choice3(n, m, caller, 0, 0, "1", eta_tv) == "back_pass_gps", (n, m)           # DDP_GPS_WIDE=1
+                assert _choice3(n, m, caller, 0, 0, eta_tv=eta_tv, mid="1") == "back_pass_gps", (n, m)   # DDP_GPS_MID=1
+                assert _choice3(n, m, caller, 1, 0, eta_tv=eta_tv) == _choice2(n, m, caller, 0, eta_tv=eta_tv), (n, m)
+                assert _choice3(n, m, caller, 1, 0, "1", eta_tv) == WIDE, (n, m)
+    for n, m in BEYOND:
+        inside = 1 <= n <= 64 and 1 <= m <= 32
+        assert _choice3(n, m, caller, 0, 0) == "none", (n, m)                                        # refused by the shape check first
+        assert _choice3(n, m, caller, 0, 1) == ("back_pass_gps" if inside else "none"), (n, m)
+        assert _choice3(n, m, caller, 1, 1) == (WIDE if inside else "none"), (n, m)
 
 
 # ------------------------------------------------------------------------------------------------ refusals before any launch

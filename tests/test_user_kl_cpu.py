@@ -1,11 +1,14 @@
 """User problems through the KL-constrained loop (ddp_user_ilqgkl_*) without a GPU: the entry points are declared, exported, listed and
 bound from Julia; the build's resource records hold the GPS instantiations of back_pass_mid_kernel with no more scratch than their iLQG
-twins; ddp_gps_choice names the back_pass_gps kernel each kind of call gets; kl.iLQGkl checks a DeviceProblem's extents before any launch."""
+twins; ddp_gps_choice names the back_pass_gps kernel each kind of call gets; kl.iLQGkl checks a DeviceProblem's extents before any launch;
+the driver's workspace layout holds together (tests/kl_workspace_check.cpp, a host program of its own)."""
 import ctypes as C
 import glob
 import json
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -128,3 +131,35 @@ def test_ilqgkl_rejects_wrong_extents_before_any_launch():
                                          np.zeros((m, m, N, B))))
     with pytest.raises(ddp_amd.DDPError, match="lims"):
         call(lims=np.zeros((3, 2)))
+
+
+# ------------------------------------------------------------------------------------------------------------- the workspace layout
+def _cxx():
+    for c in ("c++", "g++", "clang++", "/opt/rocm/llvm/bin/clang++"):
+        p = shutil.which(c) or (c if os.path.isabs(c) and os.path.exists(c) else None)
+        if p:
+            return p
+    raise RuntimeError("no host C++ compiler")
+
+
+def test_driver_workspace_layout(tmp_path):
+    """csrc/kl_workspace.h, compiled for the host with the address and undefined-behaviour sanitizers and run as a program of its own:
+    pieces disjoint, 256-byte aligned, the counter block first, no gap, and the size the hand-written sum gave — (4, 1), (10, 2), (32, 8),
+    (40, 20), (64, 32), with and without a family, constant Hessians, their repetition and the driver's own dynamics"""
+    exe = tmp_path / "kl_workspace_check"
+    cxx = _cxx()
+    # g++ links the sanitizers' runtimes as shared libraries unless told otherwise, and a shared runtime insists on being the first library
+    # of the process; linked statically (clang's default) the program runs in whatever environment the suite has
+    static = [] if "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout else ["-static-libasan", "-static-libubsan"]
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + static + [
+        "-I", os.path.join(ROOT, "differentialdynamicprogramming.jl_amd", "csrc"), "-o", str(exe),
+        os.path.join(ROOT, "tests", "kl_workspace_check.cpp")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[:4000]
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    lines = r.stdout.splitlines()
+    assert lines[-1] == "ok: 70 cases", lines[-3:]
+    for n, m in ((4, 1), (10, 2), (32, 8), (40, 20), (64, 32)):
+        for tag in ("family=0", "family=1", "const_hessian=1 hrep=0", "const_hessian=1 hrep=1", "fx_own=0", "fx_own=1"):
+            assert any(l.startswith("n=%d m=%d " % (n, m)) and tag in l for l in lines), (n, m, tag)
