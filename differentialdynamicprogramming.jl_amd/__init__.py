@@ -903,7 +903,7 @@ def sample_policy(problem, traj, x0, x, u, S, *, seed=0, noise=None, lims=None, 
 
 
 # ------------------------------------------------------------------------------ fit_dynamics
-def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
+def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None, wide=False):
     """Time-varying linear-Gaussian dynamics ``x̂[i+1] ≈ fx[:,:,i] x̂[i] + fu[:,:,i] û[i] + fc[:,i]`` with residual covariance
     ``cov[:,:,i]``, fitted on the device to the rollouts ``xs[n,N,S(,B)]``, ``us[m,N,S(,B)]`` that ``sample_policy`` returns — the
     step between sampling and ``kl.iLQGkl`` in a guided-policy-search round, and the way to a model of a ``plant`` whose equations
@@ -917,8 +917,11 @@ def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
     pivot ``c`` of the factorisation that is not a positive finite number (``n + m + 1``: every pivot is fine but the results are not
     finite, a NaN in ``x̂_{i+1}``) — that step's outputs are NaN and no other step is touched.
     Every rollout of the sampler starts at the same ``x0``, so without ``ridge`` and ``prior`` step 0 reports pivot 1.  Slot ``N-1`` has
-    no transition: zeros.  1 <= n <= 32, 1 <= m <= 8, S >= 2.  Two calls give the same bits, and a call on some of the trajectories
-    gives the bits of their slice of the full call."""
+    no transition: zeros.  1 <= n <= 32, 1 <= m <= 8, S >= 2; with ``wide=True`` 1 <= n <= 64, 1 <= m <= 32 (the box of
+    ``sample_policy(..., sample_wave=True)`` and ``kl.iLQGkl(..., wide=True)``): a shape inside the small box keeps its kernel and
+    its bits, every other one runs the blocked kernel of ``ddp_fit_dynamics_wide_f64``, which forms ``cov`` as ``C_yy - Y1ᵀY1`` with
+    ``Y1 = L⁻¹C_zy`` (the same matrix).  Two calls give the same bits, and a call on some of the trajectories gives the bits of
+    their slice of the full call."""
     xs, us = _lib.f64(xs), _lib.f64(us)
     if xs.ndim not in (3, 4) or us.ndim != xs.ndim:
         raise DDPError("fit_dynamics: xs, us should be (n, N, S), (m, N, S) [+ batch axis], got %s, %s" % (xs.shape, us.shape))
@@ -947,9 +950,9 @@ def fit_dynamics(xs, us, *, ridge=0.0, prior=None, handle=None):
     h = handle or default_handle()
     fx = _lib.result_array((n, n, N, B)); fu = _lib.result_array((n, m, N, B)); fc = _lib.result_array((n, N, B))
     cov = _lib.result_array((n, n, N, B)); status = np.zeros((N, B), dtype=np.int32, order="F")
-    _lib.check(_lib.lib().ddp_fit_dynamics_f64(h.raw, n, m, N, S, B, _lib.ptr(xs), _lib.ptr(us), float(ridge), _lib.ptr(Phi), _lib.ptr(mu0), m0,
-                                               n0, layout, _lib.ptr(fx), _lib.ptr(fu), _lib.ptr(fc), _lib.ptr(cov),
-                                               status.ctypes.data_as(_lib.vp)))
+    entry = _lib.lib().ddp_fit_dynamics_wide_f64 if wide else _lib.lib().ddp_fit_dynamics_f64
+    _lib.check(entry(h.raw, n, m, N, S, B, _lib.ptr(xs), _lib.ptr(us), float(ridge), _lib.ptr(Phi), _lib.ptr(mu0), m0, n0, layout, _lib.ptr(fx),
+                     _lib.ptr(fu), _lib.ptr(fc), _lib.ptr(cov), status.ctypes.data_as(_lib.vp)))
     if not batched:
         return fx[..., 0], fu[..., 0], fc[..., 0], cov[..., 0], status[..., 0]
     return fx, fu, fc, cov, status

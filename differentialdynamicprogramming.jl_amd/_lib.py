@@ -43,14 +43,16 @@ EXPORTS = [
     "ddp_gmm_fit_f64_dev", "ddp_gmm_fit_f64", "ddp_gmm_prior_f64_dev", "ddp_gmm_prior_f64",
     "ddp_user_cost_fit_f64_dev", "ddp_user_cost_fit_f64", "ddp_user_ilqgkl_cost_f64_dev", "ddp_user_ilqgkl_cost_f64",
     "ddp_expected_cost_f64_dev", "ddp_expected_cost_f64", "ddp_kl_step_adjust_f64_dev", "ddp_kl_step_adjust_f64", "ddp_kl_set_steps_f64_dev", "ddp_kl_set_steps_f64",
+    "ddp_fit_dynamics_wide_f64_dev", "ddp_fit_dynamics_wide_f64",
 ]
-EXPECT_EXPORTS = tuple(EXPORTS[-6:])           # expected_cost, kl_step_adjust, the table of kl_steps: absent from A/B builds of the library from before them
-COST_FIT_EXPORTS = tuple(EXPORTS[-10:-6])      # the entries of DDP_USER_COST_FIT and of a cost model: absent from A/B builds of the library from before them
-GMM_EXPORTS = tuple(EXPORTS[-14:-10])          # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
-FITTED_EXPORTS = tuple(EXPORTS[-18:-14])       # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
-FIT_EXPORTS = tuple(EXPORTS[-20:-18])           # fit_dynamics: absent from A/B builds of the library from before it
-SAMPLE_EXPORTS = tuple(EXPORTS[-24:-20])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
-CONSTRAINTS_EXPORTS = tuple(EXPORTS[-32:-24])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
+FIT_WIDE_EXPORTS = tuple(EXPORTS[-2:])         # fit_dynamics(wide=True): absent from A/B builds of the library from before it
+EXPECT_EXPORTS = tuple(EXPORTS[-8:-2])           # expected_cost, kl_step_adjust, the table of kl_steps: absent from A/B builds of the library from before them
+COST_FIT_EXPORTS = tuple(EXPORTS[-12:-8])      # the entries of DDP_USER_COST_FIT and of a cost model: absent from A/B builds of the library from before them
+GMM_EXPORTS = tuple(EXPORTS[-16:-12])          # fit_gmm, gmm_prior: absent from A/B builds of the library from before them
+FITTED_EXPORTS = tuple(EXPORTS[-20:-16])       # the entries of DDP_USER_FITTED: absent from A/B builds of the library from before the flag
+FIT_EXPORTS = tuple(EXPORTS[-22:-20])           # fit_dynamics: absent from A/B builds of the library from before it
+SAMPLE_EXPORTS = tuple(EXPORTS[-26:-22])        # the entries of DDP_USER_SAMPLE: absent from A/B builds of the library from before the flag
+CONSTRAINTS_EXPORTS = tuple(EXPORTS[-34:-26])     # the entries of DDP_USER_CONSTRAINTS: absent from A/B builds of the library from before the flag
 
 
 class BPDesc(C.Structure):
@@ -211,6 +213,9 @@ def lib():
             fit_args = [vp] + [ci] * 5 + [cd, cd, C.c_double, cd, cd, C.c_double, C.c_double, ci] + [cd] * 4 + [vp]
             L.ddp_fit_dynamics_f64.argtypes = fit_args
             L.ddp_fit_dynamics_f64_dev.argtypes = fit_args
+        if hasattr(L, "ddp_fit_dynamics_wide_f64"):           # absent from A/B builds of the library from before it
+            L.ddp_fit_dynamics_wide_f64.argtypes = [vp] + [ci] * 5 + [cd, cd, C.c_double, cd, cd, C.c_double, C.c_double, ci] + [cd] * 4 + [vp]
+            L.ddp_fit_dynamics_wide_f64_dev.argtypes = [vp] + [ci] * 5 + [cd, cd, C.c_double, cd, cd, C.c_double, C.c_double, ci] + [cd] * 4 + [vp]
         if hasattr(L, "ddp_user_rollout_fit_f64"):            # DDP_USER_FITTED; absent from A/B builds of the library from before the flag
             L.ddp_user_rollout_fit_f64.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 6 + [ci, cd] + [cd] * 3 + [cd] * 4
             L.ddp_user_rollout_fit_f64_dev.argtypes = [vp, vp, ci, ci, cd, ci] + [cd] * 6 + [ci, cd, vp] + [cd] * 3 + [cd] * 4
@@ -248,7 +253,7 @@ def lib():
         if hasattr(L, "ddp_df_expm_plan"):                    # debug hook; absent from A/B builds of the library from before it
             L.ddp_df_expm_plan.argtypes = [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for name in EXPORTS:
-            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS + COST_FIT_EXPORTS + EXPECT_EXPORTS and not hasattr(L, name):
+            if name in ("ddp_user_set_t0", "ddp_df_expm_plan") + CONSTRAINTS_EXPORTS + SAMPLE_EXPORTS + FIT_EXPORTS + FITTED_EXPORTS + GMM_EXPORTS + COST_FIT_EXPORTS + EXPECT_EXPORTS + FIT_WIDE_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             if name not in ("ddp_last_error", "ddp_version", "ddp_stream", "ddp_last_kernel", "ddp_user_compile_log"):

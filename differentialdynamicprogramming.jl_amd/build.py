@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libddp_amd.so")
 SOURCES = ["capi.hip", "back_pass.hip", "back_pass_dpp.hip", "back_pass_dppw.hip", "back_pass_row.hip", "back_pass_row_hi.hip", "back_pass_mid.hip", "back_pass_big.hip", "back_pass_gps_lane.hip", "back_pass_mfma.hip", "back_pass_mfma_lims.hip", "back_pass_mf2.hip", "back_pass_mf2_lims.hip", "back_pass_mx.hip", "back_pass_mxg.hip", "back_pass_mx2.hip", "back_pass_sh.hip", "back_pass_q4.hip", "back_pass_wide.hip",
-           "forward_pass.hip", "forward_pass_dpp.hip", "forward_pass_row.hip", "forward_pass_pipe.hip", "forward_pass_big.hip", "forward_pass_wide.hip", "df.hip", "ilqg.hip", "kl.hip", "kl_wide.hip", "comm.hip", "boxqp_big.hip", "user_program.hip", "user_problem.hip", "sample.hip", "fit.hip", "gmm.hip", "expect.hip"]
+           "forward_pass.hip", "forward_pass_dpp.hip", "forward_pass_row.hip", "forward_pass_pipe.hip", "forward_pass_big.hip", "forward_pass_wide.hip", "df.hip", "ilqg.hip", "kl.hip", "kl_wide.hip", "comm.hip", "boxqp_big.hip", "user_program.hip", "user_problem.hip", "sample.hip", "fit.hip", "gmm.hip", "expect.hip", "fit_wide.hip"]
 HEADERS = ["ddp_internal.h", "boxqp_dev.h", "boxqp_rows.h", "staging.h", os.path.join("..", "..", "include", "ddp_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage", "-Wall", "-Wno-unused-function",
          "-Wno-unused-but-set-variable", "-Wno-unused-variable"]
@@ -34,6 +34,7 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "back_pass_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "kl_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "fit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "fit_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gmm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "expect.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "user_program.hip": ["-I", OBJ]}                  # the headers of PROGRAM_TEXTS, written to build/
@@ -42,7 +43,7 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_sample_wave_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
               "user_problem.hip": ["user_program.h", "user_problem_kernels.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "wide_tile.h", "back_pass_wide_kernel.h"], "sample.hip": ["philox.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
-              "ilqg.hip": ["ilqg_model.h", "carver.h"], "kl.hip": ["ilqg_model.h", "carver.h", "kl_workspace.h"], "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"], "fit.hip": ["wide_tile.h"], "gmm.hip": ["wide_tile.h", "philox.h"], "expect.hip": ["wide_tile.h"]}
+              "ilqg.hip": ["ilqg_model.h", "carver.h"], "kl.hip": ["ilqg_model.h", "carver.h", "kl_workspace.h"], "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"], "fit.hip": ["wide_tile.h"], "fit_wide.hip": ["wide_tile.h"], "gmm.hip": ["wide_tile.h", "philox.h"], "expect.hip": ["wide_tile.h"]}
 
 
 # Headers of csrc/ as program text for hiprtc (user_program.hip): output file -> [(symbol, header)].  The kernels compiled at run time take

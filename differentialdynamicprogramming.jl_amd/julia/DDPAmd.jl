@@ -1312,7 +1312,7 @@ function sample_policy(problem::DeviceProblem, traj, x0, x, u, S::Integer; seed:
 end
 
 """
-    fit_dynamics(xs, us; ridge=0.0, prior=nothing, handle) -> fx, fu, fc, cov, status
+    fit_dynamics(xs, us; ridge=0.0, prior=nothing, wide=false, handle) -> fx, fu, fc, cov, status
 
 Time-varying linear-Gaussian dynamics `x̂[i+1] ≈ fx[:,:,i] x̂[i] + fu[:,:,i] û[i] + fc[:,i]` with residual covariance `cov[:,:,i]`, fitted
 on the device to the rollouts `xs[n,N,S(,B)]`, `us[m,N,S(,B)]` of `sample_policy` (ddp_fit_dynamics_f64; the formula is in
@@ -1320,8 +1320,9 @@ include/ddp_amd.h).  `prior = (Φ, μ0, m0, n0)` is a normal-inverse-Wishart pri
 `μ0[p,N(,B)]` one each (`p = 2n + m`); `ridge >= 0` is added to the diagonal of `C_zz`.  `status[N(,B)]` is per step: 0, or `c + 1` for
 the first pivot `c` of the Cholesky factorisation that is not a positive finite number, `n + m + 1` when only the results are not
 finite (that step's outputs are NaN, no other step is touched); slot `N` has no transition and is zeros.  `Model(fx, fu, R1)` of `iLQGkl` takes the first two as they are.
+`n <= 32`, `m <= 8`; `wide=true` takes `n <= 64`, `m <= 32` (ddp_fit_dynamics_wide_f64: a shape inside the small box keeps its kernel and its bits).
 """
-function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, handle::Handle=default_handle())
+function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, wide::Bool=false, handle::Handle=default_handle())
     batched = ndims(xs) == 4
     n, N, S = size(xs, 1), size(xs, 2), size(xs, 3)
     m = size(us, 1)
@@ -1345,9 +1346,15 @@ function fit_dynamics(xs, us; ridge::Real=0.0, prior=nothing, handle::Handle=def
     status = zeros(Int32, N, bt...)
     rdg = Float64(ridge)
     GC.@preserve xs us Phi mu0 fx fu fc cov status begin
-        check(@ccall libddp.ddp_fit_dynamics_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, xs::Ptr{Float64},
-            us::Ptr{Float64}, rdg::Cdouble, _ptr_or_null(Phi)::Ptr{Float64}, _ptr_or_null(mu0)::Ptr{Float64}, m0::Cdouble, n0::Cdouble,
-            layout::Cint, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, cov::Ptr{Float64}, status::Ptr{Int32})::Cint)
+        if wide
+            check(@ccall libddp.ddp_fit_dynamics_wide_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, xs::Ptr{Float64},
+                us::Ptr{Float64}, rdg::Cdouble, _ptr_or_null(Phi)::Ptr{Float64}, _ptr_or_null(mu0)::Ptr{Float64}, m0::Cdouble, n0::Cdouble,
+                layout::Cint, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, cov::Ptr{Float64}, status::Ptr{Int32})::Cint)
+        else
+            check(@ccall libddp.ddp_fit_dynamics_f64(handle.ptr::Ptr{Cvoid}, n::Cint, m::Cint, N::Cint, S::Cint, B::Cint, xs::Ptr{Float64},
+                us::Ptr{Float64}, rdg::Cdouble, _ptr_or_null(Phi)::Ptr{Float64}, _ptr_or_null(mu0)::Ptr{Float64}, m0::Cdouble, n0::Cdouble,
+                layout::Cint, fx::Ptr{Float64}, fu::Ptr{Float64}, fc::Ptr{Float64}, cov::Ptr{Float64}, status::Ptr{Int32})::Cint)
+        end
     end
     return fx, fu, fc, cov, status
 end

@@ -914,6 +914,21 @@ int ddp_fit_dynamics_f64(ddp_handle h, int n, int m, int N, int S, int B, const 
                          const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
                          double *fc, double *cov, int32_t *status);
 
+/* The same fit for large problems, 1 <= n <= 64 (DDP_MAX_N_USER_WAVE), 1 <= m <= 32 (DDP_MAX_M_WIDE): the arguments, layouts, formula,
+ * outputs and status of ddp_fit_dynamics_f64(_dev) above; anything outside that box is refused by name before the handle is looked
+ * at.  A shape inside the small box (n <= 32 and m <= 8) is handed to ddp_fit_dynamics_f64(_dev) and gives its bits; every other
+ * shape runs kernel ddp_fit_dynamics_wide (fit_wide.hip): one work-group per step and trajectory, the Gram matrix, the blocked
+ * Cholesky factorisation (16 columns a block) and both substitutions on v_mfma_f64_16x16x4, the matrices as 16 x 16 blocks in
+ * dynamic LDS sized from (n, m) (117 KiB at (64, 32)).  cov is formed as C_yy - Y1' Y1 with Y1 = L^-1 C_zy, the same matrix as
+ * C_yy - [fx fu] C_zy and symmetric to the bit.  The chunking of the samples and the order of every sum come from (n, m) alone:
+ * two calls give the same bits, a call on a slice of the trajectories gives the bits of that slice, and the two flavours agree.  */
+int ddp_fit_dynamics_wide_f64_dev(ddp_handle h, int n, int m, int N, int S, int B, const double *xs, const double *us, double ridge,
+                                  const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
+                                  double *fc, double *cov, int32_t *status);
+int ddp_fit_dynamics_wide_f64(ddp_handle h, int n, int m, int N, int S, int B, const double *xs, const double *us, double ridge,
+                              const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
+                              double *fc, double *cov, int32_t *status);
+
 /* DDP_USER_FITTED problems only (a problem made without the flag is refused by name).  The rollout of ddp_user_forward_pass_f64(_dev),
  * arguments and outputs alike, on the fitted model fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] (see DDP_USER_FITTED above).                  */
 int ddp_user_rollout_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
