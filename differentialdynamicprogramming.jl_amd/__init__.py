@@ -218,13 +218,20 @@ class DeviceProblem:
     ``m <= 32`` — the program also holds ``ddp_user_sample_wave`` (a group of lanes per sample, the vectors in LDS) and ``sample_policy``
     takes the problem, with the semantics of ``sample=True`` word for word; every other entry point ignores the flag.  Legal with
     ``terminal``, ``const_hessian``, ``autodiff``, ``plant``, ``second_order_wave`` and ``diff``; not with ``clock`` or ``constraints``
-    (deferred).  ``sample=True`` stays the flag of a problem without ``wave``."""
+    (deferred).  ``sample=True`` stays the flag of a problem without ``wave``.
+    ``fitted_wave=True`` (DDP_USER_FITTED_WAVE, needs ``wave=True``): the fitted rollout at the shapes of ``wave=True``, ``n <= 64`` and
+    ``m <= 32`` — the program also holds ``ddp_user_rollout_fit_wave`` (a group of lanes per rollout, the vectors in LDS, the rows of the
+    tables streamed by the group); ``forward_pass(..., model=(fx, fu, fc))`` runs it and ``kl.iLQGkl(..., fitted=True, wide=True)`` plans
+    on the tables ``fit_dynamics(..., wide=True)`` returns, with the semantics of ``fitted=True`` word for word; every other entry point
+    ignores the flag.  Legal with ``terminal``, ``const_hessian``, ``autodiff``, ``plant``, ``sample_wave``, ``second_order_wave`` and
+    ``diff``; not with ``clock`` or ``constraints`` (deferred).  ``fitted=True`` stays the flag of a problem without ``wave``."""
     kind = 2
 
     def __init__(self, source, n, m, *, nparam=0, params=None, terminal=False, const_hessian=False, autodiff=False, diff=None, plant=False,
                  second_order=False, wave=False, second_order_wave=False, clock=False, constraints=0, sample=False, fitted=False, cost_fit=False,
-                 sample_wave=False):
+                 sample_wave=False, fitted_wave=False):
         self.clock = bool(clock)
+        self.fitted_wave = bool(fitted_wave)
         self.sample_wave = bool(sample_wave)
         self.cost_fit = bool(cost_fit)
         self.sample = bool(sample)
@@ -237,6 +244,9 @@ class DeviceProblem:
         if self.sample_wave and not self.wave:
             raise DDPError("DeviceProblem: DDP_USER_SAMPLE_WAVE needs DDP_USER_WAVE (sample_wave=True needs wave=True; without wave the "
                            "sampler is sample=True)")
+        if self.fitted_wave and not self.wave:
+            raise DDPError("DeviceProblem: DDP_USER_FITTED_WAVE needs DDP_USER_WAVE (fitted_wave=True needs wave=True; without wave the "
+                           "fitted rollout is fitted=True)")
         self.source, self.n, self.m, self.nparam = str(source), int(n), int(m), int(nparam)
         self.terminal, self.const_hessian, self.autodiff, self.plant = bool(terminal), bool(const_hessian), bool(autodiff), bool(plant)
         self.flags = ((1 if self.terminal else 0) | (2 if self.const_hessian else 0) | (4 if self.autodiff else 0) |
@@ -244,7 +254,7 @@ class DeviceProblem:
                       (_lib.USER_SECOND_ORDER_WAVE if self.second_order_wave else 0) | (_lib.USER_CLOCK if self.clock else 0) |
                       (_lib.USER_CONSTRAINTS if self.nc else 0) | (_lib.USER_SAMPLE if self.sample else 0) |
                       (_lib.USER_FITTED if self.fitted else 0) | (_lib.USER_COST_FIT if self.cost_fit else 0) |
-                      (_lib.USER_SAMPLE_WAVE if self.sample_wave else 0))
+                      (_lib.USER_SAMPLE_WAVE if self.sample_wave else 0) | (_lib.USER_FITTED_WAVE if self.fitted_wave else 0))
         self.diff_mask = _diff_mask(diff, self.n)                # WrappedDiff holds coordinates below 32 at every n
         self.params = params
         self._made = {}                                          # id(handle) -> (handle, problem pointer)
@@ -567,8 +577,9 @@ def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=Non
     ``traj_new`` may be an empty ``GaussianPolicy`` (then ``x`` is ignored, iLQG.jl:185).
     A vector ``α`` rolls all step sizes out concurrently (outputs get a trailing α axis).
     A ``DeviceProblem`` takes ``params`` (default: its own); its ``diff`` is compiled in; made with ``clock=True`` it takes ``t0``, made
-    with ``constraints=nc`` it takes ``multipliers=(λ, μ)`` (the augmented cost); made with ``fitted=True`` it takes
-    ``model=(fx, fu, fc)``, the tables ``fit_dynamics`` returns (``(n,n,N)``, ``(n,m,N)``, ``(n,N)`` [+ batch axis]): the rollout then runs
+    with ``constraints=nc`` it takes ``multipliers=(λ, μ)`` (the augmented cost); made with ``fitted=True`` (or with ``wave=True,
+    fitted_wave=True``: ``n <= 64``, ``m <= 32``, kernel ``ddp_user_rollout_fit_wave``) it takes ``model=(fx, fu, fc)``, the tables
+    ``fit_dynamics`` returns (``(n,n,N)``, ``(n,m,N)``, ``(n,N)`` [+ batch axis]): the rollout then runs
     ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` under the problem's cost (``ddp_user_rollout_fit``; slot ``N-1`` of the tables is not read).
     With ``traj_new=None`` that is the open-loop rollout which makes ``(x, u)`` consistent with the fit before ``kl.iLQGkl(..., fitted=True)``.
     Returns ``(xnew, unew, cnew)``."""
@@ -576,7 +587,7 @@ def forward_pass(traj_new, x0, u, x, α, problem, lims, diff=None, *, handle=Non
         return _user_forward_pass(traj_new, x0, u, x, α, problem, lims, diff, handle=handle, params=params, t0=t0, multipliers=multipliers,
                                   model=model)
     if model is not None:
-        raise DDPError("model= needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
+        raise DDPError("model= needs a DeviceProblem made with fitted=True (DDP_USER_FITTED) or with wave=True, fitted_wave=True (DDP_USER_FITTED_WAVE)")
     h = handle or default_handle()
     _no_clock(t0)
     _no_multipliers(multipliers)
@@ -659,9 +670,10 @@ def _user_batch(x_or_x0, u, problem, x0_has_time=False):
 
 def _fitted_tables(problem, model, n, m, N, B, batched, who):
     """``(fx, fu, fc)`` of a ``model=`` keyword as the library takes them, ``[.,.,N,B]``; refused by name on a problem made without
-    ``fitted=True`` or on a malformed shape, before anything is launched"""
-    if not problem.fitted:
-        raise DDPError("%s: a fitted model needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)" % who)
+    ``fitted=True`` or ``fitted_wave=True``, or on a malformed shape, before anything is launched"""
+    if not (problem.fitted or problem.fitted_wave):
+        raise DDPError("%s: a fitted model needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)%s"
+                       % (who, "; a wave=True problem: with fitted_wave=True (DDP_USER_FITTED_WAVE)" if problem.wave else ""))
     try:
         fx, fu, fc = model
     except (TypeError, ValueError):

@@ -96,6 +96,7 @@ class ALOpts(C.Structure):
 
 
 ILQGKL_NSTATS = 12
+USER_FITTED_WAVE = 65536       # DDP_USER_FITTED_WAVE: the flag of DeviceProblem(..., wave=True, fitted_wave=True)
 USER_SAMPLE_WAVE = 16384       # DDP_USER_SAMPLE_WAVE: the flag of DeviceProblem(..., wave=True, sample_wave=True)
 USER_COST_FIT = 8192           # DDP_USER_COST_FIT: the flag of DeviceProblem(..., cost_fit=True)
 USER_FITTED = 4096             # DDP_USER_FITTED: the flag of DeviceProblem(..., fitted=True)

@@ -40,7 +40,7 @@ EXTRA_FLAGS = {"back_pass_mx.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "user_program.hip": ["-I", OBJ]}                  # the headers of PROGRAM_TEXTS, written to build/
 
 
-EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_sample_wave_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
+EXTRA_DEPS = {"user_program.hip": ["user_program.h", "user_problem_kernels.h", "user_problem_wave_kernels.h", "user_autodiff.h", "user_constraints.h", "user_sample_kernels.h", "user_sample_wave_kernels.h", "user_fitted_kernels.h", "user_fitted_wave_kernels.h", "user_cost_fit_kernels.h", "philox.h", "wide_tile.h", "back_pass_wide_kernel.h"],
               "user_problem.hip": ["user_program.h", "user_problem_kernels.h", "user_constraints.h", "user_sample_kernels.h", "user_fitted_kernels.h", "user_cost_fit_kernels.h", "wide_tile.h", "back_pass_wide_kernel.h"], "sample.hip": ["philox.h"], "back_pass_mf2.hip": ["back_pass_mf2_kernel.h"], "back_pass_mf2_lims.hip": ["back_pass_mf2_kernel.h"], "back_pass_row_hi.hip": ["back_pass_row.hip"], "back_pass_mfma.hip": ["back_pass_mfma_kernel.h"], "back_pass_mfma_lims.hip": ["back_pass_mfma_kernel.h"],
               "back_pass_mx.hip": ["back_pass_mx_common.h"], "back_pass_mxg.hip": ["back_pass_mx_common.h"], "back_pass_mx2.hip": ["back_pass_mx_common.h"], "back_pass_sh.hip": ["back_pass_mx_common.h"],
               "ilqg.hip": ["ilqg_model.h", "carver.h"], "kl.hip": ["ilqg_model.h", "carver.h", "kl_workspace.h"], "forward_pass_dpp.hip": ["pend_math.h"], "back_pass_wide.hip": ["wide_tile.h", "back_pass_wide_kernel.h"], "kl_wide.hip": ["wide_tile.h"], "fit.hip": ["wide_tile.h"], "fit_wide.hip": ["wide_tile.h"], "gmm.hip": ["wide_tile.h", "philox.h"], "expect.hip": ["wide_tile.h"]}

@@ -68,7 +68,8 @@ struct Module {
     hipFunction_t sample = nullptr;                              // ddp_user_sample (DDP_USER_SAMPLE) or ddp_user_sample_wave (DDP_USER_SAMPLE_WAVE)
     const char *sample_name = nullptr;
     int sample_per = 0;                                          // samples per work-group of `sample`
-    hipFunction_t rollfit = nullptr;                             // ddp_user_rollout_fit (DDP_USER_FITTED)
+    hipFunction_t rollfit = nullptr;                             // ddp_user_rollout_fit (DDP_USER_FITTED) or ddp_user_rollout_fit_wave (DDP_USER_FITTED_WAVE)
+    const char *rollfit_name = nullptr;
     hipFunction_t costfit = nullptr;                             // ddp_user_cost_fit (DDP_USER_COST_FIT)
     hipFunction_t con = nullptr, alup = nullptr;                 // ddp_user_constraints, ddp_user_al_update (DDP_USER_CONSTRAINTS)
     const char *df_name = nullptr;                               // ddp_user_df, ddp_user_df_ad (DDP_USER_AUTODIFF) or ddp_user_df_wave (+ DDP_USER_WAVE)
@@ -176,7 +177,7 @@ struct UserProblem final : ddp_family {
         DDP_CHECK((K == nullptr) == (k == nullptr), "forward_pass: K and k must both be given or both NULL");
         DDP_CHECK(!K || x, "forward_pass: a non-empty policy needs the nominal trajectory x");
         if (fit_fx) {                                            // the fitted model of the call in place of `dynamics` (FitScope)
-            DDP_CHECK(mod->rollfit, "forward_pass: the problem was made without DDP_USER_FITTED");
+            DDP_CHECK(mod->rollfit, "forward_pass: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE)");
             UserRollFitArgs a;
             a.N = N; a.B = Bc; a.nalpha = nalpha; a.has_policy = K != nullptr; a.has_lims = lims != nullptr; a.params_batched = params_batched;
             a.params = params; a.K = K; a.k = k; a.x0 = x0; a.u = u; a.x = x; a.lims = lims; a.active = active; a.map = map;
@@ -186,7 +187,7 @@ struct UserProblem final : ddp_family {
             const long total = (long)Bc * nalpha;
             DDP_HIP(hipModuleLaunchKernel(mod->rollfit, (unsigned)((total + mod->L.flanes - 1) / mod->L.flanes), 1, 1, 64, 1, 1, 0, hh->stream,
                                           args, nullptr));
-            hh->last_kernel[1] = "ddp_user_rollout_fit";
+            hh->last_kernel[1] = mod->rollfit_name;
             return 0;
         }
         UserRollArgs a;
@@ -389,6 +390,7 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
         M.roll_name = wave ? "ddp_user_rollout_wave" : "ddp_user_rollout";
         M.sample_name = (flags & DDP_USER_SAMPLE_WAVE) ? "ddp_user_sample_wave" : "ddp_user_sample";
         M.sample_per = (flags & DDP_USER_SAMPLE_WAVE) ? 64 / M.L.wg : M.L.slanes;
+        M.rollfit_name = (flags & DDP_USER_FITTED_WAVE) ? "ddp_user_rollout_fit_wave" : "ddp_user_rollout_fit";
         DDP_HIP(hipModuleLoadData(&M.mod, code.data()));
         // the kernels of the program: mask 0 = every program has it, else the flags (any of them) whose programs do
         const struct { int mask; const char *name; hipFunction_t Module::*fn; } kernels[] = {
@@ -398,7 +400,8 @@ static int user_create(ddp_handle h, const char *source, int n, int m, int npara
             {DDP_USER_SECOND_ORDER_WAVE, "ddp_user_back_pass2_wave", &Module::bp2w},
             {DDP_USER_SECOND_ORDER | DDP_USER_SECOND_ORDER_WAVE, "ddp_user_vhess", &Module::vhess},
             {DDP_USER_CONSTRAINTS, "ddp_user_constraints", &Module::con}, {DDP_USER_CONSTRAINTS, "ddp_user_al_update", &Module::alup},
-            {DDP_USER_SAMPLE | DDP_USER_SAMPLE_WAVE, M.sample_name, &Module::sample}, {DDP_USER_FITTED, "ddp_user_rollout_fit", &Module::rollfit},
+            {DDP_USER_SAMPLE | DDP_USER_SAMPLE_WAVE, M.sample_name, &Module::sample},
+            {DDP_USER_FITTED | DDP_USER_FITTED_WAVE, M.rollfit_name, &Module::rollfit},
             {DDP_USER_COST_FIT, "ddp_user_cost_fit", &Module::costfit}};
         bool ok = true;
         for (const auto &k : kernels)
@@ -951,8 +954,8 @@ int ddp_user_cost_fit_f64(ddp_handle h, void *up, int N, int S, int B, const dou
 }
 
 // ---- the rollout, on the problem's own `dynamics` (ddp_user_forward_pass) or on the tables fx, fu, fc of ddp_fit_dynamics
-// (ddp_user_rollout_fit, DDP_USER_FITTED): the tables ride on the family for the time of the call (FitScope), rollout() then launches
-// ddp_user_rollout_fit
+// (ddp_user_rollout_fit, DDP_USER_FITTED; ddp_user_rollout_fit_wave, DDP_USER_FITTED_WAVE): the tables ride on the family for the time
+// of the call (FitScope), rollout() then launches the fitted rollout of the program
 int ddp_user_forward_pass_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
                                   const double *K, const double *k, const double *x0, const double *u, const double *x,
                                   const double *alpha, int nalpha, const double *lims, const int32_t *active,
@@ -974,7 +977,7 @@ int ddp_user_rollout_fit_f64_dev(ddp_handle h, void *up, int N, int B, const dou
     UserProblem *P;
     int rc = enter(h, up, N, B, params, params_batched, &P, ON_DEVICE);
     if (rc) return rc;
-    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE)");
     DDP_CHECK(x0 && u && alpha && fx && fu && fc && xnew && unew && cnew && csum, "rollout_fit: null argument");
     FitScope fit(P, fx, fu, fc);
     return P->rollout(h, B, nullptr, K, k, x0, u, x, alpha, nalpha, lims, active, xnew, unew, cnew, csum);
@@ -1023,7 +1026,7 @@ int ddp_user_rollout_fit_f64(ddp_handle h, void *up, int N, int B, const double 
     UserProblem *P;
     int rc = enter(h, up, N, B, params, params_batched, &P);
     if (rc) return rc;
-    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(P->mod->rollfit, "rollout_fit: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE)");
     DDP_CHECK(x0 && u && alpha && fx && fu && fc && xnew && unew && cnew && csum, "rollout_fit: null argument");
     return rollout_host(h, up, P, N, B, params, params_batched, K, k, x0, u, x, alpha, nalpha, lims, fx, fu, fc, xnew, unew, cnew, csum);
 }
@@ -1059,7 +1062,7 @@ int ddp_user_ilqgkl_fit_f64_dev(ddp_handle h, void *up, int N, int B, const doub
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE)");
     DDP_CHECK(fx && fu && fc, "ilqgkl_fit: null argument");
     KlCall c;
     c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;
@@ -1075,7 +1078,8 @@ static int ilqgkl_cost_check(const UserProblem *U, const KlCall &c)
 {
     DDP_CHECK((c.fit_fx && c.fit_fu && c.fit_fc) || (!c.fit_fx && !c.fit_fu && !c.fit_fc),
               "ilqgkl_cost: fx, fu and fc are given all three (the plan is made on the tables) or all three NULL (on the problem's own model)");
-    DDP_CHECK(!c.fit_fx || U->mod->rollfit, "ilqgkl_cost: the problem was made without DDP_USER_FITTED (the tables fx, fu, fc need it)");
+    DDP_CHECK(!c.fit_fx || U->mod->rollfit, "ilqgkl_cost: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE; the tables "
+                                            "fx, fu, fc need it)");
     DDP_CHECK(c.cm_cx && c.cm_cu && c.cm_cxx && c.cm_cxu && c.cm_cuu, "ilqgkl_cost: a cost model is cx, cu, cxx, cxu and cuu (null argument)");
     return 0;
 }
@@ -1152,7 +1156,7 @@ int ddp_user_ilqgkl_fit_f64(ddp_handle h, void *up, int N, int B, const double *
     UserProblem *U;
     int rc = enter(h, up, N, B, params, params_batched, &U, ON_HOST, "ilqgkl");
     if (rc) return rc;
-    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED");
+    DDP_CHECK(U->mod->rollfit, "ilqgkl_fit: the problem was made without DDP_USER_FITTED (a DDP_USER_WAVE problem: without DDP_USER_FITTED_WAVE)");
     DDP_CHECK(fx && fu && fc, "ilqgkl_fit: null argument");
     KlCall c;
     c.opts = o; c.x0 = x0; c.cost0 = cost0; c.Kp = Kp; c.kp = kp; c.Sp = Sp; c.Sip = Sip; c.model_fx = model_fx;

@@ -17,6 +17,7 @@
 #include "user_sample_kernels.h"
 #include "user_sample_wave_kernels.h"
 #include "user_fitted_kernels.h"
+#include "user_fitted_wave_kernels.h"
 #include "user_cost_fit_kernels.h"
 #include "boxqp_dev_text.h"      // kBoxqpDevText: the text of boxqp_dev.h (written by build.py)
 #include "philox_text.h"         // kPhiloxText: the text of philox.h (written by build.py)
@@ -140,6 +141,8 @@ Layout layout_of(int n, int m, int flags)
         L.chunk = 1;
         L.rlanes = 64 / L.wg;
         L.dflanes = (flags & DDP_USER_AUTODIFF) ? 1 : 64;
+        // ddp_user_rollout_fit_wave (DDP_USER_FITTED_WAVE): the groups of ddp_user_rollout_wave, a step at a time, nothing staged
+        if (flags & DDP_USER_FITTED_WAVE) { L.flanes = L.rlanes; L.fchunk = 1; }
     }
     return L;
 }
@@ -248,7 +251,7 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
               DDP_USER_MAX_NPARAM);
     DDP_CHECK((flags & ~(DDP_USER_TERMINAL | DDP_USER_CONST_HESSIAN | DDP_USER_AUTODIFF | DDP_USER_PLANT | DDP_USER_SECOND_ORDER |
                          DDP_USER_WAVE | DDP_USER_SECOND_ORDER_WAVE | DDP_USER_CLOCK | DDP_USER_CONSTRAINTS | DDP_USER_SAMPLE | DDP_USER_FITTED |
-                         DDP_USER_COST_FIT | DDP_USER_SAMPLE_WAVE)) == 0,
+                         DDP_USER_COST_FIT | DDP_USER_SAMPLE_WAVE | DDP_USER_FITTED_WAVE)) == 0,
               "user problem: unknown flags 0x%x", flags);
     // deferred, not impossible: the sampled kernels keep a lane's state in registers or its cost derivatives in LDS (n <= 32, m <= 8) and hand
     // the user's functions neither a clock nor multipliers
@@ -274,6 +277,16 @@ int validate(const char *source, int n, int m, int nparam, int flags, unsigned w
                                              "takes no clock)");
         DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_SAMPLE_WAVE | DDP_USER_CONSTRAINTS is refused (deferred: "
                                                    "ddp_user_sample_wave takes no multipliers)");
+    }
+    if (flags & DDP_USER_FITTED_WAVE) {
+        // the fitted rollout at the wave sizes is a flag of its own (DDP_USER_FITTED | DDP_USER_WAVE stays refused, as it always was);
+        // deferred, not impossible: ddp_user_rollout_fit_wave hands the user's cost neither a clock nor multipliers, as ddp_user_rollout_fit
+        DDP_CHECK(wave, "user problem: DDP_USER_FITTED_WAVE needs DDP_USER_WAVE (ddp_user_rollout_fit_wave runs in the layout of "
+                        "ddp_user_rollout_wave; without DDP_USER_WAVE the fitted rollout is DDP_USER_FITTED)");
+        DDP_CHECK(!(flags & DDP_USER_CLOCK), "user problem: DDP_USER_FITTED_WAVE | DDP_USER_CLOCK is refused (deferred: "
+                                             "ddp_user_rollout_fit_wave takes no clock)");
+        DDP_CHECK(!(flags & DDP_USER_CONSTRAINTS), "user problem: DDP_USER_FITTED_WAVE | DDP_USER_CONSTRAINTS is refused (deferred: "
+                                                   "ddp_user_rollout_fit_wave takes no multipliers)");
     }
     if (flags & DDP_USER_CONSTRAINTS) {
         // deferred, not impossible: the augmented cost is differentiated by AD, its Hessian is not constant, and the clocked and
@@ -446,6 +459,8 @@ static std::string program_text(const char *source, int n, int m, int nparam, in
         s += kPhiloxText;
         section(s, "", "ddp_user_kernels_sample_wave", DDP_USER_ABI_SAMPLE_TEXT, kUserKernelsSampleWave);
     }
+    if (flags & DDP_USER_FITTED_WAVE)                            // (never next to DDP_USER_FITTED: one copy of the struct)
+        section(s, "", "ddp_user_kernels_fit_wave", DDP_USER_ABI_FIT_TEXT, kUserKernelsFitWave);
     return s;
 }
 

@@ -551,6 +551,7 @@ const USER_CONSTRAINTS = 1024          # DDP_USER_CONSTRAINTS: the flag of Devic
 const USER_MAX_NC = 16                 # DDP_USER_MAX_NC
 const USER_SAMPLE = 2048               # DDP_USER_SAMPLE: the flag of DeviceProblem(...; sample=true)
 const USER_FITTED = 4096               # DDP_USER_FITTED: the flag of DeviceProblem(...; fitted=true)
+const USER_FITTED_WAVE = 65536         # DDP_USER_FITTED_WAVE: the flag of DeviceProblem(...; wave=true, fitted_wave=true)
 const USER_SAMPLE_WAVE = 16384         # DDP_USER_SAMPLE_WAVE: the flag of DeviceProblem(...; wave=true, sample_wave=true)
 const USER_COST_FIT = 8192             # DDP_USER_COST_FIT: the flag of DeviceProblem(...; cost_fit=true)
 const USER_SECOND_ORDER_WAVE = 128     # DDP_USER_SECOND_ORDER_WAVE: the flag of DeviceProblem(...; second_order_wave=true); 64 is not assigned
@@ -994,6 +995,9 @@ end
 # with wave, second_order_wave, clock or constraints.
 # sample_wave=true (DDP_USER_SAMPLE_WAVE, needs wave=true): the sampler at the shapes of wave=true, n <= 64 and m <= 32 — the program also
 # holds ddp_user_sample_wave, and sample_policy takes the problem with the semantics of sample=true.  Not together with clock or constraints.
+# fitted_wave=true (DDP_USER_FITTED_WAVE, needs wave=true): the fitted rollout at the shapes of wave=true — the program also holds
+# ddp_user_rollout_fit_wave; forward_pass(...; model=(fx, fu, fc)) runs it and iLQGkl(...; fitted=true, wide=true) plans on the tables,
+# with the semantics of fitted=true.  Not together with clock or constraints.
 mutable struct DeviceProblem
     source::String
     n::Int
@@ -1008,14 +1012,15 @@ end
 function DeviceProblem(source::AbstractString, n::Integer, m::Integer; nparam::Integer=0, params=Float64[], terminal::Bool=false,
                        const_hessian::Bool=false, autodiff::Bool=false, diff=-, plant::Bool=false, second_order::Bool=false, wave::Bool=false,
                        second_order_wave::Bool=false, clock::Bool=false, constraints::Integer=0, sample::Bool=false,
-                       fitted::Bool=false, cost_fit::Bool=false, sample_wave::Bool=false)
+                       fitted::Bool=false, cost_fit::Bool=false, sample_wave::Bool=false, fitted_wave::Bool=false)
     wrap = Int(_diff_mask(diff, n))
     wave = wave || second_order_wave
     sample_wave && !wave && error("DeviceProblem: DDP_USER_SAMPLE_WAVE needs DDP_USER_WAVE (sample_wave=true needs wave=true)")
+    fitted_wave && !wave && error("DeviceProblem: DDP_USER_FITTED_WAVE needs DDP_USER_WAVE (fitted_wave=true needs wave=true)")
     flags = (terminal ? 1 : 0) | (const_hessian ? 2 : 0) | (autodiff ? 4 : 0) | (plant ? 8 : 0) | (second_order ? 16 : 0) | (wave ? 32 : 0) |
             (second_order_wave ? USER_SECOND_ORDER_WAVE : 0) | (clock ? USER_CLOCK : 0) | (constraints > 0 ? USER_CONSTRAINTS : 0) |
             (sample ? USER_SAMPLE : 0) | (fitted ? USER_FITTED : 0) | (cost_fit ? USER_COST_FIT : 0) |
-            (sample_wave ? USER_SAMPLE_WAVE : 0)
+            (sample_wave ? USER_SAMPLE_WAVE : 0) | (fitted_wave ? USER_FITTED_WAVE : 0)
     p = DeviceProblem(String(source), n, m, nparam, flags, wrap, _f64(params), Dict{Ptr{Cvoid},Ptr{Cvoid}}(), Int(constraints))
     finalizer(q -> foreach(up -> (@ccall libddp.ddp_user_destroy(up::Ptr{Cvoid})::Cint), values(q.made)), p)
     return p
@@ -1106,7 +1111,8 @@ end
 
 # the tables (fx, fu, fc) of a fitted model as [.,.,N,B] arrays, checked against the call's sizes and the problem's flag
 function _fitted_tables(problem::DeviceProblem, model, n, m, N, B, who)
-    (problem.flags & USER_FITTED) != 0 || throw(DDPError(-1, who * ": a fitted model needs a DeviceProblem made with fitted=true (DDP_USER_FITTED)"))
+    (problem.flags & (USER_FITTED | USER_FITTED_WAVE)) != 0 ||
+        throw(DDPError(-1, who * ": a fitted model needs a DeviceProblem made with fitted=true (DDP_USER_FITTED) or with wave=true, fitted_wave=true (DDP_USER_FITTED_WAVE)"))
     length(model) == 3 || throw(DDPError(-1, who * ": the fitted model should be a triple (fx, fu, fc)"))
     fx, fu, fc = _f64(model[1]), _f64(model[2]), _f64(model[3])
     (size(fx) in ((n, n, N), (n, n, N, B)) && size(fu) in ((n, m, N), (n, m, N, B)) && size(fc) in ((n, N), (n, N, B)) &&
@@ -1652,8 +1658,10 @@ end
 function iLQGkl(problem::DeviceProblem, x0, traj_prev, fx_model, R1; params=nothing, t0=nothing, kl_step=1.0, lims=[], max_iter=50, cost=[],
                 ηbracket=[1e-8, 1.0, 1e16], del0=1e-4, constrain_per_step=false, handle::Handle=default_handle(), policy=GaussianPolicy{Float64},
                 fitted::Bool=false, fu_model=nothing, fc_model=nothing, cost_model=nothing, wide::Bool=false)
-    fitted && wide && throw(DDPError(-1, "iLQGkl: fitted=true together with wide=true is refused (deferred)"))
-    cost_model !== nothing && wide && throw(DDPError(-1, "iLQGkl: cost_model together with wide=true is refused (deferred)"))
+    fitted && wide && (problem.flags & USER_FITTED_WAVE) == 0 &&
+        throw(DDPError(-1, "iLQGkl: fitted=true together with wide=true needs a DeviceProblem made with wave=true, fitted_wave=true (DDP_USER_FITTED_WAVE)"))
+    cost_model !== nothing && wide && (problem.flags & 32) == 0 &&                                           # 32: DDP_USER_WAVE
+        throw(DDPError(-1, "iLQGkl: cost_model together with wide=true needs a DeviceProblem made with wave=true (DDP_USER_WAVE)"))
     constrain_per_step && error("constrain_per_step (iLQGkl.jl:180-232) is not offloaded (it cannot run upstream either: klutils.jl:195)")
     isempty(cost) && error("Initial trajectory supplied, initial cost must also be supplied")                 # :69
     batched = ndims(x0) == 3

@@ -235,29 +235,33 @@ def iLQGkl(problem, x0, traj_prev, model, *, kl_step=1.0, lims=None, max_iter=50
     ``wide=True``: n <= 64, m <= 32 — an ``LQProblem``, or a ``DeviceProblem`` made with ``wave=True``.
     ``t0``: the clock of every trajectory of a ``DeviceProblem`` made with ``clock=True`` (an int or B ints, default 0): STEP 1 and
     every rollout evaluate the model at the absolute step ``t0 + i``.
-    ``fitted=True`` (a ``DeviceProblem`` made with ``fitted=True``, ``model = Model(fx, fu, R1, fc)`` from ``fit_dynamics``): the whole
-    loop plans on the fitted time-varying affine model ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` under the problem's cost — back_pass_gps
-    takes ``model.fx, model.fu``, every rollout runs ``ddp_user_rollout_fit`` on the tables, forward_covariance takes ``model.fx``; the
-    problem's ``dynamics`` and the fx, fu of its ``derivatives`` are not used.  ``x0`` should be the rollout of ``traj_prev.k`` on the
-    tables (``forward_pass(None, x0, u, None, 1.0, problem, lims, model=(fx, fu, fc))``).  The tables must be finite at every step (a step
-    ``fit_dynamics`` rejected is NaN).  ``fitted=False`` (default): the plan is made on the problem's own model, ``model.fx`` only shapes
-    the state covariance.
+    ``fitted=True`` (a ``DeviceProblem`` made with ``fitted=True``, or with ``wave=True, fitted_wave=True`` — the only kind that goes with
+    ``wide=True``; ``model = Model(fx, fu, R1, fc)`` from ``fit_dynamics``): the whole loop plans on the fitted time-varying affine model
+    ``x̂[i+1] = fx_i x̂_i + fu_i û_i + fc_i`` under the problem's cost — back_pass_gps takes ``model.fx, model.fu``, every rollout runs
+    ``ddp_user_rollout_fit`` (``ddp_user_rollout_fit_wave`` on a ``fitted_wave`` problem) on the tables, forward_covariance takes
+    ``model.fx``; the problem's ``dynamics`` and the fx, fu of its ``derivatives`` are not used.  ``x0`` should be the rollout of
+    ``traj_prev.k`` on the tables (``forward_pass(None, x0, u, None, 1.0, problem, lims, model=(fx, fu, fc))``).  The tables must be
+    finite at every step (a step ``fit_dynamics`` rejected is NaN).  ``fitted=False`` (default): the plan is made on the problem's own
+    model, ``model.fx`` only shapes the state covariance.
     ``cost_model=(cx, cu, cxx, cxu, cuu)`` (a ``DeviceProblem``; ``[n,N(,B)]``, ``[m,N(,B)]``, ``[n,n,N(,B)]``, ``[n,m,N(,B)]``,
     ``[m,m,N(,B)]``, e.g. the first five arrays ``fit_cost`` returns): every backward pass of the loop takes these arrays in place of the
     cost derivatives STEP 1 evaluates at ``(x0, traj_prev.k)``; ``cost``, the problem's own cost of the rollouts (what the loop compares
-    and returns) and the loop itself are as without it.  With and without ``fitted=True``; the arrays must be finite.
+    and returns) and the loop itself are as without it.  With and without ``fitted=True``; the arrays must be finite.  Together with
+    ``wide=True`` on a ``DeviceProblem`` made with ``wave=True`` (``back_pass_gps_wide`` takes the five arrays).
     ``kl_step``: a scalar, or with a batched call ``B`` values, ONE STEP PER TRAJECTORY (e.g. ``kl_step_adjust(...)[0]``): trajectory
     ``b`` is held to ``kl_step[b]`` and runs as it does in a call with that scalar.  (The reference's per-time-step meaning of a
     vector ``kl_step`` belongs to ``constrain_per_step``, which stays refused.)  The values are the handle's for the duration of the call
     (``ddp_kl_set_steps``) and cleared on every way out; every loop variant reads them, ``DDP_KL_HOSTLOOP=1`` included."""
     if cost_model is not None:
-        if wide:
-            raise DDPError("iLQGkl: cost_model= together with wide=True is refused (deferred: a cost model is sized for n <= 32, m <= 8)")
+        if wide and not (isinstance(problem, DeviceProblem) and problem.wave):
+            raise DDPError("iLQGkl: cost_model= together with wide=True needs a DeviceProblem made with wave=True (DDP_USER_WAVE); on any "
+                           "other problem it is refused (a cost model there is sized for n <= 32, m <= 8)")
         if not isinstance(problem, DeviceProblem):
             raise DDPError("iLQGkl: cost_model= needs a DeviceProblem (the registered problems bring their own quadratic cost)")
     if fitted:
-        if wide:
-            raise DDPError("iLQGkl: fitted=True together with wide=True is refused (deferred: ddp_user_rollout_fit is sized for n <= 32, m <= 8)")
+        if wide and not (isinstance(problem, DeviceProblem) and problem.fitted_wave):
+            raise DDPError("iLQGkl: fitted=True together with wide=True needs a DeviceProblem made with wave=True, fitted_wave=True "
+                           "(DDP_USER_FITTED_WAVE); on any other problem it is refused (ddp_user_rollout_fit is sized for n <= 32, m <= 8)")
         if not isinstance(problem, DeviceProblem):
             raise DDPError("iLQGkl: fitted=True needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
     if constrain_per_step:
@@ -338,8 +342,9 @@ def _cost_model_tables(cost_model, n, m, N, B):
 
 def _fitted_kl_tables(problem, model, n, m, N, B):
     """``fitted=True``: the tables of ``model`` as [.,.,N,B] arrays; every missing condition is refused by name before any launch"""
-    if not problem.fitted:
-        raise DDPError("iLQGkl: fitted=True needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)")
+    if not (problem.fitted or problem.fitted_wave):
+        raise DDPError("iLQGkl: fitted=True needs a DeviceProblem made with fitted=True (DDP_USER_FITTED)%s"
+                       % ("; a wave=True problem: with fitted_wave=True (DDP_USER_FITTED_WAVE)" if problem.wave else ""))
     if model.fx is None or model.fu is None:
         raise DDPError("iLQGkl: fitted=True needs model.fx, model.fu and model.fc (Model(fx, fu, R1, fc) from fit_dynamics)")
     if model.fc is None:

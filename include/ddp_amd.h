@@ -718,14 +718,29 @@ int ddp_ilqgkl_f64(ddp_handle h, const ddp_problem *p, const ddp_ilqgkl_opts *o,
  * DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SECOND_ORDER_WAVE and diff_wrap.  Without DDP_USER_WAVE, or
  * together with DDP_USER_CLOCK or DDP_USER_CONSTRAINTS, it is refused by name — the last two deferred, not impossible.  A problem
  * without the flag compiles the text it always did; the tail of the flag goes last in the program.  user_examples/chain_plant_ad.hip is
- * chain_ad.hip with a plant (an actuator gain per joint, another damping; 9 parameters), for use_plant = 1 at these sizes. */
+ * chain_ad.hip with a plant (an actuator gain per joint, another damping; 9 parameters), for use_plant = 1 at these sizes.
+ *
+ * DDP_USER_FITTED_WAVE: the rollout on a fitted model, and the KL-constrained loop on it, of DDP_USER_FITTED at the shapes of
+ * DDP_USER_WAVE, n <= 64, m <= 32 (ddp_user_rollout_fit_*, ddp_user_ilqgkl_fit_*, ddp_user_ilqgkl_cost_*, below; every other entry point
+ * ignores the flag).  A flag of its own, which needs DDP_USER_WAVE: DDP_USER_FITTED | DDP_USER_WAVE stays refused.  The step, the
+ * tables and their layout, map, active, nalpha, has_policy, lims, the fused csum, slot N-1 that is never read and the order of the sum
+ * (per component fc, j = 0..n-1, q = 0..m-1) are those of DDP_USER_FITTED, word for word; nothing depends on B, nalpha or the launch
+ * geometry.  Kernel ddp_user_rollout_fit_wave (ddp_last_kernel(h, 1)): a group of lanes per rollout (8, 16 or 32: the power of two
+ * >= m), 64 / group rollouts per one-wave work-group; x^, diff(x^, x_i) and u^ in LDS; lane q of the group forms row q of
+ * u_i + alpha k_i + K_i dx streaming row q of K_i, then rows q, q + group, ... of [fc | fx | fu] against x^ and u^ (the tables are
+ * column-major: the lanes of a group read consecutive doubles of every column); one lane of the group calls the user's cost.  Legal
+ * with DDP_USER_TERMINAL, DDP_USER_CONST_HESSIAN, DDP_USER_AUTODIFF, DDP_USER_PLANT, DDP_USER_SAMPLE_WAVE, DDP_USER_SECOND_ORDER_WAVE
+ * and diff_wrap.  Without DDP_USER_WAVE, or together with DDP_USER_CLOCK or DDP_USER_CONSTRAINTS, it is refused by name — the last two
+ * deferred, not impossible.  A problem without the flag compiles the text it always did; the tail of the flag goes last in the
+ * program, behind that of DDP_USER_SAMPLE_WAVE. */
 #define DDP_MAX_N_USER 32
 #define DDP_USER_MAX_NPARAM 4096
 #define DDP_MAX_N_USER_WAVE 64   /* with DDP_USER_WAVE: n <= 64, m <= DDP_MAX_M_WIDE */
 enum { DDP_USER_TERMINAL = 1, DDP_USER_CONST_HESSIAN = 2, DDP_USER_AUTODIFF = 4, DDP_USER_PLANT = 8, DDP_USER_SECOND_ORDER = 16,
        DDP_USER_WAVE = 32, DDP_USER_SECOND_ORDER_WAVE = 128, DDP_USER_CLOCK = 512,
        DDP_USER_CONSTRAINTS = 1024, DDP_USER_SAMPLE = 2048, DDP_USER_FITTED = 4096,
-       DDP_USER_COST_FIT = 8192, DDP_USER_SAMPLE_WAVE = 16384 };                           /* 64: not assigned, refused as unknown (256 too) */
+       DDP_USER_COST_FIT = 8192, DDP_USER_SAMPLE_WAVE = 16384,
+       DDP_USER_FITTED_WAVE = 65536 };                            /* 64: not assigned, refused as unknown (256 and 32768 too) */
 #define DDP_USER_MAX_NC 16       /* with DDP_USER_CONSTRAINTS: 1 <= nc <= 16 */
 /* compile-only check for gfx950 (no handle, no GPU): 0 = compiled, < 0 = refused or the compiler failed (ddp_user_compile_log()).
  * extra_options: more hiprtc options separated by spaces, or NULL (e.g. "-Rpass-analysis=kernel-resource-usage")               */
@@ -929,8 +944,9 @@ int ddp_fit_dynamics_wide_f64(ddp_handle h, int n, int m, int N, int S, int B, c
                               const double *Phi, const double *mu0, double m0, double n0, int prior_layout, double *fx, double *fu,
                               double *fc, double *cov, int32_t *status);
 
-/* DDP_USER_FITTED problems only (a problem made without the flag is refused by name).  The rollout of ddp_user_forward_pass_f64(_dev),
- * arguments and outputs alike, on the fitted model fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] (see DDP_USER_FITTED above).                  */
+/* DDP_USER_FITTED and DDP_USER_FITTED_WAVE problems only (a problem made without either flag is refused by name).  The rollout of
+ * ddp_user_forward_pass_f64(_dev), arguments and outputs alike, on the fitted model fx[n,n,N,B], fu[n,m,N,B], fc[n,N,B] (see
+ * DDP_USER_FITTED above; kernel ddp_user_rollout_fit, with DDP_USER_FITTED_WAVE ddp_user_rollout_fit_wave).                           */
 int ddp_user_rollout_fit_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched,
                                  const double *K, const double *k, const double *x0, const double *u, const double *x,
                                  const double *alpha, int nalpha, const double *lims, const int32_t *active,
@@ -973,7 +989,7 @@ int ddp_user_cost_fit_f64(ddp_handle h, void *up, int N, int S, int B, const dou
 /* iLQGkl with a cost model: arguments and outputs as ddp_user_ilqgkl_fit_f64(_dev), then cx[n,N,B], cu[m,N,B], cxx[n,n,N,B],
  * cxu[n,m,N,B], cuu[m,m,N,B] (all five, time-varying and batched), which every backward pass of the loop takes in place of the cost
  * derivatives STEP 1 evaluates at (x0, kp).  fx, fu, fc: all three given — the loop plans on the tables as ddp_user_ilqgkl_fit_* does
- * (a DDP_USER_FITTED problem) — or all three NULL — on the problem's own model, as ddp_user_ilqgkl_* does.  Everything else is as
+ * (a DDP_USER_FITTED or DDP_USER_FITTED_WAVE problem) — or all three NULL — on the problem's own model, as ddp_user_ilqgkl_* does.  Everything else is as
  * without a cost model: cost0, the user's cost of the rollouts (the cost the loop compares and reports) and the loop itself.  The
  * tables need not come from ddp_user_cost_fit_* and the problem needs no DDP_USER_COST_FIT; non-finite tables are the caller's to check. */
 int ddp_user_ilqgkl_cost_f64_dev(ddp_handle h, void *up, int N, int B, const double *params, int params_batched, const ddp_ilqgkl_opts *o,
